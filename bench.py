@@ -2,13 +2,23 @@
 """bench.py - headline benchmark of the VSR captioning decoder hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload beam5|beam5idx|greedy|xe|xeidx|scst]
-                    [--scaling weak|strong] [--dtype f16x2|f32x3|f32|bf16] [--no-cpu] [--no-secondary] [--no-alt]
+                    [--scaling weak|strong] [--dtype f16x2|f32x3|f32|bf16] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-secondary] [--no-alt]]
+
+A plain run sets up, warms up, times the K steps of the chosen workload, writes the last step's outputs if --dump-outputs
+is given, and prints the result line.  --full adds everything beside the headline: the GEMM roofline (HIP events around
+every 5th GEMM launch of the timed region), the CPU baseline, the XE step and the other GEMM flavours and workloads of the
+default line, and the dense-format comparison of beam5idx.
+--dump-outputs DIR: what the timed path returned to its caller in the last timed step (rank 0), as DIR/<name>.npy in
+float32 / float64: word and gate ids (and beam log-probs) of a decode call, the losses of a training step and a fixed
+seeded sample of 4 096 elements per parameter after it.  The inputs are synthetic and seeded: the same arguments give the
+same inputs from run to run.
 
 Headline (BASELINE.json metric, configs[2]): beam-5 decode through ControllableCaptioningModel.beam_search, batch 100
 images per GPU, 36 regions x 2048-d, 10 slots, seq_len 20, vocab 10 000, fp32 operands and accumulation (the reference's
 precision; token parity holds: every GPU test runs in this flavour and in the exact-chain one).  A "step" = ONE full decode call on one batch of synthetic inputs already resident in HBM: hoisted
 statics (vsr_prepare) + 20 timesteps + back-tracking.  tokens/s = B_total * T * steps / wall time (top-1 hypothesis
-tokens).  The default line also carries the second half of the BASELINE metric as "secondary": the XE
+tokens).  The --full line also carries the second half of the BASELINE metric as "secondary": the XE
 training step (configs[3] shapes; forward + NLL losses + hand-written BPTT + Adam [+ RCCL gradient all-reduce]).
 
 Multi-GPU (one process per GPU, RCCL):  `--gpus N` with no torch.distributed environment starts the N ranks itself
@@ -26,6 +36,8 @@ import subprocess
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "vsr-guided-cic_amd"))
 
@@ -36,6 +48,35 @@ PROFILE_EVERY = 5
 PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 / 16x16x4_f32, dense, spec
 PEAK_BF16_MFMA_TFLOPS = 2500.0   # dense bf16 (never the 2:1-sparsity figure)
 PEAK_HBM_GBS = 8000.0
+PARAM_SAMPLE = 4096              # --dump-outputs: elements per trained parameter
+
+
+def host_outputs(named):
+    """{name: tensor} of the last timed step -> {name: host array}: float64 stays float64, everything else (ids < 2^24,
+    fp32 log-probs) becomes float32"""
+    out = {}
+    for k, t in named.items():
+        a = t.detach().cpu().numpy()
+        out[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    return out
+
+
+def param_sample(torch, model):
+    """a fixed, seeded sample of PARAM_SAMPLE elements of every parameter (all of a smaller one)"""
+    out = {}
+    for k, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), PARAM_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out["param_" + k] = flat
+    return out
+
+
+def dump_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------- rank launch
@@ -325,34 +366,38 @@ def decode_bench(args, D, torch, dist, synth):
         det, ctrl = batches[i & 1]
         with torch.no_grad():
             if beam > 1:
-                (w, g), _ = m.beam_search((det, ctrl), [EOS, -1], beam, 1)
+                (w, g), (lw, lg) = m.beam_search((det, ctrl), [EOS, -1], beam, 1)
+                out = {"words": w, "gates": g, "logp_words": lw, "logp_gates": lg}
             else:
                 w, g = m.test(det, ctrl)
+                out = {"words": w, "gates": g}
             if strong:      # the one exchange of a sharded decode: (B, T) ids of every shard
-                w = D.gather_ids(parallel, w, c["B"])
-            return w
+                out["words"] = D.gather_ids(parallel, w, c["B"])
+            return out
 
     for i in range(args.warmup):
         one_step(i)
     eng = m._engine(dev)
     D.barrier()
-    # HIP events around every 5th GEMM launch of the timed region (3 launch kinds per timestep: every kind is sampled
-    # equally often); an event pair on EVERY launch costs the timed region 3 %
-    eng.profile_begin(every=PROFILE_EVERY)
+    if args.full:
+        # HIP events around every 5th GEMM launch of the timed region (3 launch kinds per timestep: every kind is sampled
+        # equally often); an event pair on EVERY launch costs the timed region 3 %
+        eng.profile_begin(every=PROFILE_EVERY)
     t0 = time.perf_counter()
-    last_ids = None
+    last = None
     for i in range(args.steps):
-        last_ids = one_step(i)
+        last = one_step(i)
     D.barrier()
     dt = time.perf_counter() - t0
-    gemm_seen = eng.profile_seen()
-    gemm_bytes = eng.profile_bytes()
-    gemm_ms, gemm_n, gemm_flops = eng.profile_end(dev)
+    if args.full:
+        gemm_seen = eng.profile_seen()
+        gemm_bytes = eng.profile_bytes()
+        gemm_ms, gemm_n, gemm_flops = eng.profile_end(dev)
     dt = D.max_time(dt)
     images = c["B"] if strong else world * c["B"]
     name = "beam-5" if beam > 1 else "greedy"
     traffic, tsrc = (None, None)
-    if beam > 1 and not indexed:                                        # the workloads the committed PMC passes were taken on
+    if args.full and beam > 1 and not indexed:                          # the workloads the committed PMC passes were taken on
         traffic, tsrc = traffic_from_profiles({"f32": "gemm", "bf16": "gemm_bf16", "f32x3": "gemm_f32x3", "f16x2": "gemm_f16x2"}[args.dtype])
     line = {
         "metric": ("decoded tokens/sec at batch=100, beam=5, 36x2048 regions" + (", index-list region format" if indexed else ""))
@@ -368,11 +413,13 @@ def decode_bench(args, D, torch, dist, synth):
                    "host_sync_per_call": "none (caller-supplied bound on the non-padding region rows)" if (args.rows_bound and valid_rows > 0) else "one 8-byte read-back in vsr_prepare (the number of non-padding region rows)",
                    "decode_cache": "prebuilt, weight-only (embedding rows through the x columns of the LSTM1 / gate input weights, "
                                    "240 MB, built once per weight version outside the timed call; all per-image hoisting is inside)"},
-        "roofline": roofline_block(args.dtype, gemm_ms, gemm_n, gemm_seen, gemm_flops, dt, traffic, tsrc, gemm_bytes),
     }
+    if args.full:
+        line["roofline"] = roofline_block(args.dtype, gemm_ms, gemm_n, gemm_seen, gemm_flops, dt, traffic, tsrc, gemm_bytes)
     if getattr(args, "emit_ids", False) and rank == 0:
-        line["config"]["ids"] = last_ids.cpu().tolist()
-    if indexed and rank == 0:
+        line["config"]["ids"] = last["words"].cpu().tolist()
+    outputs = host_outputs(last) if args.dump_outputs and rank == 0 else None
+    if args.full and indexed and rank == 0:
         dense = [(d, r.dense().contiguous()) for d, r in batches]
         with torch.no_grad():
             for i in range(2):
@@ -386,7 +433,7 @@ def decode_bench(args, D, torch, dist, synth):
         line["config"]["region_bytes_per_batch"] = {"index_lists": int(batches[0][1].slot_idx.numel() * 4), "dense": int(dense[0][1].numel() * 4)}
     del m, batches
     torch.cuda.empty_cache()
-    return line, weights, beam
+    return line, weights, beam, outputs
 
 
 # ---------------------------------------------------------------------------------------------- eval-side caller (C3 / N1)
@@ -415,14 +462,17 @@ def eval_bench(args, D, torch, dist, synth):
         one_step(i)
     eng = m._engine(dev)
     D.barrier()
-    eng.profile_begin(every=PROFILE_EVERY)
+    if args.full:
+        eng.profile_begin(every=PROFILE_EVERY)
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        one_step(i)
+        last = one_step(i)
     D.barrier()
     dt = time.perf_counter() - t0
-    gemm_seen, gemm_bytes = eng.profile_seen(), eng.profile_bytes()
-    gemm_ms, gemm_n, gemm_flops = eng.profile_end(dev)
+    if args.full:
+        gemm_seen, gemm_bytes = eng.profile_seen(), eng.profile_bytes()
+        gemm_ms, gemm_n, gemm_flops = eng.profile_end(dev)
     dt = D.max_time(dt)
     rows = n_img * n_caps * D.world
     line = {"metric": "decoded tokens/sec, beam_search_v at the eval caller's shapes (16 images x 5 caption rows, beam 5)",
@@ -430,11 +480,16 @@ def eval_bench(args, D, torch, dist, synth):
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": "beam_search_v (verb forcing, gt=False) through evalbatch.beam_search_v_batched: 16 images x 5 caption rows per GPU, 100 pooled "
                                    "detections x 2048-d, 10 slots x 20 regions, seq_len 20, vocab 10000, beam 5 (eval_coco.py:55-57,240-247; data/field.py:18,115)",
-                       "beam": BEAM, "rows_per_gpu": n_img * n_caps, "seq_len": c["T"], "parallelism": "dp%d, no data-path collective" % D.world},
-            "roofline": roofline_block(args.dtype, gemm_ms, gemm_n, gemm_seen, gemm_flops, dt, None, None, gemm_bytes)}
+                       "beam": BEAM, "rows_per_gpu": n_img * n_caps, "seq_len": c["T"], "parallelism": "dp%d, no data-path collective" % D.world}}
+    if args.full:
+        line["roofline"] = roofline_block(args.dtype, gemm_ms, gemm_n, gemm_seen, gemm_flops, dt, None, None, gemm_bytes)
+    outputs = None
+    if args.dump_outputs and D.rank == 0:       # per image ([words, gates], [lp_w, lp_g]), concatenated over the images' caption rows
+        outputs = host_outputs({k: torch.cat([r[j][i] for r in last], 0) for k, j, i in
+                                (("words", 0, 0), ("gates", 0, 1), ("logp_words", 1, 0), ("logp_gates", 1, 1))})
     del m, batches
     torch.cuda.empty_cache()
-    return line, weights
+    return line, weights, outputs
 
 
 # ---------------------------------------------------------------------------------------------- training
@@ -501,15 +556,18 @@ def train_bench(args, D, torch, dist, synth, steps, warmup):
         one_step(i)
     eng = m._engine(dev)
     D.barrier()
-    eng.profile_begin(every=PROFILE_EVERY)
+    if args.full:
+        eng.profile_begin(every=PROFILE_EVERY)
     t0 = time.perf_counter()
+    last = None
     for i in range(steps):
-        one_step(i)
+        last = one_step(i)
     D.barrier()
     dt = time.perf_counter() - t0
-    gemm_seen = eng.profile_seen()
-    gemm_bytes = eng.profile_bytes()
-    gemm_ms, gemm_n, gemm_flops = eng.profile_end(dev)
+    if args.full:
+        gemm_seen = eng.profile_seen()
+        gemm_bytes = eng.profile_bytes()
+        gemm_ms, gemm_n, gemm_flops = eng.profile_end(dev)
     dt = D.max_time(dt)
     images = c["B"] if strong else world * c["B"]
     line = {
@@ -525,12 +583,17 @@ def train_bench(args, D, torch, dist, synth, steps, warmup):
                    "batch_per_gpu": hi - lo, "seq_len": c["T"],
                    "parallelism": "dp%d, %s gradient all-reduce (%s on the wire) in buckets on a side stream, overlapped with the weight-gradient GEMMs" % (world, "RCCL" if args.backend == "nccl" else "gloo (self-test, host-staged)", "bf16, 142 MB" if args.dtype == "bf16" else "fp32, 285 MB"),
                    "rccl_world_size_observed": D.observed_world()},
-        "roofline": roofline_block(args.dtype, gemm_ms, gemm_n, gemm_seen, gemm_flops, dt, *((traffic_from_profiles("f16x2_xe_step") if xe and not indexed and args.dtype == "f16x2" else (None, None))),
-                                   gemm_bytes=gemm_bytes),
     }
+    if args.full:
+        line["roofline"] = roofline_block(args.dtype, gemm_ms, gemm_n, gemm_seen, gemm_flops, dt,
+                                          *((traffic_from_profiles("f16x2_xe_step") if xe and not indexed and args.dtype == "f16x2" else (None, None))),
+                                          gemm_bytes=gemm_bytes)
+    outputs = None
+    if args.dump_outputs and rank == 0:         # the step's global losses (XE: loss, loss_cap, loss_gate; SCST: loss) + the trained weights
+        outputs = host_outputs(dict({"losses": last.reshape(-1)}, **param_sample(torch, m)))
     del m, opt, step, batches
     torch.cuda.empty_cache()
-    return line, weights
+    return line, weights, outputs
 
 
 def main():
@@ -548,9 +611,12 @@ def main():
                          "bf16 terms (6 MFMAs, csrc/gemm_x3.h; launches of 129-192 rows on the exact kernels); f32 = the exact fp32 fma chain for "
                          "every launch; bf16 = throughput mode (bf16 operands, fp32 accumulate, fp32 master weights).  Every parity test runs in "
                          "f16x2, f32x3 and f32 (tests/conftest.py)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the XE-step leg of the default line")
-    ap.add_argument("--no-alt", action="store_true", help="skip the other-flavour legs (f32 / f32x3 / f16x2 / bf16) and the greedy / 13-image legs of the default line")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline, CPU baseline, the default line's "
+                                                        "XE step and other flavours / workloads, beam5idx's dense-format comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the XE-step leg of the default line")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the other-flavour legs (f32 / f32x3 / f16x2 / bf16) and the greedy / 13-image legs of the default line")
     ap.add_argument("--cpu-sample", type=int, default=12)
     ap.add_argument("--cpu-full", type=int, default=1, help="1: the CPU baseline's value is ONE as-written call at the workload's own batch size (0: the bounded sample only)")
     ap.add_argument("--batch", type=int, default=0, help="images per batch instead of 100 (experiments only: not the BASELINE workload)")
@@ -569,23 +635,24 @@ def main():
     import torch
     import torch.distributed as dist
     from vsrcap import synth
+    torch.manual_seed(0)        # the SCST step draws its sampling seed from torch's generator: same arguments, same draws
     D = Dist(torch, dist, args.backend)
     if args.gpus != D.world and D.rank == 0:
         print("bench.py: --gpus %d but the launcher started %d ranks; reporting n_gpus = %d" % (args.gpus, D.world, D.world), file=sys.stderr)
 
     if args.workload == "beam5_eval":
-        line, weights = eval_bench(args, D, torch, dist, synth)
+        line, weights, outputs = eval_bench(args, D, torch, dist, synth)
     elif args.workload == "xe_real":
         CFG.update(R0=100, R=20)
         args.workload = "xe"
-        line, weights = train_bench(args, D, torch, dist, synth, args.steps, args.warmup)
+        line, weights, outputs = train_bench(args, D, torch, dist, synth, args.steps, args.warmup)
         line["metric"] = "XE-step samples/sec at the real callers' shapes (100 pooled detections, 20 slots x 20 regions)"
     elif args.workload in ("xe", "xeidx", "scst"):
-        line, weights = train_bench(args, D, torch, dist, synth, args.steps, args.warmup)
-        if D.rank == 0 and D.world == 1 and not args.no_cpu and args.workload == "xe":
+        line, weights, outputs = train_bench(args, D, torch, dist, synth, args.steps, args.warmup)
+        if args.full and D.rank == 0 and D.world == 1 and not args.no_cpu and args.workload == "xe":
             line["cpu_baseline"] = cpu_baseline_xe(weights, min(args.cpu_sample, 16), torch, synth)
     else:
-        line, weights, beam = decode_bench(args, D, torch, dist, synth)
+        line, weights, beam, outputs = decode_bench(args, D, torch, dist, synth)
         def optional(what, fn):
             # the legs below ride along with the headline: a failure in one of them (the same code on every rank, so a Python-level
             # error is raised by all ranks together) is reported in its place instead of costing the run its headline value
@@ -597,27 +664,27 @@ def main():
 
         def xe_leg(dt, full):
             xb = argparse.Namespace(**vars(args))
-            xb.workload, xb.dtype = "xe", dt
-            bl, _ = train_bench(xb, D, torch, dist, synth, max(5, args.steps // 2), 2)
+            xb.workload, xb.dtype, xb.dump_outputs = "xe", dt, None
+            bl, _, _ = train_bench(xb, D, torch, dist, synth, max(5, args.steps // 2), 2)
             keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "scaling", "dtype", "config", "roofline") if full \
                 else ("value", "unit", "ms_per_step", "steps", "dtype", "roofline")
             return {k: bl[k] for k in keys}
 
         def decode_leg(dt):
             aa = argparse.Namespace(**vars(args))
-            aa.dtype = dt
+            aa.dtype, aa.dump_outputs = dt, None
             aa.steps, aa.warmup = max(5, args.steps // 2), 2
-            al, _, _ = decode_bench(aa, D, torch, dist, synth)
+            al, _, _, _ = decode_bench(aa, D, torch, dist, synth)
             return {k: al[k] for k in ("value", "unit", "ms_per_step", "steps", "dtype", "roofline")}
 
-        if args.workload == "beam5" and not args.no_secondary:
+        if args.full and args.workload == "beam5" and not args.no_secondary:
             # the other half of BASELINE.json's metric in the same driver-timed run
             line["secondary"] = optional("secondary XE step", lambda: xe_leg(args.dtype, True))
             if not args.no_alt and "error" not in line["secondary"]:
                 # configs[3] names bf16: the same XE step in the throughput mode, and in the exact-chain flavour, side by side
                 line["secondary"]["alt_modes"] = {dt: optional("XE step " + dt, lambda dt=dt: xe_leg(dt, False))
                                                   for dt in ("f32", "bf16") if dt != args.dtype}
-        if args.workload == "beam5" and not args.no_alt:
+        if args.full and args.workload == "beam5" and not args.no_alt:
             # the same workload in the other GEMM flavours, always printed side by side (never the headline `value`):
             #   f32   = the exact k-ordered fp32 fma chain for every launch (v_mfma_f32_32x32x2_f32)
             #   f32x3 = fp32 products from three bf16 terms per operand, f16x2 = from two fp16 terms (same fixtures, same bounds: the GPU
@@ -628,37 +695,37 @@ def main():
             # strong-scaled batch (M = 13 / 65): short legs in the headline's flavour, never the headline `value`
             def workload_leg(workload, batch):
                 aa = argparse.Namespace(**vars(args))
-                aa.workload = workload
+                aa.workload, aa.dump_outputs = workload, None
                 aa.steps, aa.warmup = max(10, args.steps), 3
                 old_b = CFG["B"]
                 CFG["B"] = batch
                 try:
-                    al, _, _ = decode_bench(aa, D, torch, dist, synth)
+                    al, _, _, _ = decode_bench(aa, D, torch, dist, synth)
                 finally:
                     CFG["B"] = old_b
                 return {k: al[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "dtype")} | {"batch": batch, "gemm_avg_launch_us": al["roofline"]["avg_launch_us"]}
             def real_xe_leg():
                 xb = argparse.Namespace(**vars(args))
-                xb.workload = "xe"
+                xb.workload, xb.dump_outputs = "xe", None
                 old = (CFG["R0"], CFG["R"])
                 CFG.update(R0=100, R=20)
                 try:
-                    bl, _ = train_bench(xb, D, torch, dist, synth, max(5, args.steps // 2), 2)
+                    bl, _, _ = train_bench(xb, D, torch, dist, synth, max(5, args.steps // 2), 2)
                 finally:
                     CFG.update(R0=old[0], R=old[1])
                 return {k: bl[k] for k in ("value", "unit", "ms_per_step", "steps", "dtype")} | {"workload": bl["config"]["workload"], "roofline_frac": bl["roofline"]["frac"]}
 
             def eval_leg():
                 aa = argparse.Namespace(**vars(args))
-                aa.steps, aa.warmup = max(10, args.steps), 3
-                bl, _ = eval_bench(aa, D, torch, dist, synth)
+                aa.steps, aa.warmup, aa.dump_outputs = max(10, args.steps), 3, None
+                bl, _, _ = eval_bench(aa, D, torch, dist, synth)
                 return {k: bl[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "dtype")} | {"workload": bl["config"]["workload"]}
             if args.batch == 0 and D.world == 1:
                 line["alt_workloads"] = {"greedy": optional("greedy leg", lambda: workload_leg("greedy", CFG["B"])),
                                          "beam5_batch13": optional("13-image leg", lambda: workload_leg("beam5", 13)),
                                          "xe_real": optional("real-shape XE leg", real_xe_leg),
                                          "beam5_eval": optional("eval-caller leg", eval_leg)}
-        if D.rank == 0 and D.world == 1 and not args.no_cpu and args.workload != "beam5idx":
+        if args.full and D.rank == 0 and D.world == 1 and not args.no_cpu and args.workload != "beam5idx":
             line["cpu_baseline"] = cpu_baseline(weights, args.cpu_sample, beam, torch, synth, full_B=CFG["B"] if args.cpu_full else 0)
         # The driver's record keeps the standard top-level keys and `config`: the other half of BASELINE.json's metric (XE samples/s), the
         # exact-chain flavour and the one-m-tile regimes are therefore ALSO summarised inside `config` (full legs: `secondary`, `alt_modes`,
@@ -690,6 +757,8 @@ def main():
             cfgk["vs_cpu_baseline"] = sig2(line["value"] / line["cpu_baseline"]["value"])
             cfgk["vs_cpu_baseline_hoisted"] = sig2(line["value"] / line["cpu_baseline"]["hoisted_value"])
             cfgk["cpu_baseline_timed_calls"] = line["cpu_baseline"].get("timed_calls")
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     if D.rank == 0:
         print(json.dumps(line), flush=True)
     if D.world > 1:

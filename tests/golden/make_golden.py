@@ -31,6 +31,7 @@ Fixtures:
                                           change - "training trains", per step, whatever optimizer flavour moves the weights
   g13_flip1024                            16 FRESH seeds x 64 images (no margin search): greedy + beam-5 ids of the reference (fp32)
                                           AND of the fp64 oracle, greedy margins, beam score gaps - the flip-rate fixture
+  g15_live_small                          greedy + beam-4 / out_size 2 ids at a tiny odd-sized config (V = 61, B = 3, T = 7)
 """
 import json
 import os
@@ -132,7 +133,7 @@ def pick_seed_and_greedy(c):
 
 def main():
     """Stages are independent and resumable:
-    python tests/golden/make_golden.py [small] [greedy] [beam] [verbs] [sample] [stepv] [xe100] [scst500] [fresh] [real] [flip1024] [traj]
+    python tests/golden/make_golden.py [small] [greedy] [beam] [verbs] [sample] [stepv] [live] [xe100] [scst500] [fresh] [real] [flip1024] [traj]
     (real / flip1024 only on request: they take ~1 h of CPU; traj: ~3 min)"""
     stages = sys.argv[1:] or ["small", "greedy", "beam", "verbs", "sample", "stepv", "xe100", "scst500", "fresh"]
     torch.manual_seed(0)
@@ -151,6 +152,8 @@ def main():
         stage_small(cS, cW, tables)
     if "stepv" in stages:
         stage_stepv(cS, tables)
+    if "live" in stages:
+        stage_live()
     set_table("full")
     if "xe100" in stages:
         t0 = time.time()
@@ -166,7 +169,7 @@ def main():
         stage_real()
     if "flip1024" in stages:
         stage_flip1024()
-    if not (set(stages) - {"small", "stepv", "xe100", "scst500", "fresh", "real", "flip1024", "traj"}):
+    if not (set(stages) - {"small", "stepv", "live", "xe100", "scst500", "fresh", "real", "flip1024", "traj"}):
         return
     cF = cfg_full(256)
     if "greedy" in stages:
@@ -270,6 +273,26 @@ def stage_small(cS, cW, tables):
     save("g6_step", dict(cfg=cS, seed=5, wseed=0, bos=BOS, t=3, k0=k0.tolist(), prev_w=prev[0].tolist(), prev_g=prev[1].tolist()),
          logp_w=lw.numpy(), logp_g=lg.numpy(), h1=s1[0].numpy(), c1=s1[1].numpy(), h2=s2[0].numpy(), c2=s2[1].numpy(),
          k=k1.numpy())
+
+
+def cfg_live():
+    return dict(V=61, B=3, R0=6, R=5, D=128, L=4, T=7, E=32, H=48, A=16)
+
+
+def stage_live():
+    # ---------------- G15: greedy and beam-4 / out_size 2 at a tiny odd-sized config, empty verb tables
+    json.dump({}, open("datasets/coco/verb_2_vob_all_refine.json", "w"))
+    json.dump({}, open("datasets/coco/verb_2_vob.json", "w"))
+    c = cfg_live()
+    m, _ = build_ref(c, wseed=4)
+    m.eval()
+    det, ctrl = inputs(c, 2)
+    with torch.no_grad():
+        gw, gg = m.test(det, ctrl)
+        (bw, bg), _ = m.beam_search((det, ctrl), [3, -1], 4, 2)
+    save("g15_live_small", dict(cfg=c, seed=2, wseed=4, bos=BOS, eos=[3, -1], beam=4, out_size=2),
+         greedy_words=gw.numpy().astype(np.int32), greedy_gates=gg.numpy().astype(np.int8),
+         beam_words=bw.numpy().astype(np.int32), beam_gates=bg.numpy().astype(np.int8))
 
 
 def stage_stepv(cS, tables):

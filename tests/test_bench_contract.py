@@ -1,6 +1,6 @@
 """The JSON line `bench.py` prints is the driver's contract (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better /
-scaling / vs_baseline / dtype / data / config.workload + roofline + cpu_baseline).  Checked here on the newest committed line of a real run
-(profiles/*default_bench*.json, written on the GPU box by `python bench.py`), and on the pure helpers of bench.py - no GPU needed."""
+scaling / vs_baseline / dtype / data / config.workload; with --full also roofline + cpu_baseline).  Checked here on the newest committed line of a real run
+(profiles/*default_bench*.json, written on the GPU box by `python bench.py --full`, the default line before --full existed), and on the pure helpers of bench.py - no GPU needed."""
 import glob
 import importlib.util
 import json

@@ -18,7 +18,7 @@ def _bench(*extra, gpus=2, steps=2):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo", "--steps", str(steps), "--warmup", "1",
-           "--no-cpu", "--no-secondary", "--no-alt"] + list(extra)
+           "--full", "--no-cpu", "--no-secondary", "--no-alt"] + list(extra)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -67,3 +67,33 @@ def test_bench_eight_ranks_xe_step_bf16_wire():
     line = _bench("--workload", "xe", "--dtype", "bf16", gpus=8, steps=1)
     assert line["n_gpus"] == 8 and line["config"]["rccl_world_size_observed"] == 8
     assert line["unit"] == "samples/s" and line["value"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """a plain run times only the headline (no roofline, no CPU baseline, no side legs); --dump-outputs writes the last timed call's
+    ids and log-probs, and the same arguments give the same outputs"""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    got = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "tokens/s" and line["dtype"] == "f16x2"
+        assert abs(line["value"] - 100 * 20 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        for k in ("roofline", "cpu_baseline", "secondary", "alt_modes", "alt_workloads"):
+            assert k not in line, k
+        arrays = {n: np.load(d / (n + ".npy")) for n in ("words", "gates", "logp_words", "logp_gates")}
+        assert sorted(f.name for f in d.iterdir()) == sorted(n + ".npy" for n in arrays)
+        for a in arrays.values():
+            assert a.shape == (100, 20) and a.dtype == np.float32
+        assert ((arrays["words"] >= 0) & (arrays["words"] < 10000)).all() and np.isin(arrays["gates"], (0, 1)).all()
+        got.append(arrays)
+    for n in got[0]:
+        np.testing.assert_array_equal(got[0][n], got[1][n])

@@ -1,7 +1,4 @@
-"""Pin the CPU oracle to the golden vectors captured from the real reference (tests/golden/make_golden.py),
-and - when /root/reference is mounted (build container only) - to the reference run live."""
-import os
-
+"""Pin the CPU oracle to the golden vectors captured from the real reference (tests/golden/make_golden.py)."""
 import numpy as np
 import pytest
 import torch
@@ -89,8 +86,10 @@ def test_single_step_vector():
     np.testing.assert_array_equal(s[4].numpy(), g["k"])
     np.testing.assert_allclose(lw.numpy(), g["logp_w"], atol=1e-5, rtol=0)
     np.testing.assert_allclose(lg.numpy(), g["logp_g"], atol=1e-5, rtol=0)
+    # 2e-6, not 1e-6: the reference itself, re-run on another x86 host, lands 1.3e-6 from its recorded c1 (fp32 sums over
+    # K = 512 re-associated by the host's BLAS); on one host the oracle and the reference agree to 7e-7
     for got, key in zip(s[:4], ("h1", "c1", "h2", "c2")):
-        np.testing.assert_allclose(got.numpy(), g[key], atol=1e-6, rtol=0)
+        np.testing.assert_allclose(got.numpy(), g[key], atol=2e-6, rtol=0)
 
 
 def test_full_size_greedy_beam_sample_subset():
@@ -199,39 +198,19 @@ def test_round5_fixtures_slices():
     assert g["eval_noverb_agree64"].all() and g["xe_losses"][0] > 0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference not mounted (GPU box)")
-def test_live_against_reference(tmp_path, monkeypatch):
-    import json
-    import subprocess
-    import sys
-    # run in a subprocess: the reference's package is also called `models`
-    code = r'''
-import sys, json, os
-sys.path.insert(0, "/root/reference"); sys.path.append(%r); sys.path.insert(0, %r)   # the reference's `models` must win
-import torch, numpy as np
-from vsrcap import synth
-import vsr_oracle as vo
-from models import ControllableCaptioningModel
-c = dict(V=61, B=3, R0=6, R=5, D=128, L=4, T=7, E=32, H=48, A=16)
-w = synth.make_weights(c["V"], c["D"], c["E"], c["H"], c["A"], seed=4)
-m = ControllableCaptioningModel(c["T"], c["V"], 2, det_feat_size=c["D"], input_encoding_size=c["E"], rnn_size=c["H"], att_size=c["A"]).eval()
-m.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()})
-det = torch.from_numpy(synth.make_detections(c["B"], c["R0"], c["D"], seed=2)); ctrl = torch.from_numpy(synth.make_ctrl(c["B"], c["L"], c["R"], c["D"], seed=2))
-for aw in (True, False):
-    o = vo.Oracle(w, c["T"], 2, as_written=aw)
-    with torch.no_grad():
-        a = m.test(det, ctrl); b = o.test(det, ctrl)
-        assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
-        (a, _) = m.beam_search((det, ctrl), [3, -1], 4, 2); (b, _) = o.beam_search(det, ctrl, [3, -1], 4, 2)
-        assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
-print("LIVE-OK")
-''' % (os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vsr-guided-cic_amd"),
-       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
-    (tmp_path / "datasets" / "coco").mkdir(parents=True)
-    (tmp_path / "datasets" / "coco" / "verb_2_vob_all_refine.json").write_text("{}")
-    (tmp_path / "datasets" / "coco" / "verb_2_vob.json").write_text("{}")
-    r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
-    assert "LIVE-OK" in r.stdout, r.stderr[-2000:]
+def test_live_against_reference():
+    """g15_live_small: greedy and beam-4 / out_size 2 ids of the reference at a tiny odd-sized config, both oracle flavours"""
+    meta, g = load_golden("g15_live_small")
+    for aw in (True, False):
+        o, _ = _oracle(meta, as_written=aw)
+        det, ctrl = helpers.decode_inputs(meta["cfg"], meta["seed"])
+        with torch.no_grad():
+            gw, gg = o.test(det, ctrl)
+            (bw, bg), _ = o.beam_search(det, ctrl, meta["eos"], meta["beam"], meta["out_size"])
+        np.testing.assert_array_equal(gw.numpy(), g["greedy_words"])
+        np.testing.assert_array_equal(gg.numpy(), g["greedy_gates"])
+        np.testing.assert_array_equal(bw.numpy(), g["beam_words"])
+        np.testing.assert_array_equal(bg.numpy(), g["beam_gates"])
 
 
 def test_oracle_training_trajectory_small():

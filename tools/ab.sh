@@ -17,7 +17,7 @@ if [ -n "$GATE" ]; then
 fi
 for rep in $(seq 1 $REP); do for cfg in "$@"; do for w in $WL; do
   case $w in b13) args="--workload beam5 --batch 13";; b13nb) args="--workload beam5 --batch 13 --rows-bound";; beam5nb) args="--workload beam5 --rows-bound";; greedynb) args="--workload greedy --rows-bound";; *) args="--workload $w";; esac
-  env $(echo "$cfg" | tr ';' ' ') timeout 400 python bench.py $args --steps $STEPS --warmup 5 --no-cpu --no-secondary --no-alt 2>$OUT/last.err | tail -1 | python3 -c "
+  env $(echo "$cfg" | tr ';' ' ') timeout 400 python bench.py $args --steps $STEPS --warmup 5 --full --no-cpu --no-secondary --no-alt 2>$OUT/last.err | tail -1 | python3 -c "
 import sys, json
 try:
     d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}

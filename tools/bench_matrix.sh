@@ -7,7 +7,7 @@ for cfg in "$@"; do
   i=$((i+1))
   for w in beam5 greedy xe "beam5 --batch 13"; do
     name=$(echo "$w" | tr -d ' -')
-    env $(echo $cfg | tr ';' ' ') timeout 300 python bench.py --workload $w --no-cpu --no-secondary --no-alt --steps 10 > $OUT/c${i}_$name.json 2> $OUT/c${i}_$name.err
+    env $(echo $cfg | tr ';' ' ') timeout 300 python bench.py --workload $w --full --no-cpu --no-secondary --no-alt --steps 10 > $OUT/c${i}_$name.json 2> $OUT/c${i}_$name.err
     python3 -c "
 import json,sys
 try:

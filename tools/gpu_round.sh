@@ -12,15 +12,15 @@ smoke)
 tests)
   timeout 1500 python -m pytest tests -m gpu -q -rA --durations=15 > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log; tail -40 $OUT/pytest.log ;;
 bench)
-  timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; cat $OUT/bench_default.json ;;
+  timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; cat $OUT/bench_default.json ;;
 greedy)
-  timeout 300 python bench.py --workload greedy --no-cpu > $OUT/bench_greedy.json 2> $OUT/bench_greedy.err; cat $OUT/bench_greedy.json ;;
+  timeout 300 python bench.py --workload greedy --full --no-cpu > $OUT/bench_greedy.json 2> $OUT/bench_greedy.err; cat $OUT/bench_greedy.json ;;
 xe)
-  timeout 300 python bench.py --workload xe --no-cpu > $OUT/bench_xe.json 2> $OUT/bench_xe.err; cat $OUT/bench_xe.json ;;
+  timeout 300 python bench.py --workload xe --full --no-cpu > $OUT/bench_xe.json 2> $OUT/bench_xe.err; cat $OUT/bench_xe.json ;;
 scst)
-  timeout 300 python bench.py --workload scst --no-cpu > $OUT/bench_scst.json 2> $OUT/bench_scst.err; cat $OUT/bench_scst.json ;;
+  timeout 300 python bench.py --workload scst --full --no-cpu > $OUT/bench_scst.json 2> $OUT/bench_scst.err; cat $OUT/bench_scst.json ;;
 bf16)
-  for w in beam5 greedy xe; do timeout 300 python bench.py --workload $w --dtype bf16 --no-cpu --no-secondary > $OUT/bench_${w}_bf16.json 2> $OUT/bench_${w}_bf16.err; cat $OUT/bench_${w}_bf16.json; done
+  for w in beam5 greedy xe; do timeout 300 python bench.py --workload $w --dtype bf16 --full --no-cpu --no-secondary > $OUT/bench_${w}_bf16.json 2> $OUT/bench_${w}_bf16.err; cat $OUT/bench_${w}_bf16.json; done
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/stats_beam5_bf16 -- python3 $GRAFT_REPO_ROOT/bench.py --dtype bf16 --steps 10 --warmup 3 --no-cpu --no-secondary --no-alt > $GRAFT_REPO_ROOT/$OUT/stats_beam5_bf16.log 2>&1)
   for f in $(find $OUT/stats_beam5_bf16 -name "*kernel_stats.csv"); do head -12 $f; done
   for c in FETCH_SIZE WRITE_SIZE; do
@@ -29,11 +29,11 @@ bf16)
   python tools/hbm_traffic.py $OUT/pmc16_FETCH_SIZE $OUT/pmc16_WRITE_SIZE $OUT/gemm_bf16_hbm_traffic.json gemm_nt_bf16w
   find $OUT -name "*kernel_trace.csv" -size +20M -delete ;;
 f32)
-  for w in beam5 greedy xe; do timeout 300 python bench.py --workload $w --dtype f32 --no-cpu --no-secondary --no-alt > $OUT/bench_${w}_f32.json 2> $OUT/bench_${w}_f32.err; cat $OUT/bench_${w}_f32.json; done ;;
+  for w in beam5 greedy xe; do timeout 300 python bench.py --workload $w --dtype f32 --full --no-cpu --no-secondary --no-alt > $OUT/bench_${w}_f32.json 2> $OUT/bench_${w}_f32.err; cat $OUT/bench_${w}_f32.json; done ;;
 idx)
-  for w in beam5idx xeidx; do timeout 300 python bench.py --workload $w --no-cpu --no-secondary --no-alt > $OUT/bench_${w}.json 2> $OUT/bench_${w}.err; cat $OUT/bench_${w}.json; done ;;
+  for w in beam5idx xeidx; do timeout 300 python bench.py --workload $w --full --no-cpu --no-secondary --no-alt > $OUT/bench_${w}.json 2> $OUT/bench_${w}.err; cat $OUT/bench_${w}.json; done ;;
 b13)
-  timeout 300 python bench.py --batch 13 --no-cpu --no-secondary --no-alt > $OUT/bench_beam5_batch13.json 2> $OUT/bench_beam5_batch13.err; cat $OUT/bench_beam5_batch13.json
+  timeout 300 python bench.py --batch 13 --full --no-cpu --no-secondary --no-alt > $OUT/bench_beam5_batch13.json 2> $OUT/bench_beam5_batch13.err; cat $OUT/bench_beam5_batch13.json
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/stats_batch13 -- python3 $GRAFT_REPO_ROOT/bench.py --batch 13 --steps 20 --warmup 3 --no-cpu --no-secondary --no-alt > $GRAFT_REPO_ROOT/$OUT/stats_batch13.log 2>&1)
   find $OUT -name "*kernel_trace.csv" -size +20M -delete ;;
 stats)
