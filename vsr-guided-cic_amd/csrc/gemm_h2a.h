@@ -4,17 +4,25 @@
 // landed] [barrier].  The A images carry their CLASS exponent (the producing kernel scales by it), so the segments of one problem
 // multiply in different units: a mover leaves the product exponent of every k-tile beside its stage and the multipliers move their
 // accumulators to the new unit at a segment boundary (a power of two: exact).
+// MF: the multipliers' MFMA shape.  16 (default): v_mfma_f32_16x16x32_f16, one instruction per 16 x 16 block and term covers the whole
+// 32-k tile; the chip holds a higher clock on this shape than on 32x32x16 at the same cycles per FLOP (it runs at its power limit here).
+// 32: v_mfma_f32_32x32x16_f16, two k halves per k-tile (VSR_H2_MFMA=32, gemm_bench H2_MFMA=32).  Same wave tile, ring, image and plans.
 #pragma once
 #include "gemm_h2.h"
 
 namespace vsr {
 
-template <int TM, int TN, int NW = 3>
+template <int TM, int TN, int NW = 3, int MF = 16>
 __global__ __launch_bounds__(H2_THREADS)
 void gemm_nt_h2a_kernel(const GemmArgs args) {
     constexpr int WM = 4 / TM, WN = 8 / WM;
     constexpr int BM = 128, BN = 32 * TN * WN, BK = H2_BK;
     static_assert(32 * TM * WM == BM, "tile shape");
+    static_assert(MF == 16 || MF == 32, "MFMA shape");
+    // accumulator blocks of MF x MF: AM x AN of them per wave, AE floats each; C layout of a block: lane l holds column l & (MF - 1)
+    // and, for element e, row 4 (l >> 4) + e (16 x 16) / (e & 3) + 8 (e >> 2) + 4 (l >> 5) (32 x 32)
+    constexpr int AM = TM * 32 / MF, AN = TN * 32 / MF, AE = MF * MF / 64;
+    using acc_t = float __attribute__((ext_vector_type(AE)));
     constexpr int WSTAGE = BN * 64;                       // fp16 elements of the W rows of a stage (BN rows x 128 bytes)
     constexpr int ASTAGE = BM * 64;                       // ... of its A rows
     constexpr int STG = WSTAGE + ASTAGE;
@@ -33,7 +41,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const bool mover = wave >= 8;
-    const int r = lane & 31, hh = lane >> 5;
+    const int r = lane & (MF - 1);                        // the lane's operand row in an MF-row block
 
     int cur_s = 0;                                         // multipliers: exponent of the products accumulated so far (2^cur_s units)
     int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;
@@ -67,7 +75,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
     // stage exactly).  Every request in flight is waited for first: the stage may be the target of nothing then, and stores share vmcnt.
     constexpr int ST_LD = BN;
     static_assert(32 * ST_LD * 4 <= WSTAGE * 2, "staging band must fit one W stage");
-    f32x16 acc[TM][TN];
+    acc_t acc[AM][AN];
     auto flush = [&](auto MULT, float* stage, bool range_done) __attribute__((always_inline)) {
         const GemmProb& P = args.p[c_prob];
         const float unscale = h2_pow2(-cur_s);
@@ -75,9 +83,20 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
         float* C = P.C + (long long)c_piece * P.slab_stride;
         const int extra = c_last ? P.nslab - 1 - c_piece : 0;
         const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
+        // (the flush's indices start from an opaque copy of the thread id: computed here, they are not hoisted into the k loop's live
+        // range - at 4 waves per SIMD the 16 x 16 loop has no register to spare for them)
+        int ft = tid;
+        asm volatile("" : "+v"(ft));
+        const int fc = ft & (MF - 1);                      // the lane's accumulator column in a block ...
+        auto c_row = [&](int e) __attribute__((always_inline)) {      // ... and its row of element e
+            return MF == 16 ? 4 * ((ft & 63) >> 4) + e : (e & 3) + 8 * (e >> 2) + 4 * ((ft & 63) >> 5);
+        };
+        // 16 x 16: the staged rows with bit 2 set hold their columns XOR 16 - the two row quads a 32-lane group of ds_write_b32 stores
+        // to then fall into different banks (row strides are multiples of 32 banks); every reader applies the same swizzle
+        auto swz = [](int row) __attribute__((always_inline)) { return MF == 16 ? (row & 4) << 2 : 0; };
         constexpr int TPR = BN / 4;
         constexpr int RPP = H2_THREADS / TPR;
-        const int c4 = (tid % TPR) * 4;
+        const int c4 = (ft % TPR) * 4;
         const int n = n0 + c4;
         const int wm = wave / WN, wn = wave % WN;
         wait_loads<0>();
@@ -91,20 +110,20 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
             float* const all = reinterpret_cast<float*>(sW);
             if constexpr (decltype(MULT)::value) {
 #pragma unroll
-                for (int ti = 0; ti < TM; ++ti)
+                for (int ti = 0; ti < AM; ++ti)
 #pragma unroll
-                    for (int tj = 0; tj < TN; ++tj)
+                    for (int tj = 0; tj < AN; ++tj)
 #pragma unroll
-                        for (int e = 0; e < 16; ++e)
-                            all[(32 * (wm * TM + ti) + (e & 3) + 8 * (e >> 2) + 4 * hh) * ST_LD + wn * (32 * TN) + tj * 32 + r] = acc[ti][tj][e] * unscale;
+                        for (int e = 0; e < AE; ++e)
+                            all[(32 * TM * wm + MF * ti + c_row(e)) * ST_LD + ((wn * (32 * TN) + tj * MF + fc) ^ swz(c_row(e)))] = acc[ti][tj][e] * unscale;
             }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < BM / RPP; ++i) {
-                const int sr = tid / TPR + RPP * i;
+                const int sr = ft / TPR + RPP * i;
                 const int m = m0 + sr;
                 if (m < P.M && n < P.N) {
-                    const float4 v = *reinterpret_cast<const float4*>(all + sr * ST_LD + c4);
+                    const float4 v = *reinterpret_cast<const float4*>(all + sr * ST_LD + (c4 ^ swz(sr)));
                     float* dst = C + (long long)m * P.ldc + n;
                     if (vec_ok && n + 3 < P.N) {
                         *reinterpret_cast<float4*>(dst) = v;
@@ -129,22 +148,22 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
             if (m0 + band * 32 >= P.M) break;
             if constexpr (decltype(MULT)::value) {
 #pragma unroll
-                for (int ti = 0; ti < TM; ++ti)
-                    if (wm * TM + ti == band) {
+                for (int ti = 0; ti < AM; ++ti)                   // (16 x 16: a band is two blocks)
+                    if ((32 * TM * wm + MF * ti) / 32 == band) {
 #pragma unroll
-                        for (int tj = 0; tj < TN; ++tj)
+                        for (int tj = 0; tj < AN; ++tj)
 #pragma unroll
-                            for (int e = 0; e < 16; ++e)
-                                stage[((e & 3) + 8 * (e >> 2) + 4 * hh) * ST_LD + wn * (32 * TN) + tj * 32 + r] = acc[ti][tj][e] * unscale;
+                            for (int e = 0; e < AE; ++e)
+                                stage[((MF * ti) % 32 + c_row(e)) * ST_LD + ((wn * (32 * TN) + tj * MF + fc) ^ swz(c_row(e)))] = acc[ti][tj][e] * unscale;
                     }
             }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < (32 + RPP - 1) / RPP; ++i) {
-                const int sr = tid / TPR + RPP * i;
+                const int sr = ft / TPR + RPP * i;
                 const int m = m0 + band * 32 + sr;
                 if (sr < 32 && m < P.M && n < P.N) {
-                    const float4 v = *reinterpret_cast<const float4*>(stage + sr * ST_LD + c4);
+                    const float4 v = *reinterpret_cast<const float4*>(stage + sr * ST_LD + (c4 ^ swz(sr)));
                     float* dst = C + (long long)m * P.ldc + n;
                     if (vec_ok && n + 3 < P.N) {
                         *reinterpret_cast<float4*>(dst) = v;
@@ -275,14 +294,14 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
     } else {
         // ================================================================================================ multipliers
         const int wm = wave / WN, wn = wave % WN;
-        const int wsw = (r >> 1) & 7;                      // both kinds of rows: ((32 t + r) >> 1) & 7
+        const int wsw = (r >> 1) & 7;                      // both kinds of rows: ((MF t + r) >> 1) & 7
         auto zero_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < AM; ++i)
 #pragma unroll
-                for (int jj = 0; jj < TN; ++jj)
+                for (int jj = 0; jj < AN; ++jj)
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
+                    for (int e = 0; e < AE; ++e) acc[i][jj][e] = 0.f;
         };
         zero_acc();
         bool first = true;
@@ -298,37 +317,71 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
                     dlt = dlt < -126 ? -126 : (dlt > 127 ? 127 : dlt);
                     const float f = h2_pow2(dlt);
 #pragma unroll
-                    for (int i = 0; i < TM; ++i)
+                    for (int i = 0; i < AM; ++i)
 #pragma unroll
-                        for (int jj = 0; jj < TN; ++jj)
+                        for (int jj = 0; jj < AN; ++jj)
 #pragma unroll
-                            for (int e = 0; e < 16; ++e) acc[i][jj][e] *= f;
+                            for (int e = 0; e < AE; ++e) acc[i][jj][e] *= f;
                 }
                 cur_s = sj;
             }
             first = false;
+            // per accumulator the terms go lo·hi, hi·lo, hi·hi in either shape
+            if constexpr (MF == 16) {
+                // lane l reads row l & 15 of a 16-row block: hi chunk l >> 4, lo chunk 4 + (l >> 4) - all 32 k's of the k-tile.  The A
+                // operands of the wave's AM row blocks stay in registers, the B pairs of its AN column blocks come one at a time (the next
+                // pair is read during the current block's 3 AM MFMAs; a scheduling barrier keeps the compiler from hoisting every B read,
+                // which spills at the 128-register budget of 4 waves per SIMD).  Consecutive MFMAs hit different accumulators.
+                const int q = lane >> 4;
+                const int wh = 8 * (q ^ wsw), wl = 8 * ((4 + q) ^ wsw);
+                f16x8_t ah[AM], al[AM], bh, bl;
+                bh = *reinterpret_cast<const f16x8_t*>(b_row + wh);
 #pragma unroll
-            for (int kk = 0; kk < BK / 16; ++kk) {
-                const int wh = 8 * ((2 * kk + hh) ^ wsw), wl = 8 * ((4 + 2 * kk + hh) ^ wsw);
-                f16x8_t ah[TM], al[TM], bh[TN], bl[TN];
+                for (int i = 0; i < AM; ++i) al[i] = *reinterpret_cast<const f16x8_t*>(a_row + i * 16 * 64 + wl);
+                bl = *reinterpret_cast<const f16x8_t*>(b_row + wl);
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    ah[i] = *reinterpret_cast<const f16x8_t*>(a_row + i * 32 * 64 + wh);
-                    al[i] = *reinterpret_cast<const f16x8_t*>(a_row + i * 32 * 64 + wl);
+                for (int i = 0; i < AM; ++i) ah[i] = *reinterpret_cast<const f16x8_t*>(a_row + i * 16 * 64 + wh);
+#pragma unroll
+                for (int jj = 0; jj < AN; ++jj) {
+                    f16x8_t nbh = bh, nbl = bl;
+                    if (jj + 1 < AN) {
+                        nbh = *reinterpret_cast<const f16x8_t*>(b_row + (jj + 1) * 16 * 64 + wh);
+                        nbl = *reinterpret_cast<const f16x8_t*>(b_row + (jj + 1) * 16 * 64 + wl);
+                    }
+#pragma unroll
+                    for (int i = 0; i < AM; ++i) acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh, acc[i][jj], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < AM; ++i) acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl, acc[i][jj], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < AM; ++i) acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh, acc[i][jj], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    bh = nbh; bl = nbl;
                 }
+            } else {
+                const int hh = lane >> 5;
 #pragma unroll
-                for (int jj = 0; jj < TN; ++jj) {
-                    bh[jj] = *reinterpret_cast<const f16x8_t*>(b_row + jj * 32 * 64 + wh);
-                    bl[jj] = *reinterpret_cast<const f16x8_t*>(b_row + jj * 32 * 64 + wl);
-                }
+                for (int kk = 0; kk < BK / 16; ++kk) {
+                    const int wh = 8 * ((2 * kk + hh) ^ wsw), wl = 8 * ((4 + 2 * kk + hh) ^ wsw);
+                    f16x8_t ah[TM], al[TM], bh[TN], bl[TN];
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+                        ah[i] = *reinterpret_cast<const f16x8_t*>(a_row + i * 32 * 64 + wh);
+                        al[i] = *reinterpret_cast<const f16x8_t*>(a_row + i * 32 * 64 + wl);
+                    }
+#pragma unroll
+                    for (int jj = 0; jj < TN; ++jj) {
+                        bh[jj] = *reinterpret_cast<const f16x8_t*>(b_row + jj * 32 * 64 + wh);
+                        bl[jj] = *reinterpret_cast<const f16x8_t*>(b_row + jj * 32 * 64 + wl);
+                    }
 #define H2A_TERM(X, Y)                                                                                  \
     _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                     \
         _Pragma("unroll") for (int jj = 0; jj < TN; ++jj)                                              \
             acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(X[i], Y[jj], acc[i][jj], 0, 0, 0);
-                H2A_TERM(al, bh)
-                H2A_TERM(ah, bl)
-                H2A_TERM(ah, bh)
+                    H2A_TERM(al, bh)
+                    H2A_TERM(ah, bl)
+                    H2A_TERM(ah, bh)
 #undef H2A_TERM
+                }
             }
             if (end_of_ktile(std::true_type{})) { zero_acc(); first = true; }
         }

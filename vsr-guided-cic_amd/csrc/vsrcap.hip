@@ -133,6 +133,7 @@ struct vsr_handle {
     // and launches whose A operands all have one take the all-DMA kernel (gemm_h2a.h); VSR_H2_AIMG=0: in-kernel split of fp32 A only
     double aligned_eff_min = 0.75;    // wide launches: k-aligned pieces when they keep at least this share of the CUs busy, stream-K ranges otherwise (VSR_ALIGNED_EFF, percent)
     bool h2_aimg = true;
+    int h2_mfma = 16;                 // MFMA shape of the all-DMA kernel's multipliers: 16 (v_mfma_f32_16x16x32_f16) or 32 (32x32x16; VSR_H2_MFMA=32)
     // the selection of step t inside the LSTM1 kernel of step t + 1 (kernels.h: k_select_lstm1, k_select_simple_lstm1); VSR_FUSE_SELECT=0: a launch of its own
     int fuse_select = 3;              // bit 0: greedy / sampling / replay (k_select_simple_lstm1), bit 1: beam search (k_select_lstm1)
     bool b16_dma = true;              // bf16 mode: launches whose A operands all have bf16 images take the all-DMA kernel (VSR_B16_DMA=0: register-staged)
@@ -536,6 +537,8 @@ int GemmBuilder::launch(hipStream_t s, vsr_handle* h) {
 #undef H2S_CASE
     } else if (big == 38 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_b16a_kernel<2, 2>), grid, block, 0, s, a);
     else if (big == 38) hipLaunchKernelGGL((gemm_nt_b16a_kernel<2, 1>), grid, block, 0, s, a);
+    else if (big == 37 && h->h2_mfma == 32 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 2, 3, 32>), grid, block, 0, s, a);
+    else if (big == 37 && h->h2_mfma == 32) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1, 3, 32>), grid, block, 0, s, a);
     else if (big == 37 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 2>), grid, block, 0, s, a);
     else if (big == 37) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1>), grid, block, 0, s, a);       // (a ring of four stages fits this tile and changes nothing: tools/gemm_bench H2_NW=4, profiles/r05_e_*)
     else if (big == 35 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 2>), grid, block, 0, s, a);
@@ -621,6 +624,7 @@ extern "C" int vsr_create(const vsr_dims* dims, vsr_handle** out) {
     if (const char* e = getenv("VSR_H2_ALIGNED_MIN")) h->h2_aligned_min = std::max(1, atoi(e));
     if (const char* e = getenv("VSR_H2_ALIGNED_MIN_SMALL")) h->h2_aligned_min_small = std::max(1, atoi(e));
     if (const char* e = getenv("VSR_H2_AIMG")) h->h2_aimg = atoi(e) != 0;
+    if (const char* e = getenv("VSR_H2_MFMA")) h->h2_mfma = atoi(e) == 32 ? 32 : 16;
     if (const char* e = getenv("VSR_FUSE_SELECT")) h->fuse_select = atoi(e);
     if (const char* e = getenv("VSR_B16_DMA")) h->b16_dma = atoi(e) != 0;
     if (const char* e = getenv("VSR_ALIGNED_EFF")) h->aligned_eff_min = atoi(e) / 100.0;
