@@ -13,13 +13,7 @@
 // GEMM_STAMP / GEMM_PHASES / X3_EXP / B16_ABLATE ...) that produced the ablation numbers of DESIGN.md section 4 are in the history:
 // `git show 4789752:tools/ablate/gemm_f32.h` etc.  tools/x3_ablate.py patches scratch copies of the shipped headers instead.
 #define GEMM_ABLATE 0
-#include "../vsr-guided-cic_amd/csrc/gemm_f32.h"
-#include "../vsr-guided-cic_amd/csrc/gemm_bf16.h"
-#include "../vsr-guided-cic_amd/csrc/gemm_x3.h"
-#include "../vsr-guided-cic_amd/csrc/gemm_x3s.h"
-#include "../vsr-guided-cic_amd/csrc/gemm_h2.h"
-#include "../vsr-guided-cic_amd/csrc/gemm_h2a.h"
-#include "../vsr-guided-cic_amd/csrc/gemm_b16a.h"
+#include "../vsr-guided-cic_amd/csrc/gemm_dispatch.h"
 
 using namespace vsr;
 
@@ -154,70 +148,45 @@ struct Builder {
         return ns;
     }
     double flops() const { return gemm_flops(a); }
+    // every instantiation the library ships goes through its dispatcher (gemm_dispatch.h); launched here: the experiment-only ones
     void launch(hipStream_t st) {
-        dim3 g(gemm_grid(a)), b(256);
-#define R16(TM_) else if (tm == 1600 + TM_ && tn == 2) hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<TM_, 2>), g, dim3(512), 0, st, a); \
-                 else if (tm == 1600 + TM_ && tn == 4) hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<TM_, 4>), g, dim3(512), 0, st, a);
+        dim3 g(gemm_grid(a));
+#define GO(THREADS_, ...) hipLaunchKernelGGL((__VA_ARGS__), g, dim3(THREADS_), 0, st, a)
+        int maxM = 0; for (int i = 0; i < a.nprob; ++i) maxM = a.p[i].M > maxM ? a.p[i].M : maxM;
+        const int mt = tn > 1 && tn <= 8 ? tn : (maxM + 15) / 16;                 // streaming kernels: 16-row tiles of A
+        const int wtn = tn == 21 ? 2 : 4;                                         // 128-row MFMA kernels: 128 x 128 or 128 x 256 tile
+        const int nw = getenv("H2_NW") ? atoi(getenv("H2_NW")) : 3;               // f16x2 wide kernels: ring stages (the 128 x 256 tile of the all-DMA kernel has room for three)
+        const bool r16 = tm > 1600 && tm <= 1608;
+        GemmRoute r;                      // {kernel, tm, tn, mt, mf, a16}
         if (tm == 3400) {
-            int maxM = 0; for (int i = 0; i < a.nprob; ++i) maxM = a.p[i].M > maxM ? a.p[i].M : maxM;
-            const int mt = tn > 1 && tn <= 8 ? tn : (maxM + 15) / 16;
-            const bool ns1 = getenv("X3S_NS") && atoi(getenv("X3S_NS")) == 1;
-            switch (mt) {
-                case 1: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<1, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<1, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                case 2: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<2, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<2, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                case 3: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<3, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<3, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                case 4: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<4, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<4, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                case 5: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<5, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<5, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                case 6: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<6, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<6, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                case 7: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<7, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<7, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-                default: if (ns1) hipLaunchKernelGGL((gemm_nt_x3s_kernel<8, 1>), g, dim3(X3S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_x3s_kernel<8, 2>), g, dim3(X3S_THREADS), 0, st, a); break;
-            }
+            if (getenv("X3S_NS") && atoi(getenv("X3S_NS")) == 1) r = {GemmKernel::X3S, 0, 1, mt};
+            else return with_const_1to8(mt, [&](auto MT) { GO(X3S_THREADS, gemm_nt_x3s_kernel<decltype(MT)::value, 2>); });
         }
-        else if (tm == 5300) {
-            int maxM = 0; for (int i = 0; i < a.nprob; ++i) maxM = a.p[i].M > maxM ? a.p[i].M : maxM;
-            const int mt = tn > 1 && tn <= 8 ? tn : (maxM + 15) / 16;
-            const bool ns2 = getenv("H2S_NS") && atoi(getenv("H2S_NS")) == 2;
-#define H2S(MT_) case MT_: if (ns2) hipLaunchKernelGGL((gemm_nt_h2s_kernel<MT_, 2>), g, dim3(H2S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_h2s_kernel<MT_, 1>), g, dim3(H2S_THREADS), 0, st, a); break;
-            switch (mt) { H2S(1) H2S(2) H2S(3) H2S(4) H2S(5) H2S(6) H2S(7) default: if (ns2) hipLaunchKernelGGL((gemm_nt_h2s_kernel<8, 2>), g, dim3(H2S_THREADS), 0, st, a); else hipLaunchKernelGGL((gemm_nt_h2s_kernel<8, 1>), g, dim3(H2S_THREADS), 0, st, a); break; }
-#undef H2S
-        }
+        else if (tm == 5300) r = {GemmKernel::H2S, 0, getenv("H2S_NS") && atoi(getenv("H2S_NS")) == 2 ? 2 : 1, mt};
         else if (tm == 5400) {
-            const int nw = getenv("H2_NW") ? atoi(getenv("H2_NW")) : 3;         // ring stages of the 128 x 128 tile (the 128 x 256 tile has room for three)
             const bool mf32 = getenv("H2_MFMA") && atoi(getenv("H2_MFMA")) == 32;  // H2_MFMA=32: the 32x32x16 multipliers (VSR_H2_MFMA=32)
-            if (mf32) {
-                if (tn == 21 && nw == 4) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1, 4, 32>), g, dim3(H2_THREADS), 0, st, a);
-                else if (tn == 21) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1, 3, 32>), g, dim3(H2_THREADS), 0, st, a);
-                else hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 2, 3, 32>), g, dim3(H2_THREADS), 0, st, a);
-            }
-            else if (tn == 21 && nw == 4) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1, 4>), g, dim3(H2_THREADS), 0, st, a);
-            else if (tn == 21) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1, 3>), g, dim3(H2_THREADS), 0, st, a);
-            else hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 2, 3>), g, dim3(H2_THREADS), 0, st, a);
+            if (tn == 21 && nw == 4) { if (mf32) GO(H2_THREADS, gemm_nt_h2a_kernel<2, 1, 4, 32>); else GO(H2_THREADS, gemm_nt_h2a_kernel<2, 1, 4>); return; }
+            r = {GemmKernel::H2A, 2, wtn, 0, mf32 ? 32 : 16};
         }
         else if (tm == 5200) {
-            const int nw = getenv("H2_NW") ? atoi(getenv("H2_NW")) : 3;
-            if (tn == 21 && nw == 4) hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 1, 4>), g, dim3(H2_THREADS), 0, st, a);
-            else if (tn == 21) hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 1, 3>), g, dim3(H2_THREADS), 0, st, a);
-            else if (nw == 4) hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 2, 4>), g, dim3(H2_THREADS), 0, st, a);
-            else hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 2, 3>), g, dim3(H2_THREADS), 0, st, a);
+            if (nw == 4) { if (tn == 21) GO(H2_THREADS, gemm_nt_h2_kernel<2, 1, 4>); else GO(H2_THREADS, gemm_nt_h2_kernel<2, 2, 4>); return; }
+            r = {GemmKernel::H2, 2, wtn};
         }
-        else if (is_x3(tm) && tn == 21) hipLaunchKernelGGL((gemm_nt_x3_kernel<2, 1>), g, dim3(X3_THREADS), 0, st, a);
-        else if (is_x3(tm)) hipLaunchKernelGGL((gemm_nt_x3_kernel<2, 2>), g, dim3(X3_THREADS), 0, st, a);
-        else if (tm == 1666 && tn == 21) hipLaunchKernelGGL((gemm_nt_b16a_kernel<2, 1>), g, dim3(B16_THREADS), 0, st, a);
-        else if (tm == 1666) hipLaunchKernelGGL((gemm_nt_b16a_kernel<2, 2>), g, dim3(B16_THREADS), 0, st, a);
-        else if (tm == 1664 && tn == 21) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<false, 1>), g, dim3(B16_THREADS), 0, st, a);
-        else if (tm == 1665 && tn == 21) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<true, 1>), g, dim3(B16_THREADS), 0, st, a);
-        else if (tm == 1664) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<false, 2>), g, dim3(B16_THREADS), 0, st, a);
-        else if (tm == 1665) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<true, 2>), g, dim3(B16_THREADS), 0, st, a);
-        else if (tm == 2 && tn == 2) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 2>), g, b, 0, st, a);
-        R16(1) R16(2) R16(3) R16(4) R16(5) R16(6) R16(7) R16(8)
-        else if (tm == 112) hipLaunchKernelGGL((gemm_nt_f32_kernel<1, 2, 2, 2>), g, b, 0, st, a);
-        else if (tm == 2242) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 2, 4, 2>), g, dim3(512), 0, st, a);
-        else if (tm == 2142) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 1, 4, 2>), g, dim3(512), 0, st, a);
-        else if (tm == 2224) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 2, 2, 4>), g, dim3(512), 0, st, a);
-        else if (tm == 121) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 1, 2, 2>), g, b, 0, st, a);
-        else if (tm == 12) hipLaunchKernelGGL((gemm_nt_f32_kernel<1, 2, 4, 2>), g, dim3(512), 0, st, a);
-        else if (tm == 21) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 1, 2, 4>), g, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((gemm_nt_f32_kernel<1, 1>), g, b, 0, st, a);
+        else if (is_x3(tm)) r = {GemmKernel::X3, 2, wtn};
+        else if (tm == 1666) r = {GemmKernel::B16A, 2, wtn};
+        else if (tm == 1664 || tm == 1665) r = {GemmKernel::BF16W, 2, wtn, 0, 16, tm == 1665};
+        else if (tm == 2 && tn == 2) r = {GemmKernel::F32, 2, 2};
+        else if (r16 && tn == 2) r = {GemmKernel::F32_R16, 0, 2, tm - 1600};
+        else if (r16 && tn == 4) return with_const_1to8(tm - 1600, [&](auto TM) { GO(512, gemm_nt_f32_r16_kernel<decltype(TM)::value, 4>); });
+        else if (tm == 112) { GO(256, gemm_nt_f32_kernel<1, 2, 2, 2>); return; }
+        else if (tm == 2242) { GO(512, gemm_nt_f32_kernel<2, 2, 4, 2>); return; }
+        else if (tm == 2142) { GO(512, gemm_nt_f32_kernel<2, 1, 4, 2>); return; }
+        else if (tm == 2224) { GO(512, gemm_nt_f32_kernel<2, 2, 2, 4>); return; }
+        else if (tm == 121) r = {GemmKernel::F32, 2, 1};
+        else if (tm == 12) { GO(512, gemm_nt_f32_kernel<1, 2, 4, 2>); return; }
+        else if (tm == 21) { GO(512, gemm_nt_f32_kernel<2, 1, 2, 4>); return; }
+#undef GO
+        gemm_dispatch(r, a, st);          // (anything else: the default route, the 64 x 64 tile of the exact kernel)
     }
 };
 

@@ -20,11 +20,7 @@ extern "C" int vsr_ssp_create(vsr_ssp** out) {
     e->cfg.x3_on = false;            // the ordering models stay on the exact fp32 chain (their fixtures pin integer-truncated log-probs)
     hipDeviceProp_t prop;
     int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) {
-        e->cfg.gemm_slots = prop.multiProcessorCount * 4;
-        e->cfg.gemm_slots_small = prop.multiProcessorCount * 3;
-        e->cfg.gemm_slots_r16 = prop.multiProcessorCount;
-    }
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) e->cfg.gk.set_cus(prop.multiProcessorCount);
     *out = e;
     return 0;
 }

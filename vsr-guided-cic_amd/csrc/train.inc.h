@@ -158,7 +158,7 @@ static int gemm_to(vsr_handle* h, TrainCtx& t, hipStream_t s, int M, int N, cons
     for (int i = 0; i < nseg; ++i) g.a_image_only = g.a_image_only || (segs[i].A16 && !h->bf16_on);
     const int ns = g.finish(h);
     for (int i = 0; i < nseg; ++i)
-        if (segs[i].A16 && !h->bf16_on && g.big != 37) return fail("training gemm: an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");
+        if (segs[i].A16 && !h->bf16_on && g.route.kernel != GemmKernel::H2A) return fail("training gemm: an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");
     const long long stride = (long long)M * N;
     if (ns == 1) {                          // every tile is produced by one workgroup: it writes the destination window itself
         g.a.p[0].C = dst; g.a.p[0].ldc = (int)ldd; g.a.p[0].slab_stride = 0;
@@ -191,7 +191,7 @@ static int gemm_group(vsr_handle* h, TrainCtx& t, hipStream_t s, const GProb* P,
     }
     const int ns = g.finish(h);
     for (int i = 0; i < n; ++i)
-        if (P[i].a_img && !h->bf16_on && g.big != 37) return fail("training gemm group: an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");
+        if (P[i].a_img && !h->bf16_on && g.route.kernel != GemmKernel::H2A) return fail("training gemm group: an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");
     if (ns == 1) {                          // every tile is produced by one workgroup: written in place
         for (int i = 0; i < n; ++i) { g.a.p[i].C = P[i].dst; g.a.p[i].ldc = (int)P[i].ldd; g.a.p[i].slab_stride = 0; }
         if (g.launch(s, h)) return fail("training gemm group launch failed");
@@ -376,7 +376,7 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
     const int TB = T * B;
     const size_t BH = (size_t)B * H;
     // f16x2 flavour: fp16-pair images of the A operands (all-DMA kernel); BH elements of 4 bytes per state slot
-    const bool im = h->h2_on && !h->bf16_on && h->x3_on && h->h2_aimg && t.h1s16 && (B * H) % 8 == 0;
+    const bool im = h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg && t.h1s16 && (B * H) % 8 == 0;
     const float isc = im ? 32768.f : 0.f;                  // (2^15: the exponent of the unit-bounded class)
     const int* att_exp = im ? h->h2_exps + H2A_ATT : nullptr;
     {   // the zero states of step 0 (and their images): one launch
@@ -605,9 +605,9 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     // f16x2 flavour: the W operands of the backward GEMMs - transposed weights here, transposed activations in phase B - are written as
     // fp16-pair images by the transposing kernel itself; the A operands are gradients: their producers fold max |x| into "dynamic" slots
     // of the exponent table (block tt of 8 slots for step tt, blocks 62 / 63 for the whole-pass operands)
-    // (the same conditions GemmBuilder::finish() routes a launch to the f16x2 kernels by: a backward pass that wrote only images for
+    // (the same conditions GemmBuilder::finish(), gemm_route.h, routes a launch to the f16x2 kernels by: a backward pass that wrote only images for
     // launches that then fall through to the fp32-operand kernels would read unwritten buffers - finish() refuses such a launch too)
-    const bool h2b = h->h2_on && h->x3_on && h->gemm_tile == 0 && !h->bf16_on && t.h2img && T <= H2_NDYN / 8 - 2;
+    const bool h2b = h->h2_on && h->x3_on && h->gk.gemm_tile == 0 && !h->bf16_on && t.h2img && T <= H2_NDYN / 8 - 2;
     h->h2t_only = h2b;
     int* dyn = h2b ? h->h2_exps + H2_DYN0 : nullptr;
     enum { DY_dpre2, DY_dga, DY_dq, DY_dhA, DY_dsent, DY_dsa, DY_dpre1 };               // per-step block
@@ -786,7 +786,7 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     const int sP1 = dslot(DW_step + DY_dpre1), sQ = dslot(DW_step + DY_dq), sP2 = dslot(DW_step + DY_dpre2);
     // the transposed gradients are the A operands of the weight-gradient GEMMs: with the whole-pass bounds known (k_h2_dyn_fold) they are
     // written as fp16-pair images IN PLACE of the fp32 values and those GEMMs take the all-DMA kernel (tyi: the buffer holds an image)
-    const bool tyi = h2b && h->h2_aimg && TBp % 8 == 0 && (reinterpret_cast<uintptr_t>(t.tY_dpre1) & 255) == 0;     // (every buffer of the workspace shares that alignment)
+    const bool tyi = h2b && h->gk.h2_aimg && TBp % 8 == 0 && (reinterpret_cast<uintptr_t>(t.tY_dpre1) & 255) == 0;     // (every buffer of the workspace shares that alignment)
     const int sY1 = dslot(DW_dpre1all);
     transpose(h, s, t.dpre1, 6 * H, TB, 6 * H, t.tY_dpre1, TBp, nullptr, tyi, sY1, nullptr, &tby);
     transpose(h, s, t.dpre2, 4 * H, TB, 4 * H, t.tY_dpre2, TBp, nullptr, tyi, sP2, nullptr, &tby);

@@ -14,7 +14,7 @@ namespace vsr {
 // Transposes, 64 x 64 tiles through LDS, 16 bytes per lane on both sides (256-byte row pieces; the 32 x 32 / 4-byte version
 // moved 1.5 TB/s).  GATHER: row r of the input is row list[r]; BF16: ONLY the bf16 image (round-to-nearest-even) is written, to
 // out16 - the bf16 mode's W operands (gemm_bf16.h); the fp32 buffer `out` then only lends its address (the twin is looked up by
-// it) and a launch that names it but cannot take the bf16 kernel is refused (GemmBuilder::launch).  Unaligned shapes (ld or a
+// it) and a launch that names it but cannot take the bf16 kernel is refused (GemmBuilder::launch; routing: gemm_route.h).  Unaligned shapes (ld or a
 // base not a multiple of 4 floats) take scalar accesses.
 __device__ __forceinline__ uint16_t to_bf16_bits(float x) {
     typedef __bf16 b2 __attribute__((ext_vector_type(2)));

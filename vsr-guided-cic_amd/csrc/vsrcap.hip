@@ -1,5 +1,6 @@
 // libvsrcap.so - C ABI + per-timestep orchestration of the VSR captioning decoder on gfx950.
-// Entry points are declared in include/vsrcap.h; reference behaviour cited there and in kernels.h.
+// Entry points are declared in include/vsrcap.h; reference behaviour cited there and in kernels.h.  GEMM routing (which kernel, tile and
+// k plan a launch takes; the VSR_* routing knobs) lives in gemm_route.h, the kernel switch in gemm_dispatch.h.
 //
 // One decoder timestep = 4 grouped fp32-MFMA GEMM launches + 5 small kernels, all on the caller's stream:
 //   S1  [h2 | x | h1_old] -> LSTM1 gates (4H) | sentinel gate (H) | shift-gate image part (H)      gemm
@@ -24,13 +25,7 @@
 #include <cstring>
 #include <vector>
 
-#include "gemm_f32.h"
-#include "gemm_bf16.h"
-#include "gemm_x3.h"
-#include "gemm_x3s.h"
-#include "gemm_h2.h"
-#include "gemm_h2a.h"
-#include "gemm_b16a.h"
+#include "gemm_route.h"
 #include "kernels.h"
 #include "train_kernels.h"
 
@@ -98,14 +93,7 @@ static void free_saved_forwards(SavedForwards*);
 static void drop_saved_forwards(SavedForwards*);                                            // all of them (a change of GEMM flavour / weights binding)
 static void drop_saved_forwards_in(SavedForwards*, const void* lo, size_t bytes);           // those whose workspaces overlap [lo, lo + bytes)
 
-struct Bf16Range { const float* lo; const float* hi; const uint16_t* b; };   // fp32 matrix [lo, hi) has a bf16 copy at b
-struct H2Range { const float* lo; const float* hi; const float* img; int slot; };   // ... an fp16-pair image (gemm_h2.h) at img, scale exponent in slot
-
-// f16x2 flavour: slots of the scale-exponent table (device ints at the head of the image buffer; a twin table of float bounds next to it).
-// 0..13: the 14 weight matrices; then the bounds of the A operands a GEMM segment can name (GemmBuilder::seg's a_cls)
-enum H2Slot { H2A_NONE = -1, H2A_EMBED = 14, H2A_UNIT = 15, H2A_REGION = 16, H2A_DET = 17, H2A_ATT = 18, H2B_SENT = 19, H2_NSLOT = 32 };
-
-struct vsr_handle {
+struct vsr_handle : GemmState {         // (gemm_route.h: the GEMM flavours switched on, the operand images and the routing knobs `gk`)
     TrainCtx* tc = nullptr;
     SavedForwards* saved = nullptr;
     hipEvent_t bucket_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // recorded by vsr_train_backward after each gradient bucket
@@ -113,105 +101,19 @@ struct vsr_handle {
     long long gen_counter = 0;        // generations of the training forwards: strictly increasing per handle
     const char* ws_lo = nullptr;      // the workspace the current vsr_prepare*() carved (h->c points into it)
     size_t ws_bytes = 0;
-    // bf16 throughput mode (gemm_bf16.h): off unless vsr_refresh_bf16_weights() has been given a buffer
-    bool bf16_on = false;
-    // f16x2 flavour (gemm_h2.h): on once vsr_refresh_h2_weights() has been given a buffer, and only together with x3_on (a launch
-    // that does not qualify - an operand without an image / a bound, sizes that are not multiples of 8 - takes the f32x3 kernels)
-    bool h2_on = false;
-    std::vector<H2Range> h2;
-    int* h2_exps = nullptr;           // device: H2_NSLOT scale exponents ...
-    unsigned* h2_bounds = nullptr;    // ... and the bounds they come from (bit patterns of non-negative floats)
-    // streaming kernel: launches of at most h2s_max rows (VSR_H2S_MAX / _SLOTS / _MIN / _NS).  Measured end to end in one run
-    // (profiles/r04_e_h2s_routing.txt): 80 - greedy (M = 100, then on the 128 x 128 tile) 660 k tokens/s against 632 k at 128, the 13-image shard
-    // (M = 65) 2.61 ms either way; 48 - greedy 668 k, the shard 2.75 ms
-    int h2s_max = 80, h2s_slots = 512, h2s_min = 8, h2s_ns = 1;
-    int h2_aligned_min = 4;      // shortest k-aligned piece of the f16x2 kernels, in 32-wide k-tiles (VSR_H2_ALIGNED_MIN) ...
-    int h2_aligned_min_small = 8;   // ... and in launches whose rows fit ONE m-tile (<= 128 rows: greedy decoding, the per-step GEMMs of training; VSR_H2_ALIGNED_MIN_SMALL).
-                                    // Round 6: 8 instead of 4 there - pieces of 4 k-tiles cost more in their flush than in their k loop: XE +2.4 %, greedy +1.1 %
-                                    // (profiles/r06_t_*).  For the wide launches 8 was REJECTED by the flip-rate fixture (one caption of 1 024 flipped in the default flavour).
-    // the producers of the decoder's A operands (h1, h2, s_t, g_t, the attended vector) write fp16-pair images next to the fp32 values
-    // and launches whose A operands all have one take the all-DMA kernel (gemm_h2a.h); VSR_H2_AIMG=0: in-kernel split of fp32 A only
-    double aligned_eff_min = 0.75;    // wide launches: k-aligned pieces when they keep at least this share of the CUs busy, stream-K ranges otherwise (VSR_ALIGNED_EFF, percent)
-    bool h2_aimg = true;
-    int h2_mfma = 16;                 // MFMA shape of the all-DMA kernel's multipliers: 16 (v_mfma_f32_16x16x32_f16) or 32 (32x32x16; VSR_H2_MFMA=32)
     // the selection of step t inside the LSTM1 kernel of step t + 1 (kernels.h: k_select_lstm1, k_select_simple_lstm1); VSR_FUSE_SELECT=0: a launch of its own
     int fuse_select = 3;              // bit 0: greedy / sampling / replay (k_select_simple_lstm1), bit 1: beam search (k_select_lstm1)
-    bool b16_dma = true;              // bf16 mode: launches whose A operands all have bf16 images take the all-DMA kernel (VSR_B16_DMA=0: register-staged)
-    int h2a_max_small = 128;          // launches of at most this many rows (and more than h2s_max) : 128 x 128 tiles of the all-DMA kernel
-    std::vector<H2Range> h2t;         // the training pass's transposed operands (vsr_train_forward registers the images of its workspace)
-    const H2Range* map_h2(const float* p, bool with_train = true) const {
-        for (const H2Range& r : h2)
-            if (p >= r.lo && p < r.hi) return &r;
-        if (with_train)
-            for (const H2Range& r : h2t)
-                if (p >= r.lo && p < r.hi) return &r;
-        return nullptr;
-    }
-    // A operands are looked up among the images registered at refresh only (the embedding table): the training workspace's
-    // ranges (h2t) describe W operands and may outlive the memory they were registered for
-    const H2Range* map_h2_a(const float* p) const { return map_h2(p, false); }
-    bool h2t_only = false;            // the running backward pass writes ONLY the images of its transposed operands (train.inc.h: h2b)
-    bool is_h2_train_image(const float* p) const {      // p lies in a transposed operand of the training pass that exists ONLY as an fp16-pair image
-        if (!h2t_only) return false;
-        for (const H2Range& r : h2t)
-            if (p >= r.lo && p < r.hi) return true;
-        return false;
-    }
-    int h2_slot_of(const float* p) const { const H2Range* r = map_h2(p); return r ? r->slot : 0; }
-    bool x3_on = true;                // launches of >= gemm_x3_min_rows rows: fp32 products through three bf16 terms per operand (gemm_f32x3.h); fp32 operands, no copies.  vsr_set_gemm_mode(h, 0): exact fma chain everywhere
-    std::vector<Bf16Range> b16;        // weights (refresh) + the training pass's transposed operands (carve_train)
-    size_t b16_weights = 0;            // entries of b16 that belong to the weights
-    int gemm_slots_bf16 = 256;         // ONE 16-wave workgroup per CU (108 KB of LDS: two 128+256-row x 64-k bf16 buffers; 147 KB for f32x3)
-    const uint16_t* map16(const float* p) const {
-        for (const Bf16Range& r : b16)
-            if (p >= r.lo && p < r.hi) return r.b + (p - r.lo);
-        return nullptr;
-    }
-    bool is_train_twin(const float* p) const {       // p lies in a transposed operand of the training pass (bf16 image only)
-        for (size_t i = b16_weights; i < b16.size(); ++i)
-            if (p >= b16[i].lo && p < b16[i].hi) return true;
-        return false;
-    }
+    int bf16_a16 = 1;            // bf16 mode: the decode step's producers write bf16 images of the GEMM A operands (VSR_BF16_A16=0: off)
     vsr_dims d;
     vsr_weights w;
     bool bound = false, prepared = false;
     const int* vt_ptr = nullptr;
     const int* vt_ids = nullptr;
     int n_verbs = 0;
-    int gemm_slots = 1024;       // resident 64x64 GEMM workgroups to fill: 256 CUs x 4 (36.9 KB LDS each)
-    int gemm_slots_small = 768;  // 64x64 tiles (M <= 192): 3 per CU measured best (greedy 473 k vs 461 k tokens/s at 4 per CU)
-    int gemm_min_iters = 8;
-    int gemm_x3_min_rows = 193;  // f32x3 flavour: launches of at least this many rows take the 128 x 256 tile (VSR_X3_MIN_ROWS)
-    int x3_skinny = 1;           // ... launches of r16_max < rows <= 128 the 128 x 128 tile (one m-tile holds every row; VSR_X3_SKINNY=0: exact kernels)
-    // k-aligned pieces (gemm_plan_aligned) or stream-K ranges.  VSR_X3_ALIGNED=<wide><skinny> as two digits; wide: 0 never, 1 whenever the
-    // tiles fit the CUs, 2 (default) per launch by its efficiency (GemmBuilder::finish) and always from 1024 rows up.  Measured end to
-    // end: beam-5 (M = 500) 265.7 k tokens/s with stream-K ranges everywhere against 256.5 k with aligned pieces everywhere; XE step
-    // (its wide launches have 2000 rows) 9.52 k against 9.40 k samples/s; greedy (M = 100) 572 k with aligned pieces against 550 k
-    int x3_aligned_wide = 2, x3_aligned_skinny = 1;
-    int x3_aligned_min = 4;      // shortest k-aligned piece of the f32x3 kernels, in 32-wide k-tiles
-    // f32x3 launches of at most x3s_max rows: the weight-streaming kernel (gemm_x3s.h) when its k-aligned plan exists.  Measured over
-    // the four step GEMMs (tools/gemm_bench, one 16-column strip per wave, two workgroups per CU): M = 13: 53 us against 65 (rows-16
-    // kernel); M = 32: 61 against 76; M = 65: 99 against 107 (128 x 128 tile); M = 100: 123 against 112 - so up to 80 rows.
-    // VSR_X3S_MAX=0 turns it off.
-    int x3s_max = 80, x3s_slots = 512, x3s_min = 8;
-    int gemm_slots_r16 = 256;    // rows-16 kernel: ONE 8-wave workgroup per CU (two waves per SIMD)
-    // Problems with at most this many rows take the rows-16 kernel (VSR_GEMM_R16_MAX=0 disables it).  Measured end to end on
-    // one MI355X: at M = 100 it is level with the 64x64 kernel inside a GEMM (61.5 vs 60.6 TF/s) but its tiles are cut into
-    // 7-8 stream-K pieces instead of 4-6, and the consumers' extra slab reads cost more than its 11 %-instead-of-28 %
-    // padding saves (greedy 459 k vs 481 k tokens/s, XE step 6.8 k vs 7.4 k samples/s).  Below 64 rows (a data-parallel
-    // shard of 12-13 images and its 65 beam rows, small eval batches) the 64-row tiles are mostly padding and the rows-16 kernel wins
-    // (M = 13: 19.5 vs 13.2 TF/s over the four step GEMMs; beam-5 over a 13-image shard, M = 65: 3.48 vs 3.81 ms per call).
-    int gemm_r16_max = 40;
-    int bf16_p_fp32 = 1;         // bf16 mode: the hoisted att_va(regions) GEMM of vsr_prepare*() stays fp32-equivalent (VSR_BF16_P_FP32=0: bf16 like the rest)
-    int bf16_a16 = 1;            // bf16 mode: the decode step's producers write bf16 images of the GEMM A operands (VSR_BF16_A16=0: off)
-    int gemm_aligned = 1;        // 128 x 256 kernels: k-aligned pieces (gemm_plan_aligned) when the tiles fit the CUs; VSR_GEMM_ALIGNED=0: stream-K always
-    int gemm_aligned_min = 8;    // shortest piece, in 64-wide k-tiles (VSR_GEMM_ALIGNED_MIN)
     const float* xproj = nullptr;     // decode cache: (V, 6H) projection of the embedding table, valid for the bound weights
     long long rows_bound = 0;    // vsr_set_valid_rows_bound: > 0 = the caller's upper bound on the non-padding region rows; vsr_prepare*() then never waits for the host
     int attend_parts = 2, attend_limit = 256;        // workgroups per row of k_attend in launches of <= attend_limit / parts rows (VSR_ATTEND_PARTS, VSR_ATTEND_LIMIT)
     int split_pre1 = 1;          // the h1 part of the next step's LSTM1 sums in the S5 launch, the h2 part with the vocabulary (run_step; VSR_SPLIT_PRE1=0: all of it with the vocabulary, as in rounds 2-5)
-    int xcd_groups = 0;          // VSR_XCD_GROUPS=1: k-aligned plans deal whole m-groups of tiles to an XCD (gemm_plan_aligned).  Measured: 2 % less fabric traffic on the wide kernel, 1.3 % SLOWER end to end (profiles/r06_d_xcd_group_dealing_ab.txt): off
-    int gemm_tile = 0;           // 0 = by M; VSR_GEMM_TILE=64 | 12864 | 128 forces 64x64 / 128x64 / 128x128
     Ctx c;
     // measurement
     bool profiling = false;
@@ -305,280 +207,19 @@ static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
     return (b.off + 255) & ~size_t(255);
 }
 
-// ---------------------------------------------------------------------------------------------- GEMM launch
-struct GemmBuilder {
-    GemmArgs a;
-    GemmBuilder() { memset(&a, 0, sizeof(a)); }
-    GemmProb& prob(int M, int N, float* C, int ldc) {
-        GemmProb& p = a.p[a.nprob++];
-        p.M = M; p.N = N; p.C = C; p.ldc = ldc; p.nseg = 0;
-        return p;
-    }
-    // a_cls: which bound the A operand obeys (H2Slot; the f16x2 kernels scale A by it); H2A_NONE: the launch cannot take them
-    static void seg(GemmProb& p, const float* A, int lda, const int* idx, const float* W, int ldw, int K, const uint16_t* A16 = nullptr, int a_cls = H2A_NONE) {
-        if (K <= 0) return;
-        GemmSeg& s = p.seg[p.nseg++];
-        s.A = A; s.lda = lda; s.a_idx = idx; s.W = W; s.ldw = ldw; s.K = K; s.A16 = A16;
-        s.exp_idx = a_cls;               // (finish() turns it into (a slot << 16) | w slot when the launch takes the f16x2 kernels)
-    }
-    int big = 0;       // 2: 128x128 workgroup tiles, 1: 128x64, 0: 64x64 (32x32x2 MFMA); 16: rows-16 kernel (16x16x4 MFMA), r16_tm tiles
-    int r16_tm = 0;
-    int x3_tn = 2;       // f32x3 and bf16 kernels: workgroup tile 128 x 256 (2) or 128 x 128 (1)
-    int x3s_mt = 0;      // weight-streaming f32x3 kernel (big = 34): 16-row tiles of A
-    bool a16_all = false;   // bf16 kernel: every segment's A operand has a bf16 image (GemmSeg::A16)
-    bool keep_fp32 = false; // bf16 mode: this launch stays fp32-equivalent (f32x3 kernels): the hoisted att_va(regions) projection, whose
-                            // outputs are summed RAW over up to 36 rows into the shift logit (step :187) - bf16 rounding adds up coherently there
-    bool a_image_only = false;   // f16x2 flavour: an A operand exists ONLY as an fp16-pair image (GemmSeg::A16; the training pass's transposed gradients): the launch must take the all-DMA kernel
-    bool stale_h2 = false;  // f16x2 flavour: a W operand exists only as an fp16-pair image (a transposed operand of the training pass) but the launch does not take an f16x2 kernel
-    bool stale_w = false;   // bf16 mode: a W operand exists only as a bf16 image but the launch does not qualify for the bf16 kernel
-    // stream-K plan: returns the slab count; the caller then sets every problem's C / slab_stride
-    int finish(const vsr_handle* h) {
-        int maxM = 0;
-        for (int i = 0; i < a.nprob; ++i) maxM = std::max(maxM, a.p[i].M);
-        if (h->bf16_on && !(keep_fp32 && h->bf16_p_fp32)) {
-            // bf16 mode: every W operand of the launch must have a bf16 copy (and 16-byte-aligned 8-element chunks);
-            // a launch that does not qualify runs on the fp32 kernel
-            bool ok = true;
-            for (int i = 0; i < a.nprob && ok; ++i)
-                for (int sg = 0; sg < a.p[i].nseg && ok; ++sg) {
-                    const GemmSeg& S = a.p[i].seg[sg];
-                    const uint16_t* w16 = h->map16(S.W);
-                    ok = w16 && (S.K % 8 == 0) && (S.ldw % 8 == 0) && (S.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(w16) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(S.A) & 15) == 0);
-                }
-            if (!ok) {
-                // the transposing kernels of the training pass write ONLY the bf16 image of such an operand: the fp32 kernel
-                // would read a stale buffer.  (Does not happen for sizes the mode accepts: every K / leading dimension is a
-                // multiple of 8.)
-                for (int i = 0; i < a.nprob; ++i)
-                    for (int sg = 0; sg < a.p[i].nseg; ++sg) stale_w = stale_w || h->is_train_twin(a.p[i].seg[sg].W);
-            }
-            if (ok) {
-                a16_all = true;
-                for (int i = 0; i < a.nprob; ++i)
-                    for (int sg = 0; sg < a.p[i].nseg; ++sg) {
-                        GemmSeg& S = a.p[i].seg[sg];
-                        S.W = reinterpret_cast<const float*>(h->map16(S.W));
-                        a16_all = a16_all && S.A16 && (S.lda % 8 == 0) && ((reinterpret_cast<uintptr_t>(S.A16) & 15) == 0);
-                    }
-                big = (a16_all && h->b16_dma) ? 38 : 32;        // 38: both operands are images: the all-DMA kernel (gemm_b16a.h)
-                // launches whose rows fit one m-tile: 128 x 128 tiles (twice the tiles, half the k pieces per tile), as for f32x3
-                x3_tn = (h->x3_skinny && maxM <= 128) ? 1 : 2;
-                const int BN = x3_tn == 1 ? 128 : 256;
-                if (h->gemm_aligned)
-                    if (const int ns = gemm_plan_aligned(a, h->gemm_slots_bf16, x3_tn == 1 ? 2 : h->gemm_aligned_min, 128, BN, B16_BK)) return ns;
-                return gemm_plan(a, h->gemm_slots_bf16, 4, 128, BN, B16_BK);
-            }
-        }
-        big = h->gemm_tile == 128 ? 2 : h->gemm_tile == 12864 ? 1 : h->gemm_tile == 64 ? 0 : (maxM >= 1024 ? 2 : maxM > 192 ? 1 : 0);
-        if (h->h2_on && h->x3_on && h->gemm_tile == 0) {
-            // f16x2 (gemm_h2.h): every W operand has an fp16-pair image (window starts and leading dimensions in whole 8-element
-            // groups), every A operand a bound class
-            bool ok = true;
-            for (int i = 0; i < a.nprob && ok; ++i)
-                for (int sg = 0; sg < a.p[i].nseg && ok; ++sg) {
-                    const GemmSeg& S = a.p[i].seg[sg];
-                    const H2Range* r = h->map_h2(S.W);
-                    ok = r && S.exp_idx >= 0 && (S.K % 8 == 0) && (S.ldw % 8 == 0) && (S.lda % 4 == 0) && ((S.W - r->lo) % 8 == 0) &&
-                         ((reinterpret_cast<uintptr_t>(S.A) & 15) == 0);
-                }
-            if (ok) {
-                GemmArgs ah = a;
-                for (int i = 0; i < ah.nprob; ++i)
-                    for (int sg = 0; sg < ah.p[i].nseg; ++sg) {
-                        GemmSeg& S = ah.p[i].seg[sg];
-                        const H2Range* r = h->map_h2(S.W);
-                        S.exp_idx = (S.exp_idx << 16) | r->slot;
-                        S.W = r->img + (S.W - r->lo);
-                    }
-                ah.exps = h->h2_exps;
-                // all-DMA kernel (gemm_h2a.h): every A operand has an fp16-pair image too - written by its producer (GemmSeg::A16 in this
-                // flavour) or a registered one (the embedding table)
-                bool aimg = h->h2_aimg;
-                for (int i = 0; i < ah.nprob && aimg; ++i)
-                    for (int sg = 0; sg < ah.p[i].nseg && aimg; ++sg) {
-                        const GemmSeg& S = ah.p[i].seg[sg];
-                        const H2Range* ra = S.A16 ? nullptr : h->map_h2_a(S.A);
-                        aimg = (S.lda % 8 == 0) && (S.A16 ? (reinterpret_cast<uintptr_t>(S.A16) & 31) == 0
-                                                          : (ra && ra->slot == (S.exp_idx >> 16) && (S.A - ra->lo) % 8 == 0));
-                    }
-                auto with_a_images = [&](GemmArgs& g) {
-                    for (int i = 0; i < g.nprob; ++i)
-                        for (int sg = 0; sg < g.p[i].nseg; ++sg) {
-                            GemmSeg& S = g.p[i].seg[sg];
-                            if (S.A16) S.A = reinterpret_cast<const float*>(S.A16);
-                            else { const H2Range* ra = h->map_h2_a(S.A); S.A = ra->img + (S.A - ra->lo); }
-                        }
-                };
-                const int slots = h->gemm_slots_bf16;
-                if (maxM <= h->h2s_max && maxM <= 128 && !(a_image_only && aimg)) {
-                    GemmArgs as = ah;
-                    if (const int ns = gemm_plan_aligned(as, h->h2s_slots, h->h2s_min, 128, h2s_bn(h->h2s_ns), H2_BK)) { a = as; big = 36; x3s_mt = (maxM + 15) / 16; return ns; }
-                }
-                big = aimg ? 37 : 35;
-                a = ah;
-                if (aimg) with_a_images(a);
-                auto aligned_eff = [&](GemmArgs& g) {
-                    int T = 1;
-                    for (int i = 0; i < g.nprob; ++i) T = std::max(T, (g.p[i].ktiles + g.p[i].split - 1) / g.p[i].split);
-                    return (double)g.total_iters / ((double)slots * T);
-                };
-                if (maxM <= 128) {
-                    x3_tn = 1;
-                    if (const int ns = gemm_plan_aligned(a, slots, h->h2_aligned_min_small, 128, 128, H2_BK)) return ns;
-                    return gemm_plan(a, slots, 4, 128, 128, H2_BK);
-                }
-                if (h->x3_aligned_wide != 0) {             // (the planner of the f32x3 wide kernel, below)
-                    const bool force = h->x3_aligned_wide == 1 || maxM >= 1024;
-                    GemmArgs a22 = a, a21 = a;
-                    const int ns22 = gemm_plan_aligned(a22, slots, h->h2_aligned_min, 128, 256, H2_BK);
-                    int tiles22 = 0;
-                    for (int i = 0; i < a.nprob; ++i) tiles22 += ((a.p[i].M + 127) / 128) * ((a.p[i].N + 255) / 256);
-                    if (tiles22 <= 64 && maxM < 1024) {
-                        const int ns21 = gemm_plan_aligned(a21, slots, h->h2_aligned_min, 128, 128, H2_BK);
-                        if (ns21 && aligned_eff(a21) >= 0.95 && (!ns22 || ns21 < ns22)) { a = a21; x3_tn = 1; return ns21; }
-                    }
-                    if (ns22 && (force || aligned_eff(a22) >= h->aligned_eff_min)) { a = a22; x3_tn = 2; return ns22; }
-                }
-                x3_tn = 2;
-                return gemm_plan(a, slots, 4, 128, 256, H2_BK);
-            }
-        }
-        // from here on the launch reads fp32 operands: the transposing kernels of an f16x2 backward pass wrote ONLY the images of theirs
-        if (h->h2_on && !h->bf16_on)
-            for (int i = 0; i < a.nprob; ++i)
-                for (int sg = 0; sg < a.p[i].nseg; ++sg) stale_h2 = stale_h2 || h->is_h2_train_image(a.p[i].seg[sg].W);
-        if ((h->x3_on || (keep_fp32 && h->bf16_on && h->bf16_p_fp32)) && h->gemm_tile == 0) {
-            // f32x3 (gemm_x3.h): 128 x 256 tiles from 193 rows up; 128 x 128 tiles for launches whose rows fit ONE m-tile (greedy
-            // decoding, sampling, the per-step GEMMs of the training pass at batch 100, a shard of a strong-scaled decode): the
-            // number of tiles is then the number of n-tiles, which 256-wide tiles would have to cut into ~10 k pieces each.
-            // Measured over the four step GEMMs (tools/gemm_bench): M = 100: 112 us against 160 us for the exact 64 x 64 kernel;
-            // M = 65: 107 against 120 (rows-16) / 154; M = 13: 100 against 64 for the rows-16 kernel, which keeps the shortest launches.
-            bool ok = true;
-            for (int i = 0; i < a.nprob && ok; ++i)
-                for (int sg = 0; sg < a.p[i].nseg && ok; ++sg) {
-                    const GemmSeg& S = a.p[i].seg[sg];
-                    ok = (S.K % 4 == 0) && (S.ldw % 4 == 0) && (S.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(S.W) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(S.A) & 15) == 0);
-                }
-            const bool wide = ok && maxM >= h->gemm_x3_min_rows;
-            const bool stream = ok && !wide && h->x3_skinny && maxM <= h->x3s_max;
-            if (stream) {
-                // weight-streaming kernel: 64-column blocks x k-aligned pieces, two workgroups per CU
-                GemmArgs as = a;
-                if (const int ns = gemm_plan_aligned(as, h->x3s_slots, h->x3s_min, 128, x3s_bn(1), X3_BK)) { a = as; big = 34; x3s_mt = (maxM + 15) / 16; return ns; }
-            }
-            const bool skinny = ok && !wide && h->x3_skinny && maxM <= 128 && maxM > h->gemm_r16_max;
-            if (wide || skinny) {
-                big = 33;
-                const int slots = h->gemm_slots_bf16;
-                // efficiency of a k-aligned plan: work units over (slots x longest piece); 1 = every CU busy for the whole launch
-                auto aligned_eff = [&](GemmArgs& g) {
-                    int T = 1;
-                    for (int i = 0; i < g.nprob; ++i) T = std::max(T, (g.p[i].ktiles + g.p[i].split - 1) / g.p[i].split);
-                    return (double)g.total_iters / ((double)slots * T);
-                };
-                if (skinny) {
-                    x3_tn = 1;
-                    if (h->x3_aligned_skinny)
-                        if (const int ns = gemm_plan_aligned(a, slots, h->x3_aligned_min, 128, 128, X3_BK)) return ns;
-                    return gemm_plan(a, slots, 4, 128, 128, X3_BK);
-                }
-                // Wide launches: stream-K ranges keep every CU busy but cut a tile into 3-5 pieces (slabs every consumer has to add);
-                // k-aligned pieces share their k-windows in L2 and write exactly `split` slabs, but leave CUs idle when tiles x split
-                // does not fill the chip.  Measured on the beam-5 step shapes (tools/gemm_bench, M = 500): S2 (64 tiles of K = 1000)
-                // 42 us / 5 slabs with stream-K ranges, 35 us / 2 slabs with k-aligned halves of 128 x 128 tiles; S5 125 us / 5 slabs
-                // vs 124 us / 3 slabs (efficiency 0.76); S1 120 vs 137 us (0.74); the vocabulary GEMM 82 vs 88 us (0.63).
-                if (h->x3_aligned_wide != 0) {
-                    const bool force = h->x3_aligned_wide == 1 || maxM >= 1024;
-                    GemmArgs a22 = a, a21 = a;
-                    const int ns22 = gemm_plan_aligned(a22, slots, h->x3_aligned_min, 128, 256, X3_BK);
-                    int tiles22 = 0;
-                    for (int i = 0; i < a.nprob; ++i) tiles22 += ((a.p[i].M + 127) / 128) * ((a.p[i].N + 255) / 256);
-                    if (tiles22 <= 64 && maxM < 1024) {              // a small launch: halves of narrow tiles fill the chip with fewer slabs
-                        const int ns21 = gemm_plan_aligned(a21, slots, h->x3_aligned_min, 128, 128, X3_BK);
-                        if (ns21 && aligned_eff(a21) >= 0.95 && (!ns22 || ns21 < ns22)) { a = a21; x3_tn = 1; return ns21; }
-                    }
-                    if (ns22 && (force || aligned_eff(a22) >= h->aligned_eff_min)) { a = a22; x3_tn = 2; return ns22; }
-                }
-                x3_tn = 2;
-                return gemm_plan(a, slots, 4, 128, 256, X3_BK);
-            }
-        }
-        if (h->gemm_tile == 0 && maxM <= h->gemm_r16_max) {
-            // short problems: every row of an m-tile in one workgroup, rows in units of 16 (M = 100 -> 112, not 128)
-            const int tiles = (maxM + 127) / 128;
-            r16_tm = (((maxM + tiles - 1) / tiles) + 15) / 16;
-            big = 16;
-            return gemm_plan(a, h->gemm_slots_r16, 4, 16 * r16_tm, 128);
-        }
-        // resident workgroups per CU: 4 at 36.9 KB LDS (64x64), 2 at 55.3 KB (128x64) or 73.7 KB (128x128).
-        // 128x128 for M >= 1024 (weight-gradient GEMMs: one tile per workgroup, 130 TF/s at long K);
-        // 128x64 is the default for tall problems: as fast as 128x128 in the GEMM itself (91.8 vs 93.7 TF/s) but its
-        // tiles are cut into ~3 stream-K pieces instead of ~5, so every consumer kernel reads 40 % fewer slab bytes.
-        return gemm_plan(a, big ? h->gemm_slots / 2 : h->gemm_slots_small, h->gemm_min_iters, big ? 128 : 64, big == 2 ? 128 : 64);
-    }
-    int launch(hipStream_t s, vsr_handle* h);
-};
-
-int GemmBuilder::launch(hipStream_t s, vsr_handle* h) {
+// ------------------------------------------- GEMM launch (routing and planning: GemmBuilder::finish, gemm_route.h; the kernel switch: gemm_dispatch.h)
+int vsr::GemmBuilder::launch(hipStream_t s, vsr_handle* h) {
     if (stale_h2) return fail("f16x2 flavour: a GEMM launch names a transposed operand of the training pass that only exists as an fp16-pair image but cannot take an f16x2 kernel (gemm mode / tile override changed since vsr_train_forward, or K / leading dimensions not multiples of 8)");
     if (stale_w) return fail("bf16 mode: a GEMM launch names a transposed operand that only exists as a bf16 image but cannot take the bf16 kernel (K / leading dimensions must be multiples of 8)");
-    if (!h->xcd_groups) a.xcd_chunk = 0;              // VSR_XCD_GROUPS=0: ceil(G / 8) workgroups per XCD whatever the m-groups (A/B)
-    dim3 grid(gemm_grid(a)), block((big == 32 || big == 38) ? B16_THREADS : (big == 33 || big == 35 || big == 37) ? X3_THREADS : big == 16 ? 512 : 256);       // (big == 34 / 36: 256 = X3S_THREADS = H2S_THREADS)
+    if (!h->gk.xcd_groups) a.xcd_chunk = 0;              // VSR_XCD_GROUPS=0: ceil(G / 8) workgroups per XCD whatever the m-groups (A/B)
     const bool prof = h->profiling && (h->prof_seen++ % h->prof_every) == 0 && h->ev_used + 2 <= h->ev.size();
     if (prof) (void)hipEventRecord(h->ev[h->ev_used], s);
-    if (big == 36) {
-#define H2S_CASE(MT_) case MT_: if (h->h2s_ns == 2) hipLaunchKernelGGL((gemm_nt_h2s_kernel<MT_, 2>), grid, block, 0, s, a); else hipLaunchKernelGGL((gemm_nt_h2s_kernel<MT_, 1>), grid, block, 0, s, a); break;
-        switch (x3s_mt) {
-            H2S_CASE(1) H2S_CASE(2) H2S_CASE(3) H2S_CASE(4) H2S_CASE(5) H2S_CASE(6) H2S_CASE(7)
-            default: if (h->h2s_ns == 2) hipLaunchKernelGGL((gemm_nt_h2s_kernel<8, 2>), grid, block, 0, s, a); else hipLaunchKernelGGL((gemm_nt_h2s_kernel<8, 1>), grid, block, 0, s, a); break;
-        }
-#undef H2S_CASE
-    } else if (big == 38 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_b16a_kernel<2, 2>), grid, block, 0, s, a);
-    else if (big == 38) hipLaunchKernelGGL((gemm_nt_b16a_kernel<2, 1>), grid, block, 0, s, a);
-    else if (big == 37 && h->h2_mfma == 32 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 2, 3, 32>), grid, block, 0, s, a);
-    else if (big == 37 && h->h2_mfma == 32) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1, 3, 32>), grid, block, 0, s, a);
-    else if (big == 37 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 2>), grid, block, 0, s, a);
-    else if (big == 37) hipLaunchKernelGGL((gemm_nt_h2a_kernel<2, 1>), grid, block, 0, s, a);       // (a ring of four stages fits this tile and changes nothing: tools/gemm_bench H2_NW=4, profiles/r05_e_*)
-    else if (big == 35 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 2>), grid, block, 0, s, a);
-    else if (big == 35) hipLaunchKernelGGL((gemm_nt_h2_kernel<2, 1>), grid, block, 0, s, a);
-    else if (big == 34) {
-        switch (x3s_mt) {
-            case 1: hipLaunchKernelGGL((gemm_nt_x3s_kernel<1, 1>), grid, block, 0, s, a); break;
-            case 2: hipLaunchKernelGGL((gemm_nt_x3s_kernel<2, 1>), grid, block, 0, s, a); break;
-            case 3: hipLaunchKernelGGL((gemm_nt_x3s_kernel<3, 1>), grid, block, 0, s, a); break;
-            case 4: hipLaunchKernelGGL((gemm_nt_x3s_kernel<4, 1>), grid, block, 0, s, a); break;
-            case 5: hipLaunchKernelGGL((gemm_nt_x3s_kernel<5, 1>), grid, block, 0, s, a); break;
-            case 6: hipLaunchKernelGGL((gemm_nt_x3s_kernel<6, 1>), grid, block, 0, s, a); break;
-            case 7: hipLaunchKernelGGL((gemm_nt_x3s_kernel<7, 1>), grid, block, 0, s, a); break;
-            default: hipLaunchKernelGGL((gemm_nt_x3s_kernel<8, 1>), grid, block, 0, s, a); break;
-        }
-    } else if (big == 33 && x3_tn == 2) hipLaunchKernelGGL((gemm_nt_x3_kernel<2, 2>), grid, block, 0, s, a);
-    else if (big == 33) hipLaunchKernelGGL((gemm_nt_x3_kernel<2, 1>), grid, block, 0, s, a);
-    else if (big == 32 && a16_all && x3_tn == 1) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<true, 1>), grid, block, 0, s, a);
-    else if (big == 32 && x3_tn == 1) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<false, 1>), grid, block, 0, s, a);
-    else if (big == 32 && a16_all) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<true, 2>), grid, block, 0, s, a);
-    else if (big == 32) hipLaunchKernelGGL((gemm_nt_bf16w_kernel<false, 2>), grid, block, 0, s, a);
-    else if (big == 16) {
-        switch (r16_tm) {
-            case 1: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<1, 2>), grid, block, 0, s, a); break;
-            case 2: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<2, 2>), grid, block, 0, s, a); break;
-            case 3: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<3, 2>), grid, block, 0, s, a); break;
-            case 4: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<4, 2>), grid, block, 0, s, a); break;
-            case 5: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<5, 2>), grid, block, 0, s, a); break;
-            case 6: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<6, 2>), grid, block, 0, s, a); break;
-            case 7: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<7, 2>), grid, block, 0, s, a); break;
-            default: hipLaunchKernelGGL((gemm_nt_f32_r16_kernel<8, 2>), grid, block, 0, s, a); break;
-        }
-    } else if (big == 2) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 2>), grid, block, 0, s, a);
-    else if (big == 1) hipLaunchKernelGGL((gemm_nt_f32_kernel<2, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gemm_nt_f32_kernel<1, 1>), grid, block, 0, s, a);
+    gemm_dispatch(route, a, s);
     if (prof) {
         (void)hipEventRecord(h->ev[h->ev_used + 1], s);
         h->ev_used += 2;
         h->prof_flops += gemm_flops(a);
-        h->prof_bytes += gemm_bytes(a, big == 32 ? 2 : 4);
+        h->prof_bytes += gemm_bytes(a, route.kernel == GemmKernel::BF16W ? 2 : 4);      // (quirk kept: the all-DMA bf16 kernel, B16A, is accounted with 4-byte weights)
     }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -606,47 +247,13 @@ extern "C" int vsr_create(const vsr_dims* dims, vsr_handle** out) {
     h->saved = new_saved_forwards();
     hipDeviceProp_t prop;
     int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) {
-        h->gemm_slots = prop.multiProcessorCount * 4;
-        h->gemm_slots_small = prop.multiProcessorCount * 3;
-        h->gemm_slots_r16 = prop.multiProcessorCount;
-        h->gemm_slots_bf16 = prop.multiProcessorCount;
-        h->x3s_slots = prop.multiProcessorCount * 2;
-        h->h2s_slots = prop.multiProcessorCount * 2;
-    }
-    if (const char* e = getenv("VSR_X3_MIN_ROWS")) h->gemm_x3_min_rows = atoi(e);
-    if (const char* e = getenv("VSR_X3_SKINNY")) h->x3_skinny = atoi(e);
-    if (const char* e = getenv("VSR_X3S_MAX")) h->x3s_max = std::min(atoi(e), 128);     // (the streaming kernels hold every row in ONE m-tile)
-    if (const char* e = getenv("VSR_H2S_MAX")) h->h2s_max = std::min(atoi(e), 128);
-    if (const char* e = getenv("VSR_H2S_SLOTS")) h->h2s_slots = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_H2S_MIN")) h->h2s_min = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_H2S_NS")) h->h2s_ns = atoi(e) == 2 ? 2 : 1;
-    if (const char* e = getenv("VSR_H2_ALIGNED_MIN")) h->h2_aligned_min = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_H2_ALIGNED_MIN_SMALL")) h->h2_aligned_min_small = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_H2_AIMG")) h->h2_aimg = atoi(e) != 0;
-    if (const char* e = getenv("VSR_H2_MFMA")) h->h2_mfma = atoi(e) == 32 ? 32 : 16;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) h->gk.set_cus(prop.multiProcessorCount);
+    h->gk.read_env();
     if (const char* e = getenv("VSR_FUSE_SELECT")) h->fuse_select = atoi(e);
-    if (const char* e = getenv("VSR_B16_DMA")) h->b16_dma = atoi(e) != 0;
-    if (const char* e = getenv("VSR_ALIGNED_EFF")) h->aligned_eff_min = atoi(e) / 100.0;
-    if (const char* e = getenv("VSR_X3S_SLOTS")) h->x3s_slots = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_X3S_MIN")) h->x3s_min = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_X3_ALIGNED")) { h->x3_aligned_wide = atoi(e) / 10; h->x3_aligned_skinny = atoi(e) % 10; }
-    if (const char* e = getenv("VSR_X3_ALIGNED_MIN")) h->x3_aligned_min = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_SLOTS_BF16")) h->gemm_slots_bf16 = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_SLOTS_R16")) h->gemm_slots_r16 = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_R16_MAX")) h->gemm_r16_max = atoi(e);
-    if (const char* e = getenv("VSR_GEMM_ALIGNED")) h->gemm_aligned = atoi(e);
     if (const char* e = getenv("VSR_BF16_A16")) h->bf16_a16 = atoi(e);
-    if (const char* e = getenv("VSR_BF16_P_FP32")) h->bf16_p_fp32 = atoi(e);
-    if (const char* e = getenv("VSR_GEMM_ALIGNED_MIN")) h->gemm_aligned_min = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_SLOTS")) h->gemm_slots = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_SLOTS_SMALL")) h->gemm_slots_small = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_TILE")) h->gemm_tile = atoi(e);
-    if (const char* e = getenv("VSR_XCD_GROUPS")) h->xcd_groups = atoi(e);
     if (const char* e = getenv("VSR_SPLIT_PRE1")) h->split_pre1 = atoi(e);
     if (const char* e = getenv("VSR_ATTEND_PARTS")) h->attend_parts = std::max(1, atoi(e));
     if (const char* e = getenv("VSR_ATTEND_LIMIT")) h->attend_limit = std::max(1, atoi(e));
-    if (const char* e = getenv("VSR_GEMM_MIN_ITERS")) h->gemm_min_iters = std::max(1, atoi(e));
     *out = h;
     return 0;
 }
@@ -1188,7 +795,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     float *h1n = sn[0], *c1n = sn[1], *h2n = sn[2], *c2n = sn[3];
     // bf16 images of the A operands (bf16 mode): the producers below write them, the GEMM segments name them
     // ... or fp16-pair images (f16x2 flavour, gemm_h2a.h): isc = the scale of the unit-bounded ones (2^15), the attended vector's from the table
-    const bool sh2 = h->h2_on && !h->bf16_on && h->x3_on && h->h2_aimg;
+    const bool sh2 = h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg;
     const bool sh = (h->bf16_on && h->bf16_a16) || sh2;
     const float isc = sh2 ? 32768.f : 0.f;
     const int* att_exp = sh2 ? h->h2_exps + H2A_ATT : nullptr;
