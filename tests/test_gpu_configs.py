@@ -334,7 +334,10 @@ def test_prepare_cache_invalidation():
                                  dict(VSR_GEMM_SLOTS="384", VSR_GEMM_MIN_ITERS="4"),
                                  # round 6: the launch compositions / plans that are NOT the default stay token-exact too
                                  dict(VSR_SPLIT_PRE1="0"), dict(VSR_ATTEND_PARTS="1"), dict(VSR_XCD_GROUPS="1"),
-                                 dict(VSR_H2_ALIGNED_MIN_SMALL="4")])
+                                 dict(VSR_H2_ALIGNED_MIN_SMALL="4"),
+                                 # stream-K ranges so short that the split composition of S5 / S6 does not fit pre1's 8 slabs in the exact-fp32
+                                 # flavour (3-4 slabs for the h1 pair + 8 for the h2 part at all three shapes): run_step falls back to round 5's
+                                 dict(VSR_GEMM_SLOTS_SMALL="4096", VSR_GEMM_SLOTS_R16="2048", VSR_GEMM_MIN_ITERS="4")])
 def test_gemm_kernel_variants_keep_token_parity(env, monkeypatch):
     """The tile / kernel overrides read by vsr_create (64x64, 128x64, 128x128 tiles of the 32x32x2 kernel; the rows-16
     16x16x4 kernel up to 0 / 256 / 512 rows; other stream-K grids) change the summation order, never the tokens: greedy on

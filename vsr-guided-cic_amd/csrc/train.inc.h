@@ -364,7 +364,6 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
     const int B = c.B, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
-    const int in1 = (d.h2_first_lstm ? H : 0) + D + E, xoff = (d.h2_first_lstm ? H : 0) + D, in2 = H + D + (d.img_second_lstm ? D : 0);
     TrainCtx& t = *h->tc;
     t.valid = false;
     t.B = B; t.T = T;
@@ -385,19 +384,17 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
         if (im) { zl.add(t.h1s16, BH * 2 * sizeof(uint16_t)); zl.add(t.h2s16, BH * 2 * sizeof(uint16_t)); }
         if (zl.launch(s)) return fail("vsr_train_forward: zero launch failed");
     }
+    StepOperands all;                                      // the operands of the two launches over all T B rows (step_gemms.h)
+    all.M = TB;
+    // (with images: the rows are gathered from the embedding table's image by the GEMM itself)
+    all.x = im ? w.embed_weight : t.x_all; all.word = im ? t.word32 : nullptr;
+    all.h2_new = t.h2s; all.h2_new16 = im ? t.h2s16 : nullptr;
     hipLaunchKernelGGL(k_train_indices, dim3(cdiv(TB, 256)), dim3(256), 0, s, word_in, slots, T, B, V, c.L, t.word32, t.slot32, t.rows_bt, c.nvalid_dev + 2);
     hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((long long)TB * E, 256)), dim3(256), 0, s, w.embed_weight, t.word32, TB, E, t.x_all);
     LAUNCHCHK();
     {   // the x part of every step's LSTM1 / gate pre-activations does not depend on the recurrence: one GEMM with M = T B
         GemmBuilder g;
-        const float* Wih[3] = {w.lstm1_weight_ih, w.W1_is_weight, w.W1_ig_weight};
-        const int Nn[3] = {4 * H, H, H}, off[3] = {0, 4 * H, 5 * H};
-        for (int i = 0; i < 3; ++i) {
-            GemmProb& p = g.prob(TB, Nn[i], t.scratch + off[i], 6 * H);
-            // (with images: the rows are gathered from the embedding table's image by the GEMM itself)
-            if (im) GemmBuilder::seg(p, w.embed_weight, E, t.word32, Wih[i] + xoff, in1, E, nullptr, H2A_EMBED);
-            else GemmBuilder::seg(p, t.x_all, E, nullptr, Wih[i] + xoff, in1, E, nullptr, H2A_EMBED);
-        }
+        add_lstm1(g, d, w, all, t.scratch, L1_X);
         const int ns = g.finish(h);
         const long long stride = (long long)TB * 6 * H;
         if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
@@ -416,23 +413,19 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
         float *hA = t.hAs + (size_t)tt * B * A, *sa = t.sas + (size_t)tt * B * A, *ga = t.gas + (size_t)tt * B * A;
         float *sent = t.sents + (size_t)tt * B * D, *att = t.atts + (size_t)tt * B * D, *alpha = t.alphas + (size_t)tt * B * (c.R + 1);
         const int* slot = t.slot32 + (size_t)tt * B;
-        const uint16_t *h1o16 = im ? t.h1s16 + (size_t)tt * BH * 2 : nullptr, *h2o16 = im ? t.h2s16 + (size_t)tt * BH * 2 : nullptr;
         uint16_t *h1n16 = im ? t.h1s16 + (size_t)(tt + 1) * BH * 2 : nullptr, *h2n16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
         uint16_t *s_t16 = im ? t.s_t16 : nullptr, *g_t16 = im ? t.g_t16 : nullptr, *att16 = im ? t.att16 : nullptr;
+        StepOperands o;
+        o.M = B;
+        o.h1_old = h1o; o.h2_old = h2o; o.h1_new = h1n; o.h2_new = h2n; o.s_t = s_t; o.g_t = g_t; o.att = att;
+        if (im) { o.h1_old16 = t.h1s16 + (size_t)tt * BH * 2; o.h2_old16 = t.h2s16 + (size_t)tt * BH * 2; }
+        o.h1_new16 = h1n16; o.h2_new16 = h2n16; o.s_t16 = s_t16; o.g_t16 = g_t16; o.att16 = att16;
         {   // S1: the recurrent parts only (h2, h1 of the previous step); nothing to multiply at step 0
             int ns = 0;
             const long long stride = (long long)B * 6 * H;
             if (tt > 0) {
                 GemmBuilder g;
-                const float* Wih[3] = {w.lstm1_weight_ih, w.W1_is_weight, w.W1_ig_weight};
-                const float* Whh[3] = {w.lstm1_weight_hh, w.W1_hs_weight, nullptr};
-                const int Nn[3] = {4 * H, H, H}, off[3] = {0, 4 * H, 5 * H};
-                for (int i = 0; i < 3; ++i) {
-                    if (!d.h2_first_lstm && !Whh[i]) continue;
-                    GemmProb& p = g.prob(B, Nn[i], c.scratch + off[i], 6 * H);
-                    if (d.h2_first_lstm) GemmBuilder::seg(p, h2o, H, nullptr, Wih[i], in1, H, h2o16, H2A_UNIT);
-                    if (Whh[i]) GemmBuilder::seg(p, h1o, H, nullptr, Whh[i], H, H, h1o16, H2A_UNIT);
-                }
+                add_lstm1(g, d, w, o, c.scratch, L1_H2 | L1_H1);
                 ns = g.finish(h);
                 for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
                 if (g.launch(s, h)) return fail("train S1 gemm launch failed");
@@ -443,43 +436,20 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
         }
         {   // S2
             GemmBuilder g;
-            GemmProb& p0 = g.prob(B, H, c.scratch, H + A);
-            GemmBuilder::seg(p0, h1n, H, nullptr, w.W1_hg_weight, H, H, h1n16, H2A_UNIT);
-            GemmProb& p1 = g.prob(B, A, c.scratch + H, H + A);
-            GemmBuilder::seg(p1, h1n, H, nullptr, w.att_ha_weight, H, H, h1n16, H2A_UNIT);
-            GemmProb& p2 = g.prob(B, D, nullptr, D + A);
-            GemmBuilder::seg(p2, s_t, H, nullptr, w.s_fc_weight, H, H, s_t16, H2A_UNIT);
-            GemmProb& p3 = g.prob(B, A, nullptr, D + A);
-            GemmBuilder::seg(p3, s_t, H, nullptr, w.att_sa_weight, H, H, s_t16, H2A_UNIT);
+            add_s2(g, d, w, o, c.scratch);
             const int ns = g.finish(h);
-            const long long stride_a = (long long)B * (H + A), stride_b = (long long)B * (D + A);
-            float* c2b = c.scratch + stride_a * ns;
-            g.a.p[0].slab_stride = g.a.p[1].slab_stride = stride_a;
-            g.a.p[2].C = c2b; g.a.p[3].C = c2b + D;
-            g.a.p[2].slab_stride = g.a.p[3].slab_stride = stride_b;
+            const S2Layout l = place_s2(g, d, B, c.scratch, ns);
             if (g.launch(s, h)) return fail("train S2 gemm launch failed");
             // (Round 5: k_gate2's work inside the attention kernel's row blocks, as in decoding, with the sentinel / s_a / the shift gate stored
             // on the way for the backward pass: measured at no gain - 10.99-11.06 k against 10.85-11.10 k samples/s, profiles/r05_h_* - and not kept.)
             const long long n = (long long)B * (H + A + D + A);
-            hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, c2b, ns, stride_a, stride_b, c.gpre, c1n, w.s_fc_bias,
+            hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias,
                                B, H, A, D, g_t, hA, sent, sa, g1, g_t16, isc);
         }
-        {
-            const size_t smem = (size_t)(2 * A + D + c.R + 1 + 8 + c.R) * sizeof(float);
-            const int np = (h->attend_parts > 1 && B * h->attend_parts <= h->attend_limit && D % (4 * h->attend_parts) == 0) ? h->attend_parts : 1;      // (as in run_step)
-            if (D >= 2048) hipLaunchKernelGGL(k_attend<512>, dim3(cdiv(B * np, 8) * 8), dim3(512), smem, s, Gate2Args{}, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx, slot, 0, 1, B, c.L,
-                               c.R, A, D, w.att_a_weight, w.att_s_weight, att, c.zsum, alpha, att16, att_exp, np);
-            else hipLaunchKernelGGL(k_attend<256>, dim3(cdiv(B * np, 8) * 8), dim3(256), smem, s, Gate2Args{}, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx, slot, 0, 1, B, c.L,
-                               c.R, A, D, w.att_a_weight, w.att_s_weight, att, c.zsum, alpha, att16, att_exp, np);
-        }
+        launch_attend(h, s, Gate2Args{}, B, 1, slot, 0, hA, sa, sent, att, alpha, att16, att_exp);
         {   // S5
             GemmBuilder g;
-            GemmProb& p0 = g.prob(B, 4 * H, c.scratch, 4 * H);
-            GemmBuilder::seg(p0, h1n, H, nullptr, w.lstm2_weight_ih, in2, H, h1n16, H2A_UNIT);
-            GemmBuilder::seg(p0, att, D, nullptr, w.lstm2_weight_ih + H, in2, D, att16, H2A_ATT);
-            if (tt > 0) GemmBuilder::seg(p0, h2o, H, nullptr, w.lstm2_weight_hh, H, H, h2o16, H2A_UNIT);
-            GemmProb& p1 = g.prob(B, A, nullptr, A);
-            GemmBuilder::seg(p1, g_t, H, nullptr, w.att_ga_weight, H, H, g_t16, H2A_UNIT);
+            add_s5(g, d, w, o, c.scratch, tt > 0);
             const int ns = g.finish(h);
             const long long stride = (long long)B * 4 * H, stride_g = (long long)B * A;
             float* gas = c.scratch + stride * ns;
@@ -498,21 +468,16 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
     {   // S6 for all steps at once: logits = h2[(b, t)] . out_fc^T (M = T B rows gathered in (b, t) order, so that the
         // (B, T, V) log-prob tensor is written row by row), then one log_softmax launch
         GemmBuilder g;
-        GemmProb& p0 = g.prob(TB, V, t.scratch, V);
-        GemmBuilder::seg(p0, t.h2s, H, t.rows_bt, w.out_fc_weight, H, H, im ? t.h2s16 : nullptr, H2A_UNIT);
+        add_vocab(g, d, w, all, t.scratch, t.rows_bt);
         const int ns = g.finish(h);
         const long long stride = (long long)TB * V;
         if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns);
         g.a.p[0].slab_stride = stride;
         if (g.launch(s, h)) return fail("train S6 gemm launch failed");
-        const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;
-        const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
         const GateLogitArgs no_gate{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr, 0};
-#define TRAIN_VOCAB_ARGS t.scratch, ns, stride, w.out_fc_bias, TB, V, (int)VM_FULL, c.top_v, c.top_i, logp_words, (long long)V, (const int*)nullptr, \
-                         (uint64_t)0, (uint32_t)0, (const float*)nullptr, (const int*)nullptr, 1, c.L, 0, h->vt_ptr, h->vt_ids, h->n_verbs, lds_row, no_gate, c.nvalid_dev + 2
-        if (V >= 4096) hipLaunchKernelGGL((k_vocab<1, 512>), dim3(TB), dim3(512), vsm, s, TRAIN_VOCAB_ARGS);
-        else hipLaunchKernelGGL((k_vocab<1, 256>), dim3(TB), dim3(256), vsm, s, TRAIN_VOCAB_ARGS);
-#undef TRAIN_VOCAB_ARGS
+        StepIO io;                                         // (K = 1, no gate logits: the whole log_softmax rows)
+        io.M = TB; io.vmode = VM_FULL; io.full_out = logp_words; io.full_stride = V;
+        launch_vocab(h, s, io, t.scratch, ns, stride, no_gate);
         LAUNCHCHK();
     }
     t.logp_w = logp_words;
@@ -714,8 +679,7 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
                                t.dalpha);
             // two workgroups per row in launches of <= 128 rows (as k_attend): half the A columns each, its 512 threads = 256 columns x 2 row groups
             const int NTb = A >= 512 ? 512 : 256;
-            int np = (h->attend_parts > 1 && B * h->attend_parts <= h->attend_limit && A % h->attend_parts == 0 && D % (4 * h->attend_parts) == 0) ? h->attend_parts : 1;
-            if (np > 1 && (NTb % (A / np) != 0 || NTb / (A / np) < 1 || (A / np) > NTb)) np = 1;
+            const int np = attend_bwd_parts(h, B, NTb);
             const int RG = np > 1 ? NTb / (A / np) : 1;
             const size_t smem = (size_t)(R1 + 8 + (np > 1 ? (RG - 1) * (A / np) * 2 : 0)) * sizeof(float);
             if (A >= 512) hipLaunchKernelGGL(k_attend_bwd<512>, dim3(cdiv(B * np, 8) * 8), dim3(512), smem, s, t.datt, t.dalpha, t.dzsum, alpha, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx,

@@ -1,6 +1,7 @@
 // libvsrcap.so - C ABI + per-timestep orchestration of the VSR captioning decoder on gfx950.
 // Entry points are declared in include/vsrcap.h; reference behaviour cited there and in kernels.h.  GEMM routing (which kernel, tile and
-// k plan a launch takes; the VSR_* routing knobs) lives in gemm_route.h, the kernel switch in gemm_dispatch.h.
+// k plan a launch takes; the VSR_* routing knobs) lives in gemm_route.h, the kernel switch in gemm_dispatch.h, the problem lists of the
+// step's launches (shared with the training forward) in step_gemms.h.
 //
 // One decoder timestep = 4 grouped fp32-MFMA GEMM launches + 5 small kernels, all on the caller's stream:
 //   S1  [h2 | x | h1_old] -> LSTM1 gates (4H) | sentinel gate (H) | shift-gate image part (H)      gemm
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "gemm_route.h"
+#include "step_gemms.h"
 #include "kernels.h"
 #include "train_kernels.h"
 
@@ -760,18 +762,18 @@ extern "C" int vsr_reorder_slots(const int32_t* slot_idx, const int32_t* rank, c
 
 // ---------------------------------------------------------------------------------------------- one timestep
 struct StepIO {
-    int t, M, rpi, cur;
-    const int* parent;       // state-row gather (beam parents) or null
-    const int* word_prev;    // (M) int32
-    const int* slot;         // (M) int32 or null -> fixed_slot
-    int fixed_slot;
-    int vmode, K;
-    float* full_out; long long full_stride;
-    const int* forced;
-    uint64_t seed;
-    const float* verbs; int gt;
-    float* lg_out; long long lg_stride;
-    float* alpha_out;
+    int t = 0, M = 0, rpi = 1, cur = 0;
+    const int* parent = nullptr;       // state-row gather (beam parents) or null
+    const int* word_prev = nullptr;    // (M) int32
+    const int* slot = nullptr;         // (M) int32 or null -> fixed_slot
+    int fixed_slot = 0;
+    int vmode = VM_TOPK, K = 1;
+    float* full_out = nullptr; long long full_stride = 0;
+    const int* forced = nullptr;
+    uint64_t seed = 0;
+    const float* verbs = nullptr; int gt = 0;
+    float* lg_out = nullptr; long long lg_stride = 2;
+    float* alpha_out = nullptr;
     bool s1_from_prev = false;   // this step's LSTM1 sums are already in c.pre1 (computed over the parent rows)
     // the selection of the PREVIOUS step, still to be made: it rides in this step's LSTM1 kernel (k_select_lstm1 / k_select_simple_lstm1;
     // only with s1_from_prev).  sel_images: images of the beam selection (its parents are sel_beam->cb rows per image).
@@ -780,18 +782,54 @@ struct StepIO {
     bool s1_for_next = false;    // compute the next step's LSTM1 sums together with this step's vocabulary GEMM
 };
 
+// Workgroups per row of k_attend.  Launches of <= 128 rows: two workgroups per row (each forms half of the attended vector's columns): every
+// row's ~370 KB then come in through two CUs' ingest instead of one while the other half of the chip idles (k_attend, nparts; VSR_ATTEND_PARTS=1: off)
+static int attend_parts(const vsr_handle* h, int M) {
+    const int np = h->attend_parts;
+    return (np > 1 && M * np <= h->attend_limit && h->d.det_feat_size % (4 * np) == 0) ? np : 1;
+}
+// ... and of k_attend_bwd (NT threads): a part also takes A / parts of the A columns, and its threads are those columns x whole row groups
+static int attend_bwd_parts(const vsr_handle* h, int M, int NT) {
+    const int np = attend_parts(h, M), A = h->d.att_size;
+    return (np > 1 && A % np == 0 && NT % (A / np) == 0) ? np : 1;
+}
+static void launch_attend(vsr_handle* h, hipStream_t s, const Gate2Args& g2, int M, int rpi, const int* slot, int fixed_slot, const float* hA,
+                          const float* sa, const float* sent, float* att, float* alpha_out, uint16_t* att16, const int* att_exp) {
+    const Ctx& c = h->c;
+    const int A = h->d.att_size, D = h->d.det_feat_size, np = attend_parts(h, M);
+    const size_t smem = (size_t)(2 * A + D + c.R + 1 + 8 + c.R) * sizeof(float);
+    auto go = [&](auto NT) {
+        hipLaunchKernelGGL(k_attend<decltype(NT)::value>, dim3(cdiv(M * np, 8) * 8), dim3(decltype(NT)::value), smem, s, g2, hA, sa, sent, c.P, c.regions,
+                           c.rmask, c.ridx, slot, fixed_slot, rpi, M, c.L, c.R, A, D, h->w.att_a_weight, h->w.att_s_weight, att, c.zsum, alpha_out, att16, att_exp, np);
+    };
+    if (D >= 2048) go(std::integral_constant<int, 512>{}); else go(std::integral_constant<int, 256>{});
+}
+// k_vocab over the io.M rows of `logits` (ns slabs): K = io.K exactly (fewer selection rounds than rounding up to a power of two); 512
+// threads per row from V = 4096 up
+static void launch_vocab(vsr_handle* h, hipStream_t s, const StepIO& io, const float* logits, int ns, long long stride, const GateLogitArgs& gate) {
+    const Ctx& c = h->c;
+    const int V = h->d.vocab_size;
+    const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;          // combined logits row staged in LDS (<= 96 KB)
+    const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
+    with_const_1to8(io.K, [&](auto KK) {
+        auto go = [&](auto NT) {
+            hipLaunchKernelGGL((k_vocab<decltype(KK)::value, decltype(NT)::value>), dim3(io.M), dim3(decltype(NT)::value), vsm, s, logits, ns, stride, h->w.out_fc_bias,
+                               io.M, V, io.vmode, c.top_v, c.top_i, io.full_out, io.full_stride, io.forced, io.seed, (uint32_t)io.t, io.verbs, io.slot, io.rpi, c.L,
+                               io.gt, h->vt_ptr, h->vt_ids, h->n_verbs, lds_row, gate, c.nvalid_dev + 2);
+        };
+        if (V >= 4096) go(std::integral_constant<int, 512>{}); else go(std::integral_constant<int, 256>{});
+    });
+}
+
 static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
     Ctx& c = h->c;
-    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
+    const int H = d.rnn_size, A = d.att_size, V = d.vocab_size;
     const int M = io.M;
-    const int in1 = (d.h2_first_lstm ? H : 0) + D + E;
-    const int xoff = (d.h2_first_lstm ? H : 0) + D;
-    const int in2 = H + D + (d.img_second_lstm ? D : 0);
     float* const* so = c.st[io.cur];          // old state
     float* const* sn = c.st[io.cur ^ 1];      // new state
-    float *h1o = so[0], *c1o = so[1], *h2o = so[2], *c2o = so[3];
+    float *c1o = so[1], *c2o = so[3];
     float *h1n = sn[0], *c1n = sn[1], *h2n = sn[2], *c2n = sn[3];
     // bf16 images of the A operands (bf16 mode): the producers below write them, the GEMM segments name them
     // ... or fp16-pair images (f16x2 flavour, gemm_h2a.h): isc = the scale of the unit-bounded ones (2^15), the attended vector's from the table
@@ -801,20 +839,22 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     const int* att_exp = sh2 ? h->h2_exps + H2A_ATT : nullptr;
     const bool sh_old = sh && c.st16_ok[io.cur];
     uint16_t *h1n16 = sh ? c.st16[io.cur ^ 1][0] : nullptr, *h2n16 = sh ? c.st16[io.cur ^ 1][1] : nullptr;
-    const uint16_t *h1o16 = sh_old ? c.st16[io.cur][0] : nullptr, *h2o16 = sh_old ? c.st16[io.cur][1] : nullptr;
     uint16_t *s_t16 = sh ? c.s_t16 : nullptr, *g_t16 = sh ? c.g_t16 : nullptr, *att16 = sh ? c.att16 : nullptr;
+    StepOperands o;                           // what the step's GEMMs multiply (step_gemms.h)
+    o.M = M; o.parent = io.parent; o.x = w.embed_weight; o.word = io.word_prev;
+    o.h1_old = so[0]; o.h2_old = so[2]; o.h1_new = h1n; o.h2_new = h2n; o.s_t = c.s_t; o.g_t = c.g_t; o.att = c.att;
+    o.h1_old16 = sh_old ? c.st16[io.cur][0] : nullptr; o.h2_old16 = sh_old ? c.st16[io.cur][1] : nullptr;
+    o.h1_new16 = h1n16; o.h2_new16 = h2n16; o.s_t16 = s_t16; o.g_t16 = g_t16; o.att16 = att16;
+    const long long stride1 = (long long)M * 6 * H;      // a slab of the LSTM1 / gate sums
 
     // ---- S1
     if (io.s1_from_prev && io.sel_beam) {
         const SelBeamArgs& sb = *io.sel_beam;
         const int nslice = cdiv(H, SL_UB);
-#define SELL_LAUNCH(KK) hipLaunchKernelGGL((k_select_lstm1<KK>), dim3(sb.B * nslice), dim3((KK + 1) * 64), 0, s, sb, c.pre1, c.pre1_ns, c.pre1_stride, c.vproj, \
-                                           c1o, H, nslice, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5); break;
-        switch (sb.beam) {
-            case 1: SELL_LAUNCH(1) case 2: SELL_LAUNCH(2) case 3: SELL_LAUNCH(3) case 4: SELL_LAUNCH(4)
-            case 5: SELL_LAUNCH(5) case 6: SELL_LAUNCH(6) case 7: SELL_LAUNCH(7) default: SELL_LAUNCH(8)
-        }
-#undef SELL_LAUNCH
+        with_const_1to8(sb.beam, [&](auto KK) {
+            hipLaunchKernelGGL((k_select_lstm1<decltype(KK)::value>), dim3(sb.B * nslice), dim3((decltype(KK)::value + 1) * 64), 0, s, sb, c.pre1, c.pre1_ns, c.pre1_stride,
+                               c.vproj, c1o, H, nslice, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5);
+        });
     } else if (io.s1_from_prev && io.sel_simple) {
         hipLaunchKernelGGL(k_select_simple_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, *io.sel_simple, c.pre1, c.pre1_ns, c.pre1_stride,
                            c.vproj, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5);
@@ -822,119 +862,69 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
         hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.pre1, c.pre1_ns, c.pre1_stride, c.vproj, io.rpi,
                            io.parent, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, io.word_prev, c.pre1_nblk, 1, h1n16, s_t16, isc, c.pre1_skip5);
     } else {
-        const bool xc = h->xproj != nullptr;            // embedding part comes from the decode cache
+        // the state parts from step 1 on; the embedding part unless it comes from the decode cache
         GemmBuilder g;
-        const float* Wih[3] = {w.lstm1_weight_ih, w.W1_is_weight, w.W1_ig_weight};
-        const float* Whh[3] = {w.lstm1_weight_hh, w.W1_hs_weight, nullptr};
-        const int Nn[3] = {4 * H, H, H};
-        const int off[3] = {0, 4 * H, 5 * H};
-        int nblk = 0;
-        for (int i = 0; i < 3; ++i) {
-            const bool has_h2 = d.h2_first_lstm && io.t > 0, has_x = !xc, has_h1 = Whh[i] && io.t > 0;
-            if (!has_h2 && !has_x && !has_h1) continue;
-            GemmProb& p = g.prob(M, Nn[i], c.scratch + off[i], 6 * H);
-            if (has_h2) GemmBuilder::seg(p, h2o, H, io.parent, Wih[i], in1, H, h2o16, H2A_UNIT);
-            if (has_x) GemmBuilder::seg(p, w.embed_weight, E, io.word_prev, Wih[i] + xoff, in1, E, nullptr, H2A_EMBED);
-            if (has_h1) GemmBuilder::seg(p, h1o, H, io.parent, Whh[i], H, H, h1o16, H2A_UNIT);
-            nblk = i == 0 ? 4 : i == 1 ? 5 : 6;
-        }
+        const int nblk = add_lstm1(g, d, w, o, c.scratch, (io.t > 0 ? L1_H2 | L1_H1 : 0) | (h->xproj ? 0 : L1_X));
         int ns = 0;
-        const long long stride = (long long)M * 6 * H;
         if (g.a.nprob > 0) {
             ns = g.finish(h);
-            for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
+            for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride1;
             if (g.launch(s, h)) return fail("S1 gemm launch failed");
         }
-        hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj, io.rpi,
+        hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns, stride1, c.vproj, io.rpi,
                            io.parent, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, io.word_prev, nblk, 0, h1n16, s_t16, isc);
     }
     // ---- S2
     {
         GemmBuilder g;
-        float* c2a = c.scratch;
-        float* c2b_base;
-        GemmProb& p0 = g.prob(M, H, c2a, H + A);
-        GemmBuilder::seg(p0, h1n, H, nullptr, w.W1_hg_weight, H, H, h1n16, H2A_UNIT);
-        GemmProb& p1 = g.prob(M, A, c2a + H, H + A);
-        GemmBuilder::seg(p1, h1n, H, nullptr, w.att_ha_weight, H, H, h1n16, H2A_UNIT);
-        GemmProb& p2 = g.prob(M, D, nullptr, D + A);
-        GemmBuilder::seg(p2, c.s_t, H, nullptr, w.s_fc_weight, H, H, s_t16, H2A_UNIT);
-        GemmProb& p3 = g.prob(M, A, nullptr, D + A);
-        GemmBuilder::seg(p3, c.s_t, H, nullptr, w.att_sa_weight, H, H, s_t16, H2A_UNIT);
+        add_s2(g, d, w, o, c.scratch);
         const int ns = g.finish(h);
-        const long long stride_a = (long long)M * (H + A), stride_b = (long long)M * (D + A);
-        c2b_base = c2a + stride_a * ns;
-        g.a.p[0].slab_stride = g.a.p[1].slab_stride = stride_a;
-        g.a.p[2].C = c2b_base; g.a.p[3].C = c2b_base + D;
-        g.a.p[2].slab_stride = g.a.p[3].slab_stride = stride_b;
+        const S2Layout l = place_s2(g, d, M, c.scratch, ns);
         if (g.launch(s, h)) return fail("S2 gemm launch failed");
         // k_gate2's work (g_t, hA, s_a, sentinel from the S2 slabs) is done by the attention kernel's row blocks themselves
-        const Gate2Args g2{c2a, c2b_base, ns, stride_a, stride_b, c.gpre, c1n, w.s_fc_bias, H, c.g_t, c.hA, g_t16, isc};
-        const size_t smem = (size_t)(2 * A + D + c.R + 1 + 8 + c.R) * sizeof(float);
-        // launches of <= 128 rows: two workgroups per row (each forms half of the attended vector's columns): every row's ~370 KB then come in
-        // through two CUs' ingest instead of one while the other half of the chip idles (k_attend, nparts; VSR_ATTEND_PARTS=1: off)
-        const int np = (h->attend_parts > 1 && M * h->attend_parts <= h->attend_limit && D % (4 * h->attend_parts) == 0) ? h->attend_parts : 1;
-        if (D >= 2048) hipLaunchKernelGGL(k_attend<512>, dim3(cdiv(M * np, 8) * 8), dim3(512), smem, s, g2, c.hA, c.sa, c.sent, c.P, c.regions, c.rmask, c.ridx, io.slot,
-                           io.fixed_slot, io.rpi, M, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, c.att, c.zsum, io.alpha_out, att16, att_exp, np);
-        else hipLaunchKernelGGL(k_attend<256>, dim3(cdiv(M * np, 8) * 8), dim3(256), smem, s, g2, c.hA, c.sa, c.sent, c.P, c.regions, c.rmask, c.ridx, io.slot,
-                           io.fixed_slot, io.rpi, M, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, c.att, c.zsum, io.alpha_out, att16, att_exp, np);
+        const Gate2Args g2{c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias, H, c.g_t, c.hA, g_t16, isc};
+        launch_attend(h, s, g2, M, io.rpi, io.slot, io.fixed_slot, c.hA, c.sa, c.sent, c.att, io.alpha_out, att16, att_exp);
     }
+    // ---- S5 and S6 are planned together, before either is launched.
+    // S6 = the vocabulary problem + (s1_for_next) the LSTM1 / gate sums of step t+1 over THIS step's rows: they depend on (h2, h1) only (the
+    // word enters through the decode cache, the beam re-indexing through k_lstm1's parent gather), so they ride in the same launch as the
+    // vocabulary projection: 3 GEMM launches per timestep instead of 4, and a longer stream-K range per workgroup.
+    // Round 6 (split_pre1): the h1 part of those sums (h1_new . [W_hh1 ; W1_hs]) rides in S5 instead: S5's k-aligned plan left 56 of 256 CUs
+    // idle (64 LSTM2 tiles x 3 pieces + 8 att_ga tiles), and without these K = H tiles the vocabulary launch is UNIFORM (every tile K = H:
+    // one k-aligned piece per tile, no slabs at all).  Measured on the beam-5 shapes (tools/gemm_bench GEMM_REPACK=1, profiles/r06_e_*):
+    // 148-153 -> 133 us for the two launches.  Both parts land in the 8 slabs of pre1 - S5's in the leading ns_h1, S6's behind them: when
+    // the two plans would not fit (the exact-fp32 flavour cuts its 64 x 64 tiles into up to 8 stream-K pieces) both launches are planned
+    // again in the round-5 composition.
+    GemmBuilder g5, g6;
+    int ns5 = 0, ns6 = 0, ns_h1 = 0, ns_pre1 = 1, nblk6 = 0;
+    auto plan56 = [&](bool split) {
+        g5 = GemmBuilder(); g6 = GemmBuilder();
+        add_s5(g5, d, w, o, c.scratch, io.t > 0);
+        if (split) add_lstm1(g5, d, w, o, c.pre1, L1_NEXT | L1_H1);
+        add_vocab(g6, d, w, o, c.scratch);
+        nblk6 = io.s1_for_next ? add_lstm1(g6, d, w, o, c.pre1, L1_NEXT | L1_H2 | (split ? 0 : L1_H1)) : 0;
+        ns5 = g5.finish(h); ns6 = g6.finish(h);
+        // the LSTM1 / gate problems write (and k_lstm1 adds) only the slabs THEIR tiles can meet - all of a launch's get the largest of
+        // their counts, k_lstm1 takes one count for its six gate blocks
+        ns_h1 = 0; ns_pre1 = 1;
+        for (int i = 2; i < g5.a.nprob; ++i) ns_h1 = std::max(ns_h1, gemm_tight_slabs(g5.a, i));
+        for (int i = 1; i < g6.a.nprob; ++i) ns_pre1 = std::max(ns_pre1, gemm_tight_slabs(g6.a, i));
+    };
+    plan56(io.s1_for_next && h->split_pre1 && d.h2_first_lstm);
+    if (ns_h1 > 0 && ns_h1 + ns_pre1 > 8) plan56(false);
     // ---- S5
     GateLogitArgs gate_args;
     {
-        GemmBuilder g;
-        GemmProb& p0 = g.prob(M, 4 * H, c.scratch, 4 * H);
-        GemmBuilder::seg(p0, h1n, H, nullptr, w.lstm2_weight_ih, in2, H, h1n16, H2A_UNIT);
-        GemmBuilder::seg(p0, c.att, D, nullptr, w.lstm2_weight_ih + H, in2, D, att16, H2A_ATT);
-        if (io.t > 0) GemmBuilder::seg(p0, h2o, H, io.parent, w.lstm2_weight_hh, H, H, h2o16, H2A_UNIT);
-        GemmProb& p1 = g.prob(M, A, nullptr, A);
-        GemmBuilder::seg(p1, c.g_t, H, nullptr, w.att_ga_weight, H, H, g_t16, H2A_UNIT);
-        // Round 6 (split_pre1): the h1 part of the NEXT step's LSTM1 / sentinel-gate sums (h1_new . [W_hh1 ; W1_hs]) rides HERE instead
-        // of in the vocabulary launch: S5's k-aligned plan left 56 of 256 CUs idle (64 LSTM2 tiles x 3 pieces + 8 att_ga tiles), and
-        // without these K = H tiles the vocabulary launch is UNIFORM (every tile K = H: one k-aligned piece per tile, no slabs at all).
-        // Measured on the beam-5 shapes (tools/gemm_bench GEMM_REPACK=1, profiles/r06_e_*): 148-153 -> 133 us for the two launches.
-        bool split_pre1 = io.s1_for_next && h->split_pre1 && d.h2_first_lstm;
-        int ns_h1 = 0;
-        auto add_h1 = [&](GemmBuilder& gb) {
-            GemmProb& p2 = gb.prob(M, 4 * H, c.pre1, 6 * H);
-            GemmBuilder::seg(p2, h1n, H, nullptr, w.lstm1_weight_hh, H, H, h1n16, H2A_UNIT);
-            GemmProb& p3 = gb.prob(M, H, c.pre1 + 4 * H, 6 * H);
-            GemmBuilder::seg(p3, h1n, H, nullptr, w.W1_hs_weight, H, H, h1n16, H2A_UNIT);
-        };
-        if (split_pre1) {
-            // both parts land in the 8 slabs of pre1: plan the two launches first and keep the round-5 composition when they would not fit
-            // (the exact-fp32 flavour cuts its 64 x 64 tiles into up to 8 stream-K pieces)
-            GemmBuilder t5 = g, t6;
-            add_h1(t5);
-            t5.finish(h);
-            GemmProb& q0 = t6.prob(M, V, c.scratch, V);
-            GemmBuilder::seg(q0, h2n, H, nullptr, w.out_fc_weight, H, H, h2n16, H2A_UNIT);
-            const float* Wih[3] = {w.lstm1_weight_ih, w.W1_is_weight, w.W1_ig_weight};
-            const int Nn[3] = {4 * H, H, H};
-            for (int i = 0; i < 3; ++i) {
-                GemmProb& q = t6.prob(M, Nn[i], c.pre1, 6 * H);
-                GemmBuilder::seg(q, h2n, H, nullptr, Wih[i], in1, H, h2n16, H2A_UNIT);
-            }
-            t6.finish(h);
-            int n6 = 1;
-            for (int i = 1; i < 4; ++i) n6 = std::max(n6, gemm_tight_slabs(t6.a, i));
-            if (std::max(gemm_tight_slabs(t5.a, 2), gemm_tight_slabs(t5.a, 3)) + n6 > 8) split_pre1 = false;
-        }
-        if (split_pre1) add_h1(g);
-        const int ns = g.finish(h);
+        GemmBuilder& g = g5;
         const long long stride = (long long)M * 4 * H, stride_g = (long long)M * A;
         g.a.p[0].slab_stride = stride;
         g.a.p[0].nslab = gemm_tight_slabs(g.a, 0);
         g.a.p[1].C = c.ga_slabs; g.a.p[1].slab_stride = stride_g;
         g.a.p[1].nslab = gemm_tight_slabs(g.a, 1);
-        if (split_pre1) {
-            ns_h1 = std::max(gemm_tight_slabs(g.a, 2), gemm_tight_slabs(g.a, 3));
-            g.a.p[2].slab_stride = g.a.p[3].slab_stride = (long long)M * 6 * H;
-            g.a.p[2].nslab = g.a.p[3].nslab = ns_h1;
-        }
+        for (int i = 2; i < g.a.nprob; ++i) { g.a.p[i].slab_stride = stride1; g.a.p[i].nslab = ns_h1; }
         c.pre1_skip5 = ns_h1;
         const int ns_lstm2 = g.a.p[0].nslab;
-        if ((size_t)stride * ns > c.scratch_floats) return fail("S5: slabs exceed the workspace scratch");
+        if ((size_t)stride * ns5 > c.scratch_floats) return fail("S5: slabs exceed the workspace scratch");
         if (g.launch(s, h)) return fail("S5 gemm launch failed");
         hipLaunchKernelGGL(k_lstm2, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns_lstm2, stride, w.lstm2_bias_ih,
                            w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, io.rpi, io.parent, c2o, M, H, h2n, c2n, h2n16, isc);
@@ -946,62 +936,19 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     }
     // ---- S6
     {
-        GemmBuilder g;
-        GemmProb& p0 = g.prob(M, V, c.scratch, V);
-        GemmBuilder::seg(p0, h2n, H, nullptr, w.out_fc_weight, H, H, h2n16, H2A_UNIT);
-        int nblk = 0;
-        if (io.s1_for_next) {
-            // LSTM1 / gate sums of step t+1 over THIS step's rows: they depend on (h2, h1) only (the word enters through the
-            // decode cache, the beam re-indexing through k_lstm1's parent gather), so they ride in the same launch as the
-            // vocabulary projection: 3 GEMM launches per timestep instead of 4, and a longer stream-K range per workgroup.
-            const float* Wih[3] = {w.lstm1_weight_ih, w.W1_is_weight, w.W1_ig_weight};
-            const float* Whh[3] = {w.lstm1_weight_hh, w.W1_hs_weight, nullptr};
-            const int Nn[3] = {4 * H, H, H}, off[3] = {0, 4 * H, 5 * H};
-            const bool h1_done = c.pre1_skip5 > 0;         // (split_pre1: the S5 launch above already wrote the h1 part into the leading slabs of pre1)
-            for (int i = 0; i < 3; ++i) {
-                if (!d.h2_first_lstm && !Whh[i]) continue;
-                GemmProb& p = g.prob(M, Nn[i], c.pre1 + (long long)c.pre1_skip5 * M * 6 * H + off[i], 6 * H);
-                if (d.h2_first_lstm) GemmBuilder::seg(p, h2n, H, nullptr, Wih[i], in1, H, h2n16, H2A_UNIT);
-                if (Whh[i] && !h1_done) GemmBuilder::seg(p, h1n, H, nullptr, Whh[i], H, H, h1n16, H2A_UNIT);
-                nblk = i == 0 ? 4 : i == 1 ? 5 : 6;
-            }
-        }
-        const int ns = g.finish(h);
+        GemmBuilder& g = g6;
         const long long stride = (long long)M * V;
         g.a.p[0].slab_stride = stride;
-        for (int i = 1; i < g.a.nprob; ++i) g.a.p[i].slab_stride = (long long)M * 6 * H;
-        // ... and the LSTM1 / gate problems of the next step write (and k_lstm1 adds) only the slabs THEIR tiles can meet - all three get
-        // the largest of their counts, k_lstm1 takes one count for its six gate blocks
-        int ns_pre1 = 1;
-        for (int i = 1; i < g.a.nprob; ++i) ns_pre1 = std::max(ns_pre1, gemm_tight_slabs(g.a, i));
-        for (int i = 1; i < g.a.nprob; ++i) g.a.p[i].nslab = ns_pre1;
-        c.pre1_ns = (g.a.nprob > 1 ? ns_pre1 : ns) + c.pre1_skip5; c.pre1_nblk = nblk; c.pre1_stride = (long long)M * 6 * H;
+        for (int i = 1; i < g.a.nprob; ++i) {             // (behind the slabs the S5 launch above wrote the h1 part into)
+            g.a.p[i].C += c.pre1_skip5 * stride1; g.a.p[i].slab_stride = stride1; g.a.p[i].nslab = ns_pre1;
+        }
+        c.pre1_ns = (g.a.nprob > 1 ? ns_pre1 : ns6) + c.pre1_skip5; c.pre1_nblk = nblk6; c.pre1_stride = stride1;
         if (c.pre1_ns > 8) return fail("S6: the LSTM1 sums of the next step would need %d slabs (8 fit)", c.pre1_ns);
         // the vocabulary tiles (K = H) are cut into fewer pieces than the LSTM1 tiles (K = 2 H) they share the launch with: k_vocab
         // adds only the slabs they wrote (60 -> 40 MB of logits per beam-5 step)
         const int ns_vocab = g.a.p[0].nslab = gemm_tight_slabs(g.a, 0);
         if (g.launch(s, h)) return fail("S6 gemm launch failed");
-#define VOCAB_ARGS c.scratch, ns_vocab, stride, w.out_fc_bias, M, V, io.vmode, c.top_v, c.top_i, io.full_out, io.full_stride, io.forced, \
-                   io.seed, (uint32_t)io.t, io.verbs, io.slot, io.rpi, c.L, io.gt, h->vt_ptr, h->vt_ids, h->n_verbs, lds_row, gate_args, c.nvalid_dev + 2
-        const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;          // combined logits row staged in LDS (<= 96 KB)
-        const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
-        // K = beam exactly (fewer selection rounds than rounding up to a power of two); 512 threads per row from V = 4096 up
-#define VOCAB_LAUNCH(KK)                                                                                              \
-    if (V >= 4096) hipLaunchKernelGGL((k_vocab<KK, 512>), dim3(M), dim3(512), vsm, s, VOCAB_ARGS);                  \
-    else hipLaunchKernelGGL((k_vocab<KK, 256>), dim3(M), dim3(256), vsm, s, VOCAB_ARGS);                            \
-    break;
-        switch (io.K) {
-            case 1: VOCAB_LAUNCH(1)
-            case 2: VOCAB_LAUNCH(2)
-            case 3: VOCAB_LAUNCH(3)
-            case 4: VOCAB_LAUNCH(4)
-            case 5: VOCAB_LAUNCH(5)
-            case 6: VOCAB_LAUNCH(6)
-            case 7: VOCAB_LAUNCH(7)
-            default: VOCAB_LAUNCH(8)
-        }
-#undef VOCAB_LAUNCH
-#undef VOCAB_ARGS
+        launch_vocab(h, s, io, c.scratch, ns_vocab, stride, gate_args);
     }
     c.st16_ok[io.cur ^ 1] = sh;               // the new state's bf16 images exist iff this step wrote them
     LAUNCHCHK();
@@ -1063,13 +1010,13 @@ static int decode_simple(vsr_handle* h, int vmode, uint64_t seed, const int64_t*
     bool have_pending = false;
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1;
-        StepIO io{};
-        io.t = t; io.M = B; io.rpi = 1; io.cur = cur;
-        io.parent = nullptr; io.word_prev = c.word[cur]; io.slot = c.slot[cur]; io.fixed_slot = 0;
+        StepIO io;
+        io.t = t; io.M = B; io.cur = cur;
+        io.word_prev = c.word[cur]; io.slot = c.slot[cur];
         io.sel_simple = have_pending ? &pending : nullptr;
-        io.vmode = vmode; io.K = 1; io.full_out = nullptr; io.full_stride = 0;
+        io.vmode = vmode;
         io.forced = (vmode == VM_FORCED) ? c.forced_w32 + (size_t)t * B : nullptr;
-        io.seed = seed; io.verbs = verbs; io.gt = gt; io.lg_out = c.lg; io.lg_stride = 2; io.alpha_out = nullptr;
+        io.seed = seed; io.verbs = verbs; io.gt = gt; io.lg_out = c.lg;
         io.s1_from_prev = t > 0 && h->xproj != nullptr;
         io.s1_for_next = t + 1 < T && h->xproj != nullptr;
         if (run_step(h, io, s)) return 1;
@@ -1118,12 +1065,11 @@ extern "C" int vsr_beam(vsr_handle* h, int32_t beam, int32_t out_size, int64_t e
         const int cur = t & 1;
         const int cb = t == 0 ? 1 : beam;
         const int M = B * cb;
-        StepIO io{};
+        StepIO io;
         io.sel_beam = have_pending ? &pending : nullptr;
         io.t = t; io.M = M; io.rpi = cb; io.cur = cur;
-        io.parent = t == 0 ? nullptr : c.parent; io.word_prev = c.word[cur]; io.slot = c.slot[cur]; io.fixed_slot = 0;
-        io.vmode = VM_TOPK; io.K = K; io.forced = nullptr; io.seed = 0; io.verbs = verbs; io.gt = gt;
-        io.lg_out = c.lg; io.lg_stride = 2; io.alpha_out = nullptr;
+        io.parent = t == 0 ? nullptr : c.parent; io.word_prev = c.word[cur]; io.slot = c.slot[cur];
+        io.K = K; io.verbs = verbs; io.gt = gt; io.lg_out = c.lg;
         io.s1_from_prev = t > 0 && h->xproj != nullptr;
         io.s1_for_next = t + 1 < T && h->xproj != nullptr;
         if (run_step(h, io, s)) return 1;
@@ -1132,16 +1078,7 @@ extern "C" int vsr_beam(vsr_handle* h, int32_t beam, int32_t out_size, int64_t e
                              c.hist_parent, c.hist_word, c.hist_gate, c.hist_lpw, c.hist_lpg, B};
         have_pending = (h->fuse_select & 2) && t + 1 < T && h->xproj != nullptr;       // (the next step is then s1_from_prev)
         if (have_pending) pending = sa;
-        else switch (K) {
-            case 1: hipLaunchKernelGGL((k_select_beam<1>), dim3(B), dim3(64), 0, s, sa); break;
-            case 2: hipLaunchKernelGGL((k_select_beam<2>), dim3(B), dim3(64), 0, s, sa); break;
-            case 3: hipLaunchKernelGGL((k_select_beam<3>), dim3(B), dim3(64), 0, s, sa); break;
-            case 4: hipLaunchKernelGGL((k_select_beam<4>), dim3(B), dim3(64), 0, s, sa); break;
-            case 5: hipLaunchKernelGGL((k_select_beam<5>), dim3(B), dim3(64), 0, s, sa); break;
-            case 6: hipLaunchKernelGGL((k_select_beam<6>), dim3(B), dim3(64), 0, s, sa); break;
-            case 7: hipLaunchKernelGGL((k_select_beam<7>), dim3(B), dim3(64), 0, s, sa); break;
-            default: hipLaunchKernelGGL((k_select_beam<8>), dim3(B), dim3(64), 0, s, sa); break;
-        }
+        else with_const_1to8(K, [&](auto KK) { hipLaunchKernelGGL((k_select_beam<decltype(KK)::value>), dim3(B), dim3(64), 0, s, sa); });
         LAUNCHCHK();
     }
     hipLaunchKernelGGL(k_backtrack, dim3(B), dim3(64), (size_t)3 * T * beam * sizeof(int), s, T, B, beam, out_size, c.seq[T & 1], c.hist_parent, c.hist_word,
@@ -1163,12 +1100,11 @@ extern "C" int vsr_xe_forward(vsr_handle* h, const int64_t* captions, int32_t T,
     for (int t = 0; t < T; ++t)
         hipLaunchKernelGGL(k_i64_to_i32, dim3(cdiv(B, 256)), dim3(256), 0, s, captions + t, (long long)T, c.cap32 + (size_t)t * B, B, V, c.nvalid_dev + 2);
     for (int t = 0; t < T; ++t) {
-        StepIO io{};
-        io.t = t; io.M = B; io.rpi = 1; io.cur = t & 1;
-        io.parent = nullptr; io.word_prev = c.cap32 + (size_t)t * B; io.slot = nullptr; io.fixed_slot = t;
-        io.vmode = VM_FULL; io.K = 1; io.full_out = logp_words + (size_t)t * V; io.full_stride = (long long)T * V;
-        io.forced = nullptr; io.seed = 0; io.verbs = nullptr; io.gt = 0;
-        io.lg_out = logp_gates + (size_t)t * 2; io.lg_stride = (long long)T * 2; io.alpha_out = nullptr;
+        StepIO io;
+        io.t = t; io.M = B; io.cur = t & 1;
+        io.word_prev = c.cap32 + (size_t)t * B; io.fixed_slot = t;           // (no slot list: step t reads slot t)
+        io.vmode = VM_FULL; io.full_out = logp_words + (size_t)t * V; io.full_stride = (long long)T * V;
+        io.lg_out = logp_gates + (size_t)t * 2; io.lg_stride = (long long)T * 2;
         if (run_step(h, io, s)) return 1;
     }
     return 0;
@@ -1210,12 +1146,12 @@ extern "C" int vsr_step(vsr_handle* h, int32_t t, int32_t rows_per_image, const 
     hipLaunchKernelGGL(k_step_slots, dim3(cdiv(M, 256)), dim3(256), 0, s, t, slot, prev_gates, c.L, M, c.slot[0], slot_out);
     if (t == 0) hipLaunchKernelGGL(k_fill_i32, dim3(cdiv(M, 256)), dim3(256), 0, s, c.word[0], h->d.bos_idx, M);
     else hipLaunchKernelGGL(k_i64_to_i32, dim3(cdiv(M, 256)), dim3(256), 0, s, prev_words, 1LL, c.word[0], M, V, c.nvalid_dev + 2);
-    StepIO io{};
+    StepIO io;
     io.t = 1;  // state segments are always live here (the caller may pass a non-zero state at t == 0)
-    io.M = M; io.rpi = rows_per_image; io.cur = 0;
-    io.parent = nullptr; io.word_prev = c.word[0]; io.slot = c.slot[0]; io.fixed_slot = 0;
-    io.vmode = VM_FULL; io.K = 1; io.full_out = logp_words; io.full_stride = V; io.forced = nullptr; io.seed = 0;
-    io.verbs = verbs; io.gt = gt; io.lg_out = logp_gates; io.lg_stride = 2; io.alpha_out = nullptr;
+    io.M = M; io.rpi = rows_per_image;
+    io.word_prev = c.word[0]; io.slot = c.slot[0];
+    io.vmode = VM_FULL; io.full_out = logp_words; io.full_stride = V;
+    io.verbs = verbs; io.gt = gt; io.lg_out = logp_gates;
     if (run_step(h, io, s)) return 1;
     for (int j = 0; j < 4; ++j) HIPCHK(hipMemcpyAsync(out[j], c.st[1][j], n, hipMemcpyDeviceToDevice, s));
     return 0;
