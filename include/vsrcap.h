@@ -208,6 +208,13 @@ int vsr_greedy(vsr_handle* h, const float* verbs, int32_t gt, int64_t* words, in
  * of drawing (Philox4x32-10 keyed by seed, Gumbel-max).  lp_* (B,T) fp32 = log-prob of the sample. */
 int vsr_sample(vsr_handle* h, uint64_t seed, const int64_t* forced_words, const int64_t* forced_gates,
                int64_t* words, int64_t* gates, float* lp_words, float* lp_gates, void* stream);
+/* Several samples per image in one call (SCST draws 5 per image, coco_scripts/train.py:151-178; the reference's caller repeats every
+ * image instead).  rows_per_image = K in [1, the beam vsr_prepare*() was called with]: M = B K decoder rows, row b K + j is sample j
+ * of image b - the order of repeat_interleave(K, 0) - and every tensor here is (M,T).  The K rows of an image read its statics as
+ * beams do (nothing is copied) and are independent draws: the Philox key is (seed, row, t) with row = b K + j, i.e. the same noise the
+ * call on K-times repeated images would use.  vsr_sample is the rows_per_image = 1 case. */
+int vsr_sample_rows(vsr_handle* h, int32_t rows_per_image, uint64_t seed, const int64_t* forced_words, const int64_t* forced_gates,
+                    int64_t* words, int64_t* gates, float* lp_words, float* lp_gates, void* stream);
 /* CaptioningModel.beam_search / beam_search_v (:116-294): joint (word x gate) beam search.
  * words/gates (B,out_size,T) int64; lp_* (B,out_size,T) fp32 (the reference's per-slot log-probs, quirk 2
  * of SURVEY.md 8a); scores (B,out_size) fp32 final sequence log-probs, may be NULL. */
@@ -248,6 +255,15 @@ int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const int64_t* slot
                       float* logp_gates, void* train_workspace, size_t train_workspace_bytes, void* stream);
 int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
                        void* stream);
+/* The same with rows_per_image = K decoder rows per image (the replay of vsr_sample_rows' samples): vsr_prepare*(beam >= K), M = B K
+ * rows in the order of repeat_interleave(K, 0); word_in / slots (M,T), logp_words (M,T,V), logp_gates (M,T,2).  Statics are shared:
+ * att_va runs once per image, and the backward pass adds the K rows' contributions to everything that is per image - dP of an
+ * (image, slot), the gradient of the hoisted v-bar projections - in ascending row order (no float atomics: runs repeat bit for bit).
+ * vsr_train_backward / vsr_train_select take rows_per_image from the saved forward.  The functions above are the K = 1 case of these
+ * (and launch the same kernels as before).  Index lists train with row_img = NULL only (every image its own bank), as at K = 1. */
+size_t vsr_train_workspace_bytes_rows(const vsr_handle* h, int32_t B, int32_t rows_per_image, int32_t T);
+int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots, int32_t T,
+                           float* logp_words, float* logp_gates, void* train_workspace, size_t train_workspace_bytes, void* stream);
 /* More than one live forward (the reference runs under eager autograd: two forwards then (l1 + l2).backward(), micro-batches, a decode
  * call between a forward and its backward all just work, CaptioningModel.py:22-36).  A forward's saved state lives in the TWO caller
  * buffers it was given - the vsr_prepare*() workspace and the training workspace - and stays differentiable for as long as no later

@@ -1155,12 +1155,12 @@ __global__ void k_select_simple_lstm1(const SelSimpleArgs sel, const float* __re
                                       const float* __restrict__ vproj, const float* __restrict__ c1_old, int M, int H,
                                       float* __restrict__ h1n, float* __restrict__ c1n, float* __restrict__ s_t, float* __restrict__ gpre,
                                       const float* __restrict__ xproj, int nblk, uint16_t* __restrict__ h1n16, uint16_t* __restrict__ s_t16,
-                                      float isc, int skip5) {
+                                      float isc, int skip5, int rpi /* rows per image (several samples per image share the statics) */) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)M * H) return;
     const int row = (int)(i / H), j = (int)(i % H);
     const long long base = (long long)row * 6 * H + j;
-    const float* vp = vproj + (long long)row * 6 * H + j;
+    const float* vp = vproj + (long long)(row / rpi) * 6 * H + j;
     // the slab sums do not depend on the selection: their loads are in flight while it is made
     float q[6];
 #pragma unroll

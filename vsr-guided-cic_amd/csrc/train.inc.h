@@ -19,7 +19,9 @@ struct TrainCtx {                      // (plain data + two vectors: copied into
     size_t tws_bytes = 0;
     int* h2_stash = nullptr;           // f16x2: the per-batch exponents / bounds of the handle's table as they were for THIS forward (8 ints)
     long long generation = 0;          // bumped by every vsr_train_forward: identifies the saved forward a backward belongs to
-    int B = 0, T = 0, TB = 0, TBp = 0, Bp = 0, RLp = 0;
+    int B = 0, T = 0, TB = 0, TBp = 0, Bp = 0, RLp = 0;       // B: decoder ROWS (= images x rpi); Bp: the IMAGES, padded (K of the v-bar products)
+    int rpi = 1;                       // rows per image (vsr_train_forward_rows): rows b rpi .. b rpi + rpi - 1 share image b's statics
+    float* dP_rows = nullptr;          // rpi > 1: the rows' (R, A) contributions to dP of the current step (k_attend_bwd -> k_dP_rows_sum)
     const float* logp_w = nullptr;     // caller's (B,T,V) output of the forward, needed by the backward
     const float* logp_g = nullptr;     // (B,T,2)
     float *h1s, *c1s, *h2s, *c2s;      // (T+1, B, H): slot 0 = zeros
@@ -56,7 +58,8 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     const Ctx& c = h->c;
     const size_t B = t.B, T = t.T, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
     const size_t in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0);
-    const size_t TB = T * B, TBp = up4(TB), Bp = up4(B), RL = (size_t)c.B * c.L * c.R, R1 = c.R + 1;
+    const size_t Bi = B / t.rpi;       // images: what the per-image arrays (dP, the v-bar side) are sized by
+    const size_t TB = T * B, TBp = up4(TB), Bp = up4(Bi), RL = (size_t)c.B * c.L * c.R, R1 = c.R + 1;
     // rows att_va's weight gradient runs over: the slot entries (dense regions) or the feature-bank rows (index lists)
     const size_t PR = c.Rb > 0 ? (size_t)c.n_img * c.Rb : RL, RLp = up4(std::max(RL, PR));
     t.TB = (int)TB; t.TBp = (int)TBp; t.Bp = (int)Bp; t.RLp = (int)RLp;
@@ -76,11 +79,12 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     t.dwa_rows = b.take<float>(TB * A); t.dws_rows = b.take<float>(TB * A); t.dwg_rows = b.take<float>(TB * A);
     t.dP = b.take<float>(RL * A);
     t.dP_bank = c.Rb > 0 ? b.take<float>(PR * A) : nullptr;
+    t.dP_rows = t.rpi > 1 ? b.take<float>(B * c.R * A) : nullptr;
     t.datt = b.take<float>(B * D); t.dtc = b.take<float>(B * H);
     t.dh_tot = b.take<float>(B * H); t.dzsum = b.take<float>(B); t.dalpha = b.take<float>(B * R1);
     t.dh1_c = b.take<float>(B * H); t.dh2_c = b.take<float>(B * H);
     for (int i = 0; i < 2; ++i) { t.dc1_c[i] = b.take<float>(B * H); t.dc2_c[i] = b.take<float>(B * H); }
-    t.dpre1sum = b.take<float>(B * 6 * H); t.dpre2sum = b.take<float>(B * 4 * H); t.dx_all = b.take<float>(TB * E); t.xproj_all = b.take<float>(TB * 6 * H);
+    t.dpre1sum = b.take<float>(Bi * 6 * H); t.dpre2sum = b.take<float>(Bi * 4 * H); t.dx_all = b.take<float>(TB * E); t.xproj_all = b.take<float>(TB * 6 * H);
     t.wT_ih1 = b.take<float>(in1 * 4 * H); t.wT_is = b.take<float>(in1 * H); t.wT_ig = b.take<float>(in1 * H);
     t.wT_hh1 = b.take<float>(H * 4 * H); t.wT_hs = b.take<float>(H * H);
     t.wT_ih2 = b.take<float>(in2 * 4 * H); t.wT_hh2 = b.take<float>(H * 4 * H);
@@ -135,17 +139,18 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
 struct SegSpec { const float* A; int lda; const float* W; int ldw; int K; int a_cls = H2A_NONE; const uint16_t* A16 = nullptr; };
 
 // whole-pass bounds from the per-step ones (block 63: max over the steps; block 62 slots 2, 3: the sums over t of dpre1 / dpre2 rows)
-__global__ void k_h2_dyn_fold(int* __restrict__ dyn, int T) {
+// (nsum: rows one sum runs over - the T steps of a row, times the rows of an image when several share its statics)
+__global__ void k_h2_dyn_fold(int* __restrict__ dyn, int T, int nsum) {
     const int j = threadIdx.x;
     if (j >= 8) return;
     int m = 0;
     for (int tt = 0; tt < T; ++tt) m = max(m, dyn[tt * 8 + j]);
     dyn[63 * 8 + j] = m;
-    if (j == 0) dyn[62 * 8 + 3] = __float_as_int(__int_as_float(m) * (float)T);
+    if (j == 0) dyn[62 * 8 + 3] = __float_as_int(__int_as_float(m) * (float)nsum);
     if (j == 6) {
         int m2 = 0;
         for (int tt = 0; tt < T; ++tt) m2 = max(m2, dyn[tt * 8 + 2]);
-        dyn[62 * 8 + 2] = __float_as_int(fmaxf(__int_as_float(m), __int_as_float(m2)) * (float)T);
+        dyn[62 * 8 + 2] = __float_as_int(fmaxf(__int_as_float(m), __int_as_float(m2)) * (float)nsum);
         dyn[62 * 8 + 4] = max(m, m2);                                       // all six column blocks of dpre1 (its transpose is one image)
     }
 }
@@ -342,20 +347,25 @@ extern "C" int vsr_train_select(vsr_handle* h, int64_t generation, void* stream)
                 "workspaces, or the GEMM flavour / the weight binding changed)", (long long)generation);
 }
 
-extern "C" size_t vsr_train_workspace_bytes(const vsr_handle* h, int32_t B, int32_t T) {
-    if (!h || !h->prepared || B != h->c.B || T <= 0) return 0;
+extern "C" size_t vsr_train_workspace_bytes_rows(const vsr_handle* h, int32_t B, int32_t rows_per_image, int32_t T) {
+    if (!h || !h->prepared || B != h->c.B || T <= 0 || rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return 0;
     TrainCtx t;
-    t.B = B; t.T = T;
+    t.rpi = rows_per_image; t.B = B * rows_per_image; t.T = T;
     return carve_train(h, t, nullptr);
 }
+extern "C" size_t vsr_train_workspace_bytes(const vsr_handle* h, int32_t B, int32_t T) { return vsr_train_workspace_bytes_rows(h, B, 1, T); }
 
 // ---------------------------------------------------------------------------------------------- forward with saves
-extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const int64_t* slots, int32_t T, float* logp_words,
-                                 float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
+// K = rows per image: M = B K decoder rows, rows b K .. b K + K - 1 are image b's (the order of repeat_interleave(K, 0)).  Whatever is
+// per image - the hoisted projections, P, the region rows, masks and index lists - is read through row / K, as the beams of the decode
+// path do; K = 1 launches the kernels of the one-row-per-image path (the <false> instantiations).
+static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, const int64_t* slots, int32_t T, float* logp_words,
+                              float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
     if (check_ready(h, "vsr_train_forward")) return 1;
     if (!word_in || !logp_words || !logp_gates || !train_ws) return fail("vsr_train_forward: null tensor");
     Ctx& c = h->c;
-    if (c.beam != 1 && c.Mmax != c.B) return fail("vsr_train_forward: prepare() must be called with beam = 1");
+    if (K == 1 && c.beam != 1 && c.Mmax != c.B) return fail("vsr_train_forward: prepare() must be called with beam = 1");
+    if (K < 1 || K > c.beam) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, the prepared beam %d] (the workspace of vsr_prepare*() is sized by the beam)", K, c.beam);
     // index-list regions (vsr_prepare_indexed) train too, with one decoder row per image (the XE / SCST batches of train.py: every
     // sample brings its own detections): the backward pass sums dP over the entries of a row that name the same bank row
     if (c.ridx && !c.rows_are_images) return fail("vsr_train_forward: index-list regions with a row -> image map (row_img) are a decode-side format; training needs one row per image (row_img = NULL)");
@@ -363,10 +373,10 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
-    const int B = c.B, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
+    const int B = c.B * K, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;      // (B: decoder rows)
     TrainCtx& t = *h->tc;
     t.valid = false;
-    t.B = B; t.T = T;
+    t.rpi = K; t.B = B; t.T = T;
     const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
     if (need > train_ws_bytes) return fail("vsr_train_forward: training workspace too small (%zu < %zu)", train_ws_bytes, need);
     drop_saved_forwards_in(h->saved, train_ws, need);       // forwards filed in THIS buffer are overwritten now
@@ -430,9 +440,11 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
                 for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
                 if (g.launch(s, h)) return fail("train S1 gemm launch failed");
             }
-            hipLaunchKernelGGL(k_lstm1_train, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
-                               t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1,
-                               d.h2_first_lstm ? 6 : 5 /* without h2 in the input the shift-gate block has no recurrent part */, h1n16, s_t16, isc);
+            const int nblk = d.h2_first_lstm ? 6 : 5;      // without h2 in the input the shift-gate block has no recurrent part
+            if (K > 1) hipLaunchKernelGGL(k_lstm1_train<true>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
+                               t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, K);
+            else hipLaunchKernelGGL(k_lstm1_train<false>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
+                               t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, 1);
         }
         {   // S2
             GemmBuilder g;
@@ -446,7 +458,7 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
             hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias,
                                B, H, A, D, g_t, hA, sent, sa, g1, g_t16, isc);
         }
-        launch_attend(h, s, Gate2Args{}, B, 1, slot, 0, hA, sa, sent, att, alpha, att16, att_exp);
+        launch_attend(h, s, Gate2Args{}, B, K, slot, 0, hA, sa, sent, att, alpha, att16, att_exp);
         {   // S5
             GemmBuilder g;
             add_s5(g, d, w, o, c.scratch, tt > 0);
@@ -456,12 +468,14 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
             g.a.p[0].slab_stride = stride;
             g.a.p[1].C = gas; g.a.p[1].slab_stride = stride_g;
             if (g.launch(s, h)) return fail("train S5 gemm launch failed");
-            GateLogitArgs gl{gas, ns, stride_g, hA, w.att_g_weight, c.zsum, nullptr, slot, 1, c.L, B, A,
+            GateLogitArgs gl{gas, ns, stride_g, hA, w.att_g_weight, c.zsum, nullptr, slot, K, c.L, B, A,
                              logp_gates + (size_t)tt * 2, (long long)T * 2};
             gl.ga_out = ga;
             const int gblocks = B;
-            hipLaunchKernelGGL(k_fwd_tail, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
-                               w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc);
+            if (K > 1) hipLaunchKernelGGL(k_fwd_tail<true>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
+                               w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, K);
+            else hipLaunchKernelGGL(k_fwd_tail<false>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
+                               w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, 1);
         }
         LAUNCHCHK();
     }
@@ -488,6 +502,15 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
     LAUNCHCHK();
     h->saved->v.push_back(SavedForward{c, t, h->ws_lo, h->ws_bytes});
     return 0;
+}
+extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const int64_t* slots, int32_t T, float* logp_words,
+                                 float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
+    return train_forward_impl(h, 1, word_in, slots, T, logp_words, logp_gates, train_ws, train_ws_bytes, stream);
+}
+extern "C" int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots, int32_t T,
+                                      float* logp_words, float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
+    if (rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, %d]", rows_per_image, VSR_MAX_BEAM);
+    return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_words, logp_gates, train_ws, train_ws_bytes, stream);
 }
 
 // Identity of the saved forward pass (0 = none).  The training workspace holds ONE forward at a time: a caller that keeps
@@ -545,6 +568,17 @@ __global__ void k_sum_over_t(const float* __restrict__ X, int T, long long per_t
     out[i] = s;
 }
 
+// several rows per image: out[image] = sum over the image's K rows, in ascending row order, of each row's sum over t (X: (T, M, C))
+__global__ void k_sum_over_t_rows(const float* __restrict__ X, int T, int K, int C, long long per_t, long long n_out, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    const long long img = i / C, col = i % C;
+    float s = 0.f;
+    for (int j = 0; j < K; ++j)
+        for (int t = 0; t < T; ++t) s += X[t * per_t + (img * K + j) * C + col];
+    out[i] = s;
+}
+
 // ---------------------------------------------------------------------------------------------- backward
 extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
                                   void* stream) {
@@ -556,7 +590,8 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
     Ctx& c = h->c;
-    const int B = t.B, T = t.T, TB = t.TB, TBp = t.TBp, Bp = t.Bp, RLp = t.RLp;
+    const int B = t.B, T = t.T, TB = t.TB, TBp = t.TBp, Bp = t.Bp, RLp = t.RLp;          // (B: decoder rows)
+    const int K = t.rpi, Bi = B / K;                                                      // rows per image of the saved forward; images
     const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
     const int in1 = (d.h2_first_lstm ? H : 0) + D + E, voff = d.h2_first_lstm ? H : 0, xoff = voff + D, in2 = H + D + (d.img_second_lstm ? D : 0);
     const int RL = c.B * c.L * c.R, R1 = c.R + 1;
@@ -675,19 +710,29 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
         }
         // attention
         {
-            hipLaunchKernelGGL(k_dalpha, dim3(cdiv((long long)B * R1, 4)), dim3(256), 0, s, t.datt, sent, c.regions, c.rmask, c.ridx, slot, B, c.L, c.R, D,
-                               t.dalpha);
+            if (K > 1) hipLaunchKernelGGL(k_dalpha<true>, dim3(cdiv((long long)B * R1, 4)), dim3(256), 0, s, t.datt, sent, c.regions, c.rmask, c.ridx, slot, B, c.L, c.R, D,
+                               t.dalpha, K);
+            else hipLaunchKernelGGL(k_dalpha<false>, dim3(cdiv((long long)B * R1, 4)), dim3(256), 0, s, t.datt, sent, c.regions, c.rmask, c.ridx, slot, B, c.L, c.R, D,
+                               t.dalpha, 1);
             // two workgroups per row in launches of <= 128 rows (as k_attend): half the A columns each, its 512 threads = 256 columns x 2 row groups
             const int NTb = A >= 512 ? 512 : 256;
             const int np = attend_bwd_parts(h, B, NTb);
             const int RG = np > 1 ? NTb / (A / np) : 1;
             const size_t smem = (size_t)(R1 + 8 + (np > 1 ? (RG - 1) * (A / np) * 2 : 0)) * sizeof(float);
-            if (A >= 512) hipLaunchKernelGGL(k_attend_bwd<512>, dim3(cdiv(B * np, 8) * 8), dim3(512), smem, s, t.datt, t.dalpha, t.dzsum, alpha, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx,
-                               slot, 0, B, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, dsent, dsa, dhA, t.dP, dwa, dws,
-                               dptr(tt * 8 + DY_dhA), dptr(tt * 8 + DY_dsent), dptr(tt * 8 + DY_dsa), np);
-            else hipLaunchKernelGGL(k_attend_bwd<256>, dim3(cdiv(B * np, 8) * 8), dim3(256), smem, s, t.datt, t.dalpha, t.dzsum, alpha, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx,
-                               slot, 0, B, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, dsent, dsa, dhA, t.dP, dwa, dws,
-                               dptr(tt * 8 + DY_dhA), dptr(tt * 8 + DY_dsent), dptr(tt * 8 + DY_dsa), np);
+            // K > 1: rows of an image may name the same slot: each row writes its (R, A) block, the blocks are added onto dP in row order
+            auto go = [&](auto NT, auto SH) {
+                constexpr int nt = decltype(NT)::value;
+                constexpr bool sh = decltype(SH)::value;
+                hipLaunchKernelGGL((k_attend_bwd<nt, sh>), dim3(cdiv(B * np, 8) * 8), dim3(nt), smem, s, t.datt, t.dalpha, t.dzsum, alpha, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx,
+                                   slot, 0, B, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, dsent, dsa, dhA, sh ? t.dP_rows : t.dP, dwa, dws,
+                                   dptr(tt * 8 + DY_dhA), dptr(tt * 8 + DY_dsent), dptr(tt * 8 + DY_dsa), np, K);
+            };
+            if (K > 1) {
+                if (A >= 512) go(std::integral_constant<int, 512>{}, std::true_type{}); else go(std::integral_constant<int, 256>{}, std::true_type{});
+                hipLaunchKernelGGL(k_dP_rows_sum, dim3(cdiv((long long)Bi * c.R * (A / 4), 256)), dim3(256), 0, s, t.dP_rows, slot, c.rmask, Bi, K, c.L, c.R, A, t.dP);
+            } else {
+                if (A >= 512) go(std::integral_constant<int, 512>{}, std::false_type{}); else go(std::integral_constant<int, 256>{}, std::false_type{});
+            }
         }
         // grouped GEMM 2: [dq | dhA] -> dh1_b ; [dsent | dsa] -> ds_t;  then the sentinel gate and LSTM1 pointwise backward
         {
@@ -743,10 +788,10 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     transpose(h, s, t.s_ts, H, TB, H, t.tX_st, TBp, nullptr, h2b, -1, nullptr, &tbx);
     transpose(h, s, t.g_ts, H, TB, H, t.tX_gt, TBp, nullptr, h2b, -1, nullptr, &tbx);
     transpose(h, s, h2cur, H, TB, H, t.tX_h2, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, c.vbar, D, B, D, t.tX_vbar, Bp, nullptr, h2b, -1, nullptr, &tbx);
+    transpose(h, s, c.vbar, D, Bi, D, t.tX_vbar, Bp, nullptr, h2b, -1, nullptr, &tbx);
     tbx.flush(s);
     if (NV > 0) transpose(h, s, c.regions, (long long)D, NV, D, t.tX_reg, (long long)NVp, c.vlist, h2b, -1, nv_dev);
-    if (h2b) hipLaunchKernelGGL(k_h2_dyn_fold, dim3(1), dim3(64), 0, s, dyn, T);
+    if (h2b) hipLaunchKernelGGL(k_h2_dyn_fold, dim3(1), dim3(64), 0, s, dyn, T, T * K);
     const int sP1 = dslot(DW_step + DY_dpre1), sQ = dslot(DW_step + DY_dq), sP2 = dslot(DW_step + DY_dpre2);
     // the transposed gradients are the A operands of the weight-gradient GEMMs: with the whole-pass bounds known (k_h2_dyn_fold) they are
     // written as fp16-pair images IN PLACE of the fp32 values and those GEMMs take the all-DMA kernel (tyi: the buffer holds an image)
@@ -773,8 +818,10 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     }
     const bool tyiP = tyi && NVp % 8 == 0;
     if (NV > 0) transpose(h, s, dP_rows, (long long)A, NV, A, t.tY_dP, (long long)NVp, c.vlist, tyiP, dslot(DW_dP), nv_dev);
-    hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv((long long)B * 6 * H, 256)), dim3(256), 0, s, t.dpre1, T, (long long)B * 6 * H, t.dpre1sum);
-    transpose(h, s, t.dpre1sum, 6 * H, B, 6 * H, t.tY_dpre1sum, Bp);
+    // the gradient of the hoisted v-bar projection: per IMAGE, the sum over its rows (ascending) and steps
+    if (K > 1) hipLaunchKernelGGL(k_sum_over_t_rows, dim3(cdiv((long long)Bi * 6 * H, 256)), dim3(256), 0, s, t.dpre1, T, K, 6 * H, (long long)B * 6 * H, (long long)Bi * 6 * H, t.dpre1sum);
+    else hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv((long long)B * 6 * H, 256)), dim3(256), 0, s, t.dpre1, T, (long long)B * 6 * H, t.dpre1sum);
+    transpose(h, s, t.dpre1sum, 6 * H, Bi, 6 * H, t.tY_dpre1sum, Bp);
     LAUNCHCHK();
 
     // Gradients are finished bucket by bucket, largest first, and an event is recorded after each bucket
@@ -814,8 +861,9 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     }
     if (gemm_to1(h, t, s, 4 * H, D, TBp, t.tY_dpre2, TBp, t.tX_att, TBp, G[g_Wih2] + H, in2, sP2, tyi)) return 1;
     if (d.img_second_lstm) {
-        hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv((long long)B * 4 * H, 256)), dim3(256), 0, s, t.dpre2, T, (long long)B * 4 * H, t.dpre2sum);
-        transpose(h, s, t.dpre2sum, 4 * H, B, 4 * H, t.tY_dpre2sum, Bp);
+        if (K > 1) hipLaunchKernelGGL(k_sum_over_t_rows, dim3(cdiv((long long)Bi * 4 * H, 256)), dim3(256), 0, s, t.dpre2, T, K, 4 * H, (long long)B * 4 * H, (long long)Bi * 4 * H, t.dpre2sum);
+        else hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv((long long)B * 4 * H, 256)), dim3(256), 0, s, t.dpre2, T, (long long)B * 4 * H, t.dpre2sum);
+        transpose(h, s, t.dpre2sum, 4 * H, Bi, 4 * H, t.tY_dpre2sum, Bp);
         if (gemm_to1(h, t, s, 4 * H, D, Bp, t.tY_dpre2sum, Bp, t.tX_vbar, Bp, G[g_Wih2] + H + D, in2, dslot(DW_dpre2sum))) return 1;
     }
     colsum(t, s, t.dpre2, (long long)4 * H, TB, 4 * H, G[g_bih2], G[g_bhh2]);

@@ -275,21 +275,25 @@ __global__ __launch_bounds__(128) void k_dP_to_bank(const float* __restrict__ dP
 
 // ---------------------------------------------------------------------------------------------- forward saves
 // LSTM1 + gates, training flavour: also stores the post-activation gates (B, 6H) = [i f g o s_gate .]
+// SHARED: several rows per image (sample_rl with samples_per_image = rpi > 1): the hoisted projection is read by image = row / rpi
+template <bool SHARED = false>
 __global__ void k_lstm1_train(const float* __restrict__ pre, int nsplit, long long stride, const float* __restrict__ vproj,
                               const float* __restrict__ xproj /* (M, 6H) embedding part of this step, projected for all steps at once */,
                               const float* __restrict__ c1_old, int M, int H, float* __restrict__ h1n, float* __restrict__ c1n,
                               float* __restrict__ s_t, float* __restrict__ gpre, float* __restrict__ gates,
                               int nblk /* column blocks (of 6) that the recurrent GEMM wrote */,
-                              uint16_t* __restrict__ h1n16 = nullptr, uint16_t* __restrict__ s_t16 = nullptr /* optional images (img_store) */, float isc = 0.f) {
+                              uint16_t* __restrict__ h1n16 = nullptr, uint16_t* __restrict__ s_t16 = nullptr /* optional images (img_store) */, float isc = 0.f,
+                              int rpi = 1) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)M * H) return;
     const int row = (int)(i / H), j = (int)(i % H);
     const long long base = (long long)row * 6 * H + j;
+    const long long vbase = SHARED ? (long long)(row / rpi) * 6 * H + j : base;
     float q[6];
 #pragma unroll
     for (int g = 0; g < 6; ++g) {
         const float s = g < nblk ? slab_sum(pre + base + (long long)g * H, nsplit, stride) : 0.f;
-        q[g] = s + xproj[base + (long long)g * H] + vproj[base + (long long)g * H];
+        q[g] = s + xproj[base + (long long)g * H] + vproj[vbase + (long long)g * H];
     }
     const float ig = sigmoidf_(q[0]), fg = sigmoidf_(q[1]), gg = tanhf(q[2]), og = sigmoidf_(q[3]), sg = sigmoidf_(q[4]);
     const float c = fg * c1_old[i] + ig * gg;
@@ -305,11 +309,13 @@ __global__ void k_lstm1_train(const float* __restrict__ pre, int nsplit, long lo
 
 // after the S5 GEMM, one launch: blocks [0, gblocks = M) finish att_ga(g_t) from its slabs (saved for the backward pass) and
 // write the step's gate log-probs, one workgroup per row; the other blocks are LSTM2 with its post-activation gates saved
+template <bool SHARED = false>
 __global__ __launch_bounds__(256) void k_fwd_tail(const GateLogitArgs gl, int gblocks,
                                                   const float* __restrict__ pre, int nsplit, long long stride, const float* __restrict__ b_ih,
                                                   const float* __restrict__ b_hh, const float* __restrict__ vproj2, const float* __restrict__ c2_old,
                                                   int M, int H, float* __restrict__ h2n, float* __restrict__ c2n, float* __restrict__ gates,
-                                                  uint16_t* __restrict__ h2n16 = nullptr /* optional image (img_store) */, float isc = 0.f) {
+                                                  uint16_t* __restrict__ h2n16 = nullptr /* optional image (img_store) */, float isc = 0.f,
+                                                  int rpi = 1 /* SHARED: rows per image, vproj2 is read by image */) {
     if ((int)blockIdx.x < gblocks) {                      // one workgroup per row: every slab of a column in flight at once (a wave
         __shared__ float red[4];                          // per row walked the slabs in dependent rounds: 20 us at 8 slabs)
         gatelogit_block<256>(gl, blockIdx.x, red);
@@ -324,7 +330,7 @@ __global__ __launch_bounds__(256) void k_fwd_tail(const GateLogitArgs gl, int gb
     for (int g = 0; g < 4; ++g) {
         float s = slab_sum(pre + base + (long long)g * H, nsplit, stride);
         s += b_ih[g * H + j] + b_hh[g * H + j];
-        if (vproj2) s += vproj2[base + (long long)g * H];
+        if (vproj2) s += vproj2[(SHARED ? (long long)(row / rpi) * 4 * H + j : base) + (long long)g * H];
         q[g] = s;
     }
     const float ig = sigmoidf_(q[0]), fg = sigmoidf_(q[1]), gg = tanhf(q[2]), og = sigmoidf_(q[3]);
@@ -347,14 +353,17 @@ __global__ __launch_bounds__(256) void k_fwd_tail(const GateLogitArgs gl, int gb
 
 // dalpha[row][j] = datt[row] . regions_j  (j = 0: sentinel), one WAVE per (row, j): B x (R+1) independent dot products
 // over D, so that a training batch of 100 rows still fills the chip (one workgroup per row left 60 % of the CUs idle).
+// SHARED: rpi rows per image (adjacent); regions, masks and index lists are the image's (row / rpi), everything else the row's.
+template <bool SHARED = false>
 __global__ __launch_bounds__(256) void k_dalpha(const float* __restrict__ datt, const float* __restrict__ sent,
                                                 const float* __restrict__ X, const float* __restrict__ rmask,
                                                 const int* __restrict__ ridx /* index-list regions: bank row of every slot entry, or null */,
-                                                const int* __restrict__ slot, int M, int L, int R, int D, float* __restrict__ dalpha) {
+                                                const int* __restrict__ slot, int M, int L, int R, int D, float* __restrict__ dalpha,
+                                                int rpi = 1) {
     const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (item >= M * (R + 1)) return;
     const int row = item / (R + 1), j = item % (R + 1), lane = threadIdx.x & 63;
-    const long long sl = (long long)row * L + slot[row];
+    const long long sl = (long long)(SHARED ? row / rpi : row) * L + slot[row];
     float s = 0.f;
     if (j == 0 || rmask[sl * R + j - 1] != 0.f) {
         const float* g = datt + (long long)row * D;
@@ -386,7 +395,10 @@ __global__ __launch_bounds__(256) void k_dalpha(const float* __restrict__ datt, 
 //   z_r = w_a . tanh(P_r + hA) ;  z_0 = w_s . tanh(sa + hA)
 // in : datt (M,D), dzsum (M), alpha (M,R+1), saved hA, sa, sent; P, X, rmask of the row's (image, slot)
 // out: dsent (M,D) = a0 * datt; dsa (M,A); dhA (M,A) += ; dP[(image,slot)] (R,A) += ; per-row partials of dw_a, dw_s
-template <int NT>
+// SHARED (rpi > 1 rows per image, sample_rl with samples_per_image): several rows of an image may name the same slot in one step, so
+// the row's (R,A) contribution is WRITTEN to its own block of `dP` (M,R,A) - zeros where dz = 0 - and k_dP_rows_sum adds the blocks
+// onto dP[(image,slot)] in ascending row order.  P, rmask and the index lists are the image's (row / rpi).
+template <int NT, bool SHARED = false>
 __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ datt, const float* __restrict__ dalpha_in,
                                                     const float* __restrict__ dzsum,
                                                     const float* __restrict__ alpha, const float* __restrict__ hA,
@@ -400,7 +412,8 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
                                                     int nparts = 1 /* workgroups per row (round 6, launches of <= 128 rows): part p owns columns [p A / nparts, ..) of the
                                                                       A-wide outputs and [p D / nparts, ..) of dsent; the NT threads of a part are A / nparts columns x
                                                                       RG row groups (region rows r = rg, rg + RG, ..): with 256 columns and two groups a thread's chain
-                                                                      is 18 region rows whose loads are all in flight at once instead of five rounds of eight */) {
+                                                                      is 18 region rows whose loads are all in flight at once instead of five rounds of eight */,
+                                                    int rpi = 1) {
     extern __shared__ float sm[];
     float* da = sm;                 // R+1: dalpha, then dz
     float* red = sm + R + 1;        // 8
@@ -411,7 +424,7 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
     float mx[3] = {0.f, 0.f, 0.f};  // max |dhA|, |dsent|, |dsa| of this row (f16x2 bounds)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int k = slot ? slot[row] : fixed_slot;
-    const long long sl = (long long)row * L + k;
+    const long long sl = (long long)(SHARED ? row / rpi : row) * L + k;
     const float* g = datt + (long long)row * D;
     const float* al = alpha + (long long)row * (R + 1);
     const float* mk = rmask + sl * R;
@@ -447,7 +460,7 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
     __syncthreads();
     // du = dz * w * (1 - tanh^2(P + hA)); dP rows, dhA, dsa and the per-row partials of dw_a / dw_s
     const float* Pk = P + sl * R * A;
-    float* dPk = dP + sl * R * A;
+    float* dPk = dP + (SHARED ? (long long)row : sl) * R * A;
     if (nparts == 1) {
         for (int a = tid; a < A; a += NT) {
             const float h = hA[(long long)row * A + a];
@@ -462,7 +475,7 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
                     const int r = r0 + q;
                     const bool live = r < R && da[r + 1] != 0.f;            // uniform over the workgroup
                     pv[q] = live ? (ridx ? P[(long long)ridx[sl * R + r] * A + a] : Pk[(long long)r * A + a]) : 0.f;
-                    dpv[q] = live ? dPk[(long long)r * A + a] : 0.f;
+                    dpv[q] = (!SHARED && live) ? dPk[(long long)r * A + a] : 0.f;
                 }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
@@ -475,6 +488,8 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
                             dPk[(long long)r * A + a] = dpv[q] + du;           // a row visits its slots one step at a time: no race
                             dh += du;
                             dwa += dz * th;
+                        } else if constexpr (SHARED) {
+                            dPk[(long long)r * A + a] = 0.f;
                         }
                     }
                 }
@@ -504,7 +519,7 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
                 const int r = r0 + q * RG;
                 const bool live = r < R && da[r + 1] != 0.f;
                 pv[q] = live ? (ridx ? P[(long long)ridx[sl * R + r] * A + a] : Pk[(long long)r * A + a]) : 0.f;
-                dpv[q] = live ? dPk[(long long)r * A + a] : 0.f;
+                dpv[q] = (!SHARED && live) ? dPk[(long long)r * A + a] : 0.f;
             }
 #pragma unroll
             for (int q = 0; q < CH; ++q) {
@@ -517,6 +532,8 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
                         dPk[(long long)r * A + a] = dpv[q] + du;
                         dh += du;
                         dwa += dz * th;
+                    } else if constexpr (SHARED) {
+                        dPk[(long long)r * A + a] = 0.f;
                     }
                 }
             }
@@ -539,6 +556,27 @@ __global__ __launch_bounds__(NT) void k_attend_bwd(const float* __restrict__ dat
     if (bm_dhA) {
         int* const bb[3] = {bm_dhA, bm_dsent, bm_dsa};
         block_absmax_to<3>(mx, bb);
+    }
+}
+
+// Several rows per image: dP[(image, slot of row)] += the row's (R,A) block written by k_attend_bwd<.., true>, over the image's K rows
+// IN ASCENDING ROW ORDER (no float atomics: bitwise repeatable).  One thread per (image, region row, four A columns) walks the K rows;
+// rows of an image that name different slots touch different addresses, rows that share one are added one after the other.  Padding
+// entries (mask 0: their dz is 0, the block holds zeros) are skipped, as the one-row-per-image kernel never touches them.
+__global__ __launch_bounds__(256) void k_dP_rows_sum(const float* __restrict__ part, const int* __restrict__ slot, const float* __restrict__ rmask,
+                                                     int n_img, int K, int L, int R, int A, float* __restrict__ dP) {
+    const int A4 = A >> 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)n_img * R * A4) return;
+    const int a = (int)(i % A4) * 4, r = (int)((i / A4) % R), img = (int)(i / ((long long)A4 * R));
+    for (int j = 0; j < K; ++j) {
+        const long long row = (long long)img * K + j, sl = (long long)img * L + slot[row];
+        if (rmask[sl * R + r] == 0.f) continue;
+        const float4 v = *reinterpret_cast<const float4*>(part + (row * R + r) * A + a);
+        float4* d = reinterpret_cast<float4*>(dP + (sl * R + r) * A + a);
+        float4 o = *d;
+        o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+        *d = o;
     }
 }
 

@@ -857,7 +857,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
         });
     } else if (io.s1_from_prev && io.sel_simple) {
         hipLaunchKernelGGL(k_select_simple_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, *io.sel_simple, c.pre1, c.pre1_ns, c.pre1_stride,
-                           c.vproj, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5);
+                           c.vproj, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5, io.rpi);
     } else if (io.s1_from_prev) {
         hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.pre1, c.pre1_ns, c.pre1_stride, c.vproj, io.rpi,
                            io.parent, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, io.word_prev, c.pre1_nblk, 1, h1n16, s_t16, isc, c.pre1_skip5);
@@ -992,10 +992,12 @@ extern "C" int vsr_bad_ids(vsr_handle* h, int32_t* count, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------------- greedy / sampling
+// rpi rows per image (vsr_sample_rows: several independent samples of every image): the rows of an image are adjacent and read its
+// statics as beams do (row / rpi) - nothing is copied; there are no parent pointers, every row is its own history
 static int decode_simple(vsr_handle* h, int vmode, uint64_t seed, const int64_t* forced_w, const int64_t* forced_g,
-                         const float* verbs, int gt, int64_t* words, int64_t* gates, float* lp_w, float* lp_g, hipStream_t s) {
+                         const float* verbs, int gt, int64_t* words, int64_t* gates, float* lp_w, float* lp_g, hipStream_t s, int rpi = 1) {
     Ctx& c = h->c;
-    const int B = c.B, T = h->d.seq_len;
+    const int B = c.B * rpi, T = h->d.seq_len;          // (B: decoder rows)
     if (verbs && vmode != VM_TOPK) return fail("verb forcing is only defined for greedy / beam decoding");
     if (zero_state(h, B, s)) return 1;
     if (vmode == VM_FORCED) {
@@ -1011,7 +1013,7 @@ static int decode_simple(vsr_handle* h, int vmode, uint64_t seed, const int64_t*
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1;
         StepIO io;
-        io.t = t; io.M = B; io.cur = cur;
+        io.t = t; io.M = B; io.rpi = rpi; io.cur = cur;
         io.word_prev = c.word[cur]; io.slot = c.slot[cur];
         io.sel_simple = have_pending ? &pending : nullptr;
         io.vmode = vmode;
@@ -1043,6 +1045,16 @@ extern "C" int vsr_sample(vsr_handle* h, uint64_t seed, const int64_t* forced_wo
     if ((forced_words == nullptr) != (forced_gates == nullptr)) return fail("vsr_sample: forced_words and forced_gates go together");
     return decode_simple(h, forced_words ? VM_FORCED : VM_SAMPLE, seed, forced_words, forced_gates, nullptr, 0, words, gates,
                          lp_words, lp_gates, (hipStream_t)stream);
+}
+
+extern "C" int vsr_sample_rows(vsr_handle* h, int32_t rows_per_image, uint64_t seed, const int64_t* forced_words, const int64_t* forced_gates,
+                               int64_t* words, int64_t* gates, float* lp_words, float* lp_gates, void* stream) {
+    if (check_ready(h, "vsr_sample_rows")) return 1;
+    if (rows_per_image < 1 || rows_per_image > h->c.beam) return fail("vsr_sample_rows: rows_per_image %d not in [1, the prepared beam %d]", rows_per_image, h->c.beam);
+    if (!words || !gates || !lp_words || !lp_gates) return fail("vsr_sample_rows: null output");
+    if ((forced_words == nullptr) != (forced_gates == nullptr)) return fail("vsr_sample_rows: forced_words and forced_gates go together");
+    return decode_simple(h, forced_words ? VM_FORCED : VM_SAMPLE, seed, forced_words, forced_gates, nullptr, 0, words, gates,
+                         lp_words, lp_gates, (hipStream_t)stream, rows_per_image);
 }
 
 // ---------------------------------------------------------------------------------------------- beam search

@@ -58,6 +58,11 @@ def _count_optimizer_steps():
     _OPT_HOOK.append(register_optimizer_step_post_hook(_after_step))
 
 
+def _lib_max_beam():
+    from vsrcap import _lib
+    return _lib.MAX_BEAM
+
+
 def set_default_compute_dtype(dtype):
     """compute dtype of models constructed from now on ('f32' = exact fma chain everywhere, 'f32x3', 'f16x2', 'bf16'); returns the old one"""
     global DEFAULT_COMPUTE_DTYPE
@@ -281,14 +286,21 @@ class ControllableCaptioningModel(CaptioningModel):
         v = self._verbs(eng, statics[2], det.device, B, self._n_slots(ctrl)) if len(statics) > 2 and statics[2] is not None else None
         return eng.greedy(B, det.device, v, False)
 
-    def _run_sample(self, statics, seed=None, forced=None):
+    def _run_sample(self, statics, seed=None, forced=None, samples_per_image=1):
+        """samples_per_image = K (extension; the reference draws one sample per image and its SCST caller repeats every image): K
+        samples of every image in ONE call, rows b * K + j = sample j of image b (the order of repeat_interleave(K, 0)).  The image's
+        statics - region rows, att_va(regions), the pooled descriptor's projections - exist once, forward and backward."""
+        K = int(samples_per_image)
+        if not 1 <= K <= _lib_max_beam():
+            raise ValueError("samples_per_image must be in [1, %d] (the rows of an image share the beam workspace), got %r"
+                             % (_lib_max_beam(), samples_per_image))
         det, ctrl = statics[0], statics[1]
         with_grad = self._builds_graph()
         eng = self._engine(det.device, weights_may_have_moved=with_grad)
         from vsrcap.regions import IndexedRegions
         if with_grad and isinstance(ctrl, IndexedRegions) and ctrl.row_img is not None:
             raise RuntimeError("sample_rl with gradients on IndexedRegions needs one decoder row per image (row_img=None)")
-        B = self._prepare(eng, det, ctrl, 1, for_training=with_grad)
+        B = self._prepare(eng, det, ctrl, K, for_training=with_grad)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             # data-parallel ranks that called torch.manual_seed(s) with the same s would otherwise draw IDENTICAL Gumbel /
@@ -296,10 +308,10 @@ class ControllableCaptioningModel(CaptioningModel):
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
                 seed ^= (dist.get_rank() + 1) << 48
-        outs, lps = eng.sample(B, det.device, seed, forced)
+        outs, lps = eng.sample(B, det.device, seed, forced, K)
         if with_grad:
             from vsrcap.train import sample_logprobs_with_grad
-            lps = sample_logprobs_with_grad(self, eng, det, ctrl, outs, lps)
+            lps = sample_logprobs_with_grad(self, eng, det, ctrl, outs, lps, K)
         return outs, lps
 
     def _run_beam(self, statics, eos_idxs, beam_size, out_size, with_verbs, gt):

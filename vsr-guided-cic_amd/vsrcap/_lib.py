@@ -38,6 +38,8 @@ class VsrWeights(C.Structure):
     _fields_ = [(f, C.c_void_p) for f, _ in WEIGHT_FIELDS]
 
 
+MAX_BEAM = 8          # VSR_MAX_BEAM of include/vsrcap.h: beams, and rows (samples) per image
+
 P = C.c_void_p
 I32, I64, U64, SZ = C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
 
@@ -85,11 +87,14 @@ SIGNATURES = {
     "vsr_reorder_slots": (I32, [P, P, P, P, P, I32, I32, I32, I32, P, P, P]),
     "vsr_greedy": (I32, [P, P, I32, P, P, P]),
     "vsr_sample": (I32, [P, U64, P, P, P, P, P, P, P]),
+    "vsr_sample_rows": (I32, [P, I32, U64, P, P, P, P, P, P, P]),
     "vsr_beam": (I32, [P, I32, I32, I64, I64, P, I32, P, P, P, P, P, P]),
     "vsr_xe_forward": (I32, [P, P, I32, P, P, P]),
     "vsr_train_workspace_bytes": (SZ, [P, I32, I32]),
     "vsr_train_forward": (I32, [P, P, P, I32, P, P, P, SZ, P]),
     "vsr_train_backward": (I32, [P, P, P, C.POINTER(VsrWeights), P]),
+    "vsr_train_workspace_bytes_rows": (SZ, [P, I32, I32, I32]),
+    "vsr_train_forward_rows": (I32, [P, I32, P, P, I32, P, P, P, SZ, P]),
     "vsr_train_generation": (I64, [P]),
     "vsr_train_select": (I32, [P, I64, P]),
     "vsr_train_bucket_map": (I32, [C.POINTER(I32), C.POINTER(I32)]),

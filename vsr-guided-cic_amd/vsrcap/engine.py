@@ -362,13 +362,20 @@ class Engine:
 
     # ------------------------------------------------------------------ training (forward with saves + BPTT backward)
     @_on_device
-    def train_forward(self, B, device, word_in, slots=None):
+    def train_forward(self, B, device, word_in, slots=None, rows_per_image=1):
+        """B images, rows_per_image decoder rows each (word_in / slots and the outputs have B * rows_per_image rows, an image's rows
+        adjacent); prepare() must have been called with beam >= rows_per_image"""
+        K, n_img = int(rows_per_image), B
+        B = n_img * K
+        if word_in.size(0) != B:
+            raise RuntimeError("train_forward: %d rows of word ids for %d images x %d rows per image" % (word_in.size(0), n_img, K))
         T = word_in.size(1)
         V = self.dims.vocab_size
         word_in = word_in.to(device=device, dtype=torch.int64).contiguous()
         if slots is not None:
             slots = slots.to(device=device, dtype=torch.int64).contiguous()
-        need = self.lib.vsr_train_workspace_bytes(self.h, B, T)
+        need = (self.lib.vsr_train_workspace_bytes(self.h, B, T) if K == 1 else
+                self.lib.vsr_train_workspace_bytes_rows(self.h, n_img, K, T))
         if need == 0:
             raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
         if getattr(self, "_tws", None) is None or self._tws.numel() < need or self._tws.device != device:
@@ -377,8 +384,12 @@ class Engine:
         gate = torch.empty(B, T, 2, dtype=torch.float32, device=device)
         if self._slot.live():
             raise RuntimeError("internal: training forward into a slot that holds a live forward (prepare(for_training=True) first)")
-        _lib.check(self.lib.vsr_train_forward(self.h, _ptr(word_in), _ptr(slots), T, _ptr(out), _ptr(gate), _ptr(self._tws),
-                                              self._tws.numel(), self._stream(device)))
+        if K == 1:
+            _lib.check(self.lib.vsr_train_forward(self.h, _ptr(word_in), _ptr(slots), T, _ptr(out), _ptr(gate), _ptr(self._tws),
+                                                  self._tws.numel(), self._stream(device)))
+        else:
+            _lib.check(self.lib.vsr_train_forward_rows(self.h, K, _ptr(word_in), _ptr(slots), T, _ptr(out), _ptr(gate), _ptr(self._tws),
+                                                       self._tws.numel(), self._stream(device)))
         self._slot.generation = self.train_generation()
         self._slot.token = None
         self._slot.differentiated = True      # (until train.py attaches the autograd node's token: note_forward)
@@ -480,7 +491,10 @@ class Engine:
         return words, gates
 
     @_on_device
-    def sample(self, B, device, seed, forced=None):
+    def sample(self, B, device, seed, forced=None, rows_per_image=1):
+        """rows_per_image = K > 1: K samples of every image in one call, outputs (B * K, T), row b * K + j = sample j of image b"""
+        K = int(rows_per_image)
+        B = B * K
         T = self.dims.seq_len
         words = torch.empty(B, T, dtype=torch.int64, device=device)
         gates = torch.empty(B, T, dtype=torch.int64, device=device)
@@ -490,8 +504,14 @@ class Engine:
         if forced is not None:
             fw = forced[0].to(device=device, dtype=torch.int64).contiguous()
             fg = forced[1].to(device=device, dtype=torch.int64).contiguous()
-        _lib.check(self.lib.vsr_sample(self.h, C.c_uint64(seed), _ptr(fw), _ptr(fg), _ptr(words), _ptr(gates), _ptr(lpw),
-                                       _ptr(lpg), self._stream(device)))
+            if tuple(fw.shape) != (B, T) or tuple(fg.shape) != (B, T):
+                raise RuntimeError("forced samples must be two (%d, %d) tensors, got %s and %s" % (B, T, tuple(fw.shape), tuple(fg.shape)))
+        if K == 1:
+            _lib.check(self.lib.vsr_sample(self.h, C.c_uint64(seed), _ptr(fw), _ptr(fg), _ptr(words), _ptr(gates), _ptr(lpw),
+                                           _ptr(lpg), self._stream(device)))
+        else:
+            _lib.check(self.lib.vsr_sample_rows(self.h, K, C.c_uint64(seed), _ptr(fw), _ptr(fg), _ptr(words), _ptr(gates), _ptr(lpw),
+                                                _ptr(lpg), self._stream(device)))
         if forced is not None:
             self.raise_on_bad_ids(device, "sample (forced ids)")
         return (words, gates), (lpw, lpg)

@@ -259,9 +259,15 @@ class DataParallelStep:
         stats = torch.stack([loss.detach(), loss_cap.detach(), loss_gate.detach()]).double()
         return self._sum(stats)                              # global loss, loss_cap, loss_gate
 
-    def scst_step(self, det, ctrl, reward_fn):
-        """reward_fn(words (b,T)) -> (reward (b,), baseline (b,)) tensors (vsrcap.reward.CiderD on the device, or the caller's)."""
-        (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl)
+    def scst_step(self, det, ctrl, reward_fn, samples_per_image=1):
+        """reward_fn(words (b,T)) -> (reward (b,), baseline (b,)) tensors (vsrcap.reward.CiderD on the device, or the caller's).
+        samples_per_image = K > 1: sample_fn(det, ctrl, samples_per_image=K) draws K samples of each of the b images in one call
+        (model.sample_rl: statics shared); reward_fn then sees (b * K, T) words, row i * K + j = sample j of image i, and the global
+        count is the number of samples."""
+        if samples_per_image == 1:
+            (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl)
+        else:
+            (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl, samples_per_image=samples_per_image)
         reward, baseline = reward_fn(words)
         n = torch.tensor([float(words.shape[0])], dtype=torch.float64, device=lp_w.device)
         self._sum(n)
