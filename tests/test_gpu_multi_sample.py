@@ -67,6 +67,7 @@ def _grads(m):
 
 
 def _check(got, want, rtol):
+    """a ceiling against the fp32 oracle; the tight bound (fp64 oracle, per kernel route) lives in tests/test_gpu_grad_routes.py"""
     for k in want:
         g, r = got[k].double(), want[k].double()
         scale = r.abs().max().item() + 1e-12

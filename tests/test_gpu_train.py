@@ -34,6 +34,7 @@ def _device_grads(m, det, caps, ctrl_seq, gts):
 
 
 def _check(got, want, rtol):
+    """a ceiling against the fp32 oracle; the tight bound (fp64 oracle, per kernel route) lives in tests/test_gpu_grad_routes.py"""
     for k in want:
         g, r = got[k].double(), want[k].double()
         scale = r.abs().max().item() + 1e-12
