@@ -345,6 +345,35 @@ size_t vsr_sinkhorn_workspace_bytes(int32_t Q, int32_t N);
 int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, float* tr, int32_t* assign, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* ---- SinkhornNet training (coco_scripts/train_sinkhorn.py:137-215) -----------------------------------
+ * The reference calls the net once per (image, caption, verb, repeated role) at batch size 1 and adds MSE losses on the host.
+ * Here one forward, one fused loss and one backward serve all Q items of a loader batch; exact fp32 products throughout.
+ *   tape       caller-owned, vsr_sinkhorn_tape_bytes(Q, N) bytes: the post-activation outputs of the five layers, tr and the
+ *              2 n_iters N Sinkhorn divisors per item, behind a header in which the forward records its n_iters and tau.  It
+ *              belongs to ONE forward: several forwards may be alive at once, each with its own tape, and vsr_sinkhorn_assign()
+ *              between a forward and its backward touches none of them.  The backward takes n_iters and tau from the tape, not
+ *              from the binding: it differentiates the forward that wrote the tape.  N and the ten weights are the caller's to
+ *              keep bound as they were.
+ *   workspace  vsr_sinkhorn_train_workspace_bytes(Q, N) bytes, scratch of either call (nothing survives in it).
+ *   n_iters    any value >= 0 binds; the training entry points accept n_iters <= 64 (the tape's divisor rows) and fail beyond.
+ * vsr_sinkhorn_train_forward: seq (Q,N,2352) -> tr (Q,N,N), bit-identical to vsr_sinkhorn_assign's; no assignment.
+ * vsr_sinkhorn_loc_loss: train_sinkhorn.py:207-209 for Q items.  tr_locs, gt_locs (Q,N) fp32;
+ *   loss_items[q] = mean_j ((tr_locs[q] . tr[q])_j - gt_locs[q][j])^2, d_tr (Q,N,N) or NULL = the gradient of
+ *   scale * sum_q loss_items[q] with respect to tr.  The caller adds loss_items (a fixed order: torch.sum).
+ * vsr_sinkhorn_train_backward: d_tr (Q,N,N) -> the ten parameter gradients, OVERWRITTEN (the caller accumulates).  seq is the
+ *   forward's input; it receives no gradient.  Two calls on the same tape and d_tr write the same bits. */
+typedef struct vsr_sinkhorn_grads {
+    float *W1_txt_w, *W1_txt_b, *W1_vis_w, *W1_vis_b, *W2_vis_w, *W2_vis_b, *W_fc_pos_w, *W_fc_pos_b, *W_fc_w, *W_fc_b;
+} vsr_sinkhorn_grads;
+size_t vsr_sinkhorn_tape_bytes(int32_t Q, int32_t N);
+size_t vsr_sinkhorn_train_workspace_bytes(int32_t Q, int32_t N);
+int vsr_sinkhorn_train_forward(vsr_ssp* e, const float* seq, int32_t Q, float* tr, void* tape, size_t tape_bytes, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int vsr_sinkhorn_loc_loss(const float* tr, const float* tr_locs, const float* gt_locs, int32_t Q, int32_t N, float scale, float* loss_items,
+                          float* d_tr, void* stream);
+int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t Q, const void* tape, size_t tape_bytes, const float* d_tr,
+                                const vsr_sinkhorn_grads* g, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement (bench.py roofline leg) ------------------------------------------------------------ */
 /* Between begin and end every fp32-MFMA GEMM launch is bracketed by a pair of pre-created HIP events on the
  * caller's stream.  end() synchronises the stream and returns the summed launch durations, the number of

@@ -204,3 +204,180 @@ extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, floa
     LAUNCHCHK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------- SinkhornNet training
+// coco_scripts/train_sinkhorn.py:137-215 calls the net once per (image, caption, verb, repeated role) at batch size 1 and adds the
+// losses on the host; here ONE forward, ONE fused location loss and ONE backward serve all Q items of a loader batch.
+//   forward   the five linear1 products, k_sh_cat and the Sinkhorn arithmetic of vsr_sinkhorn_assign in the same order (tr is
+//             bit-identical to assign's), outputs written into the caller's TAPE; no assignment
+//   backward  k_sinkhorn_bwd (ssp_kernels.h: the divisor tape), then the five layers: ReLU masks from the taped outputs, bias
+//             gradients by the ordered column sums of the decoder's training pass (k_colsum), dW = dY^T X and dX = dY W as NT
+//             products on transposed copies (k_transpose_multi), all on the exact fp32 kernels.  No gradient flows to seq, so
+//             the two input layers have no dX product (the 2048-wide one is the largest of the pass).
+// The k extent of the dW products is R = Q N, any integer: the transposed copies have the leading dimension Rp = R rounded up to 4
+// (what gemm_f32.h asks of K and the leading dimensions) and k_transpose_* zero the padding columns.  d_pre and W_fc^T are padded
+// to Np = N rounded up to 4 in the same way.
+// The tape's size is a function of (Q, N) alone, so each item has room for 2 x SH_TRAIN_MAX_ITERS divisor rows whatever n_iters is
+// bound.  The forward RECORDS its n_iters and tau in the tape's header and packs the divisors at the stride 2 n_iters N; the
+// backward takes both from the header, never from the binding, so it differentiates the forward that wrote the tape even when
+// the object was re-bound in between (k_sinkhorn_bwd clamps the header's n_iters to the slot: a tape no forward wrote cannot
+// send it out of bounds).
+constexpr int SH_TRAIN_MAX_ITERS = 64;
+
+struct ShTape { int* hdr; float *t1, *v1, *v2, *cat, *f1, *th, *tr, *div; };
+static size_t carve_sh_tape(int Q, int N, char* base, ShTape& t) {
+    const size_t R = (size_t)Q * N;
+    Bump b{base};
+    t.hdr = b.take<int>(SH_TAPE_HDR_INTS);
+    t.t1 = b.take<float>(R * 128); t.v1 = b.take<float>(R * 512); t.v2 = b.take<float>(R * 128); t.cat = b.take<float>(R * 260);
+    t.f1 = b.take<float>(R * 256); t.th = b.take<float>(R * N); t.tr = b.take<float>(R * N);
+    t.div = b.take<float>((size_t)Q * 2 * SH_TRAIN_MAX_ITERS * N);
+    return (b.off + 255) & ~size_t(255);
+}
+struct ShTrainWs {
+    float *dpre, *df1, *dcat, *dv1;                              // gradients of the pre-activations (ReLU / tanh already applied)
+    float *wfcT, *wposT, *w2T;                                   // W^T of the three layers that pass a gradient down
+    float *dpreT, *f1T, *df1T, *catT, *dt1T, *txtT, *dv2T, *v1T, *dv1T, *visT;      // (columns, Rp) operands of the dW products
+    float* scratch;
+    size_t scratch_floats;
+};
+static size_t carve_sh_train(int Q, int N, char* base, ShTrainWs& w) {
+    const size_t R = (size_t)Q * N, Rp = (R + 3) & ~size_t(3), Np = ((size_t)N + 3) & ~size_t(3);
+    Bump b{base};
+    w.dpre = b.take<float>(R * Np); w.df1 = b.take<float>(R * 256); w.dcat = b.take<float>(R * 256); w.dv1 = b.take<float>(R * 512);
+    w.wfcT = b.take<float>(256 * Np); w.wposT = b.take<float>(260 * 256); w.w2T = b.take<float>(512 * 128);
+    w.dpreT = b.take<float>(N * Rp); w.f1T = b.take<float>(256 * Rp); w.df1T = b.take<float>(256 * Rp); w.catT = b.take<float>(260 * Rp);
+    w.dt1T = b.take<float>(128 * Rp); w.txtT = b.take<float>(300 * Rp); w.dv2T = b.take<float>(128 * Rp); w.v1T = b.take<float>(512 * Rp);
+    w.dv1T = b.take<float>(512 * Rp); w.visT = b.take<float>(2048 * Rp);
+    w.scratch_floats = std::max<size_t>((size_t)512 * 2048, R * 512) * 8;       // the forward's need (R x 512 x 8 slabs) and W1_vis's gradient in 8 slabs
+    w.scratch = b.take<float>(w.scratch_floats);
+    return (b.off + 255) & ~size_t(255);
+}
+extern "C" size_t vsr_sinkhorn_tape_bytes(int32_t Q, int32_t N) {
+    if (Q <= 0 || N < 2 || N > 16) return 0;
+    ShTape t;
+    return carve_sh_tape(Q, N, nullptr, t);
+}
+extern "C" size_t vsr_sinkhorn_train_workspace_bytes(int32_t Q, int32_t N) {
+    if (Q <= 0 || N < 2 || N > 16) return 0;
+    ShTrainWs w;
+    return carve_sh_train(Q, N, nullptr, w);
+}
+
+extern "C" int vsr_sinkhorn_train_forward(vsr_ssp* e, const float* seq, int32_t Q, float* tr, void* tape, size_t tape_bytes, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    if (!e || !e->has_sh) return fail("vsr_sinkhorn_train_forward: Sinkhorn weights not bound");
+    if (!seq || !tr || !tape || !workspace || Q <= 0) return fail("vsr_sinkhorn_train_forward: bad arguments");
+    const vsr_sinkhorn_weights& w = e->sw;
+    if (w.n_iters > SH_TRAIN_MAX_ITERS) return fail("vsr_sinkhorn_train_forward: n_iters %d exceeds the training cap of %d (the tape's divisor rows)", w.n_iters, SH_TRAIN_MAX_ITERS);
+    const int N = w.N, R = Q * N;
+    if ((long long)Q * N * 2352 > INT_MAX) return fail("vsr_sinkhorn_train_forward: Q %d too large", Q);
+    ShTape t;
+    ShTrainWs tw;
+    if (carve_sh_tape(Q, N, reinterpret_cast<char*>(tape), t) > tape_bytes) return fail("vsr_sinkhorn_train_forward: tape too small");
+    if (carve_sh_train(Q, N, reinterpret_cast<char*>(workspace), tw) > workspace_bytes) return fail("vsr_sinkhorn_train_forward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    SspWs ws{};
+    ws.scratch = tw.scratch;
+    ws.scratch_floats = tw.scratch_floats;
+    if (linear1(e, ws, s, R, 128, 300, seq, 2352, w.W1_txt_w, w.W1_txt_b, 1, nullptr, t.t1)) return 1;
+    if (linear1(e, ws, s, R, 512, 2048, seq + 300, 2352, w.W1_vis_w, w.W1_vis_b, 1, nullptr, t.v1)) return 1;
+    if (linear1(e, ws, s, R, 128, 512, t.v1, 512, w.W2_vis_w, w.W2_vis_b, 1, nullptr, t.v2)) return 1;
+    hipLaunchKernelGGL(k_sh_cat, dim3(cdiv((long long)R * 260, 256)), dim3(256), 0, s, t.t1, t.v2, seq, R, t.cat);
+    if (linear1(e, ws, s, R, 256, 260, t.cat, 260, w.W_fc_pos_w, w.W_fc_pos_b, 1, nullptr, t.f1)) return 1;
+    if (linear1(e, ws, s, R, N, 256, t.f1, 256, w.W_fc_w, w.W_fc_b, 2, nullptr, t.th)) return 1;
+    hipLaunchKernelGGL(k_sinkhorn_train_fwd, dim3(Q), dim3(64), 0, s, t.th, N, w.n_iters, w.tau, tr, t.tr, t.div, t.hdr);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int vsr_sinkhorn_loc_loss(const float* tr, const float* tr_locs, const float* gt_locs, int32_t Q, int32_t N, float scale, float* loss_items,
+                                     float* d_tr, void* stream) {
+    if (!tr || !tr_locs || !gt_locs || !loss_items || Q <= 0 || N < 2 || N > 16) return fail("vsr_sinkhorn_loc_loss: bad arguments (2 <= N <= 16)");
+    hipLaunchKernelGGL(k_sinkhorn_loc_loss, dim3(Q), dim3(64), 0, (hipStream_t)stream, tr, tr_locs, gt_locs, N, scale, loss_items, d_tr);
+    LAUNCHCHK();
+    return 0;
+}
+
+// dst (M, N; leading dimension ldd) = A (M, K) . W (N, K)^T on the exact fp32 kernels; relu_y: masked by the ReLU whose output it is
+static int sh_product(vsr_ssp* e, ShTrainWs& ws, hipStream_t s, int M, int N, int K, const float* A, int lda, const float* W, int ldw, float* dst,
+                      int ldd, const float* relu_y = nullptr, int ldy = 0) {
+    if ((K & 3) || (lda & 3) || (ldw & 3) || !aligned16(A) || !aligned16(W)) return fail("sinkhorn backward: operand not in whole 16-byte groups (K %d, lda %d, ldw %d)", K, lda, ldw);
+    GemmBuilder g;
+    GemmProb& p = g.prob(M, N, nullptr, N);
+    GemmBuilder::seg(p, A, lda, nullptr, W, ldw, K);
+    const int ns = g.finish(&e->cfg);
+    if (ns == 1 && !relu_y) {                     // every tile is produced by one workgroup: written in place
+        g.a.p[0].C = dst; g.a.p[0].ldc = ldd; g.a.p[0].slab_stride = 0;
+        if (g.launch(s, &e->cfg)) return fail("sinkhorn backward: gemm launch failed");
+        return 0;
+    }
+    const long long tot = (long long)M * N;
+    if ((size_t)tot * ns > ws.scratch_floats) return fail("sinkhorn backward: GEMM scratch too small");
+    g.a.p[0].C = ws.scratch; g.a.p[0].slab_stride = tot;
+    if (g.launch(s, &e->cfg)) return fail("sinkhorn backward: gemm launch failed");
+    if (relu_y) hipLaunchKernelGGL(k_relu_bwd_finish, dim3(cdiv(tot, 256)), dim3(256), 0, s, ws.scratch, ns, tot, M, N, relu_y, (long long)ldy, dst, (long long)ldd);
+    else hipLaunchKernelGGL(k_slab_reduce_2d, dim3(cdiv(tot, 256)), dim3(256), 0, s, ws.scratch, ns, tot, M, N, dst, (long long)ldd);
+    return 0;
+}
+// out[c] = sum over rows of X[r][c], in the fixed order of k_colsum / k_colsum_finish, through the (idle) slab scratch
+static void sh_colsum(ShTrainWs& ws, hipStream_t s, const float* X, long long ld, int R, int C, float* out) {
+    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, ld, R, C, ws.scratch);
+    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, ws.scratch, C, 0, C, out, (float*)nullptr);
+}
+
+extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t Q, const void* tape, size_t tape_bytes, const float* d_tr,
+                                           const vsr_sinkhorn_grads* g, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || !e->has_sh) return fail("vsr_sinkhorn_train_backward: Sinkhorn weights not bound");
+    if (!seq || !tape || !d_tr || !g || !workspace || Q <= 0) return fail("vsr_sinkhorn_train_backward: bad arguments");
+    if (!g->W1_txt_w || !g->W1_txt_b || !g->W1_vis_w || !g->W1_vis_b || !g->W2_vis_w || !g->W2_vis_b || !g->W_fc_pos_w || !g->W_fc_pos_b || !g->W_fc_w || !g->W_fc_b)
+        return fail("vsr_sinkhorn_train_backward: all ten gradient pointers are required");
+    const vsr_sinkhorn_weights& w = e->sw;
+    const int N = w.N, R = Q * N, Rp = (R + 3) & ~3, Np = (N + 3) & ~3;
+    if ((long long)Q * N * 2352 > INT_MAX) return fail("vsr_sinkhorn_train_backward: Q %d too large", Q);
+    ShTape t;
+    ShTrainWs ws;
+    if (carve_sh_tape(Q, N, reinterpret_cast<char*>(const_cast<void*>(tape)), t) > tape_bytes) return fail("vsr_sinkhorn_train_backward: tape too small");
+    if (carve_sh_train(Q, N, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_sinkhorn_train_backward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_sinkhorn_bwd, dim3(Q), dim3(64), 0, s, t.hdr, SH_TRAIN_MAX_ITERS, t.tr, t.div, t.th, d_tr, N, ws.dpre, Np);
+    // everything that can be transposed before the first product: the three weights, the taped activations, the input's two column blocks
+    TransBatch tb;
+    auto tr_add = [&](const float* in, long long ld_in, int rows, int cols, float* out, long long ld_out) { tb.add(s, 0, nullptr, in, ld_in, rows, cols, out, ld_out, nullptr, 0); };
+    tr_add(w.W_fc_w, 256, N, 256, ws.wfcT, Np);
+    tr_add(w.W_fc_pos_w, 260, 256, 260, ws.wposT, 256);
+    tr_add(w.W2_vis_w, 512, 128, 512, ws.w2T, 128);
+    tr_add(ws.dpre, Np, R, N, ws.dpreT, Rp);
+    tr_add(t.f1, 256, R, 256, ws.f1T, Rp);
+    tr_add(t.cat, 260, R, 260, ws.catT, Rp);
+    tr_add(seq, 2352, R, 300, ws.txtT, Rp);
+    tr_add(t.v1, 512, R, 512, ws.v1T, Rp);
+    tr_add(seq + 300, 2352, R, 2048, ws.visT, Rp);
+    tb.flush(s);
+    // W_fc
+    sh_colsum(ws, s, ws.dpre, Np, R, N, g->W_fc_b);
+    if (sh_product(e, ws, s, N, 256, Rp, ws.dpreT, Rp, ws.f1T, Rp, g->W_fc_w, 256)) return 1;
+    if (sh_product(e, ws, s, R, 256, Np, ws.dpre, Np, ws.wfcT, Np, ws.df1, 256, t.f1, 256)) return 1;
+    // W_fc_pos: its input is [t1 | v2 | pos]; the first 256 columns carry a gradient further down, both behind a ReLU
+    tr_add(ws.df1, 256, R, 256, ws.df1T, Rp);
+    tb.flush(s);
+    sh_colsum(ws, s, ws.df1, 256, R, 256, g->W_fc_pos_b);
+    if (sh_product(e, ws, s, 256, 260, Rp, ws.df1T, Rp, ws.catT, Rp, g->W_fc_pos_w, 260)) return 1;
+    if (sh_product(e, ws, s, R, 256, 256, ws.df1, 256, ws.wposT, 256, ws.dcat, 256, t.cat, 260)) return 1;
+    // W1_txt and W2_vis
+    tr_add(ws.dcat, 256, R, 128, ws.dt1T, Rp);
+    tr_add(ws.dcat + 128, 256, R, 128, ws.dv2T, Rp);
+    tb.flush(s);
+    sh_colsum(ws, s, ws.dcat, 256, R, 128, g->W1_txt_b);
+    sh_colsum(ws, s, ws.dcat + 128, 256, R, 128, g->W2_vis_b);
+    if (sh_product(e, ws, s, 128, 300, Rp, ws.dt1T, Rp, ws.txtT, Rp, g->W1_txt_w, 300)) return 1;
+    if (sh_product(e, ws, s, 128, 512, Rp, ws.dv2T, Rp, ws.v1T, Rp, g->W2_vis_w, 512)) return 1;
+    if (sh_product(e, ws, s, R, 512, 128, ws.dcat + 128, 256, ws.w2T, 128, ws.dv1, 512, t.v1, 512)) return 1;
+    // W1_vis
+    tr_add(ws.dv1, 512, R, 512, ws.dv1T, Rp);
+    tb.flush(s);
+    sh_colsum(ws, s, ws.dv1, 512, R, 512, g->W1_vis_b);
+    if (sh_product(e, ws, s, 512, 2048, Rp, ws.dv1T, Rp, ws.visT, Rp, g->W1_vis_w, 2048)) return 1;
+    LAUNCHCHK();
+    return 0;
+}

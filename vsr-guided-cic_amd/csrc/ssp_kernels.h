@@ -179,6 +179,30 @@ __global__ void k_sh_cat(const float* __restrict__ t1, const float* __restrict__
     cat[i] = c < 128 ? t1[(long long)r * 128 + c] : c < 256 ? v2[(long long)r * 128 + c - 128] : seq[(long long)r * 2352 + 2348 + c - 256];
 }
 
+// n_iters x (column-normalise, row-normalise) of the N x N matrix of one wave (N <= 16) with the reference's eps 10e-8
+// (sinkhorn_network.py:30-37).  div (optional, (2 n_iters, N)): the divisors, in the order they are applied - the tape of the
+// training forward (k_sinkhorn_train_fwd); the arithmetic does not depend on it, so both callers produce the same bits.
+__device__ __forceinline__ void sinkhorn_normalise(float (*x)[17], int N, int n_iters, int lane, float* __restrict__ div) {
+    for (int it = 0; it < n_iters; ++it) {
+        if (lane < N) {                                  // x / (eps + sum over rows): lane = column
+            float s = 0.f;
+            for (int r = 0; r < N; ++r) s += x[r][lane];
+            s += 10e-8f;
+            if (div) div[(2 * it) * N + lane] = s;
+            for (int r = 0; r < N; ++r) x[r][lane] = x[r][lane] / s;
+        }
+        __syncthreads();
+        if (lane < N) {                                  // x / (eps + sum over columns): lane = row
+            float s = 0.f;
+            for (int c = 0; c < N; ++c) s += x[lane][c];
+            s += 10e-8f;
+            if (div) div[(2 * it + 1) * N + lane] = s;
+            for (int c = 0; c < N; ++c) x[lane][c] = x[lane][c] / s;
+        }
+        __syncthreads();
+    }
+}
+
 // One wave per item: x = exp(tanh(fc) / tau) (N x N, N <= 16), n_iters x (column-normalise, row-normalise) with the reference's
 // eps 10e-8 (sinkhorn_network.py:30-37), then the assignment of eval_coco.py:185-189 on mx = x^T: columns chosen so that
 // sum(max(mx) - mx[row][col]) is minimal (Kuhn-Munkres with potentials, O(N^3), fp64, lane 0).  assign[row] = column.
@@ -190,22 +214,7 @@ __global__ __launch_bounds__(64) void k_sinkhorn_assign(const float* __restrict_
     const float* f = fc + (long long)qi * N * N;
     for (int i = lane; i < N * N; i += 64) x[i / N][i % N] = expf(f[i] / tau);
     __syncthreads();
-    for (int it = 0; it < n_iters; ++it) {
-        if (lane < N) {                                  // x / (eps + sum over rows): lane = column
-            float s = 0.f;
-            for (int r = 0; r < N; ++r) s += x[r][lane];
-            s += 10e-8f;
-            for (int r = 0; r < N; ++r) x[r][lane] = x[r][lane] / s;
-        }
-        __syncthreads();
-        if (lane < N) {                                  // x / (eps + sum over columns): lane = row
-            float s = 0.f;
-            for (int c = 0; c < N; ++c) s += x[lane][c];
-            s += 10e-8f;
-            for (int c = 0; c < N; ++c) x[lane][c] = x[lane][c] / s;
-        }
-        __syncthreads();
-    }
+    sinkhorn_normalise(x, N, n_iters, lane, nullptr);
     if (tr)
         for (int i = lane; i < N * N; i += 64) tr[(long long)qi * N * N + i] = x[i / N][i % N];
     if (lane == 0) {
@@ -247,6 +256,112 @@ __global__ __launch_bounds__(64) void k_sinkhorn_assign(const float* __restrict_
         }
         for (int j = 1; j <= N; ++j) assign[(long long)qi * N + p[j] - 1] = j - 1;
     }
+}
+
+// ---------------------------------------------------------------------------------------------- SinkhornNet training
+// TAPE of the Sinkhorn part (chosen: the DIVISORS, 2 n_iters N floats per item, not the O(n_iters N^2) intermediate matrices).
+// With y = x / d, d = eps + sum of x along the normalised axis, the backward of one normalisation is
+//     dx = (dy - sum(dy . y)) / d        (sum along the same axis)
+// and x = y d rebuilds the step's input from its output, so the walk back needs tr, the divisors and nothing else.  The rebuilt
+// x differs from the forward's by one rounding per step; the first matrix exp(tanh / tau) is recomputed from the taped tanh.
+
+// The tape's header: what the forward ran with, written by the forward and read by the backward.
+constexpr int SH_TAPE_HDR_INTS = 4;      // [0] n_iters, [1] the bits of tau, [2] N, [3] unused
+
+// the training forward's Sinkhorn: k_sinkhorn_assign's arithmetic (same helper, same order => the same bits in tr) without the
+// assignment; div (Q, 2 n_iters, N) receives the divisors, hdr the n_iters and tau they belong to.  One wave per item.
+__global__ __launch_bounds__(64) void k_sinkhorn_train_fwd(const float* __restrict__ th /* (Q, N, N): tanh output */, int N, int n_iters, float tau,
+                                                           float* __restrict__ tr, float* __restrict__ tr_tape, float* __restrict__ div, int* __restrict__ hdr) {
+    __shared__ float x[16][17];
+    const int qi = blockIdx.x, lane = threadIdx.x;
+    if (qi == 0 && lane < SH_TAPE_HDR_INTS) hdr[lane] = lane == 0 ? n_iters : lane == 1 ? __float_as_int(tau) : lane == 2 ? N : 0;
+    const float* f = th + (long long)qi * N * N;
+    for (int i = lane; i < N * N; i += 64) x[i / N][i % N] = expf(f[i] / tau);
+    __syncthreads();
+    sinkhorn_normalise(x, N, n_iters, lane, div + (long long)qi * 2 * n_iters * N);
+    for (int i = lane; i < N * N; i += 64) {
+        const float v = x[i / N][i % N];
+        tr[(long long)qi * N * N + i] = v;
+        tr_tape[(long long)qi * N * N + i] = v;
+    }
+}
+
+// Backward of the Sinkhorn part, one wave per item (N <= 16): d_tr -> the 2 n_iters normalisations walked backwards -> exp(. / tau)
+// -> tanh -> d_pre (Q N, ld) = the gradient of W_fc's pre-activation; columns N .. ld - 1 (the k padding of the GEMMs that read it)
+// receive zeros.  Every sum is a sequential loop of one lane: no atomics, the same bits on every run.  n_iters and tau are the
+// FORWARD's, from the tape's header (n_iters clamped to the max_iters pairs of divisor rows an item's slot holds).
+__global__ __launch_bounds__(64) void k_sinkhorn_bwd(const int* __restrict__ hdr, int max_iters, const float* __restrict__ tr, const float* __restrict__ div,
+                                                     const float* __restrict__ th, const float* __restrict__ d_tr, int N, float* __restrict__ d_pre, int ld) {
+    __shared__ float y[16][17], g[16][17];
+    const int qi = blockIdx.x, lane = threadIdx.x;
+    const int n_iters = min(max(hdr[0], 0), max_iters);
+    const float tau = __int_as_float(hdr[1]);
+    const long long base = (long long)qi * N * N;
+    for (int i = lane; i < N * N; i += 64) { y[i / N][i % N] = tr[base + i]; g[i / N][i % N] = d_tr[base + i]; }
+    __syncthreads();
+    const float* dv = div + (long long)qi * 2 * n_iters * N;
+    for (int it = n_iters - 1; it >= 0; --it) {
+        if (lane < N) {                                  // the row normalisation: lane = row
+            const float d = dv[(2 * it + 1) * N + lane];
+            float s = 0.f;
+            for (int c = 0; c < N; ++c) s += g[lane][c] * y[lane][c];
+            for (int c = 0; c < N; ++c) { g[lane][c] = (g[lane][c] - s) / d; y[lane][c] = y[lane][c] * d; }
+        }
+        __syncthreads();
+        if (lane < N) {                                  // the column normalisation: lane = column
+            const float d = dv[(2 * it) * N + lane];
+            float s = 0.f;
+            for (int r = 0; r < N; ++r) s += g[r][lane] * y[r][lane];
+            for (int r = 0; r < N; ++r) { g[r][lane] = (g[r][lane] - s) / d; y[r][lane] = y[r][lane] * d; }
+        }
+        __syncthreads();
+    }
+    for (int i = lane; i < N * ld; i += 64) {
+        const int r = i / ld, c = i % ld;
+        float o = 0.f;
+        if (c < N) {
+            const float t = th[base + r * N + c];
+            o = g[r][c] * (expf(t / tau) / tau) * (1.f - t * t);
+        }
+        d_pre[((long long)qi * N + r) * ld + c] = o;
+    }
+}
+
+// The location loss of train_sinkhorn.py:207-209 for Q items, one wave per item (lane = column j of tr):
+//   resort_j = sum_i tr_locs[q][i] tr[q][i][j];   loss_items[q] = mean_j (resort_j - gt_locs[q][j])^2
+//   d_tr[q][i][j] = scale (2 / N) (resort_j - gt_j) tr_locs[q][i]          (the gradient of scale x sum_q loss_items[q])
+// The N squares are added by lane 0 in column order.
+__global__ __launch_bounds__(64) void k_sinkhorn_loc_loss(const float* __restrict__ tr, const float* __restrict__ tr_locs, const float* __restrict__ gt_locs,
+                                                          int N, float scale, float* __restrict__ loss_items, float* __restrict__ d_tr) {
+    __shared__ float diff[16];
+    const int qi = blockIdx.x, lane = threadIdx.x;
+    const float* t = tr + (long long)qi * N * N;
+    const float* a = tr_locs + (long long)qi * N;
+    if (lane < N) {
+        float s = 0.f;
+        for (int i = 0; i < N; ++i) s += a[i] * t[i * N + lane];
+        diff[lane] = s - gt_locs[(long long)qi * N + lane];
+    }
+    __syncthreads();
+    if (lane == 0) {
+        float s = 0.f;
+        for (int j = 0; j < N; ++j) s += diff[j] * diff[j];
+        loss_items[qi] = s / (float)N;
+    }
+    if (d_tr) {
+        const float k = scale * 2.f / (float)N;
+        for (int i = lane; i < N * N; i += 64) d_tr[(long long)qi * N * N + i] = k * diff[i % N] * a[i / N];
+    }
+}
+
+// dX = (sum of slabs) masked by the ReLU whose OUTPUT is y: out[m][n] = y[m][n] > 0 ? sum : 0
+__global__ void k_relu_bwd_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ y, long long ldy,
+                                  float* __restrict__ out, long long ldo) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)M * N) return;
+    const int m = (int)(i / N), n = (int)(i % N);
+    const float s = slab_sum(slabs + i, nslab, stride);
+    out[(long long)m * ldo + n] = y[(long long)m * ldy + n] > 0.f ? s : 0.f;
 }
 
 }  // namespace vsr

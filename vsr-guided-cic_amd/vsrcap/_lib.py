@@ -64,6 +64,10 @@ class VsrSinkhornWeights(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in SINKHORN_FIELDS] + [("N", C.c_int32), ("n_iters", C.c_int32), ("tau", C.c_float)]
 
 
+class VsrSinkhornGrads(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in SINKHORN_FIELDS]
+
+
 # name -> (restype, argtypes); must list every symbol include/vsrcap.h declares
 SIGNATURES = {
     "vsr_abi_version": (I32, []),
@@ -110,6 +114,11 @@ SIGNATURES = {
     "vsr_ssp_generate": (I32, [P, P, P, I32, P, P, P, SZ, P]),
     "vsr_sinkhorn_workspace_bytes": (SZ, [I32, I32]),
     "vsr_sinkhorn_assign": (I32, [P, P, I32, P, P, P, SZ, P]),
+    "vsr_sinkhorn_tape_bytes": (SZ, [I32, I32]),
+    "vsr_sinkhorn_train_workspace_bytes": (SZ, [I32, I32]),
+    "vsr_sinkhorn_train_forward": (I32, [P, P, I32, P, P, SZ, P, SZ, P]),
+    "vsr_sinkhorn_loc_loss": (I32, [P, P, P, I32, I32, C.c_float, P, P, P]),
+    "vsr_sinkhorn_train_backward": (I32, [P, P, I32, P, SZ, P, C.POINTER(VsrSinkhornGrads), P, SZ, P]),
     "vsr_profile_begin": (I32, [P]),
     "vsr_profile_begin_sampled": (I32, [P, I32]),
     "vsr_profile_seen": (I64, [P]),
