@@ -374,6 +374,62 @@ int vsr_sinkhorn_loc_loss(const float* tr, const float* tr_locs, const float* gt
 int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t Q, const void* tape, size_t tape_bytes, const float* d_tr,
                                 const vsr_sinkhorn_grads* g, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- S_SSP training (coco_scripts/train_region_sort.py:181-185, models/sort_model.py:80-103) ----------
+ * loss = S_SSP.forward(verb (S), roles (S,10), gt (S,10)) for the S (caption, verb) sequences of a loader batch: the encoder, the
+ * decoder teacher-forced in one pass over [bos, gt_0 .. gt_9], the label-smoothed KL loss over the shifted mask - one forward that
+ * ends in a DEVICE float and one hand-written backward, exact fp32 products throughout, no float atomics (two runs: the same bits).
+ *   masks      dropout is data: a caller-owned byte buffer (1 = keep) of vsr_ssp_mask_bytes(S) bytes that holds the 33 tensors
+ *              nn.Dropout sees in the reference's call order, one after the other, each in its contiguous order from a 16-byte
+ *              boundary (vsr_ssp_mask_offset(S, site)):
+ *                0 sqrt(512) v_embed[verb] (S,1,512)    1 sqrt(512) sr_embed[roles] (S,10,512)
+ *                2+4l .. 5+4l, encoder layer l: softmax weights (S,8,10,10), linear_O output (S,10,512), relu(w_1 .) (S,10,2048),
+ *                  w_2 output (S,10,512)
+ *                14 sqrt(512) sr_embed[bos, gt] (S,11,512)
+ *                15+6l .. 20+6l, decoder layer l: self weights (S,8,11,11), self linear_O (S,11,512), cross weights (S,8,11,10),
+ *                  cross linear_O (S,11,512), relu(w_1 .) (S,11,2048), w_2 output (S,11,512)
+ *              NULL = no dropout (.eval()).  vsr_ssp_dropout_masks fills a buffer in one launch: element n of a site keeps iff
+ *              u01 >= p for word n % 4 of Philox4x32-10(key = seed, counter = (n / 4, site, 0, a constant of this use)).  The
+ *              forward applies keep / (1 - p); the backward re-reads the same bytes.
+ *   tape       caller-owned, vsr_ssp_tape_bytes(S) bytes, a function of S alone; it belongs to ONE forward (several may be alive).
+ *              Its header records S, the p applied, whether masks were given, sum(m) and the one_hot values; the backward takes
+ *              them from there.  A tape whose header does not match the backward's S / mask mode yields NaN gradients.
+ *   workspace  vsr_ssp_train_workspace_bytes(S) bytes, scratch of either call (nothing survives in it).
+ *   one_hot    label_smooth.one_hot (26 fp32 on the device): the off-target probabilities of the smoothed target (0.9 at the target).
+ * vsr_ssp_train_forward: ids as vsr_ssp_generate's (verbs taken % 10000; gt (S,10) int32, 0 = padding) -> loss[0].
+ * vsr_ssp_train_backward: d_loss[0] (device) -> every gradient of vsr_ssp_grads, OVERWRITTEN (the caller accumulates); v_embed's is
+ *   dense (n_verbs rows, unused rows 0).  cross_attention.* is never used by the model and has no gradient. */
+typedef struct vsr_ssp_layer_grads {
+    float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ln3_w, *ln3_b;           /* ln3: decoder layers only */
+    float *Wq, *bq, *Wk, *bk, *Wv, *bv, *Wo, *bo;                   /* decoder layers: the sum of the self and the cross attention's use */
+    float *W1, *b1, *W2, *b2;
+} vsr_ssp_layer_grads;
+typedef struct vsr_ssp_grads {           /* mirrors vsr_ssp_weights field for field */
+    float* sr_embed;                     /* the encoder's and the decoder's use */
+    float* v_embed;
+    int64_t n_verbs;                     /* rows of v_embed's gradient: must equal the bound table's */
+    float *fc_w, *fc_b;
+    vsr_ssp_layer_grads enc[3];
+    float *enc_ln_w, *enc_ln_b;
+    vsr_ssp_layer_grads dec[3];
+    float *dec_ln_w, *dec_ln_b;
+    float *exp_w, *exp_b;
+} vsr_ssp_grads;
+size_t vsr_ssp_mask_bytes(int32_t S);
+size_t vsr_ssp_mask_offset(int32_t S, int32_t site);
+int vsr_ssp_dropout_masks(uint64_t seed, float p, int32_t S, uint8_t* masks, void* stream);
+size_t vsr_ssp_tape_bytes(int32_t S);
+size_t vsr_ssp_train_workspace_bytes(int32_t S);
+/* TEST ONLY - the tape's layout is private and may change; no product code may depend on this.
+ * Byte offset, in the tape, of the feed-forward hidden of encoder (decoder = 0) or decoder layer 0..2: rows x 2048 fp32 after ReLU and
+ * dropout; an element is > 0 exactly where the forward let the unit pass (tests put their reference on the same side of a ReLU kink) */
+size_t vsr_ssp_tape_ff_offset(int32_t S, int32_t decoder, int32_t layer);
+int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int32_t* roles, const int32_t* gt, int32_t S, const uint8_t* masks /* or NULL */,
+                          float p, const float* one_hot, float* loss, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const int32_t* roles, const int32_t* gt, int32_t S, const uint8_t* masks /* or NULL */,
+                           const void* tape, size_t tape_bytes, const float* d_loss, const vsr_ssp_grads* g, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- measurement (bench.py roofline leg) ------------------------------------------------------------ */
 /* Between begin and end every fp32-MFMA GEMM launch is bracketed by a pair of pre-created HIP events on the
  * caller's stream.  end() synchronises the stream and returns the summed launch durations, the number of

@@ -381,3 +381,460 @@ extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t
     LAUNCHCHK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------- S-SSP training
+// S_SSP.forward (sort_model.py:80-103) for S sequences: ONE forward that ends in the loss (a device float) and ONE hand-written backward.
+//   forward   k_ssp_train_prep, the embeddings, the encoder, the decoder teacher-forced in one pass over [bos, gt_0 .. gt_9] (Rd = 11 S
+//             rows), expander_nn, k_ssp_kl_loss / k_ssp_loss_finish.  The products are linear_n's (same planner, same exact fp32 kernels)
+//             behind k_ssp_finish, which adds the dropout bytes to bias / ReLU / residual.
+//   tape      per LayerNorm its output, the normalised rows and 1 / std; per attention q, k, v, the softmax WEIGHTS before dropout (taped,
+//             not recomputed: at most 8 x 11 x 11 floats per sequence and layer) and the context; the feed-forward hidden AFTER ReLU and
+//             dropout (its sign pattern is both masks); the encoder's summed embeddings; logp.  `prior` is the encoder LayerNorm's output.
+//   backward  k_ssp_kl_bwd, then the layers in reverse.  Per linear layer: the bias gradient by the ordered column sums (k_colsum), dW = dY^T X
+//             and dX = dY W as NT products on transposed copies (TransBatch), k dimension padded to Rp = rows rounded up to 4 with zeroed
+//             padding columns.  What the reference adds up by re-using a module is ONE product with several k segments: the decoder's
+//             attention.linear_{Q,K,V,O} serve the self AND the cross attention (d W_q = dq^T y1 + dq2^T y2, ...), the three projections of
+//             one input give d y1 = dq W_q + dk W_k + dv W_v, and the three decoder layers accumulate into d prior.
+//             cross_attention.* is never used and has no gradient.  Every sum has a fixed order: two runs give the same bits.
+// The backward trusts the tape's header, not its caller, for p and for whether masks were applied; a header that does not carry the call's
+// S and mask mode turns every gradient into NaN (k_ssp_kl_bwd).
+constexpr int SSP_TRAIN_MAX_S = 32768;            // Rd x 2048 elements and every row index stay far inside int
+
+static void ssp_sites(int S, SspSites& st) {
+    const long long Te = SSP_LEN, Td = SSP_TD, H = SSP_H, F = SSP_FF, NH = SSP_HEADS, s = S;
+    long long n[SSP_SITES];
+    int i = 0;
+    n[i++] = s * H; n[i++] = s * Te * H;
+    for (int l = 0; l < 3; ++l) { n[i++] = s * NH * Te * Te; n[i++] = s * Te * H; n[i++] = s * Te * F; n[i++] = s * Te * H; }
+    n[i++] = s * Td * H;
+    for (int l = 0; l < 3; ++l) { n[i++] = s * NH * Td * Td; n[i++] = s * Td * H; n[i++] = s * NH * Td * Te; n[i++] = s * Td * H; n[i++] = s * Td * F; n[i++] = s * Td * H; }
+    long long off = 0;
+    for (i = 0; i < SSP_SITES; ++i) { st.off[i] = off; st.n[i] = n[i]; off += (n[i] + 15) & ~15LL; }
+    st.off[SSP_SITES] = off;
+}
+extern "C" size_t vsr_ssp_mask_bytes(int32_t S) {
+    if (S <= 0 || S > SSP_TRAIN_MAX_S) return 0;
+    SspSites st;
+    ssp_sites(S, st);
+    return (size_t)st.off[SSP_SITES];
+}
+extern "C" size_t vsr_ssp_mask_offset(int32_t S, int32_t site) {
+    if (S <= 0 || S > SSP_TRAIN_MAX_S || site < 0 || site >= SSP_SITES) return 0;
+    SspSites st;
+    ssp_sites(S, st);
+    return (size_t)st.off[site];
+}
+extern "C" int vsr_ssp_dropout_masks(uint64_t seed, float p, int32_t S, uint8_t* masks, void* stream) {
+    if (!masks || S <= 0 || S > SSP_TRAIN_MAX_S || !(p >= 0.f && p < 1.f)) return fail("vsr_ssp_dropout_masks: bad arguments (1 <= S <= %d, 0 <= p < 1)", SSP_TRAIN_MAX_S);
+    if (!aligned16(masks)) return fail("vsr_ssp_dropout_masks: the mask buffer must start on a 16-byte boundary");      // (the kernel stores whole words)
+    SspSites st;
+    ssp_sites(S, st);
+    hipLaunchKernelGGL(k_ssp_dropout_masks, dim3(cdiv(st.off[SSP_SITES] / 4, 256)), dim3(256), 0, (hipStream_t)stream, st, seed, p, masks);
+    LAUNCHCHK();
+    return 0;
+}
+
+struct SspLnTape { float *y, *xhat, *rstd; };
+// lnA / lnC / lnF: the LayerNorm in front of the self attention / cross attention (decoder only) / feed-forward
+struct SspLayerTape { SspLnTape lnA, lnC, lnF; float *q, *k, *v, *P1, *ctx1, *q2, *pk, *pv, *P2, *ctx2, *ff; };
+struct SspTape { int* hdr; float* emb; SspLayerTape enc[3], dec[3]; SspLnTape encln, decln; float* logp; };
+static size_t carve_ssp_tape(int S, char* base, SspTape& t) {
+    const size_t Re = (size_t)S * SSP_LEN, Rd = (size_t)S * SSP_TD, H = SSP_H;
+    Bump b{base};
+    auto ln = [&](SspLnTape& l, size_t R) { l.y = b.take<float>(R * H); l.xhat = b.take<float>(R * H); l.rstd = b.take<float>(R); };
+    t.hdr = b.take<int>(SSP_TAPE_HDR_INTS);
+    t.emb = b.take<float>(Re * H);
+    for (int l = 0; l < 3; ++l) {
+        SspLayerTape& e = t.enc[l];
+        memset(&e, 0, sizeof(e));
+        ln(e.lnA, Re); ln(e.lnF, Re);
+        e.q = b.take<float>(Re * H); e.k = b.take<float>(Re * H); e.v = b.take<float>(Re * H);
+        e.P1 = b.take<float>((size_t)S * SSP_HEADS * SSP_LEN * SSP_LEN); e.ctx1 = b.take<float>(Re * H); e.ff = b.take<float>(Re * SSP_FF);
+    }
+    ln(t.encln, Re);
+    for (int l = 0; l < 3; ++l) {
+        SspLayerTape& d = t.dec[l];
+        ln(d.lnA, Rd); ln(d.lnC, Rd); ln(d.lnF, Rd);
+        d.q = b.take<float>(Rd * H); d.k = b.take<float>(Rd * H); d.v = b.take<float>(Rd * H);
+        d.P1 = b.take<float>((size_t)S * SSP_HEADS * SSP_TD * SSP_TD); d.ctx1 = b.take<float>(Rd * H);
+        d.q2 = b.take<float>(Rd * H); d.pk = b.take<float>(Re * H); d.pv = b.take<float>(Re * H);
+        d.P2 = b.take<float>((size_t)S * SSP_HEADS * SSP_TD * SSP_LEN); d.ctx2 = b.take<float>(Rd * H); d.ff = b.take<float>(Rd * SSP_FF);
+    }
+    ln(t.decln, Rd);
+    t.logp = b.take<float>(Rd * SSP_ROLES);
+    return (b.off + 255) & ~size_t(255);
+}
+
+constexpr int SSP_LOGIT_LD = (SSP_ROLES + 3) & ~3;        // d logits and expander_nn^T: the 26 classes as a k dimension, padded to 28
+struct SspTrainWs {
+    int *verbs32, *roles, *gt, *tok;
+    float *r[10], *ddec;             // (Rd, 512) rows: the residual stream of the forward, the gradients of the backward
+    float *dff;                      // (Rd, 2048)
+    float *logits, *row_loss, *dlog; // (Rd, 26), (Rd), (Rd, 28)
+    float *dprior, *dpk, *dpv;       // (Re, 512)
+    float *dbk1, *dbk2;              // (S, 512): k_ssp_mha_bwd's per-sequence sums of dk (self, cross) for linear_K's bias
+    float *t512[10], *t2048[2];      // transposed activations / gradients (columns, Rp)
+    float *tE[3];                    // (512, Rep): d pk^T, d pv^T, prior^T
+    float *wT[4];                    // transposed weights of the block at hand, up to 2048 x 512 each
+    float *part;                     // two k_colsum tables
+    float *scratch;
+    size_t scratch_floats;
+};
+static size_t carve_ssp_train(int S, char* base, SspTrainWs& w) {
+    const size_t Re = (size_t)S * SSP_LEN, Rd = (size_t)S * SSP_TD, H = SSP_H, Rp = (Rd + 3) & ~size_t(3), Rep = (Re + 3) & ~size_t(3);
+    Bump b{base};
+    w.verbs32 = b.take<int>(S); w.roles = b.take<int>(Re); w.gt = b.take<int>(Re); w.tok = b.take<int>(Rd);
+    for (auto& p : w.r) p = b.take<float>(Rd * H);
+    w.ddec = b.take<float>(Rd * H);
+    w.dff = b.take<float>(Rd * SSP_FF);
+    w.logits = b.take<float>(Rd * SSP_ROLES); w.row_loss = b.take<float>(Rd); w.dlog = b.take<float>(Rd * SSP_LOGIT_LD);
+    w.dprior = b.take<float>(Re * H); w.dpk = b.take<float>(Re * H); w.dpv = b.take<float>(Re * H);
+    w.dbk1 = b.take<float>((size_t)S * H); w.dbk2 = b.take<float>((size_t)S * H);
+    for (auto& p : w.t512) p = b.take<float>(H * Rp);
+    for (auto& p : w.t2048) p = b.take<float>((size_t)SSP_FF * Rp);
+    for (auto& p : w.tE) p = b.take<float>(H * Rep);
+    for (auto& p : w.wT) p = b.take<float>((size_t)SSP_FF * H);
+    w.part = b.take<float>((size_t)2 * COLSUM_CHUNKS * SSP_FF);
+    w.scratch_floats = std::max<size_t>(Rd * SSP_FF, (size_t)SSP_FF * H) * 8;      // 8 slabs of the widest activation / of W1's gradient
+    w.scratch = b.take<float>(w.scratch_floats);
+    return (b.off + 255) & ~size_t(255);
+}
+extern "C" size_t vsr_ssp_tape_bytes(int32_t S) {
+    if (S <= 0 || S > SSP_TRAIN_MAX_S) return 0;
+    SspTape t;
+    return carve_ssp_tape(S, nullptr, t);
+}
+// TEST ONLY: byte offset, in the tape, of a layer's feed-forward hidden (rows x 2048 fp32, after ReLU and dropout): > 0 there is the
+// gate the forward applied, which a test needs to put its reference on the same side of a ReLU kink.  The tape's layout is otherwise private.
+extern "C" size_t vsr_ssp_tape_ff_offset(int32_t S, int32_t decoder, int32_t layer) {
+    if (S <= 0 || S > SSP_TRAIN_MAX_S || layer < 0 || layer > 2) return 0;
+    SspTape t;
+    char* base = reinterpret_cast<char*>(uintptr_t(4096));
+    carve_ssp_tape(S, base, t);
+    return (size_t)(reinterpret_cast<char*>(decoder ? t.dec[layer].ff : t.enc[layer].ff) - base);
+}
+extern "C" size_t vsr_ssp_train_workspace_bytes(int32_t S) {
+    if (S <= 0 || S > SSP_TRAIN_MAX_S) return 0;
+    SspTrainWs w;
+    return carve_ssp_train(S, nullptr, w);
+}
+
+// One launch of up to four products out (M, N) = gate(sum over segments of A_i (M, K_i) . W_i (N, K_i)^T + bias) (+ residual), each behind
+// k_ssp_finish; every out / keep / relu_y / residual is compact.  The forward gives `scale`, the backward the tape's header.
+struct SspSeg { const float* A; int lda; const float* W; int ldw; int K; };
+struct SspProd {
+    int M, N;
+    SspSeg seg[3];
+    int nseg;
+    float* out;
+    const float* bias; int relu; const uint8_t* keep; const float* relu_y; const float* residual;
+};
+struct SspRun { vsr_ssp* e; hipStream_t s; float* scratch; size_t scratch_floats; const int* hdr; float scale; };
+static SspProd ssp_prod1(int M, int N, int K, const float* A, int lda, const float* W, int ldw, float* out) {
+    SspProd p{};
+    p.M = M; p.N = N; p.seg[0] = SspSeg{A, lda, W, ldw, K}; p.nseg = 1; p.out = out;
+    return p;
+}
+static int ssp_products(SspRun& c, const SspProd* P, int n) {
+    GemmBuilder g;
+    for (int i = 0; i < n; ++i) {
+        GemmProb& p = g.prob(P[i].M, P[i].N, nullptr, P[i].N);
+        for (int k = 0; k < P[i].nseg; ++k) {
+            const SspSeg& sg = P[i].seg[k];
+            if ((sg.K & 3) || (sg.lda & 3) || (sg.ldw & 3) || !aligned16(sg.A) || !aligned16(sg.W))
+                return fail("ssp training: operand not in whole 16-byte groups (K %d, lda %d, ldw %d)", sg.K, sg.lda, sg.ldw);
+            GemmBuilder::seg(p, sg.A, sg.lda, nullptr, sg.W, sg.ldw, sg.K);
+        }
+    }
+    const int ns = g.finish(&c.e->cfg);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        g.a.p[i].C = c.scratch + off;
+        g.a.p[i].slab_stride = (long long)P[i].M * P[i].N;
+        off += (size_t)P[i].M * P[i].N * ns;
+    }
+    if (off > c.scratch_floats) return fail("ssp training: GEMM scratch too small");
+    if (g.launch(c.s, &c.e->cfg)) return fail("ssp training: gemm launch failed");
+    for (int i = 0; i < n; ++i) {
+        const long long tot = (long long)P[i].M * P[i].N;
+        hipLaunchKernelGGL(k_ssp_finish, dim3(cdiv(tot, 256)), dim3(256), 0, c.s, g.a.p[i].C, ns, tot, P[i].M, P[i].N, P[i].bias, P[i].relu, P[i].keep, c.hdr,
+                           c.scale, P[i].relu_y, P[i].residual, P[i].out);
+    }
+    return 0;
+}
+static void layernorm_train(hipStream_t s, const float* x, const float* w, const float* b, int rows, const SspLnTape& t) {
+    hipLaunchKernelGGL(k_layernorm512_train, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, t.y, t.xhat, t.rstd);
+}
+
+static int ssp_train_args(const char* who, vsr_ssp* e, const void* verbs, const void* roles, const void* gt, int32_t S, const void* tape, const void* ws) {
+    if (!e || !e->has_ssp) return fail("%s: S-SSP weights not bound", who);
+    if (!verbs || !roles || !gt || !tape || !ws || S <= 0 || S > SSP_TRAIN_MAX_S) return fail("%s: bad arguments (1 <= S <= %d)", who, SSP_TRAIN_MAX_S);
+    if (e->w.n_verbs > INT_MAX / SSP_H) return fail("%s: verb table too large", who);
+    return 0;
+}
+
+extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int32_t* roles, const int32_t* gt, int32_t S, const uint8_t* masks, float p,
+                                     const float* one_hot, float* loss, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (ssp_train_args("vsr_ssp_train_forward", e, verbs, roles, gt, S, tape, workspace)) return 1;
+    if (!one_hot || !loss) return fail("vsr_ssp_train_forward: bad arguments");
+    if (masks && !(p >= 0.f && p < 1.f)) return fail("vsr_ssp_train_forward: dropout p %g outside [0, 1)", (double)p);
+    if (masks && !aligned16(masks)) return fail("vsr_ssp_train_forward: the mask buffer must start on a 16-byte boundary");
+    SspTape t;
+    SspTrainWs ws;
+    if (carve_ssp_tape(S, reinterpret_cast<char*>(tape), t) > tape_bytes) return fail("vsr_ssp_train_forward: tape too small");
+    if (carve_ssp_train(S, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_ssp_train_forward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const vsr_ssp_weights& w = e->w;
+    const int H = SSP_H, Re = S * SSP_LEN, Rd = S * SSP_TD;
+    const float p_applied = masks ? p : 0.f, scale = 1.0f / (1.0f - p_applied);
+    SspSites st;
+    ssp_sites(S, st);
+    auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
+    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, scale};
+    auto lin = [&](int M, int N, int K, const float* A, const float* W, const float* bias, float* out) {
+        SspProd pr = ssp_prod1(M, N, K, A, K, W, K, out);
+        pr.bias = bias;
+        return pr;
+    };
+    hipLaunchKernelGGL(k_ssp_train_prep, dim3(cdiv(Rd, 256)), dim3(256), 0, s, verbs, roles, gt, S, (int)w.n_verbs, ws.verbs32, ws.roles, ws.gt, ws.tok);
+    // one layer of either stack: x (in ws.r[0]) -> x (in ws.r[0]); site0: the layer's first dropout site
+    auto layer = [&](const vsr_ssp_layer& ly, SspLayerTape& lt, int R, int T, bool dec, int site0, const float* prior) -> int {
+        float *x = ws.r[0], *x1 = ws.r[1];
+        layernorm_train(s, x, ly.ln1_w, ly.ln1_b, R, lt.lnA);
+        SspProd qkv[3] = {lin(R, H, H, lt.lnA.y, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, ly.Wv, ly.bv, lt.v)};
+        if (ssp_products(run, qkv, 3)) return 1;
+        hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD, lt.ctx1, lt.P1,
+                           keep(site0), scale);
+        SspProd o = lin(R, H, H, lt.ctx1, ly.Wo, ly.bo, x1);
+        o.keep = keep(site0 + 1); o.residual = x;
+        if (ssp_products(run, &o, 1)) return 1;                                                       // x1 = drop(attn) + x
+        int site = site0 + 2;
+        if (dec) {
+            layernorm_train(s, x1, ly.ln2_w, ly.ln2_b, R, lt.lnC);
+            SspProd q2 = lin(R, H, H, lt.lnC.y, ly.Wq, ly.bq, lt.q2);                                   // the SAME projections (sort_modules.py:87)
+            if (ssp_products(run, &q2, 1)) return 1;
+            SspProd kv[2] = {lin(Re, H, H, prior, ly.Wk, ly.bk, lt.pk), lin(Re, H, H, prior, ly.Wv, ly.bv, lt.pv)};
+            if (ssp_products(run, kv, 2)) return 1;
+            hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, T, SSP_LEN, (const int*)nullptr, 0, lt.ctx2, lt.P2,
+                               keep(site), scale);
+            SspProd o2 = lin(R, H, H, lt.ctx2, ly.Wo, ly.bo, x);
+            o2.keep = keep(site + 1); o2.residual = x1;
+            if (ssp_products(run, &o2, 1)) return 1;                                                  // x = drop(cross) + x1
+            std::swap(x, x1);                                                                         // (x1 names the feed-forward's input again)
+            site += 2;
+        }
+        layernorm_train(s, x1, dec ? ly.ln3_w : ly.ln2_w, dec ? ly.ln3_b : ly.ln2_b, R, lt.lnF);
+        SspProd f1 = lin(R, SSP_FF, H, lt.lnF.y, ly.W1, ly.b1, lt.ff);
+        f1.relu = 1; f1.keep = keep(site);
+        if (ssp_products(run, &f1, 1)) return 1;
+        SspProd f2 = lin(R, H, SSP_FF, lt.ff, ly.W2, ly.b2, x);
+        f2.keep = keep(site + 1); f2.residual = x1;
+        if (ssp_products(run, &f2, 1)) return 1;                                                      // x = drop(ff) + x1
+        if (x != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
+        return 0;
+    };
+    // ---- encoder
+    hipLaunchKernelGGL(k_ssp_embed_train, dim3(Re), dim3(128), 0, s, ws.roles, SSP_LEN, w.sr_embed, ws.verbs32, w.v_embed, keep(1), keep(0), scale, t.emb);
+    SspProd fc = lin(Re, H, H, t.emb, w.fc_w, w.fc_b, ws.r[0]);
+    if (ssp_products(run, &fc, 1)) return 1;
+    for (int l = 0; l < 3; ++l)
+        if (layer(w.enc[l], t.enc[l], Re, SSP_LEN, false, 2 + 4 * l, nullptr)) return 1;
+    layernorm_train(s, ws.r[0], w.enc_ln_w, w.enc_ln_b, Re, t.encln);
+    LAUNCHCHK();
+    // ---- decoder
+    hipLaunchKernelGGL(k_ssp_embed_train, dim3(Rd), dim3(128), 0, s, ws.tok, SSP_TD, w.sr_embed, (const int*)nullptr, (const float*)nullptr, keep(14),
+                       (const uint8_t*)nullptr, scale, ws.r[0]);
+    for (int l = 0; l < 3; ++l)
+        if (layer(w.dec[l], t.dec[l], Rd, SSP_TD, true, 15 + 6 * l, t.encln.y)) return 1;
+    layernorm_train(s, ws.r[0], w.dec_ln_w, w.dec_ln_b, Rd, t.decln);
+    // ---- loss
+    SspProd ex = lin(Rd, SSP_ROLES, H, t.decln.y, w.exp_w, w.exp_b, ws.logits);
+    if (ssp_products(run, &ex, 1)) return 1;
+    hipLaunchKernelGGL(k_ssp_kl_loss, dim3(cdiv(Rd, 4)), dim3(256), 0, s, ws.logits, ws.gt, one_hot, Rd, t.logp, ws.row_loss);
+    hipLaunchKernelGGL(k_ssp_loss_finish, dim3(1), dim3(256), 0, s, ws.row_loss, ws.gt, one_hot, S, p_applied, masks ? 1 : 0, loss, t.hdr);
+    LAUNCHCHK();
+    return 0;
+}
+
+// out[c] = column sums of X (R, C) (+ those of X2 (R2, C)), in the fixed order of k_colsum and k_ssp_colsum_finish
+static void ssp_colsum(SspTrainWs& ws, hipStream_t s, const float* X, int R, int C, float* out, const float* X2 = nullptr, int R2 = 0) {
+    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, (long long)C, R, C, ws.part);
+    if (X2) hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X2, (long long)C, R2, C, ws.part + (size_t)COLSUM_CHUNKS * C);
+    hipLaunchKernelGGL(k_ssp_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, ws.part, (X2 ? 2 : 1) * COLSUM_CHUNKS, C, out);
+}
+
+extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const int32_t* roles, const int32_t* gt, int32_t S, const uint8_t* masks, const void* tape,
+                                      size_t tape_bytes, const float* d_loss, const vsr_ssp_grads* g, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (ssp_train_args("vsr_ssp_train_backward", e, verbs, roles, gt, S, tape, workspace)) return 1;
+    if (!d_loss || !g) return fail("vsr_ssp_train_backward: bad arguments");
+    if (masks && !aligned16(masks)) return fail("vsr_ssp_train_backward: the mask buffer must start on a 16-byte boundary");
+    if (g->n_verbs != e->w.n_verbs) return fail("vsr_ssp_train_backward: the v_embed gradient has %lld rows, the bound table %lld", (long long)g->n_verbs, (long long)e->w.n_verbs);
+    {
+        bool all = g->sr_embed && g->v_embed && g->fc_w && g->fc_b && g->enc_ln_w && g->enc_ln_b && g->dec_ln_w && g->dec_ln_b && g->exp_w && g->exp_b;
+        for (int l = 0; l < 3; ++l)
+            for (int d = 0; d < 2; ++d) {
+                const vsr_ssp_layer_grads& ly = d ? g->dec[l] : g->enc[l];
+                all = all && ly.ln1_w && ly.ln1_b && ly.ln2_w && ly.ln2_b && (!d || (ly.ln3_w && ly.ln3_b)) && ly.Wq && ly.bq && ly.Wk && ly.bk && ly.Wv && ly.bv &&
+                      ly.Wo && ly.bo && ly.W1 && ly.b1 && ly.W2 && ly.b2;
+            }
+        if (!all) return fail("vsr_ssp_train_backward: every gradient pointer that has a weight is required");
+    }
+    SspTape t;
+    SspTrainWs ws;
+    if (carve_ssp_tape(S, reinterpret_cast<char*>(const_cast<void*>(tape)), t) > tape_bytes) return fail("vsr_ssp_train_backward: tape too small");
+    if (carve_ssp_train(S, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_ssp_train_backward: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const vsr_ssp_weights& w = e->w;
+    const int H = SSP_H, F = SSP_FF, Re = S * SSP_LEN, Rd = S * SSP_TD, Rdp = (Rd + 3) & ~3, Rep = (Re + 3) & ~3, LD = SSP_LOGIT_LD;
+    SspSites st;
+    ssp_sites(S, st);
+    auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
+    SspRun run{e, s, ws.scratch, ws.scratch_floats, t.hdr, 1.f};
+    TransBatch tb;
+    auto tr_add = [&](const float* in, int ld_in, int rows, int cols, float* out, int ld_out) { tb.add(s, 0, nullptr, in, ld_in, rows, cols, out, ld_out, nullptr, 0); };
+    // the gradient of x where y = drop(x) (site) and dy is given: dy itself without masks, else a masked copy in `buf`
+    auto undrop = [&](const float* dy, int site, long long n, float* buf) -> const float* {
+        if (!masks) return dy;
+        hipLaunchKernelGGL(k_ssp_drop_bwd, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, dy, keep(site), t.hdr, n, buf);
+        return buf;
+    };
+    auto ln_bwd = [&](const float* dy, const float* gamma, const SspLnTape& lt, const float* add, int R, float* dx, float* dgamma, float* dbeta) {
+        hipLaunchKernelGGL(k_layernorm512_bwd, dim3(cdiv(R, 4)), dim3(256), 0, s, dy, gamma, lt.xhat, lt.rstd, add, R, dx, ws.r[9]);
+        ssp_colsum(ws, s, ws.r[9], R, H, dgamma);
+        ssp_colsum(ws, s, dy, R, H, dbeta);
+    };
+    hipLaunchKernelGGL(k_ssp_train_prep, dim3(cdiv(Rd, 256)), dim3(256), 0, s, verbs, roles, gt, S, (int)w.n_verbs, ws.verbs32, ws.roles, ws.gt, ws.tok);
+
+    // ---- loss and expander_nn: d logits -> ws.r[2] = d (decoder LayerNorm output) -> ws.r[0] = d (last decoder layer's output)
+    hipLaunchKernelGGL(k_ssp_kl_bwd, dim3(cdiv((long long)Rd * LD, 256)), dim3(256), 0, s, t.logp, ws.gt, t.hdr, S, masks ? 1 : 0, d_loss, Rd, LD, ws.dlog);
+    tr_add(ws.dlog, LD, Rd, SSP_ROLES, ws.t512[0], Rdp);
+    tr_add(t.decln.y, H, Rd, H, ws.t512[1], Rdp);
+    tr_add(w.exp_w, H, SSP_ROLES, H, ws.wT[0], LD);
+    tr_add(t.encln.y, H, Re, H, ws.tE[2], Rep);                      // prior^T: the k operand of the three layers' cross-attention d W_k, d W_v
+    tb.flush(s);
+    ssp_colsum(ws, s, ws.dlog, Rd, LD, ws.r[9]);                     // (28 columns; the first 26 are the bias gradient)
+    HIPCHK(hipMemcpyAsync(g->exp_b, ws.r[9], SSP_ROLES * sizeof(float), hipMemcpyDeviceToDevice, s));
+    {
+        SspProd pw = ssp_prod1(SSP_ROLES, H, Rdp, ws.t512[0], Rdp, ws.t512[1], Rdp, g->exp_w);
+        SspProd px = ssp_prod1(Rd, H, LD, ws.dlog, LD, ws.wT[0], LD, ws.r[2]);
+        if (ssp_products(run, &pw, 1) || ssp_products(run, &px, 1)) return 1;
+    }
+    ln_bwd(ws.r[2], w.dec_ln_w, t.decln, nullptr, Rd, ws.r[0], g->dec_ln_w, g->dec_ln_b);
+
+    // one layer of either stack, backwards: d (layer output) in ws.r[0] -> d (layer input) in ws.r[0]
+    //   r[0] A: the running gradient   r[1] B   r[2] Y, r[5] C, r[6] D, r[7] E: products   r[3] Z, r[4] Z2: masked copies   r[8] Q2   r[9]: dy x^
+    auto layer_bwd = [&](const vsr_ssp_layer& ly, const vsr_ssp_layer_grads& gl, const SspLayerTape& lt, int R, int Rp, int T, bool dec, int site0, bool first_dec) -> int {
+        float *A = ws.r[0], *B = ws.r[1], *Y = ws.r[2], *Z = ws.r[3], *Z2 = ws.r[4], *C = ws.r[5], *D = ws.r[6], *E = ws.r[7], *Q2 = ws.r[8];
+        const int site_ff = site0 + (dec ? 4 : 2);
+        const long long n = (long long)R * H;
+        // ---- feed-forward: out = drop(W2 ff + b2) + h, ff = drop(relu(W1 yF + b1)), yF = LN(h)
+        const float* dz2 = undrop(A, site_ff + 1, n, Z);
+        tr_add(dz2, H, R, H, ws.t512[0], Rp);
+        tr_add(lt.ff, F, R, F, ws.t2048[0], Rp);
+        tr_add(lt.lnF.y, H, R, H, ws.t512[1], Rp);
+        tr_add(ly.W2, F, H, F, ws.wT[0], H);
+        tr_add(ly.W1, H, F, H, ws.wT[1], F);
+        tb.flush(s);
+        ssp_colsum(ws, s, dz2, R, H, gl.b2);
+        SspProd pw2 = ssp_prod1(H, F, Rp, ws.t512[0], Rp, ws.t2048[0], Rp, gl.W2);
+        SspProd pff = ssp_prod1(R, F, H, dz2, H, ws.wT[0], H, ws.dff);
+        pff.relu_y = lt.ff;                                                                           // d (W1 yF + b1): relu and the site's dropout in one
+        if (ssp_products(run, &pw2, 1) || ssp_products(run, &pff, 1)) return 1;
+        tr_add(ws.dff, F, R, F, ws.t2048[1], Rp);
+        tb.flush(s);
+        ssp_colsum(ws, s, ws.dff, R, F, gl.b1);
+        SspProd pw1 = ssp_prod1(F, H, Rp, ws.t2048[1], Rp, ws.t512[1], Rp, gl.W1);
+        SspProd pyf = ssp_prod1(R, H, F, ws.dff, F, ws.wT[1], F, Y);
+        if (ssp_products(run, &pw1, 1) || ssp_products(run, &pyf, 1)) return 1;
+        ln_bwd(Y, dec ? ly.ln3_w : ly.ln2_w, lt.lnF, A, R, B, dec ? gl.ln3_w : gl.ln2_w, dec ? gl.ln3_b : gl.ln2_b);       // B = d h
+        // the four attention weights, transposed once for both uses
+        tr_add(ly.Wo, H, H, H, ws.wT[0], H);
+        tr_add(ly.Wq, H, H, H, ws.wT[1], H);
+        tr_add(ly.Wk, H, H, H, ws.wT[2], H);
+        tr_add(ly.Wv, H, H, H, ws.wT[3], H);
+        const float* dzo2 = nullptr;
+        if (dec) {
+            // ---- cross attention: h = drop(Wo ctx2 + bo) + h1, ctx2 = mha(q2 = Wq yC + bq, pk = Wk prior + bk, pv = Wv prior + bv), yC = LN(h1)
+            dzo2 = undrop(B, site0 + 3, n, Z2);
+            tr_add(dzo2, H, R, H, ws.t512[0], Rp);
+            tr_add(lt.ctx2, H, R, H, ws.t512[1], Rp);
+            tb.flush(s);
+            SspProd pc = ssp_prod1(R, H, H, dzo2, H, ws.wT[0], H, Y);
+            if (ssp_products(run, &pc, 1)) return 1;
+            hipLaunchKernelGGL(k_ssp_mha_bwd, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, lt.P2, keep(site0 + 2), t.hdr, Y, T, SSP_LEN, (const int*)nullptr, 0,
+                               Q2, ws.dpk, ws.dpv, ws.dbk2);
+            tr_add(Q2, H, R, H, ws.t512[2], Rp);
+            tr_add(lt.lnC.y, H, R, H, ws.t512[3], Rp);
+            tr_add(ws.dpk, H, Re, H, ws.tE[0], Rep);
+            tr_add(ws.dpv, H, Re, H, ws.tE[1], Rep);
+            tb.flush(s);
+            SspProd pyc = ssp_prod1(R, H, H, Q2, H, ws.wT[1], H, C);
+            SspProd pp = ssp_prod1(Re, H, H, ws.dpk, H, ws.wT[2], H, ws.dprior);
+            pp.seg[1] = SspSeg{ws.dpv, H, ws.wT[3], H, H}; pp.nseg = 2;
+            pp.residual = first_dec ? nullptr : ws.dprior;                                            // the three layers accumulate into d prior
+            if (ssp_products(run, &pyc, 1) || ssp_products(run, &pp, 1)) return 1;
+            ln_bwd(C, ly.ln2_w, lt.lnC, B, R, A, gl.ln2_w, gl.ln2_b);                                   // A = d h1
+        } else {
+            tb.flush(s);
+            std::swap(A, B);                                                                          // A = d h1 here too
+        }
+        // ---- self attention: h1 = drop(Wo ctx1 + bo) + x, ctx1 = mha(q, k, v = W yA + b), yA = LN(x)
+        const float* dzo1 = undrop(A, site0 + 1, n, Z);
+        tr_add(dzo1, H, R, H, ws.t512[4], Rp);
+        tr_add(lt.ctx1, H, R, H, ws.t512[5], Rp);
+        tb.flush(s);
+        ssp_colsum(ws, s, dzo1, R, H, gl.bo, dzo2, R);
+        SspProd pc1 = ssp_prod1(R, H, H, dzo1, H, ws.wT[0], H, Y);
+        SspProd pwo = ssp_prod1(H, H, Rp, ws.t512[4], Rp, ws.t512[5], Rp, gl.Wo);
+        if (dec) { pwo.seg[1] = SspSeg{ws.t512[0], Rp, ws.t512[1], Rp, Rp}; pwo.nseg = 2; }
+        if (ssp_products(run, &pc1, 1) || ssp_products(run, &pwo, 1)) return 1;
+        hipLaunchKernelGGL(k_ssp_mha_bwd, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, lt.P1, keep(site0), t.hdr, Y, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD,
+                           C, D, E, ws.dbk1);
+        tr_add(C, H, R, H, ws.t512[6], Rp);
+        tr_add(D, H, R, H, ws.t512[7], Rp);
+        tr_add(E, H, R, H, ws.t512[8], Rp);
+        tr_add(lt.lnA.y, H, R, H, ws.t512[9], Rp);
+        tb.flush(s);
+        ssp_colsum(ws, s, C, R, H, gl.bq, dec ? Q2 : nullptr, R);
+        ssp_colsum(ws, s, ws.dbk1, S, H, gl.bk, dec ? ws.dbk2 : nullptr, S);                           // (k_ssp_mha_bwd: summed per sequence in fp64)
+        ssp_colsum(ws, s, E, R, H, gl.bv, dec ? ws.dpv : nullptr, Re);
+        SspProd pw[3] = {ssp_prod1(H, H, Rp, ws.t512[6], Rp, ws.t512[9], Rp, gl.Wq), ssp_prod1(H, H, Rp, ws.t512[7], Rp, ws.t512[9], Rp, gl.Wk),
+                         ssp_prod1(H, H, Rp, ws.t512[8], Rp, ws.t512[9], Rp, gl.Wv)};
+        if (dec) {
+            pw[0].seg[1] = SspSeg{ws.t512[2], Rp, ws.t512[3], Rp, Rp}; pw[0].nseg = 2;
+            pw[1].seg[1] = SspSeg{ws.tE[0], Rep, ws.tE[2], Rep, Rep}; pw[1].nseg = 2;
+            pw[2].seg[1] = SspSeg{ws.tE[1], Rep, ws.tE[2], Rep, Rep}; pw[2].nseg = 2;
+        }
+        if (ssp_products(run, pw, 3)) return 1;
+        SspProd pya = ssp_prod1(R, H, H, C, H, ws.wT[1], H, Y);
+        pya.seg[1] = SspSeg{D, H, ws.wT[2], H, H}; pya.seg[2] = SspSeg{E, H, ws.wT[3], H, H}; pya.nseg = 3;
+        if (ssp_products(run, &pya, 1)) return 1;
+        ln_bwd(Y, ly.ln1_w, lt.lnA, A, R, B, gl.ln1_w, gl.ln1_b);                                       // B = d x
+        if (B != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
+        return 0;
+    };
+    for (int l = 2; l >= 0; --l)
+        if (layer_bwd(w.dec[l], g->dec[l], t.dec[l], Rd, Rdp, SSP_TD, true, 15 + 6 * l, l == 2)) return 1;
+    LAUNCHCHK();
+    std::swap(ws.r[0], ws.ddec);                 // d (decoder embeddings) waits for the embedding kernel while the encoder's pass uses the row buffers
+    const float* d_dec = ws.ddec;
+    // ---- encoder: d prior -> its LayerNorm -> the layers -> fc_feat -> the embeddings
+    ln_bwd(ws.dprior, w.enc_ln_w, t.encln, nullptr, Re, ws.r[0], g->enc_ln_w, g->enc_ln_b);
+    for (int l = 2; l >= 0; --l)
+        if (layer_bwd(w.enc[l], g->enc[l], t.enc[l], Re, Rep, SSP_LEN, false, 2 + 4 * l, false)) return 1;
+    tr_add(ws.r[0], H, Re, H, ws.t512[0], Rep);
+    tr_add(t.emb, H, Re, H, ws.t512[1], Rep);
+    tr_add(w.fc_w, H, H, H, ws.wT[0], H);
+    tb.flush(s);
+    ssp_colsum(ws, s, ws.r[0], Re, H, g->fc_b);
+    {
+        SspProd pw = ssp_prod1(H, H, Rep, ws.t512[0], Rep, ws.t512[1], Rep, g->fc_w);
+        SspProd px = ssp_prod1(Re, H, H, ws.r[0], H, ws.wT[0], H, ws.r[2]);
+        if (ssp_products(run, &pw, 1) || ssp_products(run, &px, 1)) return 1;
+    }
+    hipLaunchKernelGGL(k_ssp_sr_embed_bwd, dim3(SSP_ROLES, H / 64), dim3(256), 0, s, ws.roles, ws.r[2], keep(1), Re, ws.tok, d_dec, keep(14), Rd, t.hdr, g->sr_embed);
+    hipLaunchKernelGGL(k_ssp_v_embed_bwd, dim3((int)w.n_verbs), dim3(128), 0, s, ws.verbs32, ws.r[2], keep(0), t.hdr, S, g->v_embed);
+    LAUNCHCHK();
+    return 0;
+}

@@ -36,9 +36,11 @@ __global__ __launch_bounds__(128) void k_ssp_embed(const int* __restrict__ tok, 
     *reinterpret_cast<float4*>(out + (long long)row * SSP_H + threadIdx.x * 4) = o;
 }
 
-// nn.LayerNorm(512), eps 1e-5, biased variance: one wave per row
-__global__ __launch_bounds__(256) void k_layernorm512(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                      int rows, float* __restrict__ out) {
+// nn.LayerNorm(512), eps 1e-5, biased variance: one wave per row.  TRAIN: the same arithmetic, and the normalised row x^ and 1 / std
+// go to the training tape (k_layernorm512_bwd reads them)
+template <bool TRAIN>
+__device__ __forceinline__ void layernorm512_row(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, int rows,
+                                                 float* __restrict__ out, float* __restrict__ xhat, float* __restrict__ rstd_out) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
@@ -55,6 +57,7 @@ __global__ __launch_bounds__(256) void k_layernorm512(const float* __restrict__ 
         q += dx * dx + dy * dy + dz * dz + dw * dw;
     }
     const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / SSP_H) + 1e-5f);
+    if (TRAIN && lane == 0) rstd_out[row] = rstd;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int c = i * 256 + lane * 4;
@@ -63,7 +66,14 @@ __global__ __launch_bounds__(256) void k_layernorm512(const float* __restrict__ 
         o.x = (v[i].x - mean) * rstd * ww.x + bb.x; o.y = (v[i].y - mean) * rstd * ww.y + bb.y;
         o.z = (v[i].z - mean) * rstd * ww.z + bb.z; o.w = (v[i].w - mean) * rstd * ww.w + bb.w;
         *reinterpret_cast<float4*>(out + (long long)row * SSP_H + c) = o;
+        if (TRAIN)
+            *reinterpret_cast<float4*>(xhat + (long long)row * SSP_H + c) =
+                make_float4((v[i].x - mean) * rstd, (v[i].y - mean) * rstd, (v[i].z - mean) * rstd, (v[i].w - mean) * rstd);
     }
+}
+__global__ __launch_bounds__(256) void k_layernorm512(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                      int rows, float* __restrict__ out) {
+    layernorm512_row<false>(x, w, b, rows, out, nullptr, nullptr);
 }
 
 // out[m][n] = act(sum of slabs + bias[n]) (+ residual[m][n]);  act: 0 none, 1 relu, 2 tanh
@@ -83,8 +93,12 @@ __global__ void k_linear_finish(const float* __restrict__ slabs, int nslab, long
 //   logits[i][j] = q_i . k_j / 8, masked entries -1e3 (transformer_modules.py:36-53), softmax over ALL Tk keys, ctx = weights . v
 // mask_tok (optional): decoder self-attention, key j visible to query i iff j <= i and tok[s][j] != 0 (sort_modules.py:121-128);
 // a query with no visible key gets the uniform softmax of Tk equal logits, as in the reference.
-__global__ __launch_bounds__(64) void k_ssp_mha(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int Tq, int Tk,
-                                                const int* __restrict__ mask_tok, int ld_tok, float* __restrict__ ctx) {
+// TRAIN (k_ssp_mha_train): the softmax weights go to the tape (P (S, 8, Tq, Tk), before dropout) and the optional keep bytes of the
+// site (same shape, 1 = keep) scale them by 1 / (1 - p) or zero them - dropout on the softmax OUTPUT, no renormalisation.
+template <bool TRAIN>
+__device__ __forceinline__ void ssp_mha_wave(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int Tq, int Tk,
+                                             const int* __restrict__ mask_tok, int ld_tok, float* __restrict__ ctx, float* __restrict__ P,
+                                             const uint8_t* __restrict__ keep, float scale) {
     const int s = blockIdx.x, hd = blockIdx.y, lane = threadIdx.x;
     const long long col = (long long)hd * SSP_HD + lane;
     float kk[SSP_LEN + 1], vv[SSP_LEN + 1];
@@ -111,11 +125,23 @@ __global__ __launch_bounds__(64) void k_ssp_mha(const float* __restrict__ q, con
         for (int j = 0; j < SSP_LEN + 1; ++j)
             if (j < Tk) { lg[j] = expf(lg[j] - mx); se += lg[j]; }
         float o = 0.f;
+        const long long pw = (((long long)s * SSP_HEADS + hd) * Tq + i) * Tk;
 #pragma unroll
         for (int j = 0; j < SSP_LEN + 1; ++j)
-            if (j < Tk) o += (lg[j] / se) * vv[j];
+            if (j < Tk) {
+                float pj = lg[j] / se;
+                if (TRAIN) {
+                    if (lane == j) P[pw + j] = pj;
+                    if (keep) pj = keep[pw + j] ? pj * scale : 0.f;
+                }
+                o += pj * vv[j];
+            }
         ctx[((long long)s * Tq + i) * SSP_H + col] = o;
     }
+}
+__global__ __launch_bounds__(64) void k_ssp_mha(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int Tq, int Tk,
+                                                const int* __restrict__ mask_tok, int ld_tok, float* __restrict__ ctx) {
+    ssp_mha_wave<false>(q, k, v, Tq, Tk, mask_tok, ld_tok, ctx, nullptr, nullptr, 1.f);
 }
 
 // one step of the greedy "pick from the remaining roles" decode (sort_model.py:146-175): one wave per sequence.
@@ -362,6 +388,347 @@ __global__ void k_relu_bwd_finish(const float* __restrict__ slabs, int nslab, lo
     const int m = (int)(i / N), n = (int)(i % N);
     const float s = slab_sum(slabs + i, nslab, stride);
     out[(long long)m * ldo + n] = y[(long long)m * ldy + n] > 0.f ? s : 0.f;
+}
+
+
+// ---------------------------------------------------------------------------------------------- S-SSP training
+// S_SSP.forward (sort_model.py:80-103): the encoder on (verb, roles), the decoder teacher-forced in ONE pass over [bos, gt_0 .. gt_9],
+// the label-smoothed KL loss.  Rows: encoder r = s * 10 + j, decoder r = s * 11 + t.  Dropout masks are DATA: a byte per element
+// (1 = keep) of each of the 33 tensors nn.Dropout sees, in the reference's call order (ssp.inc.h: ssp_sites); a kernel that already
+// touches an element applies keep / (1 - p).  No float atomics: every sum below has a fixed order.
+constexpr int SSP_TD = SSP_LEN + 1;
+constexpr int SSP_SITES = 33;
+constexpr uint32_t SSP_DROPOUT_STREAM = 0x53535044u;       // "SSPD": the Philox counter word that keeps this use apart from the samplers'
+constexpr float SSP_CONFIDENCE = 0.9f;                     // LabelSmoothingKLDivLoss(0.1, 26): 1 - label_smoothing at the target
+// The tape's header, written by the forward, read by the backward's kernels:
+//   [0] S   [1] bits of the p the forward applied (0.0 when it ran without masks)   [2] 1 = it ran with masks   [3] bits of sum(m)
+//   [4 .. 29] bits of the 26 off-target values of the forward's label_smooth.one_hot buffer
+constexpr int SSP_TAPE_HDR_INTS = 32;
+__device__ __forceinline__ float ssp_keep_scale(const int* __restrict__ hdr) { return 1.0f / (1.0f - __int_as_float(hdr[1])); }
+
+struct SspSites { long long off[SSP_SITES + 1]; long long n[SSP_SITES]; };      // byte offset (16-aligned) and element count per site
+
+// keep iff u01 >= p; element e of a site draws word e % 4 of Philox(key = seed, counter = (e / 4, site, 0, SSP_DROPOUT_STREAM)).
+// One thread per 4 bytes of the buffer (sites start on 16-byte boundaries: a group never straddles two); alignment gaps get 0.
+__global__ __launch_bounds__(256) void k_ssp_dropout_masks(const SspSites st, uint64_t seed, float p, uint8_t* __restrict__ masks) {
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g * 4 >= st.off[SSP_SITES]) return;
+    int site = 0;
+    for (int i = 1; i < SSP_SITES; ++i)
+        if (g * 4 >= st.off[i]) site = i;
+    const long long e = g * 4 - st.off[site];
+    uint32_t r[4];
+    Philox::gen(seed, (uint32_t)(e >> 2), (uint32_t)site, 0u, SSP_DROPOUT_STREAM, r);
+    uint32_t w = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (e + i < st.n[site] && Philox::u01(r[i]) >= p) w |= 1u << (8 * i);
+    reinterpret_cast<uint32_t*>(masks)[g] = w;
+}
+
+// the factors of four consecutive elements: keep ? scale : 0 (all 1 without masks); idx a multiple of 4
+__device__ __forceinline__ float4 ssp_keep4(const uint8_t* __restrict__ keep, long long idx, float scale) {
+    if (!keep) return make_float4(1.f, 1.f, 1.f, 1.f);
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + idx);
+    return make_float4((w & 0xffu) ? scale : 0.f, (w & 0xff00u) ? scale : 0.f, (w & 0xff0000u) ? scale : 0.f, (w & 0xff000000u) ? scale : 0.f);
+}
+
+// ids as the kernels want them: verbs % 10000 (sort_model.py:81) as int32, roles and gt with ids outside [0, 26) read as 0 (the host
+// wrapper raises for those before it calls), tok (S, 11) = [0, gt_0 .. gt_9]
+__global__ void k_ssp_train_prep(const int64_t* __restrict__ verbs, const int* __restrict__ roles, const int* __restrict__ gt, int S, int n_verbs,
+                                 int* __restrict__ verbs32, int* __restrict__ roles_c, int* __restrict__ gt_c, int* __restrict__ tok) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    auto clean = [](int r) { return (r < 0 || r >= SSP_ROLES) ? 0 : r; };
+    if (i < S * SSP_TD) {
+        const int s = i / SSP_TD, t = i - s * SSP_TD;
+        tok[i] = t == 0 ? 0 : clean(gt[s * SSP_LEN + t - 1]);
+    }
+    if (i < S * SSP_LEN) { roles_c[i] = clean(roles[i]); gt_c[i] = clean(gt[i]); }
+    if (i < S) {
+        const long long v = verbs[i] % 10000;
+        verbs32[i] = (v < 0 || v >= n_verbs) ? 0 : (int)v;
+    }
+}
+
+// x[s, j, :] = drop(sqrt(512) table[tok[s, j]]) (+ drop(sqrt(512) vtable[verb[s]]), one mask row per sequence: site 0 is (S, 1, 512))
+__global__ __launch_bounds__(128) void k_ssp_embed_train(const int* __restrict__ tok, int len, const float* __restrict__ table, const int* __restrict__ verbs32,
+                                                         const float* __restrict__ vtable, const uint8_t* __restrict__ keep_tok,
+                                                         const uint8_t* __restrict__ keep_verb, float scale, float* __restrict__ out) {
+    const int row = blockIdx.x, s = row / len, c = threadIdx.x * 4;
+    const float sc = 22.627416997969522f;             // sqrt(512)
+    const float4 a = *reinterpret_cast<const float4*>(table + (long long)tok[row] * SSP_H + c);
+    const float4 ka = ssp_keep4(keep_tok, (long long)row * SSP_H + c, scale);
+    float4 o = make_float4(a.x * sc * ka.x, a.y * sc * ka.y, a.z * sc * ka.z, a.w * sc * ka.w);
+    if (verbs32) {
+        const float4 b = *reinterpret_cast<const float4*>(vtable + (long long)verbs32[s] * SSP_H + c);
+        const float4 kb = ssp_keep4(keep_verb, (long long)s * SSP_H + c, scale);
+        o = make_float4(b.x * sc * kb.x + o.x, b.y * sc * kb.y + o.y, b.z * sc * kb.z + o.z, b.w * sc * kb.w + o.w);
+    }
+    *reinterpret_cast<float4*>(out + (long long)row * SSP_H + c) = o;
+}
+
+__global__ __launch_bounds__(256) void k_layernorm512_train(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, int rows,
+                                                            float* __restrict__ out, float* __restrict__ xhat, float* __restrict__ rstd) {
+    layernorm512_row<true>(x, w, b, rows, out, xhat, rstd);
+}
+
+// Backward of the layer norm, one wave per row as the forward: with g = dy gamma,
+//     dx = rstd (g - mean(g) - x^ mean(g x^))   (+ add: the gradient that reaches x through the residual connection)
+// and gx = dy x^ beside dy: d gamma and d beta are the ordered column sums (k_colsum) of gx and dy.  dx may be add's buffer.
+__global__ __launch_bounds__(256) void k_layernorm512_bwd(const float* __restrict__ dy, const float* __restrict__ gamma, const float* __restrict__ xhat,
+                                                          const float* __restrict__ rstd, const float* add, int rows, float* dx, float* __restrict__ gx) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const long long base = (long long)row * SSP_H;
+    float4 g[2], xh[2];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int c = i * 256 + lane * 4;
+        const float4 d = *reinterpret_cast<const float4*>(dy + base + c), w = *reinterpret_cast<const float4*>(gamma + c);
+        xh[i] = *reinterpret_cast<const float4*>(xhat + base + c);
+        g[i] = make_float4(d.x * w.x, d.y * w.y, d.z * w.z, d.w * w.w);
+        *reinterpret_cast<float4*>(gx + base + c) = make_float4(d.x * xh[i].x, d.y * xh[i].y, d.z * xh[i].z, d.w * xh[i].w);
+        s1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
+        s2 += (g[i].x * xh[i].x + g[i].y * xh[i].y) + (g[i].z * xh[i].z + g[i].w * xh[i].w);
+    }
+    const float m1 = wave_sum(s1) * (1.0f / SSP_H), m2 = wave_sum(s2) * (1.0f / SSP_H), r = rstd[row];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int c = i * 256 + lane * 4;
+        float4 o = make_float4(r * (g[i].x - m1 - xh[i].x * m2), r * (g[i].y - m1 - xh[i].y * m2), r * (g[i].z - m1 - xh[i].z * m2), r * (g[i].w - m1 - xh[i].w * m2));
+        if (add) {
+            const float4 a = *reinterpret_cast<const float4*>(add + base + c);
+            o = make_float4(o.x + a.x, o.y + a.y, o.z + a.z, o.w + a.w);
+        }
+        *reinterpret_cast<float4*>(dx + base + c) = o;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_ssp_mha_train(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int Tq, int Tk,
+                                                      const int* __restrict__ mask_tok, int ld_tok, float* __restrict__ ctx, float* __restrict__ P,
+                                                      const uint8_t* __restrict__ keep, float scale) {
+    ssp_mha_wave<true>(q, k, v, Tq, Tk, mask_tok, ld_tok, ctx, P, keep, scale);
+}
+
+// Backward of k_ssp_mha_train, its mirror: one wave per (sequence, head), lane = channel.  With Pd = P keep / (1 - p) the dropped weights,
+//     dv_j += Pd_ij dctx_i      dPd_ij = dctx_i . v_j      dP = dPd keep / (1 - p)      dlogit_ij = P_ij (dP_ij - sum_j' P_ij' dP_ij' / sum_j' P_ij')
+//     dq_i += dlogit_ij k_j / 8      dk_j += dlogit_ij q_i / 8      for the VISIBLE (i, j) only: a masked logit is the constant -1e3
+// (query 0 of the decoder sees no key: uniform weights over all keys, full gradient into v, none into q and k).
+// The softmax part runs in fp64 and divides by the taped weights' own sum, so that a row's dlogits add up to zero as they do on paper: the
+// gradient of linear_K's BIAS is exactly that sum weighted by q (a constant added to every key's logit changes nothing), i.e. zero, and
+// the column sums of an fp32 dk would leave 1e-9 .. 1e-8 of rounding noise there where fp64 autograd leaves 1e-17.  dbk (S, 512) receives
+// this wave's sum_j dk_j from the fp64 accumulators; d bias = its ordered column sum over the sequences.
+__global__ __launch_bounds__(64) void k_ssp_mha_bwd(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                    const float* __restrict__ P, const uint8_t* __restrict__ keep, const int* __restrict__ hdr,
+                                                    const float* __restrict__ dctx, int Tq, int Tk, const int* __restrict__ mask_tok, int ld_tok,
+                                                    float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv, float* __restrict__ dbk) {
+    const int s = blockIdx.x, hd = blockIdx.y, lane = threadIdx.x;
+    const long long col = (long long)hd * SSP_HD + lane;
+    const float scale = ssp_keep_scale(hdr);
+    float kk[SSP_TD], vv[SSP_TD], dvv[SSP_TD];
+    double dkk[SSP_TD];
+#pragma unroll
+    for (int j = 0; j < SSP_TD; ++j) {
+        kk[j] = j < Tk ? k[((long long)s * Tk + j) * SSP_H + col] : 0.f;
+        vv[j] = j < Tk ? v[((long long)s * Tk + j) * SSP_H + col] : 0.f;
+        dkk[j] = 0.0; dvv[j] = 0.f;
+    }
+    for (int i = 0; i < Tq; ++i) {
+        const long long row = ((long long)s * Tq + i) * SSP_H + col;
+        const float qi = q[row], di = dctx[row];
+        const long long pw = (((long long)s * SSP_HEADS + hd) * Tq + i) * Tk;
+        double pp[SSP_TD], dp[SSP_TD];
+        double dot = 0.0, sp = 0.0;
+#pragma unroll
+        for (int j = 0; j < SSP_TD; ++j)
+            if (j < Tk) {
+                const float f = keep ? (keep[pw + j] ? scale : 0.f) : 1.f;
+                const float pj = P[pw + j];
+                dvv[j] += pj * f * di;
+                pp[j] = (double)pj;
+                dp[j] = (double)(wave_sum(di * vv[j]) * f);
+                dot += pp[j] * dp[j];
+                sp += pp[j];
+            }
+        dot /= sp;
+        double dqi = 0.0;
+#pragma unroll
+        for (int j = 0; j < SSP_TD; ++j)
+            if (j < Tk) {
+                const bool masked = mask_tok && !(j <= i && mask_tok[s * ld_tok + j] != 0);
+                const double dl = masked ? 0.0 : pp[j] * (dp[j] - dot) * 0.125;
+                dqi += dl * (double)kk[j];
+                dkk[j] += dl * (double)qi;
+            }
+        dq[row] = (float)dqi;
+    }
+    double bs = 0.0;
+#pragma unroll
+    for (int j = 0; j < SSP_TD; ++j)
+        if (j < Tk) {
+            dk[((long long)s * Tk + j) * SSP_H + col] = (float)dkk[j];
+            dv[((long long)s * Tk + j) * SSP_H + col] = dvv[j];
+            bs += dkk[j];
+        }
+    dbk[(long long)s * SSP_H + col] = (float)bs;
+}
+
+// out[m][n] = gate(sum of slabs + bias[n]) (+ residual[m][n]), every matrix compact (leading dimension N).  gate, in this order:
+//   relu                    forward: max(., 0)
+//   keep (M N bytes)        dropout: keep ? . scale : 0 - the forward's site, or in the backward the site of the tensor whose gradient this is
+//   relu_y                  backward through relu + dropout in one: the taped y = drop(relu(.)) is > 0 exactly where both let the gradient
+//                           pass, and the factor there is scale
+// scale = 1 / (1 - p): the forward passes it, the backward passes the tape's header instead.  out may be residual's buffer (accumulation).
+__global__ void k_ssp_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ bias, int relu,
+                             const uint8_t* __restrict__ keep, const int* __restrict__ hdr, float scale, const float* __restrict__ relu_y,
+                             const float* residual, float* out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)M * N) return;
+    const int n = (int)(i % N);
+    if (hdr) scale = ssp_keep_scale(hdr);
+    float s = slab_sum(slabs + i, nslab, stride) + (bias ? bias[n] : 0.f);
+    if (relu) s = fmaxf(s, 0.f);
+    if (keep) s = keep[i] ? s * scale : 0.f;
+    if (relu_y) s = relu_y[i] > 0.f ? s * scale : 0.f;
+    if (residual) s += residual[i];
+    out[i] = s;
+}
+
+// the gradient of x where y = drop(x): out = keep ? in scale : 0; n a multiple of 4
+__global__ void k_ssp_drop_bwd(const float* __restrict__ in, const uint8_t* __restrict__ keep, const int* __restrict__ hdr, long long n, float* __restrict__ out) {
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float4 f = ssp_keep4(keep, i, ssp_keep_scale(hdr)), v = *reinterpret_cast<const float4*>(in + i);
+    *reinterpret_cast<float4*>(out + i) = make_float4(v.x * f.x, v.y * f.y, v.z * f.z, v.w * f.w);
+}
+
+// out[c] = the sum of `chunks` partial rows of k_colsum tables laid one after the other (two uses of one bias: two tables), in order
+__global__ void k_ssp_colsum_finish(const float* __restrict__ part, int chunks, int C, float* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    float s = 0.f;
+    for (int k = 0; k < chunks; ++k) s += part[(long long)k * C + c];
+    out[c] = s;
+}
+
+// The label-smoothed KL term of one row (compute_loss, sort_model.py:66-78; LabelSmoothingKLDivLoss), one wave per row (lane = class):
+//   logp = log_softmax(logits) -> the tape;   target [gt_0 .. gt_9, 0][t];   q = one_hot[c] (the module's buffer), 0.9 at the target
+//   row_loss = m sum_c q_c (log q_c - logp_c),   m = [1, gt_0 != 0, .., gt_9 != 0][t]  (11 entries: decoder_mask[:, :-1])
+__global__ __launch_bounds__(256) void k_ssp_kl_loss(const float* __restrict__ logits, const int* __restrict__ gt, const float* __restrict__ one_hot, int R,
+                                                     float* __restrict__ logp, float* __restrict__ row_loss) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= R) return;
+    const int s = row / SSP_TD, t = row - s * SSP_TD;
+    const bool live = lane < SSP_ROLES;
+    const float x = live ? logits[(long long)row * SSP_ROLES + lane] : -INFINITY;
+    const float mx = wave_max(x);
+    const float se = wave_sum(live ? expf(x - mx) : 0.f);
+    const float lp = x - mx - logf(se);
+    const int tgt = t < SSP_LEN ? gt[s * SSP_LEN + t] : 0;
+    const bool m = t == 0 || gt[s * SSP_LEN + t - 1] != 0;
+    float term = 0.f;
+    if (live) {
+        const float qc = lane == tgt ? SSP_CONFIDENCE : one_hot[lane];
+        term = qc * (logf(qc) - lp);
+        logp[(long long)row * SSP_ROLES + lane] = lp;
+    }
+    term = wave_sum(term);
+    if (lane == 0) row_loss[row] = m ? term : 0.f;
+}
+
+// loss = sum of the row terms / sum(m), both added in a fixed order by ONE block (the row terms in fp64); sum(m) >= S: never zero.
+// Writes the tape's header.
+__global__ __launch_bounds__(256) void k_ssp_loss_finish(const float* __restrict__ row_loss, const int* __restrict__ gt, const float* __restrict__ one_hot, int S,
+                                                         float p_applied, int with_masks, float* __restrict__ loss, int* __restrict__ hdr) {
+    __shared__ double acc[256];
+    __shared__ int cnt[256];
+    double a = 0.0;
+    int n = 0;
+    for (int r = threadIdx.x; r < S * SSP_TD; r += 256) {
+        const int s = r / SSP_TD, t = r - s * SSP_TD;
+        a += (double)row_loss[r];
+        n += (t == 0 || gt[s * SSP_LEN + t - 1] != 0) ? 1 : 0;
+    }
+    acc[threadIdx.x] = a; cnt[threadIdx.x] = n;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { acc[threadIdx.x] += acc[threadIdx.x + o]; cnt[threadIdx.x] += cnt[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        loss[0] = (float)(acc[0] / (double)cnt[0]);
+        hdr[0] = S; hdr[1] = __float_as_int(p_applied); hdr[2] = with_masks; hdr[3] = __float_as_int((float)cnt[0]);
+        hdr[30] = 0; hdr[31] = 0;
+    }
+    if (threadIdx.x < SSP_ROLES) hdr[4 + threadIdx.x] = __float_as_int(one_hot[threadIdx.x]);
+}
+
+// d logits (R, ld) = d_loss (m / sum(m)) (softmax sum(q) - q), sum(q) = 0.9 + 25 off-target values (not 1); columns 26 .. ld - 1 (the
+// k padding of the products that read it) receive zeros; q's off-target values are the forward's, from the header.  A tape whose header does not carry this call's S and mask mode was not
+// written by the forward this backward belongs to: every gradient then comes out NaN.
+__global__ void k_ssp_kl_bwd(const float* __restrict__ logp, const int* __restrict__ gt, const int* __restrict__ hdr, int S, int with_masks, const float* __restrict__ d_loss, int R, int ld, float* __restrict__ dlog) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)R * ld) return;
+    const int row = (int)(i / ld), c = (int)(i % ld);
+    float o = 0.f;
+    if (c < SSP_ROLES) {
+        const int s = row / SSP_TD, t = row - s * SSP_TD;
+        const int tgt = t < SSP_LEN ? gt[s * SSP_LEN + t] : 0;
+        const bool m = t == 0 || gt[s * SSP_LEN + t - 1] != 0;
+        float sq = 0.f;
+        for (int k = 0; k < SSP_ROLES; ++k) sq += k == tgt ? SSP_CONFIDENCE : __int_as_float(hdr[4 + k]);
+        const float qc = c == tgt ? SSP_CONFIDENCE : __int_as_float(hdr[4 + c]);
+        if (m) o = (d_loss[0] / __int_as_float(hdr[3])) * (expf(logp[(long long)row * SSP_ROLES + c]) * sq - qc);
+        if (hdr[0] != S || hdr[2] != with_masks) o = __int_as_float(0x7fc00000);
+    }
+    dlog[i] = o;
+}
+
+// d sr_embed_layer.weight (26, 512): the index inverted.  One block per (table row, 64-column chunk) scans the Re encoder ids, then the
+// Rd decoder ids, in four interleaved phases that are added in a fixed order; the dropout bytes of sites 1 and 14 and sqrt(512) applied here.
+__global__ __launch_bounds__(256) void k_ssp_sr_embed_bwd(const int* __restrict__ roles, const float* __restrict__ d_enc, const uint8_t* __restrict__ keep_enc, int Re,
+                                                          const int* __restrict__ tok, const float* __restrict__ d_dec, const uint8_t* __restrict__ keep_dec, int Rd,
+                                                          const int* __restrict__ hdr, float* __restrict__ out) {
+    __shared__ float red[4][64];
+    const int id = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
+    const float scale = ssp_keep_scale(hdr);
+    float acc = 0.f;
+    for (int r = ph; r < Re; r += 4)
+        if (roles[r] == id) {
+            const long long at = (long long)r * SSP_H + c;
+            acc += keep_enc ? (keep_enc[at] ? d_enc[at] * scale : 0.f) : d_enc[at];
+        }
+    for (int r = ph; r < Rd; r += 4)
+        if (tok[r] == id) {
+            const long long at = (long long)r * SSP_H + c;
+            acc += keep_dec ? (keep_dec[at] ? d_dec[at] * scale : 0.f) : d_dec[at];
+        }
+    red[ph][threadIdx.x & 63] = acc;
+    __syncthreads();
+    if (ph == 0) out[(long long)id * SSP_H + c] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x])) * 22.627416997969522f;
+}
+
+// d v_embed_layer.weight (n_verbs, 512), dense as nn.Embedding gives it: one block per table row scans the S verbs in order; a sequence
+// contributes the sum over its 10 positions (the verb embedding is broadcast over them) under its ONE mask row of site 0.  Unused rows: 0.
+__global__ __launch_bounds__(128) void k_ssp_v_embed_bwd(const int* __restrict__ verbs32, const float* __restrict__ d_enc, const uint8_t* __restrict__ keep,
+                                                         const int* __restrict__ hdr, int S, float* __restrict__ out) {
+    const int id = blockIdx.x, c = threadIdx.x * 4;
+    const float scale = ssp_keep_scale(hdr);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int s = 0; s < S; ++s)
+        if (verbs32[s] == id) {
+            float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int j = 0; j < SSP_LEN; ++j) {
+                const float4 d = *reinterpret_cast<const float4*>(d_enc + ((long long)s * SSP_LEN + j) * SSP_H + c);
+                t = make_float4(t.x + d.x, t.y + d.y, t.z + d.z, t.w + d.w);
+            }
+            const float4 f = ssp_keep4(keep, (long long)s * SSP_H + c, scale);
+            acc = make_float4(acc.x + t.x * f.x, acc.y + t.y * f.y, acc.z + t.z * f.z, acc.w + t.w * f.w);
+        }
+    const float sc = 22.627416997969522f;
+    *reinterpret_cast<float4*>(out + (long long)id * SSP_H + c) = make_float4(acc.x * sc, acc.y * sc, acc.z * sc, acc.w * sc);
 }
 
 }  // namespace vsr

@@ -4,8 +4,9 @@ Mirrors /root/reference/models/sort_model.py:13-52 (constructor, module tree -> 
 `re_sort_net.load_state_dict(torch.load('saved_model/coco_s_ssp/model-tr.pth'))`, eval_coco.py:96, works) and
 :105-183 `generate(this_verb, det_seqs_sr, mode='not-normal')`, the call of eval_coco.py:174.  All compute is the batched
 HIP path (vsr_ssp_generate); `generate_batch` takes every (caption, verb) sequence of a loader batch in ONE call.
-Training the ordering model (forward / loss, coco_scripts/train_region_sort.py) and the free-running 'normal' decode are
-outside the hot path and raise."""
+`forward(this_verb, det_seqs_sr, gt_seqs_sr)` (:80-103) is the training loss as coco_scripts/train_region_sort.py:181-185 calls it:
+one device forward and one hand-written HIP backward behind autograd (vsr_ssp_train_forward / _backward), dropout masks drawn on the
+device from `seed` in .train() mode.  The free-running 'normal' decode and beam search are not on any script's path and raise."""
 import math
 
 import torch
@@ -141,5 +142,29 @@ class S_SSP(nn.Module):
         # the reference allocates its log-prob buffer with det_seqs_sr.new_zeros (:121): an integer tensor, values truncated
         return pred, logp.trunc().to(pred.dtype), None
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training S_SSP (coco_scripts/train_region_sort.py) is outside the hot path (SURVEY.md section 2 row 11)")
+    def forward(self, this_verb, det_seqs_sr, gt_seqs_sr, seed=None, dropout_masks=None):
+        """train_region_sort.py:181: loss = re_sort_net(batch_verb.unsqueeze(1) (S,1), batch_det_sr (S,10), batch_gt_sr (S,10)) -> a 0-d
+        fp32 loss: the label-smoothed KL of the teacher-forced decoder against [gt_0 .. gt_9, 0] over the shifted mask, / sum(mask).
+        With grad mode on and a parameter that requires grad it carries a grad_fn (gradients accumulate into .grad through autograd;
+        decoder.*.cross_attention.* is never called, so its .grad stays None as under the reference); otherwise it is a plain tensor
+        with the same bits.  Dropout (p = 0.1, 33 sites) is active in .train() mode only: the masks come from `seed` (drawn with
+        torch.randint and mixed with the data-parallel rank when None) or, if given, from `dropout_masks`, a uint8 GPU buffer laid
+        out as SspEngine.ssp_mask_layout(S) says (1 = keep) - which applies in either mode.  The reference's isnan -> pdb line is not
+        reproduced (it would need a host sync)."""
+        from vsrcap.ssp import SSP_DROPOUT_P, SSP_PARAM_KEYS, SspTrainFn
+        dev = self.expander_nn.weight.device
+        eng = self._engine(dev)
+        verbs, roles, gt = eng._check_ssp_batch(this_verb, det_seqs_sr, gt_seqs_sr, dropout_masks)
+        masks = dropout_masks
+        if masks is None and self.training:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                import torch.distributed as dist
+                if dist.is_available() and dist.is_initialized():                     # ranks seeded alike must not draw the same masks
+                    seed ^= (dist.get_rank() + 1) << 48
+            masks = eng.ssp_dropout_masks(roles.size(0), seed, SSP_DROPOUT_P)
+        named = dict(self.named_parameters())
+        params = [named[k] for k in SSP_PARAM_KEYS]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return SspTrainFn.apply(eng, verbs, roles, gt, masks, SSP_DROPOUT_P, *params)
+        return eng.ssp_train_forward(verbs, roles, gt, masks, SSP_DROPOUT_P, checked=True)[0]

@@ -57,6 +57,16 @@ class VsrSspWeights(C.Structure):
                 ("dec_ln_w", C.c_void_p), ("dec_ln_b", C.c_void_p), ("exp_w", C.c_void_p), ("exp_b", C.c_void_p)]
 
 
+class VsrSspLayerGrads(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in SSP_LAYER_FIELDS]
+
+
+class VsrSspGrads(C.Structure):          # vsr_ssp_grads: vsr_ssp_weights field for field
+    _fields_ = [("sr_embed", C.c_void_p), ("v_embed", C.c_void_p), ("n_verbs", C.c_int64), ("fc_w", C.c_void_p), ("fc_b", C.c_void_p),
+                ("enc", VsrSspLayerGrads * 3), ("enc_ln_w", C.c_void_p), ("enc_ln_b", C.c_void_p), ("dec", VsrSspLayerGrads * 3),
+                ("dec_ln_w", C.c_void_p), ("dec_ln_b", C.c_void_p), ("exp_w", C.c_void_p), ("exp_b", C.c_void_p)]
+
+
 SINKHORN_FIELDS = ["W1_txt_w", "W1_txt_b", "W1_vis_w", "W1_vis_b", "W2_vis_w", "W2_vis_b", "W_fc_pos_w", "W_fc_pos_b", "W_fc_w", "W_fc_b"]
 
 
@@ -119,6 +129,14 @@ SIGNATURES = {
     "vsr_sinkhorn_train_forward": (I32, [P, P, I32, P, P, SZ, P, SZ, P]),
     "vsr_sinkhorn_loc_loss": (I32, [P, P, P, I32, I32, C.c_float, P, P, P]),
     "vsr_sinkhorn_train_backward": (I32, [P, P, I32, P, SZ, P, C.POINTER(VsrSinkhornGrads), P, SZ, P]),
+    "vsr_ssp_mask_bytes": (SZ, [I32]),
+    "vsr_ssp_mask_offset": (SZ, [I32, I32]),
+    "vsr_ssp_dropout_masks": (I32, [U64, C.c_float, I32, P, P]),
+    "vsr_ssp_tape_bytes": (SZ, [I32]),
+    "vsr_ssp_train_workspace_bytes": (SZ, [I32]),
+    "vsr_ssp_tape_ff_offset": (SZ, [I32, I32, I32]),
+    "vsr_ssp_train_forward": (I32, [P, P, P, P, I32, P, C.c_float, P, P, P, SZ, P, SZ, P]),
+    "vsr_ssp_train_backward": (I32, [P, P, P, P, I32, P, P, SZ, P, C.POINTER(VsrSspGrads), P, SZ, P]),
     "vsr_profile_begin": (I32, [P]),
     "vsr_profile_begin_sampled": (I32, [P, I32]),
     "vsr_profile_seen": (I64, [P]),

@@ -3,7 +3,9 @@ vsr_ssp object per device, weights borrowed from torch parameters, work enqueued
 CPU tensors raise.
 
 SinkhornNet trains through SinkhornTrainFn (one forward / one hand-written backward for all Q items of a loader batch) and
-sinkhorn_loc_loss (the fused location loss of coco_scripts/train_sinkhorn.py:207-209)."""
+sinkhorn_loc_loss (the fused location loss of coco_scripts/train_sinkhorn.py:207-209).  S_SSP trains through SspTrainFn: the loss of
+models/sort_model.py:80-103 for all S sequences of a loader batch in one forward, one hand-written backward; dropout masks are a byte
+buffer (ssp_mask_layout, ssp_dropout_masks) that the forward and the backward both read."""
 import ctypes as C
 
 import torch
@@ -19,6 +21,51 @@ def _ptr(t):
 def _need_gpu(t, name):
     if not t.is_cuda:
         raise RuntimeError("%s must live on the GPU (got %s); this path has no CPU implementation" % (name, t.device))
+
+
+SSP_DROPOUT_P = 0.1          # every nn.Dropout of the reference's S_SSP (sort_modules.py, transformer_modules.py: dropout_ratio=0.1)
+
+
+def _ssp_layout():
+    """[(field path in vsr_ssp_weights / vsr_ssp_grads, state_dict key)] of every weight the model uses, in struct order
+    (decoder.*.cross_attention.* is never called, sort_modules.py:87: it is not bound and has no gradient)"""
+    def layer(stack, l, pre, dec):
+        out = [((stack, l, "ln%d_%s" % (i, f)), "%s.layer_norm%d.%s" % (pre, i, wb)) for i in (1, 2, 3) if i < 3 or dec
+               for wb, f in (("weight", "w"), ("bias", "b"))]
+        for q in "QKVO":
+            out += [((stack, l, "W" + q.lower()), "%s.attention.linear_%s.weight" % (pre, q)), ((stack, l, "b" + q.lower()), "%s.attention.linear_%s.bias" % (pre, q))]
+        return out + [((stack, l, "W1"), pre + ".ff_layer.w_1.weight"), ((stack, l, "b1"), pre + ".ff_layer.w_1.bias"),
+                      ((stack, l, "W2"), pre + ".ff_layer.w_2.weight"), ((stack, l, "b2"), pre + ".ff_layer.w_2.bias")]
+    out = [(("sr_embed",), "sr_embed_layer.weight"), (("v_embed",), "v_embed_layer.weight"),
+           (("fc_w",), "encoder.fc_feat.weight"), (("fc_b",), "encoder.fc_feat.bias")]
+    for l in range(3):
+        out += layer("enc", l, "encoder.encoder_layers.%d" % l, False)
+    out += [(("enc_ln_w",), "encoder.layer_norm.weight"), (("enc_ln_b",), "encoder.layer_norm.bias")]
+    for l in range(3):
+        out += layer("dec", l, "decoder.encoder_layers.%d" % l, True)
+    return out + [(("dec_ln_w",), "decoder.layer_norm.weight"), (("dec_ln_b",), "decoder.layer_norm.bias"),
+                  (("exp_w",), "expander_nn.weight"), (("exp_b",), "expander_nn.bias")]
+
+
+SSP_LAYOUT = _ssp_layout()
+SSP_PARAM_KEYS = [k for _, k in SSP_LAYOUT]
+
+
+def _set_field(struct, path, value):
+    for name in path[:-1]:
+        struct = struct[name] if isinstance(name, int) else getattr(struct, name)
+    setattr(struct, path[-1], value)
+
+
+def ssp_site_shapes(S):
+    """shapes of the 33 tensors nn.Dropout sees in one S_SSP.forward of S sequences, in the reference's call order (include/vsrcap.h)"""
+    sh = [(S, 1, 512), (S, 10, 512)]
+    for _ in range(3):
+        sh += [(S, 8, 10, 10), (S, 10, 512), (S, 10, 2048), (S, 10, 512)]
+    sh.append((S, 11, 512))
+    for _ in range(3):
+        sh += [(S, 8, 11, 11), (S, 11, 512), (S, 8, 11, 10), (S, 11, 512), (S, 11, 2048), (S, 11, 512)]
+    return sh
 
 
 class SspEngine:
@@ -58,30 +105,14 @@ class SspEngine:
 
     def bind_ssp(self, sd):
         """sd: state_dict-like mapping with the reference S_SSP's keys (models/sort_model.py)."""
-        def layer(pre, dec):
-            vals = {}
-            for i in (1, 2, 3):
-                for wb, f in (("weight", "w"), ("bias", "b")):
-                    vals["ln%d_%s" % (i, f)] = self._f32(sd, "%s.layer_norm%d.%s" % (pre, i, wb)) if (i < 3 or dec) else 0
-            for q in "QKVO":
-                vals["W" + q.lower()] = self._f32(sd, "%s.attention.linear_%s.weight" % (pre, q))
-                vals["b" + q.lower()] = self._f32(sd, "%s.attention.linear_%s.bias" % (pre, q))
-            vals["W1"], vals["b1"] = self._f32(sd, pre + ".ff_layer.w_1.weight"), self._f32(sd, pre + ".ff_layer.w_1.bias")
-            vals["W2"], vals["b2"] = self._f32(sd, pre + ".ff_layer.w_2.weight"), self._f32(sd, pre + ".ff_layer.w_2.bias")
-            return _lib.VsrSspLayer(**vals)
         w = _lib.VsrSspWeights()
-        w.sr_embed, w.v_embed = self._f32(sd, "sr_embed_layer.weight"), self._f32(sd, "v_embed_layer.weight")
+        for path, key in SSP_LAYOUT:
+            _set_field(w, path, self._f32(sd, key))
         w.n_verbs = sd["v_embed_layer.weight"].shape[0]
-        w.fc_w, w.fc_b = self._f32(sd, "encoder.fc_feat.weight"), self._f32(sd, "encoder.fc_feat.bias")
-        for l in range(3):
-            w.enc[l] = layer("encoder.encoder_layers.%d" % l, False)
-            w.dec[l] = layer("decoder.encoder_layers.%d" % l, True)
-        w.enc_ln_w, w.enc_ln_b = self._f32(sd, "encoder.layer_norm.weight"), self._f32(sd, "encoder.layer_norm.bias")
-        w.dec_ln_w, w.dec_ln_b = self._f32(sd, "decoder.layer_norm.weight"), self._f32(sd, "decoder.layer_norm.bias")
-        w.exp_w, w.exp_b = self._f32(sd, "expander_nn.weight"), self._f32(sd, "expander_nn.bias")
         with torch.cuda.device(self.device):
             _lib.check(self.lib.vsr_ssp_bind(self.h, C.byref(w), None))
         self._keep["ssp"] = sd
+        self.ssp_binding = object()               # a new one per bind: a tape's backward must meet the binding of its forward
 
     def bind_sinkhorn(self, sd, N, n_iters, tau):
         w = _lib.VsrSinkhornWeights()
@@ -191,6 +222,107 @@ class SspEngine:
         return out
 
 
+    # ---- S_SSP training (include/vsrcap.h: vsr_ssp_train_*, vsr_ssp_mask_*, vsr_ssp_dropout_masks)
+    def ssp_mask_layout(self, S):
+        """[(byte offset, shape)] of the 33 dropout sites in the mask buffer of S sequences (1 = keep, each site contiguous from a
+        16-byte boundary) and the buffer's size"""
+        S = int(S)
+        return [(self.lib.vsr_ssp_mask_offset(S, i), sh) for i, sh in enumerate(ssp_site_shapes(S))], self.lib.vsr_ssp_mask_bytes(S)
+
+    def ssp_dropout_masks(self, S, seed, p=SSP_DROPOUT_P):
+        """the library's masks of `seed` for S sequences: a uint8 GPU tensor of vsr_ssp_mask_bytes(S) bytes"""
+        S = int(S)
+        with torch.cuda.device(self.device):
+            masks = torch.empty(self.lib.vsr_ssp_mask_bytes(S), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.vsr_ssp_dropout_masks(int(seed) & (2 ** 64 - 1), float(p), S, _ptr(masks), self._stream()))
+        return masks
+
+    def _check_ssp_batch(self, verbs, roles, gt, masks):
+        for t, name in ((verbs, "this_verb"), (roles, "det_seqs_sr"), (gt, "gt_seqs_sr")):
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError("%s must be a tensor on the GPU" % name)
+            _need_gpu(t, name)
+        S = roles.size(0) if roles.dim() == 2 else 0
+        if S < 1 or tuple(roles.shape) != (S, 10) or tuple(gt.shape) != (S, 10) or tuple(verbs.shape) not in ((S,), (S, 1)):
+            raise RuntimeError("expected this_verb (S,1) or (S,), det_seqs_sr (S,10), gt_seqs_sr (S,10) with S >= 1; got %s, %s, %s"
+                               % (tuple(verbs.shape), tuple(roles.shape), tuple(gt.shape)))
+        verbs = verbs.detach().to(torch.int64).reshape(-1).contiguous()
+        roles, gt = roles.detach().to(torch.int32).contiguous(), gt.detach().to(torch.int32).contiguous()
+        # the reference's embeddings raise IndexError for ids outside their tables (sort_model.py:81-83); the kernels would read row 0
+        lo, hi = int(torch.minimum(roles.min(), gt.min())), int(torch.maximum(roles.max(), gt.max()))
+        if lo < 0 or hi >= 26:
+            raise IndexError("semantic-role ids must lie in [0, 26) (0 = padding); got [%d, %d]" % (lo, hi))
+        n_verbs = self._keep["ssp"]["v_embed_layer.weight"].shape[0]
+        v = verbs % 10000
+        if int(v.min()) < 0 or int(v.max()) >= n_verbs:
+            raise IndexError("verb ids %% 10000 must lie in [0, %d); got [%d, %d]" % (n_verbs, int(v.min()), int(v.max())))
+        if masks is not None:
+            _need_gpu(masks, "dropout_masks")
+            need = self.lib.vsr_ssp_mask_bytes(S)
+            if masks.dtype != torch.uint8 or masks.dim() != 1 or masks.numel() != need or not masks.is_contiguous():
+                raise RuntimeError("dropout_masks must be a contiguous uint8 buffer of %d bytes (ssp_mask_layout(%d)); got %s %s"
+                                   % (need, S, masks.dtype, tuple(masks.shape)))
+        return verbs, roles, gt
+
+    def _one_hot(self):
+        t = self._keep["ssp"]["label_smooth.one_hot"]
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != 26:
+            raise RuntimeError("label_smooth.one_hot must be a contiguous fp32 GPU buffer of 26 values")
+        return t
+
+    def ssp_train_forward(self, verbs, roles, gt, masks=None, p=SSP_DROPOUT_P, checked=False):
+        """S_SSP.forward for S sequences -> (loss, a 0-d fp32 GPU tensor; tape, a uint8 tensor the caller owns: what ssp_train_backward
+        needs of this forward).  masks: None (no dropout) or a buffer laid out as ssp_mask_layout(S) says.  checked: the ids and masks
+        are _check_ssp_batch's own results (its range checks read the device: once per step is enough)"""
+        if not checked:
+            verbs, roles, gt = self._check_ssp_batch(verbs, roles, gt, masks)
+        S = roles.size(0)
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            tape = torch.empty(self.lib.vsr_ssp_tape_bytes(S), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(self.lib.vsr_ssp_train_workspace_bytes(S))
+            _lib.check(self.lib.vsr_ssp_train_forward(self.h, _ptr(verbs), _ptr(roles), _ptr(gt), S, _ptr(masks), float(p), _ptr(self._one_hot()), _ptr(loss),
+                                                      _ptr(tape), tape.numel(), _ptr(ws), ws.numel(), self._stream()))
+        return loss, tape
+
+    def ssp_relu_gates(self, S, tape):
+        """TEST ONLY (the tape's layout is private): the six ReLU gate patterns of the forward that wrote `tape` (encoder layers 0..2, decoder layers 0..2): bool (rows, 2048),
+        True where the unit passed (and, with dropout, was kept)"""
+        out = []
+        for dec in (0, 1):
+            rows = int(S) * (11 if dec else 10)
+            for l in range(3):
+                off = self.lib.vsr_ssp_tape_ff_offset(int(S), dec, l)
+                out.append(tape[off:off + rows * 2048 * 4].view(torch.float32).view(rows, 2048) > 0)
+        return out
+
+    def ssp_train_backward(self, verbs, roles, gt, masks, tape, d_loss, binding=None, checked=False):
+        """-> the gradients of SSP_PARAM_KEYS, in that order (fresh tensors: the library overwrites).  d_loss: a 0-d GPU tensor, read on
+        the device.  binding: the engine's ssp_binding at the time of the forward that wrote the tape; a bind_ssp() since then raises"""
+        if binding is not None and binding is not self.ssp_binding:
+            raise RuntimeError("S_SSP backward: bind_ssp() was called between this forward and its backward - the tape belongs to the earlier weights")
+        if not checked:
+            verbs, roles, gt = self._check_ssp_batch(verbs, roles, gt, masks)
+        _need_gpu(d_loss, "d_loss")
+        if d_loss.numel() != 1:
+            raise RuntimeError("expected a scalar d_loss; got %s" % (tuple(d_loss.shape),))
+        d_loss = d_loss.detach().float().contiguous()
+        S = roles.size(0)
+        sd = self._keep["ssp"]
+        g = _lib.VsrSspGrads()
+        out = []
+        for path, key in SSP_LAYOUT:
+            t = torch.empty_like(sd[key])
+            _set_field(g, path, t.data_ptr())
+            out.append(t)
+        g.n_verbs = sd["v_embed_layer.weight"].shape[0]
+        with torch.cuda.device(self.device):
+            ws = self._workspace(self.lib.vsr_ssp_train_workspace_bytes(S))
+            _lib.check(self.lib.vsr_ssp_train_backward(self.h, _ptr(verbs), _ptr(roles), _ptr(gt), S, _ptr(masks), _ptr(tape), tape.numel(), _ptr(d_loss),
+                                                       C.byref(g), _ptr(ws), ws.numel(), self._stream()))
+        return out
+
+
 def _no_double_backward(what):
     if torch.is_grad_enabled():
         raise RuntimeError("%s: create_graph=True is not supported - the backward is a hand-written HIP pass with no graph of its own" % what)
@@ -247,3 +379,30 @@ class SinkhornLocLossFn(torch.autograd.Function):
         seq = ctx.saved_tensors[0]
         grads = ctx.eng.sinkhorn_train_backward(seq, ctx.tape, ctx.d_tr * d_loss, ctx.binding)
         return (None,) * 5 + tuple(g if ctx.needs_input_grad[5 + i] else None for i, g in enumerate(grads))
+
+
+class SspTrainFn(torch.autograd.Function):
+    """loss = S_SSP.forward(verbs, roles, gt) with a grad_fn.  The tape and the dropout masks of a forward live on its ctx, not in the
+    engine: several forwards may be alive at once ((l1 + l2).backward(), micro-batches, a generate() in between).  params: the
+    parameters of SSP_PARAM_KEYS in that order - the library reads their storage live; they go through save_for_backward so that
+    autograd's in-place check applies.  The ids are data (no gradient) and arrive checked (SspEngine._check_ssp_batch)."""
+
+    @staticmethod
+    def forward(ctx, eng, verbs, roles, gt, masks, p, *params):
+        loss, tape = eng.ssp_train_forward(verbs, roles, gt, masks, p, checked=True)
+        ctx.eng, ctx.tape, ctx.masks, ctx.binding = eng, tape, masks, eng.ssp_binding
+        ctx.ids = (verbs, roles, gt)
+        ctx.save_for_backward(*params)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):                    # undecorated for the same reason as SinkhornTrainFn.backward
+        _no_double_backward("S_SSP.forward")
+        return SspTrainFn._backward(ctx, d_loss)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, d_loss):
+        ctx.saved_tensors                         # (autograd's check that no parameter was modified in place since the forward)
+        grads = ctx.eng.ssp_train_backward(*ctx.ids, ctx.masks, ctx.tape, d_loss, ctx.binding, checked=True)
+        return (None,) * 6 + tuple(g if ctx.needs_input_grad[6 + i] else None for i, g in enumerate(grads))
