@@ -345,6 +345,42 @@ size_t vsr_sinkhorn_workspace_bytes(int32_t Q, int32_t N);
 int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, float* tr, int32_t* assign, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* ---- caption ranking on the device ---------------------------------------------------
+ * eval_coco.py:141-221 / eval_flickr.py:146-227 for the N caption rows of a loader batch: from the loader's integer annotations to the
+ * (N, L) rank tensor of vsr_reorder_slots as one stream of launches on the caller's stream - no read-back, no allocation.
+ *   control_verb (N, MV) int32 (0 = none; a caption's verbs end at the first 0), det_seqs_v (N, L, MV) int32, det_seqs_sr (N, L, MS)
+ *   int32 (indexed with the verb column: MS >= MV), seqs_perm (N, L, 2352) fp32, n_verbs: rows of S-SSP's verb table.
+ *   Limits (beyond them every call fails): L == 10 (S-SSP's sequence length), 1 <= MV <= 8, 2 <= N_sink <= 16.
+ * A JOB is one (caption, verb column); its slot is s = n MV + v whether it is active or not.  Padded job slots and items cost real
+ * launch rows: S-SSP runs on S = N MV sequences (the padded count, not the active one) and SinkhornNet on Q = max_items items.
+ *   max_items = 0 is the static maximum N MV 10 (overflow impossible); a caller who knows a bound on the repeated roles of a batch
+ *   passes it and checks status - the contract of vsr_set_valid_rows_bound.  Items beyond max_items are not evaluated.
+ * vsr_rank_plan: the scan.  job_verbs (S) int64 and job_roles (S, 10) int32 are vsr_ssp_generate's inputs (0 / zeros for an inactive
+ *   slot, which makes it emit nothing); item_gather (max_items, N_sink) int32 holds n L + slot for the rows of each Sinkhorn item (one
+ *   per repeated role of a job, jobs in slot order, roles in ascending id) and -1 for padding rows and unused items; plan
+ *   (vsr_rank_plan_bytes) keeps the jobs' tables for vsr_rank_finish.
+ * vsr_rank_finish: pred (S, 10) int32 as vsr_ssp_generate writes it, assign (max_items, N_sink) int32 as vsr_sinkhorn_assign writes it
+ *   (it MUST have the max_items rows given to vsr_rank_plan: the kernel indexes it with the bound stored in the plan) -> rank (N, L) int32 padded with -1 and status (N) int32, a bit set:
+ *     1 no active job (the reference raises)   2 an item of the caption lies beyond max_items   4 a matched role id outside [0, 26)
+ *     8 a negative verb, or verb % 10000 outside [0, n_verbs)   16 the plan was written for another (N, MV, N_sink)
+ *   A caption with a non-zero status gets an all -1 rank row.  The two calls are public so that a caller can put its own decisions
+ *   between them.
+ * vsr_rank_captions: plan, gather of the items' rows, vsr_ssp_generate at S = N MV, SinkhornNet's layers over the max_items items in
+ *   chunks of 128 (max_items rounded up to whole chunks, so that every GEMM launch has one shape and an item's assignment does not depend
+ *   on the bound the caller chose), vsr_sinkhorn_assign's Sinkhorn + assignment kernel once over all items, finish; both models must be
+ *   bound on `e`, N_sink and n_verbs must be theirs.  workspace: vsr_rank_workspace_bytes (plan + S-SSP at S + Sinkhorn at one chunk +
+ *   the gathered rows, 94 KB per item at N_sink = 10). */
+size_t vsr_rank_plan_bytes(int32_t N, int32_t MV, int32_t max_items);
+size_t vsr_rank_workspace_bytes(int32_t N, int32_t MV, int32_t max_items, int32_t N_sink);
+int vsr_rank_plan(const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, int32_t N, int32_t L, int32_t MV, int32_t MS,
+                  int32_t N_sink, int64_t n_verbs, int32_t max_items, int64_t* job_verbs, int32_t* job_roles, int32_t* item_gather,
+                  void* plan, size_t plan_bytes, void* stream);
+int vsr_rank_finish(const void* plan, size_t plan_bytes, const int32_t* pred, const int32_t* assign, int32_t N, int32_t L, int32_t MV,
+                    int32_t N_sink, int32_t* rank, int32_t* status, void* stream);
+int vsr_rank_captions(vsr_ssp* e, const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, int32_t N, int32_t L,
+                      int32_t MV, int32_t MS, int32_t N_sink, int64_t n_verbs, const float* seqs_perm, int32_t max_items, int32_t* rank,
+                      int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SinkhornNet training (coco_scripts/train_sinkhorn.py:137-215) -----------------------------------
  * The reference calls the net once per (image, caption, verb, repeated role) at batch size 1 and adds MSE losses on the host.
  * Here one forward, one fused loss and one backward serve all Q items of a loader batch; exact fp32 products throughout.

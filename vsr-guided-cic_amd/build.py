@@ -19,6 +19,10 @@ OUT = os.path.join(HERE, "vsrcap", "libvsrcap.so")
 TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "gemm_bench.hip")
 TOOL_DEPS = [TOOL_SRC] + GEMM_HEADERS
 TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "gemm_bench")
+# the caption-ranking logic (csrc/rank_logic.h) on the CPU: plain C++, host compiler; driven by tests/test_rank_logic.py
+RANK_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "rank_logic_host.cpp")
+RANK_TOOL_DEPS = [RANK_TOOL_SRC, os.path.join(HERE, "csrc", "rank_logic.h")]
+RANK_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "rank_logic_host")
 
 
 STAMP = OUT + ".flags"      # the extra hipcc flags the library on disk was built with
@@ -64,7 +68,18 @@ def build_tool(force=False):
     return TOOL_OUT
 
 
+def build_rank_tool(out=RANK_TOOL_OUT, force=False, extra_flags=()):
+    """tools/rank_logic_host with the host compiler ($CXX, default c++); extra_flags e.g. ("-fsanitize=address,undefined", "-g")"""
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in RANK_TOOL_DEPS):
+        return out
+    cxx = os.environ.get("CXX", "c++")
+    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-Wextra", *extra_flags, "-o", out + ".tmp", RANK_TOOL_SRC], check=True)
+    os.replace(out + ".tmp", out)
+    return out
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))
     if "--tool" in sys.argv:
         print(build_tool(force="--force" in sys.argv))
+        print(build_rank_tool(force="--force" in sys.argv))

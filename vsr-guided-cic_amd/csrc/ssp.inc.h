@@ -1,9 +1,11 @@
-// C ABI of the two ordering models that feed the decoder in the eval loop (SURVEY 8f N4); included at the end of vsrcap.hip.
+// C ABI of the two ordering models that feed the decoder in the eval loop (SURVEY 8f N4, N7); included at the end of vsrcap.hip.
 // Reference: coco_scripts/eval_coco.py:127-221 calls S_SSP.generate (batch size 1) once per (caption, verb) and
 // SinkhornNet + munkres once per repeated role, each with host round trips; here ALL sequences / items of a loader batch go
-// through one call each, and the results (role orders, assignments) stay on the device until the host glue
-// (vsrcap/evalbatch.py: rank_captions) turns them into the (N, L) rank tensor vsr_reorder_slots consumes.
+// through one call each, and the results (role orders, assignments) stay on the device: vsr_rank_captions (at the end of this
+// file, kernels in rank_kernels.h) turns them into the (N, L) rank tensor vsr_reorder_slots consumes without a read-back.
+// vsrcap/evalbatch.py: rank_captions is the same flow with the integer bookkeeping on the host.
 #include "ssp_kernels.h"
+#include "rank_kernels.h"
 
 struct vsr_ssp {
     vsr_handle cfg;                  // GEMM launch configuration only (stream-K slots, tile choice); fp32
@@ -176,14 +178,11 @@ extern "C" size_t vsr_sinkhorn_workspace_bytes(int32_t Q, int32_t N) {
     const size_t R = (size_t)Q * N;
     return (R * (128 + 512 + 128 + 260 + 256 + 16) + R * 512 * 8 + 1024) * sizeof(float);
 }
-extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, float* tr, int32_t* assign, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-    if (!e || !e->has_sh) return fail("vsr_sinkhorn_assign: Sinkhorn weights not bound");
-    if (!seq || !assign || !workspace || Q <= 0) return fail("vsr_sinkhorn_assign: bad arguments");
+// The five layers of SinkhornNet for Q items: seq (Q, N, 2352) -> (Q, N, N), tanh applied, into fc_out or (fc_out NULL) into the workspace's
+// own slot; *fc_used is where it went.  workspace: vsr_sinkhorn_workspace_bytes(Q, N), checked by the caller.
+static int sinkhorn_mlp(vsr_ssp* e, const float* seq, int Q, void* workspace, hipStream_t s, float* fc_out, float** fc_used) {
     const vsr_sinkhorn_weights& w = e->sw;
     const int N = w.N, R = Q * N;
-    if (workspace_bytes < vsr_sinkhorn_workspace_bytes(Q, N)) return fail("vsr_sinkhorn_assign: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
     Bump b{reinterpret_cast<char*>(workspace)};
     float* t1 = b.take<float>((size_t)R * 128);
     float* v1 = b.take<float>((size_t)R * 512);
@@ -191,6 +190,7 @@ extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, floa
     float* cat = b.take<float>((size_t)R * 260);
     float* f1 = b.take<float>((size_t)R * 256);
     float* fc = b.take<float>((size_t)R * 16);
+    if (fc_out) fc = fc_out;
     SspWs ws{};
     ws.scratch_floats = (size_t)R * 512 * 8;
     ws.scratch = b.take<float>(ws.scratch_floats);
@@ -200,7 +200,19 @@ extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, floa
     hipLaunchKernelGGL(k_sh_cat, dim3(cdiv((long long)R * 260, 256)), dim3(256), 0, s, t1, v2, seq, R, cat);
     if (linear1(e, ws, s, R, 256, 260, cat, 260, w.W_fc_pos_w, w.W_fc_pos_b, 1, nullptr, f1)) return 1;
     if (linear1(e, ws, s, R, N, 256, f1, 256, w.W_fc_w, w.W_fc_b, 2, nullptr, fc)) return 1;
-    hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Q), dim3(64), 0, s, fc, N, w.n_iters, w.tau, tr, assign);
+    *fc_used = fc;
+    return 0;
+}
+extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, float* tr, int32_t* assign, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    if (!e || !e->has_sh) return fail("vsr_sinkhorn_assign: Sinkhorn weights not bound");
+    if (!seq || !assign || !workspace || Q <= 0) return fail("vsr_sinkhorn_assign: bad arguments");
+    const vsr_sinkhorn_weights& w = e->sw;
+    if (workspace_bytes < vsr_sinkhorn_workspace_bytes(Q, w.N)) return fail("vsr_sinkhorn_assign: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    float* fc = nullptr;
+    if (sinkhorn_mlp(e, seq, Q, workspace, s, nullptr, &fc)) return 1;
+    hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Q), dim3(64), 0, s, fc, w.N, w.n_iters, w.tau, tr, assign);
     LAUNCHCHK();
     return 0;
 }
@@ -837,4 +849,117 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     hipLaunchKernelGGL(k_ssp_v_embed_bwd, dim3((int)w.n_verbs), dim3(128), 0, s, ws.verbs32, ws.r[2], keep(0), t.hdr, S, g->v_embed);
     LAUNCHCHK();
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- caption ranking on the device
+// eval_coco.py:141-221 for the N caption rows of a loader batch as one stream of launches: integer annotations in,
+// the (N, L) rank tensor of vsr_reorder_slots out, no read-back.  S-SSP runs on the PADDED job slots S = N MV (an inactive slot has
+// verb 0 and no roles: k_ssp_init emits nothing for it) and SinkhornNet on Q = max_items items (an unused item is all zero rows).
+// The items go through SinkhornNet's five layers (vsr_sinkhorn_assign's own: sinkhorn_mlp) in chunks of RANK_SH_CHUNK (max_items rounded
+// up to whole chunks): every GEMM launch then has the same shape whatever max_items is, so an item's assignment - down to how a tie
+// between two identical padding rows falls, which follows the last bit of the stream-K GEMMs and with it the launch's row count - does
+// not depend on the bound the caller chose.  The Sinkhorn iterations and the assignment (k_sinkhorn_assign, one wave per item, 0.37 ms
+// whether it has 128 items or 2432: its time is lane 0's serial Kuhn-Munkres) run ONCE over all items.
+constexpr int RANK_SH_CHUNK = 128;
+static int rank_qcap(int N, int MV, int max_items) { return max_items > 0 ? max_items : N * MV * RANK_L; }
+static int rank_qpad(int Qcap) { return (int)(((long long)Qcap + RANK_SH_CHUNK - 1) / RANK_SH_CHUNK * RANK_SH_CHUNK); }
+static size_t carve_rank_plan(int N, int MV, char* base, RankPlan& p) {
+    const size_t S = (size_t)N * MV;
+    Bump b{base};
+    p.hdr = b.take<int32_t>(RANK_HDR_INTS); p.item_cnt = b.take<int32_t>(S); p.item_off = b.take<int32_t>(S); p.jobs = b.take<RankJob>(S);
+    return (b.off + 255) & ~size_t(255);
+}
+static int rank_shape(const char* who, int N, int L, int MV, int MS, int N_sink, int max_items) {
+    if (N <= 0 || max_items < 0) return fail("%s: bad arguments (N %d, max_items %d)", who, N, max_items);
+    if (!rank_limits_ok(L, MV, MS, N_sink))
+        return fail("%s: outside the limits L == %d, 1 <= MV <= %d, MS >= MV, %d <= N_sink <= %d (got L %d, MV %d, MS %d, N_sink %d)", who, RANK_L, RANK_MAX_MV,
+                    RANK_MIN_SINK, RANK_MAX_SINK, L, MV, MS, N_sink);
+    if ((long long)N * MV * RANK_L > INT_MAX / 64 || max_items > INT_MAX / 64)         // job and item row indices (x 10, x N_sink) stay inside int
+        return fail("%s: N %d / max_items %d too large", who, N, max_items);
+    return 0;
+}
+extern "C" size_t vsr_rank_plan_bytes(int32_t N, int32_t MV, int32_t max_items) {
+    if (N <= 0 || MV < 1 || MV > RANK_MAX_MV || max_items < 0 || max_items > INT_MAX / 64 || (long long)N * MV * RANK_L > INT_MAX / 64) return 0;
+    RankPlan p;
+    return carve_rank_plan(N, MV, nullptr, p);
+}
+
+// Qfill >= Qcap: rows of item_gather to fill (those beyond Qcap with -1: the tail of the last Sinkhorn chunk)
+static int rank_plan_launch(const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, int N, int L, int MV, int MS, int N_sink, int64_t n_verbs,
+                            int Qcap, int Qfill, int64_t* job_verbs, int32_t* job_roles, int32_t* item_gather, const RankPlan& p, hipStream_t s) {
+    const int S = N * MV;
+    hipLaunchKernelGGL(k_rank_jobs, dim3(cdiv(S, 64)), dim3(64), 0, s, control_verb, det_seqs_v, det_seqs_sr, N, L, MV, MS, N_sink, Qcap, (long long)n_verbs, p,
+                       job_verbs, job_roles);
+    hipLaunchKernelGGL(k_rank_items, dim3(1), dim3(256), 0, s, p, S, L, MV, N_sink, Qcap, Qfill, item_gather);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int vsr_rank_plan(const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, int32_t N, int32_t L, int32_t MV, int32_t MS,
+                             int32_t N_sink, int64_t n_verbs, int32_t max_items, int64_t* job_verbs, int32_t* job_roles, int32_t* item_gather, void* plan,
+                             size_t plan_bytes, void* stream) {
+    if (!control_verb || !det_seqs_v || !det_seqs_sr || !job_verbs || !job_roles || !item_gather || !plan || n_verbs <= 0) return fail("vsr_rank_plan: bad arguments");
+    if (rank_shape("vsr_rank_plan", N, L, MV, MS, N_sink, max_items)) return 1;
+    RankPlan p;
+    if (carve_rank_plan(N, MV, reinterpret_cast<char*>(plan), p) > plan_bytes) return fail("vsr_rank_plan: plan buffer too small");
+    const int Qcap = rank_qcap(N, MV, max_items);
+    return rank_plan_launch(control_verb, det_seqs_v, det_seqs_sr, N, L, MV, MS, N_sink, n_verbs, Qcap, Qcap, job_verbs, job_roles, item_gather, p, (hipStream_t)stream);
+}
+
+extern "C" int vsr_rank_finish(const void* plan, size_t plan_bytes, const int32_t* pred, const int32_t* assign, int32_t N, int32_t L, int32_t MV, int32_t N_sink,
+                               int32_t* rank, int32_t* status, void* stream) {
+    if (!plan || !pred || !assign || !rank || !status) return fail("vsr_rank_finish: bad arguments");
+    if (rank_shape("vsr_rank_finish", N, L, MV, MV, N_sink, 0)) return 1;
+    RankPlan p;
+    if (carve_rank_plan(N, MV, reinterpret_cast<char*>(const_cast<void*>(plan)), p) > plan_bytes) return fail("vsr_rank_finish: plan buffer too small");
+    hipLaunchKernelGGL(k_rank_finish, dim3(N), dim3(64), 0, (hipStream_t)stream, p, pred, assign, N, L, MV, N_sink, rank, status);
+    LAUNCHCHK();
+    return 0;
+}
+
+struct RankWs { char* plan; size_t plan_bytes; int64_t* job_verbs; int32_t *job_roles, *item_gather, *pred, *assign; float *logp, *seq, *fc; char *ssp, *sh; size_t ssp_bytes, sh_bytes; };
+static size_t carve_rank_ws(int N, int MV, int Qcap, int N_sink, char* base, RankWs& w) {
+    const size_t S = (size_t)N * MV, R = (size_t)rank_qpad(Qcap) * N_sink;
+    Bump b{base};
+    w.plan_bytes = vsr_rank_plan_bytes(N, MV, 0);
+    w.plan = b.take<char>(w.plan_bytes);
+    w.job_verbs = b.take<int64_t>(S); w.job_roles = b.take<int32_t>(S * RANK_L); w.pred = b.take<int32_t>(S * RANK_L); w.logp = b.take<float>(S * RANK_L);
+    w.item_gather = b.take<int32_t>(R); w.assign = b.take<int32_t>(R); w.seq = b.take<float>(R * SH_ROW); w.fc = b.take<float>(R * N_sink);
+    w.ssp_bytes = vsr_ssp_workspace_bytes((int32_t)S); w.ssp = b.take<char>(w.ssp_bytes);
+    w.sh_bytes = vsr_sinkhorn_workspace_bytes(RANK_SH_CHUNK, N_sink); w.sh = b.take<char>(w.sh_bytes);
+    return (b.off + 255) & ~size_t(255);
+}
+extern "C" size_t vsr_rank_workspace_bytes(int32_t N, int32_t MV, int32_t max_items, int32_t N_sink) {
+    if (!vsr_rank_plan_bytes(N, MV, max_items) || N_sink < RANK_MIN_SINK || N_sink > RANK_MAX_SINK) return 0;
+    RankWs w;
+    return carve_rank_ws(N, MV, rank_qcap(N, MV, max_items), N_sink, nullptr, w);
+}
+
+extern "C" int vsr_rank_captions(vsr_ssp* e, const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, int32_t N, int32_t L, int32_t MV,
+                                 int32_t MS, int32_t N_sink, int64_t n_verbs, const float* seqs_perm, int32_t max_items, int32_t* rank, int32_t* status,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || !e->has_ssp || !e->has_sh) return fail("vsr_rank_captions: the S-SSP and the Sinkhorn weights must both be bound on this object");
+    if (!seqs_perm || !rank || !status || !workspace) return fail("vsr_rank_captions: bad arguments");
+    if (rank_shape("vsr_rank_captions", N, L, MV, MS, N_sink, max_items)) return 1;
+    if (N_sink != e->sw.N || n_verbs != e->w.n_verbs)
+        return fail("vsr_rank_captions: N_sink %d / n_verbs %lld differ from the bound models' (%d, %lld)", N_sink, (long long)n_verbs, e->sw.N, (long long)e->w.n_verbs);
+    const int S = N * MV, Qcap = rank_qcap(N, MV, max_items);
+    RankWs w;
+    if (carve_rank_ws(N, MV, Qcap, N_sink, reinterpret_cast<char*>(workspace), w) > workspace_bytes) return fail("vsr_rank_captions: workspace too small");
+    RankPlan p;
+    carve_rank_plan(N, MV, w.plan, p);
+    hipStream_t s = (hipStream_t)stream;
+    const int Qpad = rank_qpad(Qcap);
+    if (rank_plan_launch(control_verb, det_seqs_v, det_seqs_sr, N, L, MV, MS, N_sink, n_verbs, Qcap, Qpad, w.job_verbs, w.job_roles, w.item_gather, p, s)) return 1;
+    const long long n_rows = (long long)Qpad * N_sink;
+    hipLaunchKernelGGL(k_rank_gather, dim3((int)std::min<long long>(2048, cdiv(n_rows, 4))), dim3(256), 0, s, seqs_perm, w.item_gather, n_rows, (long long)N * L, w.seq);
+    LAUNCHCHK();
+    if (vsr_ssp_generate(e, w.job_verbs, w.job_roles, S, w.pred, w.logp, w.ssp, w.ssp_bytes, stream)) return 1;
+    for (int q = 0; q < Qpad; q += RANK_SH_CHUNK) {
+        float* fc = nullptr;
+        if (sinkhorn_mlp(e, w.seq + (size_t)q * N_sink * SH_ROW, RANK_SH_CHUNK, w.sh, s, w.fc + (size_t)q * N_sink * N_sink, &fc)) return 1;
+    }
+    hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Qpad), dim3(64), 0, s, w.fc, N_sink, e->sw.n_iters, e->sw.tau, (float*)nullptr, w.assign);
+    LAUNCHCHK();
+    return vsr_rank_finish(w.plan, w.plan_bytes, w.pred, w.assign, N, L, MV, N_sink, rank, status, stream);
 }

@@ -153,3 +153,42 @@ def rank_captions(ssp, sinkhorn, control_verb, det_seqs_v, det_seqs_sr, seqs_per
             final = verb_rank_merge(final, other)
         out.append([int(x) for x in final])
     return out
+
+
+# ---------------------------------------------------------------------------------------------- SURVEY 8f N7
+def _shared_engine(ssp, sinkhorn, dev):
+    """ONE SspEngine with both models bound: S_SSP's, with the SinkhornNet's weights bound next to them (each class keeps an engine of
+    its own for its own calls; vsr_rank_captions needs both on one object)"""
+    if next(sinkhorn.parameters()).device != dev:
+        raise RuntimeError("rank_captions_device: the two models must live on one device (got %s and %s)" % (dev, next(sinkhorn.parameters()).device))
+    eng = ssp._engine(dev)
+    key = tuple(p.data_ptr() for p in sinkhorn.parameters()) + (sinkhorn.N, sinkhorn.n_iters, sinkhorn.tau)
+    if getattr(eng, "_rank_sinkhorn_key", None) != key:
+        eng.bind_sinkhorn({k: v.data for k, v in sinkhorn.state_dict(keep_vars=True).items()}, sinkhorn.N, sinkhorn.n_iters, sinkhorn.tau)
+        eng._rank_sinkhorn_key = key
+    return eng
+
+
+def rank_captions_device(ssp, sinkhorn, control_verb, det_seqs_v, det_seqs_sr, seqs_perm, max_items=None):
+    """rank_captions without the host: the same inputs -> (rank (N, L) int32 padded with -1, status (N,) int32), both on the GPU, as one
+    stream of launches (SspEngine.rank_captions / vsr_rank_captions) - no .cpu(), no .item(), no look at a value on the host.  What
+    rank_captions raises or returns as [] becomes a status bit (SspEngine.rank_captions) and an all -1 row.  The integer annotations may
+    be host arrays (one non-blocking upload) or tensors.  S-SSP runs on all N * MV (caption, verb column) slots and the Sinkhorn net on
+    max_items items whatever the batch holds: max_items=None is the static maximum N * MV * 10, a caller who knows a bound on the
+    repeated roles of a batch passes it and checks status bit 2."""
+    dev = ssp.expander_nn.weight.device
+    return _shared_engine(ssp, sinkhorn, dev).rank_captions(control_verb, det_seqs_v, det_seqs_sr, seqs_perm, max_items)
+
+
+def beam_search_v_ranked(model, ssp, sinkhorn, detections, bank, slot_idx, row_img, control_verb, det_seqs_v, det_seqs_sr, seqs_perm, verb_list,
+                         eos_idxs, beam_size=5, out_size=1, gt=False, max_items=None):
+    """eval_coco.py:141-249 for a loader batch in three calls: rank_captions_device, regions.reorder_slots_device, model.beam_search_v.
+    Returns what beam_search_v_indexed returns, plus status (N,) int32 on the GPU (a caption with a non-zero status was decoded from an
+    all -1 rank row: check it when the captions are read).  With set_valid_rows_bound set on the model's engine, device-resident inputs
+    and verb_list on the GPU, the whole chain waits for nothing."""
+    from .regions import IndexedRegions, reorder_slots_device
+    eng = model._engine(detections.device)
+    rank, status = rank_captions_device(ssp, sinkhorn, control_verb, det_seqs_v, det_seqs_sr, seqs_perm, max_items)
+    regions, verbs = reorder_slots_device(eng, IndexedRegions(bank, slot_idx, row_img), rank, verb_list)
+    outs, lps = model.beam_search_v((detections, regions, verbs), eos_idxs=eos_idxs, beam_size=beam_size, out_size=out_size, gt=gt)
+    return outs, lps, status

@@ -10,6 +10,7 @@ dense tensor is ever built or shipped.
   * `fill_region_indices`    `COCOControlSequenceField._fill` (field.py:44-61) producing indices instead of feature copies
   * `reorder_slots`          eval_coco.py:222-241 (slot permutation, compaction, last-slot replication, verb permutation)
                              for all captions of a batch at once, on the GPU (vsr_reorder_slots)
+  * `reorder_slots_device`   the same launch for a rank tensor that is already on the GPU (evalbatch.rank_captions_device): no host copy
 """
 import numpy as np
 import torch
@@ -110,6 +111,27 @@ def reorder_slots(engine, regions, final_ranks, verb_list=None):
         verbs = torch.as_tensor(verb_list).to(device=dev, dtype=torch.float32).reshape(N, L).contiguous()
     bank_mask = engine.row_mask(regions.bank).reshape(-1).contiguous()
     out, vout = engine.reorder_slots(regions.slot_idx.contiguous(), rank_t, verbs, bank_mask, regions.row_img, regions.bank.size(1))
+    return IndexedRegions(regions.bank, out, regions.row_img), vout
+
+
+def reorder_slots_device(engine, regions, rank, verb_list=None):
+    """reorder_slots for a DEVICE rank tensor: int32 (N, L) on the GPU whose entries lie in [-1, L) by construction (what
+    evalbatch.rank_captions_device / vsr_rank_captions writes: slot positions, -1 padding).  The same engine.reorder_slots launch,
+    nothing copied to the host, no value looked at here.  verb_list: (N, L) or (N, L, 1); a GPU tensor stays where it is, a host
+    array is uploaded without blocking."""
+    N, L, R = regions.slot_idx.shape
+    dev = regions.device
+    if not torch.is_tensor(rank) or not rank.is_cuda or rank.dtype != torch.int32 or tuple(rank.shape) != (N, L):
+        raise ValueError("rank must be an int32 (%d, %d) GPU tensor" % (N, L))
+    verbs = None
+    if verb_list is not None:
+        if torch.is_tensor(verb_list) and verb_list.is_cuda:
+            verbs = verb_list.to(device=dev, dtype=torch.float32).reshape(N, L).contiguous()
+        else:
+            host = torch.as_tensor(np.asarray(verb_list.cpu() if torch.is_tensor(verb_list) else verb_list), dtype=torch.float32).reshape(N, L)
+            verbs = host.contiguous().pin_memory().to(dev, non_blocking=True)
+    bank_mask = engine.row_mask(regions.bank).reshape(-1).contiguous()
+    out, vout = engine.reorder_slots(regions.slot_idx.contiguous(), rank.contiguous(), verbs, bank_mask, regions.row_img, regions.bank.size(1))
     return IndexedRegions(regions.bank, out, regions.row_img), vout
 
 

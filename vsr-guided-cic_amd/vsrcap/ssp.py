@@ -5,9 +5,14 @@ CPU tensors raise.
 SinkhornNet trains through SinkhornTrainFn (one forward / one hand-written backward for all Q items of a loader batch) and
 sinkhorn_loc_loss (the fused location loss of coco_scripts/train_sinkhorn.py:207-209).  S_SSP trains through SspTrainFn: the loss of
 models/sort_model.py:80-103 for all S sequences of a loader batch in one forward, one hand-written backward; dropout masks are a byte
-buffer (ssp_mask_layout, ssp_dropout_masks) that the forward and the backward both read."""
+buffer (ssp_mask_layout, ssp_dropout_masks) that the forward and the backward both read.
+
+rank_captions is the eval loop's ranking (eval_coco.py:141-221) for a loader batch as one stream of launches (vsr_rank_captions): integer
+annotations in, the (N, L) rank tensor and a per-caption status out, both on the device, nothing read back; rank_plan / rank_finish are
+its two integer stages on their own."""
 import ctypes as C
 
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -66,6 +71,14 @@ def ssp_site_shapes(S):
     for _ in range(3):
         sh += [(S, 8, 11, 11), (S, 11, 512), (S, 8, 11, 10), (S, 11, 512), (S, 11, 2048), (S, 11, 512)]
     return sh
+
+
+class RankPlan:
+    """what SspEngine.rank_plan wrote and rank_finish reads: the plan buffer and the shape it was written for (kept on the host, so that
+    rank_finish can size-check pred / assign against the plan without reading the device)"""
+
+    def __init__(self, buf, N, MV, n_sink, Q):
+        self.buf, self.N, self.MV, self.n_sink, self.Q = buf, N, MV, n_sink, Q
 
 
 class SspEngine:
@@ -159,6 +172,96 @@ class SspEngine:
             ws = self._workspace(self.lib.vsr_sinkhorn_workspace_bytes(Q, self.N))
             _lib.check(self.lib.vsr_sinkhorn_assign(self.h, _ptr(seq), Q, _ptr(tr), _ptr(assign), _ptr(ws), ws.numel(), self._stream()))
         return tr, assign
+
+    # ---- caption ranking on the device (include/vsrcap.h: vsr_rank_*)
+    RANK_L = 10
+
+    def _annotations(self, control_verb, det_seqs_v, det_seqs_sr):
+        """the three integer arrays as contiguous int32 GPU tensors.  Host arrays travel together in ONE non-blocking upload from pinned
+        memory; tensors are converted where they live.  Only shapes are checked: the values are judged on the device (status)."""
+        xs = [control_verb, det_seqs_v, det_seqs_sr]
+        if all(isinstance(x, torch.Tensor) for x in xs):
+            xs = [x.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous() for x in xs]
+        else:
+            host = [x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in xs]
+            stage = torch.empty(sum(h.size for h in host), dtype=torch.int32, pin_memory=True)
+            view, lo = stage.numpy(), 0
+            for h in host:
+                view[lo:lo + h.size] = h.reshape(-1)
+                lo += h.size
+            dev, lo, xs = stage.to(self.device, non_blocking=True), 0, []
+            for h in host:
+                xs.append(dev[lo:lo + h.size].view(h.shape))
+                lo += h.size
+        cv, dv, dsr = xs
+        if cv.dim() != 2 or dv.dim() != 3 or dsr.dim() != 3 or dv.size(0) != cv.size(0) or dv.size(2) != cv.size(1) or tuple(dsr.shape[:2]) != tuple(dv.shape[:2]) or cv.size(0) == 0:
+            raise RuntimeError("expected control_verb (N, MV), det_seqs_v (N, L, MV), det_seqs_sr (N, L, MS); got %s, %s, %s"
+                               % (tuple(cv.shape), tuple(dv.shape), tuple(dsr.shape)))
+        return cv, dv, dsr
+
+    def rank_plan(self, control_verb, det_seqs_v, det_seqs_sr, n_sink=None, n_verbs=None, max_items=None):
+        """the scan of vsr_rank_plan -> (plan, job_verbs (S,) int64, job_roles (S,10) int32, item_gather (max_items, n_sink) int32) with
+        S = N * MV padded job slots; n_sink / n_verbs default to the bound models'"""
+        cv, dv, dsr = self._annotations(control_verb, det_seqs_v, det_seqs_sr)
+        N, L, MV, MS = dv.size(0), dv.size(1), dv.size(2), dsr.size(2)
+        n_sink = self.N if n_sink is None else int(n_sink)
+        n_verbs = self._keep["ssp"]["v_embed_layer.weight"].shape[0] if n_verbs is None else int(n_verbs)
+        max_items = int(max_items or 0)
+        Q = max_items if max_items > 0 else N * MV * self.RANK_L
+        with torch.cuda.device(self.device):
+            plan = torch.empty(max(1, self.lib.vsr_rank_plan_bytes(N, MV, max_items)), dtype=torch.uint8, device=self.device)
+            job_verbs = torch.empty(N * MV, dtype=torch.int64, device=self.device)
+            job_roles = torch.empty(N * MV, self.RANK_L, dtype=torch.int32, device=self.device)
+            item_gather = torch.empty(Q, max(n_sink, 1), dtype=torch.int32, device=self.device)
+            _lib.check(self.lib.vsr_rank_plan(_ptr(cv), _ptr(dv), _ptr(dsr), N, L, MV, MS, n_sink, n_verbs, max_items, _ptr(job_verbs), _ptr(job_roles),
+                                              _ptr(item_gather), _ptr(plan), plan.numel(), self._stream()))
+        return RankPlan(plan, N, MV, n_sink, Q), job_verbs, job_roles, item_gather
+
+    def rank_finish(self, plan, pred, assign, N=None, MV=None, max_items=None):
+        """vsr_rank_finish: plan as rank_plan returned it, pred (N*MV, 10) and assign (max_items, n_sink) int32 on the GPU, as generate /
+        sinkhorn_assign write them (or a caller's own decisions) -> (rank (N,10) int32, status (N,) int32).  The kernel indexes assign with
+        the item bound stored in the plan, so the shapes are held to the plan's own (N, MV, n_sink, max_items); N / MV / max_items, when given,
+        must be the plan's."""
+        if not isinstance(plan, RankPlan):
+            raise RuntimeError("rank_finish: plan must be what rank_plan returned")
+        Q = plan.Q if max_items is None else (int(max_items) or plan.N * plan.MV * self.RANK_L)      # 0 = the static maximum, as in rank_plan
+        if (N is not None and N != plan.N) or (MV is not None and MV != plan.MV) or (max_items is not None and Q != plan.Q):
+            raise RuntimeError("rank_finish: the plan was written for N %d, MV %d, max_items %d" % (plan.N, plan.MV, plan.Q))
+        N, MV, Q = plan.N, plan.MV, plan.Q
+        for t, name in ((plan.buf, "plan"), (pred, "pred"), (assign, "assign")):
+            _need_gpu(t, name)
+        pred, assign = pred.to(torch.int32).contiguous(), assign.to(torch.int32).contiguous()
+        if tuple(pred.shape) != (N * MV, self.RANK_L) or tuple(assign.shape) != (Q, plan.n_sink):
+            raise RuntimeError("expected pred (%d, 10) and assign (%d, %d); got %s, %s" % (N * MV, Q, plan.n_sink, tuple(pred.shape), tuple(assign.shape)))
+        rank = torch.empty(N, self.RANK_L, dtype=torch.int32, device=self.device)
+        status = torch.empty(N, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vsr_rank_finish(_ptr(plan.buf), plan.buf.numel(), _ptr(pred), _ptr(assign), N, self.RANK_L, MV, plan.n_sink, _ptr(rank), _ptr(status),
+                                                self._stream()))
+        return rank, status
+
+    def rank_captions(self, control_verb, det_seqs_v, det_seqs_sr, seqs_perm, max_items=None):
+        """vsr_rank_captions: control_verb (N, MV), det_seqs_v (N, L, MV), det_seqs_sr (N, L, MS) ints (host arrays or tensors), seqs_perm
+        (N, L, 2352) fp32 on the GPU -> (rank (N, L) int32, status (N,) int32) on the GPU; nothing is read back.  status: 0 = ranked; bit 1 no
+        verb of the caption matches (the host path returns [] and the reference raises), 2 an item beyond max_items, 4 a role id outside
+        [0, 26), 8 a verb outside the verb table - such a caption's row is all -1.  max_items: None = the static maximum N * MV * 10."""
+        if "ssp" not in self._keep or "sinkhorn" not in self._keep:
+            raise RuntimeError("rank_captions needs the S_SSP and the SinkhornNet weights bound on ONE engine (bind_ssp and bind_sinkhorn)")
+        _need_gpu(seqs_perm, "seqs_perm")
+        cv, dv, dsr = self._annotations(control_verb, det_seqs_v, det_seqs_sr)
+        N, L, MV, MS = dv.size(0), dv.size(1), dv.size(2), dsr.size(2)
+        if tuple(seqs_perm.shape) != (N, L, 2352):
+            raise RuntimeError("expected seqs_perm (%d, %d, 2352); got %s" % (N, L, tuple(seqs_perm.shape)))
+        seqs_perm = seqs_perm.float().contiguous()
+        max_items = int(max_items or 0)
+        rank = torch.empty(N, L, dtype=torch.int32, device=self.device)
+        status = torch.empty(N, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            need = self.lib.vsr_rank_workspace_bytes(N, MV, max_items, self.N)
+            ws = self._workspace(max(need, 1))
+            _lib.check(self.lib.vsr_rank_captions(self.h, _ptr(cv), _ptr(dv), _ptr(dsr), N, L, MV, MS, self.N, self._keep["ssp"]["v_embed_layer.weight"].shape[0],
+                                                  _ptr(seqs_perm), max_items, _ptr(rank), _ptr(status), _ptr(ws), need, self._stream()))
+        return rank, status
 
     # ---- SinkhornNet training (include/vsrcap.h: vsr_sinkhorn_train_*, vsr_sinkhorn_loc_loss)
     def _check_seq(self, seq):

@@ -279,3 +279,24 @@ def make_sinkhorn_inputs(Q, seed=0, N=10):
     for q in range(Q):
         x[q, n[q]:] = 0
     return x, n
+
+
+def make_rank_batch(N, MV, seed, L=10):
+    """A loader batch for the eval loop's caption ranking: (control_verb (N, MV), det_seqs_v (N, L, MV), det_seqs_sr (N, L, MV) int64,
+    feats (N, L, 2352) fp32).  Every caption has 1..MV verbs, 3..L filled slots that each serve some of its verbs once, and role ids in
+    [1, 7) - few distinct roles, so repeated roles (Sinkhorn items) are common.  The generator of tests/test_gpu_ssp.py's rank_captions test."""
+    rng = np.random.RandomState(seed)
+    control_verb = np.zeros((N, MV), dtype=np.int64)
+    det_seqs_v = np.zeros((N, L, MV), dtype=np.int64)
+    det_seqs_sr = np.zeros((N, L, MV), dtype=np.int64)
+    for n in range(N):
+        nv = rng.randint(1, MV + 1)
+        control_verb[n, :nv] = rng.choice(np.arange(1, 2600), nv, replace=False)
+        for j in range(rng.randint(3, L + 1)):
+            vs = rng.permutation(control_verb[n, :nv])[:rng.randint(1, nv + 1)]     # a slot serves each verb at most once
+            for k, v in enumerate(vs):
+                det_seqs_v[n, j, k] = v
+                det_seqs_sr[n, j, k] = rng.randint(1, 7)
+    feats, _ = make_sinkhorn_inputs(N, 7)
+    feats[:] = np.abs(hash_u01(feats.size, 77, 7).reshape(feats.shape).astype(np.float32))
+    return control_verb, det_seqs_v, det_seqs_sr, feats
