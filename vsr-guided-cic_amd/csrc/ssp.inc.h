@@ -67,36 +67,90 @@ extern "C" size_t vsr_ssp_workspace_bytes(int32_t S) {
     return carve_ssp(S, nullptr, w);
 }
 
-// out (M, N) = act(A (M, K) . W (N, K)^T + bias) (+ residual); up to three products of the same A in one launch
-struct LinSpec { const float* W; const float* bias; int N; float* out; int act; const float* residual; };
-static int linear_n(vsr_ssp* e, SspWs& ws, hipStream_t s, int M, int K, const float* A, int lda, const LinSpec* sp, int n) {
+// ---------------------------------------------------------------------------------------------- the dense products
+// The ONE product path of this file: inference, SinkhornNet's and S-SSP's training passes describe each product as an SspProd and hand
+// it to run_products.  out (M, N) = epilogue(sum over the k segments of A_i (M, K_i) . W_i (N, K_i)^T) on the exact fp32 kernels.
+// The epilogue (k_prod_finish), every term optional, in THIS order:
+//   + bias[n]
+//   act         SSP_ACT_RELU: max(., 0), SSP_ACT_TANH
+//   keep        (M N bytes, compact) dropout: keep ? . scale : 0 - the forward's site, or in the backward the site of the tensor whose
+//               gradient this is
+//   relu_y      backward through relu + dropout in one: the taped y = drop(relu(.)) is > 0 exactly where both let the gradient pass, and
+//               the factor there is scale (1: a ReLU without dropout)
+//   + residual  (may be out's buffer: accumulation)
+// A product has keep or relu_y, never both.  Which terms a product has selects the instance of the finish kernel (ssp_kernels.h).
+// ldo / ldy / ldr: the leading dimensions of out / relu_y / residual, 0 = N (compact).
+// in_place: where no tile of the launch is split (one slab) the GEMM writes `out` itself and no finish kernel runs.  Refused for a product
+// with an epilogue term, and meant only where the results have always been produced that way: the finish kernel's sum of ONE slab is 0.f + v,
+// which turns a -0 into +0, and the in-place write does not.
+struct SspSeg { const float* A; int lda; const float* W; int ldw; int K; };
+struct SspProd {
+    int M, N;
+    SspSeg seg[3];
+    int nseg;
+    float* out; int ldo;
+    const float* bias; int act; const uint8_t* keep; const float* relu_y; int ldy; const float* residual; int ldr;
+    bool in_place;
+};
+// what a pass gives all its products.  scale = 1 / (1 - p): the forward gives it, the backward the tape's header (hdr) that carries it.
+struct SspRun { vsr_ssp* e; hipStream_t s; float* scratch; size_t scratch_floats; const int* hdr; float scale; const char* pass; };
+static SspProd ssp_prod1(int M, int N, int K, const float* A, int lda, const float* W, int ldw, float* out, int ldo = 0) {
+    SspProd p{};
+    p.M = M; p.N = N; p.seg[0] = SspSeg{A, lda, W, ldw, K}; p.nseg = 1; p.out = out; p.ldo = ldo;
+    return p;
+}
+// a layer of a forward pass: out = act(A W^T + bias) (+ residual), W (N, K) compact
+static SspProd lin(int M, int N, int K, const float* A, int lda, const float* W, const float* bias, float* out, int act = SSP_ACT_NONE,
+                   const float* residual = nullptr) {
+    SspProd p = ssp_prod1(M, N, K, A, lda, W, K, out);
+    p.bias = bias; p.act = act; p.residual = residual;
+    return p;
+}
+// Up to four products in ONE launch.  Problems and segments go to the GEMM in the order given (it numbers the tiles and fixes the summation
+// order, step_gemms.h); every problem gets the launch's ns slabs in the scratch, then each product its finish kernel.
+static int run_products(const SspRun& c, const SspProd* P, int n) {
     GemmBuilder g;
+    bool in_place = true;
+    for (int i = 0; i < n; ++i) {
+        GemmProb& p = g.prob(P[i].M, P[i].N, nullptr, P[i].N);
+        for (int k = 0; k < P[i].nseg; ++k) {
+            const SspSeg& sg = P[i].seg[k];
+            if ((sg.K & 3) || (sg.lda & 3) || (sg.ldw & 3) || !aligned16(sg.A) || !aligned16(sg.W))
+                return fail("%s: operand not in whole 16-byte groups (K %d, lda %d, ldw %d)", c.pass, sg.K, sg.lda, sg.ldw);
+            GemmBuilder::seg(p, sg.A, sg.lda, nullptr, sg.W, sg.ldw, sg.K);
+        }
+        if (P[i].in_place && (P[i].bias || P[i].act != SSP_ACT_NONE || P[i].keep || P[i].relu_y || P[i].residual))
+            return fail("%s: an in-place product cannot have an epilogue", c.pass);
+        if (P[i].keep && P[i].relu_y) return fail("%s: a product has keep or relu_y, not both", c.pass);
+        in_place = in_place && P[i].in_place;
+    }
+    const int ns = g.finish(&c.e->cfg);
+    auto ld = [&](int i, int l) { return (long long)(l ? l : P[i].N); };
+    if (ns == 1 && in_place) {                    // every tile is produced by one workgroup: written in place
+        for (int i = 0; i < n; ++i) { g.a.p[i].C = P[i].out; g.a.p[i].ldc = (int)ld(i, P[i].ldo); g.a.p[i].slab_stride = 0; }
+        if (g.launch(c.s, &c.e->cfg)) return fail("%s: gemm launch failed", c.pass);
+        return 0;
+    }
     size_t off = 0;
-    int ns = 0;
     for (int i = 0; i < n; ++i) {
-        GemmProb& p = g.prob(M, sp[i].N, nullptr, sp[i].N);
-        GemmBuilder::seg(p, A, lda, nullptr, sp[i].W, K, K);
+        g.a.p[i].C = c.scratch + off;
+        g.a.p[i].slab_stride = (long long)P[i].M * P[i].N;
+        off += (size_t)P[i].M * P[i].N * ns;
     }
-    ns = g.finish(&e->cfg);
+    if (off > c.scratch_floats) return fail("%s: GEMM scratch too small", c.pass);
+    if (g.launch(c.s, &c.e->cfg)) return fail("%s: gemm launch failed", c.pass);
     for (int i = 0; i < n; ++i) {
-        g.a.p[i].C = ws.scratch + off;
-        g.a.p[i].slab_stride = (long long)M * sp[i].N;
-        off += (size_t)M * sp[i].N * ns;
-    }
-    if (off > ws.scratch_floats) return fail("ssp: GEMM scratch too small");
-    if (g.launch(s, &e->cfg)) return fail("ssp: gemm launch failed");
-    for (int i = 0; i < n; ++i) {
-        const long long tot = (long long)M * sp[i].N;
-        hipLaunchKernelGGL(k_linear_finish, dim3(cdiv(tot, 256)), dim3(256), 0, s, g.a.p[i].C, ns, tot, M, sp[i].N, sp[i].bias, sp[i].act,
-                           sp[i].residual, (long long)sp[i].N, sp[i].out, (long long)sp[i].N);
+        const SspProd& p = P[i];
+        const long long tot = (long long)p.M * p.N;
+        const bool lin = p.bias || p.act != SSP_ACT_NONE || p.residual;
+        auto finish = !p.keep && !p.relu_y ? (lin ? k_prod_finish<true, FIN_NONE> : k_prod_finish<false, FIN_NONE>)
+                                           : (p.keep ? k_prod_finish<true, FIN_KEEP> : k_prod_finish<true, FIN_RELU_Y>);
+        hipLaunchKernelGGL(finish, dim3(cdiv(tot, 256)), dim3(256), 0, c.s, g.a.p[i].C, ns, tot, p.M, p.N, p.bias, p.act, p.residual, ld(i, p.ldr), p.out,
+                           ld(i, p.ldo), p.keep ? (const void*)p.keep : (const void*)p.relu_y, ld(i, p.ldy), c.hdr, c.scale);
     }
     return 0;
 }
-static int linear1(vsr_ssp* e, SspWs& ws, hipStream_t s, int M, int N, int K, const float* A, int lda, const float* W, const float* bias, int act,
-                   const float* residual, float* out) {
-    LinSpec sp{W, bias, N, out, act, residual};
-    return linear_n(e, ws, s, M, K, A, lda, &sp, 1);
-}
+static int run_product(const SspRun& c, const SspProd& p) { return run_products(c, &p, 1); }
 static void layernorm(hipStream_t s, const float* x, const float* w, const float* b, int rows, float* out) {
     hipLaunchKernelGGL(k_layernorm512, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, out);
 }
@@ -114,29 +168,33 @@ extern "C" int vsr_ssp_generate(vsr_ssp* e, const int64_t* verbs, const int32_t*
     hipStream_t s = (hipStream_t)stream;
     const vsr_ssp_weights& w = e->w;
     const int H = SSP_H, L = SSP_LEN;
+    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "ssp"};
+    auto qkv = [&](const vsr_ssp_layer& ly, int R) {              // the three projections of the layer's input (in ws.y) in one launch
+        SspProd p[3] = {lin(R, H, H, ws.y, H, ly.Wq, ly.bq, ws.q), lin(R, H, H, ws.y, H, ly.Wk, ly.bk, ws.k), lin(R, H, H, ws.y, H, ly.Wv, ly.bv, ws.v)};
+        return run_products(run, p, 3);
+    };
     HIPCHK(hipMemsetAsync(ws.bad, 0, 4 * sizeof(int), s));
     hipLaunchKernelGGL(k_ssp_init, dim3(cdiv(S * (L + 1), 256)), dim3(256), 0, s, roles, S, ws.remain, ws.tokens, pred, logp, ws.bad);
     // ---- encoder (sort_modules.py:50-62): embeddings -> fc_feat -> 3 pre-LN layers -> LN
     int R = S * L;
     hipLaunchKernelGGL(k_ssp_embed, dim3(R), dim3(128), 0, s, roles, L, L, w.sr_embed, verbs, w.v_embed, w.n_verbs, S, ws.y, ws.bad);
-    if (linear1(e, ws, s, R, H, H, ws.y, H, w.fc_w, w.fc_b, 0, nullptr, ws.x)) return 1;
+    if (run_product(run, lin(R, H, H, ws.y, H, w.fc_w, w.fc_b, ws.x))) return 1;
     for (int l = 0; l < 3; ++l) {
         const vsr_ssp_layer& ly = w.enc[l];
         layernorm(s, ws.x, ly.ln1_w, ly.ln1_b, R, ws.y);
-        LinSpec qkv[3] = {{ly.Wq, ly.bq, H, ws.q, 0, nullptr}, {ly.Wk, ly.bk, H, ws.k, 0, nullptr}, {ly.Wv, ly.bv, H, ws.v, 0, nullptr}};
-        if (linear_n(e, ws, s, R, H, ws.y, H, qkv, 3)) return 1;
+        if (qkv(ly, R)) return 1;
         hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, s, ws.q, ws.k, ws.v, L, L, (const int*)nullptr, 0, ws.ctx);
-        if (linear1(e, ws, s, R, H, H, ws.ctx, H, ly.Wo, ly.bo, 0, ws.x, ws.x1)) return 1;
+        if (run_product(run, lin(R, H, H, ws.ctx, H, ly.Wo, ly.bo, ws.x1, SSP_ACT_NONE, ws.x))) return 1;
         layernorm(s, ws.x1, ly.ln2_w, ly.ln2_b, R, ws.y);
-        if (linear1(e, ws, s, R, SSP_FF, H, ws.y, H, ly.W1, ly.b1, 1, nullptr, ws.ff)) return 1;
-        if (linear1(e, ws, s, R, H, SSP_FF, ws.ff, SSP_FF, ly.W2, ly.b2, 0, ws.x1, ws.x)) return 1;
+        if (run_product(run, lin(R, SSP_FF, H, ws.y, H, ly.W1, ly.b1, ws.ff, SSP_ACT_RELU))) return 1;
+        if (run_product(run, lin(R, H, SSP_FF, ws.ff, SSP_FF, ly.W2, ly.b2, ws.x, SSP_ACT_NONE, ws.x1))) return 1;
     }
     layernorm(s, ws.x, w.enc_ln_w, w.enc_ln_b, R, ws.prior);
     // keys / values of the cross attention: prior states through each decoder layer's (self-)attention K / V projections,
     // constant over the decode steps (sort_modules.py:88 re-uses self.attention for the cross attention)
     for (int l = 0; l < 3; ++l) {
-        LinSpec kv[2] = {{w.dec[l].Wk, w.dec[l].bk, H, ws.pk[l], 0, nullptr}, {w.dec[l].Wv, w.dec[l].bv, H, ws.pv[l], 0, nullptr}};
-        if (linear_n(e, ws, s, R, H, ws.prior, H, kv, 2)) return 1;
+        SspProd kv[2] = {lin(R, H, H, ws.prior, H, w.dec[l].Wk, w.dec[l].bk, ws.pk[l]), lin(R, H, H, ws.prior, H, w.dec[l].Wv, w.dec[l].bv, ws.pv[l])};
+        if (run_products(run, kv, 2)) return 1;
     }
     LAUNCHCHK();
     // ---- decoder: step t re-runs the stack on [bos, picks 0..t-1] as the reference does (:154-160) and picks among the remaining roles
@@ -148,71 +206,74 @@ extern "C" int vsr_ssp_generate(vsr_ssp* e, const int64_t* verbs, const int32_t*
         for (int l = 0; l < 3; ++l) {
             const vsr_ssp_layer& ly = w.dec[l];
             layernorm(s, ws.x, ly.ln1_w, ly.ln1_b, R, ws.y);
-            LinSpec qkv[3] = {{ly.Wq, ly.bq, H, ws.q, 0, nullptr}, {ly.Wk, ly.bk, H, ws.k, 0, nullptr}, {ly.Wv, ly.bv, H, ws.v, 0, nullptr}};
-            if (linear_n(e, ws, s, R, H, ws.y, H, qkv, 3)) return 1;
+            if (qkv(ly, R)) return 1;
             hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, s, ws.q, ws.k, ws.v, T, T, ws.tokens, L + 1, ws.ctx);
-            if (linear1(e, ws, s, R, H, H, ws.ctx, H, ly.Wo, ly.bo, 0, ws.x, ws.x1)) return 1;            // h1 = attn + x
+            if (run_product(run, lin(R, H, H, ws.ctx, H, ly.Wo, ly.bo, ws.x1, SSP_ACT_NONE, ws.x))) return 1;            // h1 = attn + x
             layernorm(s, ws.x1, ly.ln2_w, ly.ln2_b, R, ws.y);
-            if (linear1(e, ws, s, R, H, H, ws.y, H, ly.Wq, ly.bq, 0, nullptr, ws.q)) return 1;
+            if (run_product(run, lin(R, H, H, ws.y, H, ly.Wq, ly.bq, ws.q))) return 1;
             hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, s, ws.q, ws.pk[l], ws.pv[l], T, L, (const int*)nullptr, 0, ws.ctx);
-            if (linear1(e, ws, s, R, H, H, ws.ctx, H, ly.Wo, ly.bo, 0, ws.x1, ws.x)) return 1;            // h2 = cross + h1   (in ws.x)
+            if (run_product(run, lin(R, H, H, ws.ctx, H, ly.Wo, ly.bo, ws.x, SSP_ACT_NONE, ws.x1))) return 1;            // h2 = cross + h1   (in ws.x)
             layernorm(s, ws.x, ly.ln3_w, ly.ln3_b, R, ws.y);
-            if (linear1(e, ws, s, R, SSP_FF, H, ws.y, H, ly.W1, ly.b1, 1, nullptr, ws.ff)) return 1;
-            if (linear1(e, ws, s, R, H, SSP_FF, ws.ff, SSP_FF, ly.W2, ly.b2, 0, ws.x, ws.x1)) return 1;    // h3 = ff + h2      (in ws.x1)
+            if (run_product(run, lin(R, SSP_FF, H, ws.y, H, ly.W1, ly.b1, ws.ff, SSP_ACT_RELU))) return 1;
+            if (run_product(run, lin(R, H, SSP_FF, ws.ff, SSP_FF, ly.W2, ly.b2, ws.x1, SSP_ACT_NONE, ws.x))) return 1;    // h3 = ff + h2      (in ws.x1)
             std::swap(ws.x, ws.x1);
         }
         hipLaunchKernelGGL(k_ssp_last, dim3(S), dim3(128), 0, s, ws.x, T, ws.last);
         layernorm(s, ws.last, w.dec_ln_w, w.dec_ln_b, S, ws.y);
-        if (linear1(e, ws, s, S, SSP_ROLES, H, ws.y, H, w.exp_w, w.exp_b, 0, nullptr, ws.logits)) return 1;
+        if (run_product(run, lin(S, SSP_ROLES, H, ws.y, H, w.exp_w, w.exp_b, ws.logits))) return 1;
         hipLaunchKernelGGL(k_ssp_select, dim3(S), dim3(64), 0, s, ws.logits, roles, ws.remain, t, S, ws.tokens, pred, logp);
         LAUNCHCHK();
     }
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- SinkhornNet
+// The outputs of SinkhornNet's five layers and of k_sh_cat for R = Q N rows: t1 (R, 128), v1 (R, 512), v2 (R, 128), cat (R, 260), f1 (R, 256),
+// th (R, N; tanh applied).  The training tape keeps them; inference only passes through them.
+struct ShActs { float *t1, *v1, *v2, *cat, *f1, *th; };
+static void carve_sh_acts(Bump& b, size_t R, int N, ShActs& a) {
+    a.t1 = b.take<float>(R * 128); a.v1 = b.take<float>(R * 512); a.v2 = b.take<float>(R * 128); a.cat = b.take<float>(R * 260);
+    a.f1 = b.take<float>(R * 256); a.th = b.take<float>(R * N);
+}
+struct ShWs { ShActs a; float* scratch; size_t scratch_floats; };
+static size_t carve_sh_ws(int Q, int N, char* base, ShWs& w) {
+    const size_t R = (size_t)Q * N;
+    Bump b{base};
+    carve_sh_acts(b, R, N, w.a);
+    w.scratch_floats = R * 512 * 8;
+    w.scratch = b.take<float>(w.scratch_floats);
+    return (b.off + 255) & ~size_t(255);
+}
+extern "C" size_t vsr_sinkhorn_workspace_bytes(int32_t Q, int32_t N) {
+    if (Q <= 0 || N <= 0) return 0;
+    ShWs w;
+    return carve_sh_ws(Q, N, nullptr, w);
+}
+// The five layers of SinkhornNet for Q items: seq (Q, N, 2352) -> a.th (Q, N, N).  The ONE forward of vsr_sinkhorn_assign, vsr_rank_captions
+// and vsr_sinkhorn_train_forward: with the Sinkhorn arithmetic they also share (sinkhorn_normalise), the training forward's tr has assign's bits.
+static int sinkhorn_layers(const SspRun& c, const float* seq, int Q, const ShActs& a) {
+    const vsr_sinkhorn_weights& w = c.e->sw;
+    const int N = w.N, R = Q * N;
+    if (run_product(c, lin(R, 128, 300, seq, SH_ROW, w.W1_txt_w, w.W1_txt_b, a.t1, SSP_ACT_RELU))) return 1;
+    if (run_product(c, lin(R, 512, 2048, seq + 300, SH_ROW, w.W1_vis_w, w.W1_vis_b, a.v1, SSP_ACT_RELU))) return 1;
+    if (run_product(c, lin(R, 128, 512, a.v1, 512, w.W2_vis_w, w.W2_vis_b, a.v2, SSP_ACT_RELU))) return 1;
+    hipLaunchKernelGGL(k_sh_cat, dim3(cdiv((long long)R * 260, 256)), dim3(256), 0, c.s, a.t1, a.v2, seq, R, a.cat);
+    if (run_product(c, lin(R, 256, 260, a.cat, 260, w.W_fc_pos_w, w.W_fc_pos_b, a.f1, SSP_ACT_RELU))) return 1;
+    return run_product(c, lin(R, N, 256, a.f1, 256, w.W_fc_w, w.W_fc_b, a.th, SSP_ACT_TANH));
+}
 // SinkhornNet.forward (sinkhorn_network.py:39-51) + the assignment of eval_coco.py:185-189 for Q items at once.
 //   seq (Q, N, 2352) fp32 rows [300 | 2048 | 4]; tr (Q, N, N) fp32 or NULL: the doubly-normalised matrix; assign (Q, N) int32:
 //   assign[q][i] = column chosen for row i of tr[q]^T (the munkres result "(i, assign)" of :187).
-extern "C" size_t vsr_sinkhorn_workspace_bytes(int32_t Q, int32_t N) {
-    if (Q <= 0 || N <= 0) return 0;
-    const size_t R = (size_t)Q * N;
-    return (R * (128 + 512 + 128 + 260 + 256 + 16) + R * 512 * 8 + 1024) * sizeof(float);
-}
-// The five layers of SinkhornNet for Q items: seq (Q, N, 2352) -> (Q, N, N), tanh applied, into fc_out or (fc_out NULL) into the workspace's
-// own slot; *fc_used is where it went.  workspace: vsr_sinkhorn_workspace_bytes(Q, N), checked by the caller.
-static int sinkhorn_mlp(vsr_ssp* e, const float* seq, int Q, void* workspace, hipStream_t s, float* fc_out, float** fc_used) {
-    const vsr_sinkhorn_weights& w = e->sw;
-    const int N = w.N, R = Q * N;
-    Bump b{reinterpret_cast<char*>(workspace)};
-    float* t1 = b.take<float>((size_t)R * 128);
-    float* v1 = b.take<float>((size_t)R * 512);
-    float* v2 = b.take<float>((size_t)R * 128);
-    float* cat = b.take<float>((size_t)R * 260);
-    float* f1 = b.take<float>((size_t)R * 256);
-    float* fc = b.take<float>((size_t)R * 16);
-    if (fc_out) fc = fc_out;
-    SspWs ws{};
-    ws.scratch_floats = (size_t)R * 512 * 8;
-    ws.scratch = b.take<float>(ws.scratch_floats);
-    if (linear1(e, ws, s, R, 128, 300, seq, 2352, w.W1_txt_w, w.W1_txt_b, 1, nullptr, t1)) return 1;
-    if (linear1(e, ws, s, R, 512, 2048, seq + 300, 2352, w.W1_vis_w, w.W1_vis_b, 1, nullptr, v1)) return 1;
-    if (linear1(e, ws, s, R, 128, 512, v1, 512, w.W2_vis_w, w.W2_vis_b, 1, nullptr, v2)) return 1;
-    hipLaunchKernelGGL(k_sh_cat, dim3(cdiv((long long)R * 260, 256)), dim3(256), 0, s, t1, v2, seq, R, cat);
-    if (linear1(e, ws, s, R, 256, 260, cat, 260, w.W_fc_pos_w, w.W_fc_pos_b, 1, nullptr, f1)) return 1;
-    if (linear1(e, ws, s, R, N, 256, f1, 256, w.W_fc_w, w.W_fc_b, 2, nullptr, fc)) return 1;
-    *fc_used = fc;
-    return 0;
-}
 extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, float* tr, int32_t* assign, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     if (!e || !e->has_sh) return fail("vsr_sinkhorn_assign: Sinkhorn weights not bound");
     if (!seq || !assign || !workspace || Q <= 0) return fail("vsr_sinkhorn_assign: bad arguments");
     const vsr_sinkhorn_weights& w = e->sw;
-    if (workspace_bytes < vsr_sinkhorn_workspace_bytes(Q, w.N)) return fail("vsr_sinkhorn_assign: workspace too small");
+    ShWs ws;
+    if (carve_sh_ws(Q, w.N, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_sinkhorn_assign: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    float* fc = nullptr;
-    if (sinkhorn_mlp(e, seq, Q, workspace, s, nullptr, &fc)) return 1;
-    hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Q), dim3(64), 0, s, fc, w.N, w.n_iters, w.tau, tr, assign);
+    if (sinkhorn_layers(SspRun{e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "sinkhorn forward"}, seq, Q, ws.a)) return 1;
+    hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Q), dim3(64), 0, s, ws.a.th, w.N, w.n_iters, w.tau, tr, assign);
     LAUNCHCHK();
     return 0;
 }
@@ -220,8 +281,8 @@ extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, floa
 // ---------------------------------------------------------------------------------------------- SinkhornNet training
 // coco_scripts/train_sinkhorn.py:137-215 calls the net once per (image, caption, verb, repeated role) at batch size 1 and adds the
 // losses on the host; here ONE forward, ONE fused location loss and ONE backward serve all Q items of a loader batch.
-//   forward   the five linear1 products, k_sh_cat and the Sinkhorn arithmetic of vsr_sinkhorn_assign in the same order (tr is
-//             bit-identical to assign's), outputs written into the caller's TAPE; no assignment
+//   forward   sinkhorn_layers and the Sinkhorn arithmetic of vsr_sinkhorn_assign (tr is bit-identical to assign's), the layers' outputs
+//             written into the caller's TAPE; no assignment
 //   backward  k_sinkhorn_bwd (ssp_kernels.h: the divisor tape), then the five layers: ReLU masks from the taped outputs, bias
 //             gradients by the ordered column sums of the decoder's training pass (k_colsum), dW = dY^T X and dX = dY W as NT
 //             products on transposed copies (k_transpose_multi), all on the exact fp32 kernels.  No gradient flows to seq, so
@@ -236,13 +297,13 @@ extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, floa
 // send it out of bounds).
 constexpr int SH_TRAIN_MAX_ITERS = 64;
 
-struct ShTape { int* hdr; float *t1, *v1, *v2, *cat, *f1, *th, *tr, *div; };
+struct ShTape { int* hdr; ShActs a; float *tr, *div; };
 static size_t carve_sh_tape(int Q, int N, char* base, ShTape& t) {
     const size_t R = (size_t)Q * N;
     Bump b{base};
     t.hdr = b.take<int>(SH_TAPE_HDR_INTS);
-    t.t1 = b.take<float>(R * 128); t.v1 = b.take<float>(R * 512); t.v2 = b.take<float>(R * 128); t.cat = b.take<float>(R * 260);
-    t.f1 = b.take<float>(R * 256); t.th = b.take<float>(R * N); t.tr = b.take<float>(R * N);
+    carve_sh_acts(b, R, N, t.a);
+    t.tr = b.take<float>(R * N);
     t.div = b.take<float>((size_t)Q * 2 * SH_TRAIN_MAX_ITERS * N);
     return (b.off + 255) & ~size_t(255);
 }
@@ -282,23 +343,15 @@ extern "C" int vsr_sinkhorn_train_forward(vsr_ssp* e, const float* seq, int32_t 
     if (!seq || !tr || !tape || !workspace || Q <= 0) return fail("vsr_sinkhorn_train_forward: bad arguments");
     const vsr_sinkhorn_weights& w = e->sw;
     if (w.n_iters > SH_TRAIN_MAX_ITERS) return fail("vsr_sinkhorn_train_forward: n_iters %d exceeds the training cap of %d (the tape's divisor rows)", w.n_iters, SH_TRAIN_MAX_ITERS);
-    const int N = w.N, R = Q * N;
+    const int N = w.N;
     if ((long long)Q * N * 2352 > INT_MAX) return fail("vsr_sinkhorn_train_forward: Q %d too large", Q);
     ShTape t;
     ShTrainWs tw;
     if (carve_sh_tape(Q, N, reinterpret_cast<char*>(tape), t) > tape_bytes) return fail("vsr_sinkhorn_train_forward: tape too small");
     if (carve_sh_train(Q, N, reinterpret_cast<char*>(workspace), tw) > workspace_bytes) return fail("vsr_sinkhorn_train_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    SspWs ws{};
-    ws.scratch = tw.scratch;
-    ws.scratch_floats = tw.scratch_floats;
-    if (linear1(e, ws, s, R, 128, 300, seq, 2352, w.W1_txt_w, w.W1_txt_b, 1, nullptr, t.t1)) return 1;
-    if (linear1(e, ws, s, R, 512, 2048, seq + 300, 2352, w.W1_vis_w, w.W1_vis_b, 1, nullptr, t.v1)) return 1;
-    if (linear1(e, ws, s, R, 128, 512, t.v1, 512, w.W2_vis_w, w.W2_vis_b, 1, nullptr, t.v2)) return 1;
-    hipLaunchKernelGGL(k_sh_cat, dim3(cdiv((long long)R * 260, 256)), dim3(256), 0, s, t.t1, t.v2, seq, R, t.cat);
-    if (linear1(e, ws, s, R, 256, 260, t.cat, 260, w.W_fc_pos_w, w.W_fc_pos_b, 1, nullptr, t.f1)) return 1;
-    if (linear1(e, ws, s, R, N, 256, t.f1, 256, w.W_fc_w, w.W_fc_b, 2, nullptr, t.th)) return 1;
-    hipLaunchKernelGGL(k_sinkhorn_train_fwd, dim3(Q), dim3(64), 0, s, t.th, N, w.n_iters, w.tau, tr, t.tr, t.div, t.hdr);
+    if (sinkhorn_layers(SspRun{e, s, tw.scratch, tw.scratch_floats, nullptr, 1.f, "sinkhorn forward"}, seq, Q, t.a)) return 1;
+    hipLaunchKernelGGL(k_sinkhorn_train_fwd, dim3(Q), dim3(64), 0, s, t.a.th, N, w.n_iters, w.tau, tr, t.tr, t.div, t.hdr);
     LAUNCHCHK();
     return 0;
 }
@@ -309,33 +362,6 @@ extern "C" int vsr_sinkhorn_loc_loss(const float* tr, const float* tr_locs, cons
     hipLaunchKernelGGL(k_sinkhorn_loc_loss, dim3(Q), dim3(64), 0, (hipStream_t)stream, tr, tr_locs, gt_locs, N, scale, loss_items, d_tr);
     LAUNCHCHK();
     return 0;
-}
-
-// dst (M, N; leading dimension ldd) = A (M, K) . W (N, K)^T on the exact fp32 kernels; relu_y: masked by the ReLU whose output it is
-static int sh_product(vsr_ssp* e, ShTrainWs& ws, hipStream_t s, int M, int N, int K, const float* A, int lda, const float* W, int ldw, float* dst,
-                      int ldd, const float* relu_y = nullptr, int ldy = 0) {
-    if ((K & 3) || (lda & 3) || (ldw & 3) || !aligned16(A) || !aligned16(W)) return fail("sinkhorn backward: operand not in whole 16-byte groups (K %d, lda %d, ldw %d)", K, lda, ldw);
-    GemmBuilder g;
-    GemmProb& p = g.prob(M, N, nullptr, N);
-    GemmBuilder::seg(p, A, lda, nullptr, W, ldw, K);
-    const int ns = g.finish(&e->cfg);
-    if (ns == 1 && !relu_y) {                     // every tile is produced by one workgroup: written in place
-        g.a.p[0].C = dst; g.a.p[0].ldc = ldd; g.a.p[0].slab_stride = 0;
-        if (g.launch(s, &e->cfg)) return fail("sinkhorn backward: gemm launch failed");
-        return 0;
-    }
-    const long long tot = (long long)M * N;
-    if ((size_t)tot * ns > ws.scratch_floats) return fail("sinkhorn backward: GEMM scratch too small");
-    g.a.p[0].C = ws.scratch; g.a.p[0].slab_stride = tot;
-    if (g.launch(s, &e->cfg)) return fail("sinkhorn backward: gemm launch failed");
-    if (relu_y) hipLaunchKernelGGL(k_relu_bwd_finish, dim3(cdiv(tot, 256)), dim3(256), 0, s, ws.scratch, ns, tot, M, N, relu_y, (long long)ldy, dst, (long long)ldd);
-    else hipLaunchKernelGGL(k_slab_reduce_2d, dim3(cdiv(tot, 256)), dim3(256), 0, s, ws.scratch, ns, tot, M, N, dst, (long long)ldd);
-    return 0;
-}
-// out[c] = sum over rows of X[r][c], in the fixed order of k_colsum / k_colsum_finish, through the (idle) slab scratch
-static void sh_colsum(ShTrainWs& ws, hipStream_t s, const float* X, long long ld, int R, int C, float* out) {
-    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, ld, R, C, ws.scratch);
-    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, ws.scratch, C, 0, C, out, (float*)nullptr);
 }
 
 extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t Q, const void* tape, size_t tape_bytes, const float* d_tr,
@@ -352,7 +378,15 @@ extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t
     if (carve_sh_tape(Q, N, reinterpret_cast<char*>(const_cast<void*>(tape)), t) > tape_bytes) return fail("vsr_sinkhorn_train_backward: tape too small");
     if (carve_sh_train(Q, N, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_sinkhorn_train_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_sinkhorn_bwd, dim3(Q), dim3(64), 0, s, t.hdr, SH_TRAIN_MAX_ITERS, t.tr, t.div, t.th, d_tr, N, ws.dpre, Np);
+    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "sinkhorn backward"};
+    // dst (m, n; leading dimension ldd) = A (m, k) . W (n, k)^T; relu_y: masked by the ReLU whose output it is.  The unmasked ones have
+    // no epilogue and are written in place where no tile is split.
+    auto product = [&](int m, int n, int k, const float* A, int lda, const float* W, int ldw, float* dst, int ldd, const float* relu_y = nullptr, int ldy = 0) {
+        SspProd p = ssp_prod1(m, n, k, A, lda, W, ldw, dst, ldd);
+        p.relu_y = relu_y; p.ldy = ldy; p.in_place = !relu_y;
+        return run_product(run, p);
+    };
+    hipLaunchKernelGGL(k_sinkhorn_bwd, dim3(Q), dim3(64), 0, s, t.hdr, SH_TRAIN_MAX_ITERS, t.tr, t.div, t.a.th, d_tr, N, ws.dpre, Np);
     // everything that can be transposed before the first product: the three weights, the taped activations, the input's two column blocks
     TransBatch tb;
     auto tr_add = [&](const float* in, long long ld_in, int rows, int cols, float* out, long long ld_out) { tb.add(s, 0, nullptr, in, ld_in, rows, cols, out, ld_out, nullptr, 0); };
@@ -360,36 +394,36 @@ extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t
     tr_add(w.W_fc_pos_w, 260, 256, 260, ws.wposT, 256);
     tr_add(w.W2_vis_w, 512, 128, 512, ws.w2T, 128);
     tr_add(ws.dpre, Np, R, N, ws.dpreT, Rp);
-    tr_add(t.f1, 256, R, 256, ws.f1T, Rp);
-    tr_add(t.cat, 260, R, 260, ws.catT, Rp);
+    tr_add(t.a.f1, 256, R, 256, ws.f1T, Rp);
+    tr_add(t.a.cat, 260, R, 260, ws.catT, Rp);
     tr_add(seq, 2352, R, 300, ws.txtT, Rp);
-    tr_add(t.v1, 512, R, 512, ws.v1T, Rp);
+    tr_add(t.a.v1, 512, R, 512, ws.v1T, Rp);
     tr_add(seq + 300, 2352, R, 2048, ws.visT, Rp);
     tb.flush(s);
     // W_fc
-    sh_colsum(ws, s, ws.dpre, Np, R, N, g->W_fc_b);
-    if (sh_product(e, ws, s, N, 256, Rp, ws.dpreT, Rp, ws.f1T, Rp, g->W_fc_w, 256)) return 1;
-    if (sh_product(e, ws, s, R, 256, Np, ws.dpre, Np, ws.wfcT, Np, ws.df1, 256, t.f1, 256)) return 1;
+    colsum(s, ws.scratch, ws.dpre, Np, R, N, g->W_fc_b);
+    if (product(N, 256, Rp, ws.dpreT, Rp, ws.f1T, Rp, g->W_fc_w, 256)) return 1;
+    if (product(R, 256, Np, ws.dpre, Np, ws.wfcT, Np, ws.df1, 256, t.a.f1, 256)) return 1;
     // W_fc_pos: its input is [t1 | v2 | pos]; the first 256 columns carry a gradient further down, both behind a ReLU
     tr_add(ws.df1, 256, R, 256, ws.df1T, Rp);
     tb.flush(s);
-    sh_colsum(ws, s, ws.df1, 256, R, 256, g->W_fc_pos_b);
-    if (sh_product(e, ws, s, 256, 260, Rp, ws.df1T, Rp, ws.catT, Rp, g->W_fc_pos_w, 260)) return 1;
-    if (sh_product(e, ws, s, R, 256, 256, ws.df1, 256, ws.wposT, 256, ws.dcat, 256, t.cat, 260)) return 1;
+    colsum(s, ws.scratch, ws.df1, 256, R, 256, g->W_fc_pos_b);
+    if (product(256, 260, Rp, ws.df1T, Rp, ws.catT, Rp, g->W_fc_pos_w, 260)) return 1;
+    if (product(R, 256, 256, ws.df1, 256, ws.wposT, 256, ws.dcat, 256, t.a.cat, 260)) return 1;
     // W1_txt and W2_vis
     tr_add(ws.dcat, 256, R, 128, ws.dt1T, Rp);
     tr_add(ws.dcat + 128, 256, R, 128, ws.dv2T, Rp);
     tb.flush(s);
-    sh_colsum(ws, s, ws.dcat, 256, R, 128, g->W1_txt_b);
-    sh_colsum(ws, s, ws.dcat + 128, 256, R, 128, g->W2_vis_b);
-    if (sh_product(e, ws, s, 128, 300, Rp, ws.dt1T, Rp, ws.txtT, Rp, g->W1_txt_w, 300)) return 1;
-    if (sh_product(e, ws, s, 128, 512, Rp, ws.dv2T, Rp, ws.v1T, Rp, g->W2_vis_w, 512)) return 1;
-    if (sh_product(e, ws, s, R, 512, 128, ws.dcat + 128, 256, ws.w2T, 128, ws.dv1, 512, t.v1, 512)) return 1;
+    colsum(s, ws.scratch, ws.dcat, 256, R, 128, g->W1_txt_b);
+    colsum(s, ws.scratch, ws.dcat + 128, 256, R, 128, g->W2_vis_b);
+    if (product(128, 300, Rp, ws.dt1T, Rp, ws.txtT, Rp, g->W1_txt_w, 300)) return 1;
+    if (product(128, 512, Rp, ws.dv2T, Rp, ws.v1T, Rp, g->W2_vis_w, 512)) return 1;
+    if (product(R, 512, 128, ws.dcat + 128, 256, ws.w2T, 128, ws.dv1, 512, t.a.v1, 512)) return 1;
     // W1_vis
     tr_add(ws.dv1, 512, R, 512, ws.dv1T, Rp);
     tb.flush(s);
-    sh_colsum(ws, s, ws.dv1, 512, R, 512, g->W1_vis_b);
-    if (sh_product(e, ws, s, 512, 2048, Rp, ws.dv1T, Rp, ws.visT, Rp, g->W1_vis_w, 2048)) return 1;
+    colsum(s, ws.scratch, ws.dv1, 512, R, 512, g->W1_vis_b);
+    if (product(512, 2048, Rp, ws.dv1T, Rp, ws.visT, Rp, g->W1_vis_w, 2048)) return 1;
     LAUNCHCHK();
     return 0;
 }
@@ -397,8 +431,8 @@ extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t
 // ---------------------------------------------------------------------------------------------- S-SSP training
 // S_SSP.forward (sort_model.py:80-103) for S sequences: ONE forward that ends in the loss (a device float) and ONE hand-written backward.
 //   forward   k_ssp_train_prep, the embeddings, the encoder, the decoder teacher-forced in one pass over [bos, gt_0 .. gt_9] (Rd = 11 S
-//             rows), expander_nn, k_ssp_kl_loss / k_ssp_loss_finish.  The products are linear_n's (same planner, same exact fp32 kernels)
-//             behind k_ssp_finish, which adds the dropout bytes to bias / ReLU / residual.
+//             rows), expander_nn, k_ssp_kl_loss / k_ssp_loss_finish.  The products are inference's (run_products) with the dropout bytes
+//             as one more epilogue term.
 //   tape      per LayerNorm its output, the normalised rows and 1 / std; per attention q, k, v, the softmax WEIGHTS before dropout (taped,
 //             not recomputed: at most 8 x 11 x 11 floats per sequence and layer) and the context; the feed-forward hidden AFTER ReLU and
 //             dropout (its sign pattern is both masks); the encoder's summed embeddings; logp.  `prior` is the encoder LayerNorm's output.
@@ -531,49 +565,6 @@ extern "C" size_t vsr_ssp_train_workspace_bytes(int32_t S) {
     return carve_ssp_train(S, nullptr, w);
 }
 
-// One launch of up to four products out (M, N) = gate(sum over segments of A_i (M, K_i) . W_i (N, K_i)^T + bias) (+ residual), each behind
-// k_ssp_finish; every out / keep / relu_y / residual is compact.  The forward gives `scale`, the backward the tape's header.
-struct SspSeg { const float* A; int lda; const float* W; int ldw; int K; };
-struct SspProd {
-    int M, N;
-    SspSeg seg[3];
-    int nseg;
-    float* out;
-    const float* bias; int relu; const uint8_t* keep; const float* relu_y; const float* residual;
-};
-struct SspRun { vsr_ssp* e; hipStream_t s; float* scratch; size_t scratch_floats; const int* hdr; float scale; };
-static SspProd ssp_prod1(int M, int N, int K, const float* A, int lda, const float* W, int ldw, float* out) {
-    SspProd p{};
-    p.M = M; p.N = N; p.seg[0] = SspSeg{A, lda, W, ldw, K}; p.nseg = 1; p.out = out;
-    return p;
-}
-static int ssp_products(SspRun& c, const SspProd* P, int n) {
-    GemmBuilder g;
-    for (int i = 0; i < n; ++i) {
-        GemmProb& p = g.prob(P[i].M, P[i].N, nullptr, P[i].N);
-        for (int k = 0; k < P[i].nseg; ++k) {
-            const SspSeg& sg = P[i].seg[k];
-            if ((sg.K & 3) || (sg.lda & 3) || (sg.ldw & 3) || !aligned16(sg.A) || !aligned16(sg.W))
-                return fail("ssp training: operand not in whole 16-byte groups (K %d, lda %d, ldw %d)", sg.K, sg.lda, sg.ldw);
-            GemmBuilder::seg(p, sg.A, sg.lda, nullptr, sg.W, sg.ldw, sg.K);
-        }
-    }
-    const int ns = g.finish(&c.e->cfg);
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        g.a.p[i].C = c.scratch + off;
-        g.a.p[i].slab_stride = (long long)P[i].M * P[i].N;
-        off += (size_t)P[i].M * P[i].N * ns;
-    }
-    if (off > c.scratch_floats) return fail("ssp training: GEMM scratch too small");
-    if (g.launch(c.s, &c.e->cfg)) return fail("ssp training: gemm launch failed");
-    for (int i = 0; i < n; ++i) {
-        const long long tot = (long long)P[i].M * P[i].N;
-        hipLaunchKernelGGL(k_ssp_finish, dim3(cdiv(tot, 256)), dim3(256), 0, c.s, g.a.p[i].C, ns, tot, P[i].M, P[i].N, P[i].bias, P[i].relu, P[i].keep, c.hdr,
-                           c.scale, P[i].relu_y, P[i].residual, P[i].out);
-    }
-    return 0;
-}
 static void layernorm_train(hipStream_t s, const float* x, const float* w, const float* b, int rows, const SspLnTape& t) {
     hipLaunchKernelGGL(k_layernorm512_train, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, t.y, t.xhat, t.rstd);
 }
@@ -602,53 +593,48 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
     SspSites st;
     ssp_sites(S, st);
     auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
-    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, scale};
-    auto lin = [&](int M, int N, int K, const float* A, const float* W, const float* bias, float* out) {
-        SspProd pr = ssp_prod1(M, N, K, A, K, W, K, out);
-        pr.bias = bias;
-        return pr;
-    };
+    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, scale, "ssp training"};
     hipLaunchKernelGGL(k_ssp_train_prep, dim3(cdiv(Rd, 256)), dim3(256), 0, s, verbs, roles, gt, S, (int)w.n_verbs, ws.verbs32, ws.roles, ws.gt, ws.tok);
     // one layer of either stack: x (in ws.r[0]) -> x (in ws.r[0]); site0: the layer's first dropout site
     auto layer = [&](const vsr_ssp_layer& ly, SspLayerTape& lt, int R, int T, bool dec, int site0, const float* prior) -> int {
         float *x = ws.r[0], *x1 = ws.r[1];
         layernorm_train(s, x, ly.ln1_w, ly.ln1_b, R, lt.lnA);
-        SspProd qkv[3] = {lin(R, H, H, lt.lnA.y, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, ly.Wv, ly.bv, lt.v)};
-        if (ssp_products(run, qkv, 3)) return 1;
+        SspProd qkv[3] = {lin(R, H, H, lt.lnA.y, H, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, H, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, H, ly.Wv, ly.bv, lt.v)};
+        if (run_products(run, qkv, 3)) return 1;
         hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD, lt.ctx1, lt.P1,
                            keep(site0), scale);
-        SspProd o = lin(R, H, H, lt.ctx1, ly.Wo, ly.bo, x1);
+        SspProd o = lin(R, H, H, lt.ctx1, H, ly.Wo, ly.bo, x1);
         o.keep = keep(site0 + 1); o.residual = x;
-        if (ssp_products(run, &o, 1)) return 1;                                                       // x1 = drop(attn) + x
+        if (run_product(run, o)) return 1;                                                            // x1 = drop(attn) + x
         int site = site0 + 2;
         if (dec) {
             layernorm_train(s, x1, ly.ln2_w, ly.ln2_b, R, lt.lnC);
-            SspProd q2 = lin(R, H, H, lt.lnC.y, ly.Wq, ly.bq, lt.q2);                                   // the SAME projections (sort_modules.py:87)
-            if (ssp_products(run, &q2, 1)) return 1;
-            SspProd kv[2] = {lin(Re, H, H, prior, ly.Wk, ly.bk, lt.pk), lin(Re, H, H, prior, ly.Wv, ly.bv, lt.pv)};
-            if (ssp_products(run, kv, 2)) return 1;
+            SspProd q2 = lin(R, H, H, lt.lnC.y, H, ly.Wq, ly.bq, lt.q2);                                // the SAME projections (sort_modules.py:87)
+            if (run_product(run, q2)) return 1;
+            SspProd kv[2] = {lin(Re, H, H, prior, H, ly.Wk, ly.bk, lt.pk), lin(Re, H, H, prior, H, ly.Wv, ly.bv, lt.pv)};
+            if (run_products(run, kv, 2)) return 1;
             hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, T, SSP_LEN, (const int*)nullptr, 0, lt.ctx2, lt.P2,
                                keep(site), scale);
-            SspProd o2 = lin(R, H, H, lt.ctx2, ly.Wo, ly.bo, x);
+            SspProd o2 = lin(R, H, H, lt.ctx2, H, ly.Wo, ly.bo, x);
             o2.keep = keep(site + 1); o2.residual = x1;
-            if (ssp_products(run, &o2, 1)) return 1;                                                  // x = drop(cross) + x1
+            if (run_product(run, o2)) return 1;                                                       // x = drop(cross) + x1
             std::swap(x, x1);                                                                         // (x1 names the feed-forward's input again)
             site += 2;
         }
         layernorm_train(s, x1, dec ? ly.ln3_w : ly.ln2_w, dec ? ly.ln3_b : ly.ln2_b, R, lt.lnF);
-        SspProd f1 = lin(R, SSP_FF, H, lt.lnF.y, ly.W1, ly.b1, lt.ff);
-        f1.relu = 1; f1.keep = keep(site);
-        if (ssp_products(run, &f1, 1)) return 1;
-        SspProd f2 = lin(R, H, SSP_FF, lt.ff, ly.W2, ly.b2, x);
+        SspProd f1 = lin(R, SSP_FF, H, lt.lnF.y, H, ly.W1, ly.b1, lt.ff);
+        f1.act = SSP_ACT_RELU; f1.keep = keep(site);
+        if (run_product(run, f1)) return 1;
+        SspProd f2 = lin(R, H, SSP_FF, lt.ff, SSP_FF, ly.W2, ly.b2, x);
         f2.keep = keep(site + 1); f2.residual = x1;
-        if (ssp_products(run, &f2, 1)) return 1;                                                      // x = drop(ff) + x1
+        if (run_product(run, f2)) return 1;                                                           // x = drop(ff) + x1
         if (x != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
         return 0;
     };
     // ---- encoder
     hipLaunchKernelGGL(k_ssp_embed_train, dim3(Re), dim3(128), 0, s, ws.roles, SSP_LEN, w.sr_embed, ws.verbs32, w.v_embed, keep(1), keep(0), scale, t.emb);
-    SspProd fc = lin(Re, H, H, t.emb, w.fc_w, w.fc_b, ws.r[0]);
-    if (ssp_products(run, &fc, 1)) return 1;
+    SspProd fc = lin(Re, H, H, t.emb, H, w.fc_w, w.fc_b, ws.r[0]);
+    if (run_product(run, fc)) return 1;
     for (int l = 0; l < 3; ++l)
         if (layer(w.enc[l], t.enc[l], Re, SSP_LEN, false, 2 + 4 * l, nullptr)) return 1;
     layernorm_train(s, ws.r[0], w.enc_ln_w, w.enc_ln_b, Re, t.encln);
@@ -660,8 +646,8 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
         if (layer(w.dec[l], t.dec[l], Rd, SSP_TD, true, 15 + 6 * l, t.encln.y)) return 1;
     layernorm_train(s, ws.r[0], w.dec_ln_w, w.dec_ln_b, Rd, t.decln);
     // ---- loss
-    SspProd ex = lin(Rd, SSP_ROLES, H, t.decln.y, w.exp_w, w.exp_b, ws.logits);
-    if (ssp_products(run, &ex, 1)) return 1;
+    SspProd ex = lin(Rd, SSP_ROLES, H, t.decln.y, H, w.exp_w, w.exp_b, ws.logits);
+    if (run_product(run, ex)) return 1;
     hipLaunchKernelGGL(k_ssp_kl_loss, dim3(cdiv(Rd, 4)), dim3(256), 0, s, ws.logits, ws.gt, one_hot, Rd, t.logp, ws.row_loss);
     hipLaunchKernelGGL(k_ssp_loss_finish, dim3(1), dim3(256), 0, s, ws.row_loss, ws.gt, one_hot, S, p_applied, masks ? 1 : 0, loss, t.hdr);
     LAUNCHCHK();
@@ -702,7 +688,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     SspSites st;
     ssp_sites(S, st);
     auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
-    SspRun run{e, s, ws.scratch, ws.scratch_floats, t.hdr, 1.f};
+    SspRun run{e, s, ws.scratch, ws.scratch_floats, t.hdr, 1.f, "ssp training"};
     TransBatch tb;
     auto tr_add = [&](const float* in, int ld_in, int rows, int cols, float* out, int ld_out) { tb.add(s, 0, nullptr, in, ld_in, rows, cols, out, ld_out, nullptr, 0); };
     // the gradient of x where y = drop(x) (site) and dy is given: dy itself without masks, else a masked copy in `buf`
@@ -730,7 +716,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     {
         SspProd pw = ssp_prod1(SSP_ROLES, H, Rdp, ws.t512[0], Rdp, ws.t512[1], Rdp, g->exp_w);
         SspProd px = ssp_prod1(Rd, H, LD, ws.dlog, LD, ws.wT[0], LD, ws.r[2]);
-        if (ssp_products(run, &pw, 1) || ssp_products(run, &px, 1)) return 1;
+        if (run_product(run, pw) || run_product(run, px)) return 1;
     }
     ln_bwd(ws.r[2], w.dec_ln_w, t.decln, nullptr, Rd, ws.r[0], g->dec_ln_w, g->dec_ln_b);
 
@@ -752,13 +738,13 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         SspProd pw2 = ssp_prod1(H, F, Rp, ws.t512[0], Rp, ws.t2048[0], Rp, gl.W2);
         SspProd pff = ssp_prod1(R, F, H, dz2, H, ws.wT[0], H, ws.dff);
         pff.relu_y = lt.ff;                                                                           // d (W1 yF + b1): relu and the site's dropout in one
-        if (ssp_products(run, &pw2, 1) || ssp_products(run, &pff, 1)) return 1;
+        if (run_product(run, pw2) || run_product(run, pff)) return 1;
         tr_add(ws.dff, F, R, F, ws.t2048[1], Rp);
         tb.flush(s);
         ssp_colsum(ws, s, ws.dff, R, F, gl.b1);
         SspProd pw1 = ssp_prod1(F, H, Rp, ws.t2048[1], Rp, ws.t512[1], Rp, gl.W1);
         SspProd pyf = ssp_prod1(R, H, F, ws.dff, F, ws.wT[1], F, Y);
-        if (ssp_products(run, &pw1, 1) || ssp_products(run, &pyf, 1)) return 1;
+        if (run_product(run, pw1) || run_product(run, pyf)) return 1;
         ln_bwd(Y, dec ? ly.ln3_w : ly.ln2_w, lt.lnF, A, R, B, dec ? gl.ln3_w : gl.ln2_w, dec ? gl.ln3_b : gl.ln2_b);       // B = d h
         // the four attention weights, transposed once for both uses
         tr_add(ly.Wo, H, H, H, ws.wT[0], H);
@@ -773,7 +759,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
             tr_add(lt.ctx2, H, R, H, ws.t512[1], Rp);
             tb.flush(s);
             SspProd pc = ssp_prod1(R, H, H, dzo2, H, ws.wT[0], H, Y);
-            if (ssp_products(run, &pc, 1)) return 1;
+            if (run_product(run, pc)) return 1;
             hipLaunchKernelGGL(k_ssp_mha_bwd, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, lt.P2, keep(site0 + 2), t.hdr, Y, T, SSP_LEN, (const int*)nullptr, 0,
                                Q2, ws.dpk, ws.dpv, ws.dbk2);
             tr_add(Q2, H, R, H, ws.t512[2], Rp);
@@ -785,7 +771,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
             SspProd pp = ssp_prod1(Re, H, H, ws.dpk, H, ws.wT[2], H, ws.dprior);
             pp.seg[1] = SspSeg{ws.dpv, H, ws.wT[3], H, H}; pp.nseg = 2;
             pp.residual = first_dec ? nullptr : ws.dprior;                                            // the three layers accumulate into d prior
-            if (ssp_products(run, &pyc, 1) || ssp_products(run, &pp, 1)) return 1;
+            if (run_product(run, pyc) || run_product(run, pp)) return 1;
             ln_bwd(C, ly.ln2_w, lt.lnC, B, R, A, gl.ln2_w, gl.ln2_b);                                   // A = d h1
         } else {
             tb.flush(s);
@@ -800,7 +786,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         SspProd pc1 = ssp_prod1(R, H, H, dzo1, H, ws.wT[0], H, Y);
         SspProd pwo = ssp_prod1(H, H, Rp, ws.t512[4], Rp, ws.t512[5], Rp, gl.Wo);
         if (dec) { pwo.seg[1] = SspSeg{ws.t512[0], Rp, ws.t512[1], Rp, Rp}; pwo.nseg = 2; }
-        if (ssp_products(run, &pc1, 1) || ssp_products(run, &pwo, 1)) return 1;
+        if (run_product(run, pc1) || run_product(run, pwo)) return 1;
         hipLaunchKernelGGL(k_ssp_mha_bwd, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, lt.P1, keep(site0), t.hdr, Y, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD,
                            C, D, E, ws.dbk1);
         tr_add(C, H, R, H, ws.t512[6], Rp);
@@ -818,10 +804,10 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
             pw[1].seg[1] = SspSeg{ws.tE[0], Rep, ws.tE[2], Rep, Rep}; pw[1].nseg = 2;
             pw[2].seg[1] = SspSeg{ws.tE[1], Rep, ws.tE[2], Rep, Rep}; pw[2].nseg = 2;
         }
-        if (ssp_products(run, pw, 3)) return 1;
+        if (run_products(run, pw, 3)) return 1;
         SspProd pya = ssp_prod1(R, H, H, C, H, ws.wT[1], H, Y);
         pya.seg[1] = SspSeg{D, H, ws.wT[2], H, H}; pya.seg[2] = SspSeg{E, H, ws.wT[3], H, H}; pya.nseg = 3;
-        if (ssp_products(run, &pya, 1)) return 1;
+        if (run_product(run, pya)) return 1;
         ln_bwd(Y, ly.ln1_w, lt.lnA, A, R, B, gl.ln1_w, gl.ln1_b);                                       // B = d x
         if (B != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
         return 0;
@@ -843,7 +829,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     {
         SspProd pw = ssp_prod1(H, H, Rep, ws.t512[0], Rep, ws.t512[1], Rep, g->fc_w);
         SspProd px = ssp_prod1(Re, H, H, ws.r[0], H, ws.wT[0], H, ws.r[2]);
-        if (ssp_products(run, &pw, 1) || ssp_products(run, &px, 1)) return 1;
+        if (run_product(run, pw) || run_product(run, px)) return 1;
     }
     hipLaunchKernelGGL(k_ssp_sr_embed_bwd, dim3(SSP_ROLES, H / 64), dim3(256), 0, s, ws.roles, ws.r[2], keep(1), Re, ws.tok, d_dec, keep(14), Rd, t.hdr, g->sr_embed);
     hipLaunchKernelGGL(k_ssp_v_embed_bwd, dim3((int)w.n_verbs), dim3(128), 0, s, ws.verbs32, ws.r[2], keep(0), t.hdr, S, g->v_embed);
@@ -855,7 +841,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
 // eval_coco.py:141-221 for the N caption rows of a loader batch as one stream of launches: integer annotations in,
 // the (N, L) rank tensor of vsr_reorder_slots out, no read-back.  S-SSP runs on the PADDED job slots S = N MV (an inactive slot has
 // verb 0 and no roles: k_ssp_init emits nothing for it) and SinkhornNet on Q = max_items items (an unused item is all zero rows).
-// The items go through SinkhornNet's five layers (vsr_sinkhorn_assign's own: sinkhorn_mlp) in chunks of RANK_SH_CHUNK (max_items rounded
+// The items go through SinkhornNet's five layers (vsr_sinkhorn_assign's own: sinkhorn_layers) in chunks of RANK_SH_CHUNK (max_items rounded
 // up to whole chunks): every GEMM launch then has the same shape whatever max_items is, so an item's assignment - down to how a tie
 // between two identical padding rows falls, which follows the last bit of the stream-K GEMMs and with it the launch's row count - does
 // not depend on the bound the caller chose.  The Sinkhorn iterations and the assignment (k_sinkhorn_assign, one wave per item, 0.37 ms
@@ -955,9 +941,12 @@ extern "C" int vsr_rank_captions(vsr_ssp* e, const int32_t* control_verb, const 
     hipLaunchKernelGGL(k_rank_gather, dim3((int)std::min<long long>(2048, cdiv(n_rows, 4))), dim3(256), 0, s, seqs_perm, w.item_gather, n_rows, (long long)N * L, w.seq);
     LAUNCHCHK();
     if (vsr_ssp_generate(e, w.job_verbs, w.job_roles, S, w.pred, w.logp, w.ssp, w.ssp_bytes, stream)) return 1;
+    ShWs sh;
+    if (carve_sh_ws(RANK_SH_CHUNK, N_sink, w.sh, sh) > w.sh_bytes) return fail("vsr_rank_captions: Sinkhorn slot of the workspace too small");
+    SspRun run{e, s, sh.scratch, sh.scratch_floats, nullptr, 1.f, "sinkhorn forward"};
     for (int q = 0; q < Qpad; q += RANK_SH_CHUNK) {
-        float* fc = nullptr;
-        if (sinkhorn_mlp(e, w.seq + (size_t)q * N_sink * SH_ROW, RANK_SH_CHUNK, w.sh, s, w.fc + (size_t)q * N_sink * N_sink, &fc)) return 1;
+        sh.a.th = w.fc + (size_t)q * N_sink * N_sink;
+        if (sinkhorn_layers(run, w.seq + (size_t)q * N_sink * SH_ROW, RANK_SH_CHUNK, sh.a)) return 1;
     }
     hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Qpad), dim3(64), 0, s, w.fc, N_sink, e->sw.n_iters, e->sw.tau, (float*)nullptr, w.assign);
     LAUNCHCHK();

@@ -76,16 +76,44 @@ __global__ __launch_bounds__(256) void k_layernorm512(const float* __restrict__ 
     layernorm512_row<false>(x, w, b, rows, out, nullptr, nullptr);
 }
 
-// out[m][n] = act(sum of slabs + bias[n]) (+ residual[m][n]);  act: 0 none, 1 relu, 2 tanh
-__global__ void k_linear_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ bias,
-                                int act, const float* __restrict__ residual, long long ldr, float* __restrict__ out, long long ldo) {
+// 1 / (1 - p) of the p an S-SSP training forward applied, from its tape's header (layout: SSP_TAPE_HDR_INTS below)
+__device__ __forceinline__ float ssp_keep_scale(const int* __restrict__ hdr) { return 1.0f / (1.0f - __int_as_float(hdr[1])); }
+
+// The finish of every dense product of the ordering models: out = epilogue(sum of slabs), the terms and their order as stated at SspProd
+// (ssp.inc.h).  ONE source; which terms exist is a compile-time choice (run_products picks the instance from the product's fields), so a
+// launch carries no load and no test for a term its product does not have:
+//   LIN    bias / act / residual may be present (each skipped when NULL / SSP_ACT_NONE); without LIN the kernel is the plain slab sum
+//   GATE   FIN_KEEP: `gate` is the site's keep bytes, compact (M N);  FIN_RELU_Y: `gate` is the taped y (leading dimension ldg)
+// scale = 1 / (1 - p): the forward passes it, the backward passes the tape's header instead.  out may be residual's buffer (accumulation:
+// each thread reads its element before it writes it), hence no __restrict__ on the two.  The operands are loaded BEFORE the slabs are
+// added: these launches are mostly a few waves bound by memory latency, and all their loads should be in flight together.  The product and
+// the sum that follows it are two roundings, spelled out so that no compiler fuses them.
+constexpr int SSP_ACT_NONE = 0, SSP_ACT_RELU = 1, SSP_ACT_TANH = 2;
+constexpr int FIN_NONE = 0, FIN_KEEP = 1, FIN_RELU_Y = 2;
+template <bool LIN, int GATE>
+__global__ void k_prod_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ bias, int act,
+                              const float* residual, long long ldr, float* out, long long ldo, const void* __restrict__ gate, long long ldg,
+                              const int* __restrict__ hdr, float scale) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)M * N) return;
     const int m = (int)(i / N), n = (int)(i % N);
-    float s = slab_sum(slabs + i, nslab, stride) + (bias ? bias[n] : 0.f);
-    if (act == 1) s = fmaxf(s, 0.f);
-    else if (act == 2) s = tanhf(s);
-    if (residual) s += residual[(long long)m * ldr + n];
+    float b = 0.f, r = 0.f, y = 0.f;
+    uint8_t kept = 0;
+    if (LIN && bias) b = bias[n];
+    if (LIN && residual) r = residual[(long long)m * ldr + n];
+    if (GATE == FIN_KEEP) kept = static_cast<const uint8_t*>(gate)[i];
+    if (GATE == FIN_RELU_Y) y = static_cast<const float*>(gate)[(long long)m * ldg + n];
+    float s = slab_sum(slabs + i, nslab, stride);
+    if (LIN) {
+        if (bias) s = __fadd_rn(s, b);
+        if (act == SSP_ACT_RELU) s = fmaxf(s, 0.f);
+        else if (act == SSP_ACT_TANH) s = tanhf(s);
+    }
+    if (GATE != FIN_NONE) {
+        if (hdr) scale = ssp_keep_scale(hdr);
+        s = (GATE == FIN_KEEP ? kept != 0 : y > 0.f) ? __fmul_rn(s, scale) : 0.f;
+    }
+    if (LIN && residual) s = __fadd_rn(s, r);
     out[(long long)m * ldo + n] = s;
 }
 
@@ -380,17 +408,6 @@ __global__ __launch_bounds__(64) void k_sinkhorn_loc_loss(const float* __restric
     }
 }
 
-// dX = (sum of slabs) masked by the ReLU whose OUTPUT is y: out[m][n] = y[m][n] > 0 ? sum : 0
-__global__ void k_relu_bwd_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ y, long long ldy,
-                                  float* __restrict__ out, long long ldo) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)M * N) return;
-    const int m = (int)(i / N), n = (int)(i % N);
-    const float s = slab_sum(slabs + i, nslab, stride);
-    out[(long long)m * ldo + n] = y[(long long)m * ldy + n] > 0.f ? s : 0.f;
-}
-
-
 // ---------------------------------------------------------------------------------------------- S-SSP training
 // S_SSP.forward (sort_model.py:80-103): the encoder on (verb, roles), the decoder teacher-forced in ONE pass over [bos, gt_0 .. gt_9],
 // the label-smoothed KL loss.  Rows: encoder r = s * 10 + j, decoder r = s * 11 + t.  Dropout masks are DATA: a byte per element
@@ -404,7 +421,6 @@ constexpr float SSP_CONFIDENCE = 0.9f;                     // LabelSmoothingKLDi
 //   [0] S   [1] bits of the p the forward applied (0.0 when it ran without masks)   [2] 1 = it ran with masks   [3] bits of sum(m)
 //   [4 .. 29] bits of the 26 off-target values of the forward's label_smooth.one_hot buffer
 constexpr int SSP_TAPE_HDR_INTS = 32;
-__device__ __forceinline__ float ssp_keep_scale(const int* __restrict__ hdr) { return 1.0f / (1.0f - __int_as_float(hdr[1])); }
 
 struct SspSites { long long off[SSP_SITES + 1]; long long n[SSP_SITES]; };      // byte offset (16-aligned) and element count per site
 
@@ -573,27 +589,6 @@ __global__ __launch_bounds__(64) void k_ssp_mha_bwd(const float* __restrict__ q,
             bs += dkk[j];
         }
     dbk[(long long)s * SSP_H + col] = (float)bs;
-}
-
-// out[m][n] = gate(sum of slabs + bias[n]) (+ residual[m][n]), every matrix compact (leading dimension N).  gate, in this order:
-//   relu                    forward: max(., 0)
-//   keep (M N bytes)        dropout: keep ? . scale : 0 - the forward's site, or in the backward the site of the tensor whose gradient this is
-//   relu_y                  backward through relu + dropout in one: the taped y = drop(relu(.)) is > 0 exactly where both let the gradient
-//                           pass, and the factor there is scale
-// scale = 1 / (1 - p): the forward passes it, the backward passes the tape's header instead.  out may be residual's buffer (accumulation).
-__global__ void k_ssp_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ bias, int relu,
-                             const uint8_t* __restrict__ keep, const int* __restrict__ hdr, float scale, const float* __restrict__ relu_y,
-                             const float* residual, float* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)M * N) return;
-    const int n = (int)(i % N);
-    if (hdr) scale = ssp_keep_scale(hdr);
-    float s = slab_sum(slabs + i, nslab, stride) + (bias ? bias[n] : 0.f);
-    if (relu) s = fmaxf(s, 0.f);
-    if (keep) s = keep[i] ? s * scale : 0.f;
-    if (relu_y) s = relu_y[i] > 0.f ? s * scale : 0.f;
-    if (residual) s += residual[i];
-    out[i] = s;
 }
 
 // the gradient of x where y = drop(x): out = keep ? in scale : 0; n a multiple of 4

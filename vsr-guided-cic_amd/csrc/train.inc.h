@@ -217,10 +217,11 @@ static int gemm_group(vsr_handle* h, TrainCtx& t, hipStream_t s, const GProb* P,
     }
     return 0;
 }
-// deterministic two-stage column sum through the (idle) slab scratch
-static void colsum(TrainCtx& t, hipStream_t s, const float* X, long long ld, int R, int C, float* out, float* out2 = nullptr) {
-    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, ld, R, C, t.scratch);
-    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, t.scratch, C, 0, C, out, out2);
+// deterministic two-stage column sum: out[c] (and out2[c]) = sum over rows of X[r][c], through `part` (COLSUM_CHUNKS x C floats: the idle
+// slab scratch).  Shared with the ordering models' backward passes (ssp.inc.h).
+static void colsum(hipStream_t s, float* part, const float* X, long long ld, int R, int C, float* out, float* out2 = nullptr) {
+    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, ld, R, C, part);
+    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, part, C, 0, C, out, out2);
 }
 // up to ZERO_MT buffers zeroed by one launch (sizes in bytes, multiples of 16; pointers 16-byte aligned)
 struct ZeroList {
@@ -866,11 +867,11 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
         transpose(h, s, t.dpre2sum, 4 * H, Bi, 4 * H, t.tY_dpre2sum, Bp);
         if (gemm_to1(h, t, s, 4 * H, D, Bp, t.tY_dpre2sum, Bp, t.tX_vbar, Bp, G[g_Wih2] + H + D, in2, dslot(DW_dpre2sum))) return 1;
     }
-    colsum(t, s, t.dpre2, (long long)4 * H, TB, 4 * H, G[g_bih2], G[g_bhh2]);
+    colsum(s, t.scratch, t.dpre2, (long long)4 * H, TB, 4 * H, G[g_bih2], G[g_bhh2]);
     HIPCHK(hipEventRecord(h->bucket_ev[1], s));
     // ---- bucket 2: out_fc and the embedding
     if (gemm_to1(h, t, s, V, H, TBp, t.tY_dlogits, TBp, t.tX_h2, TBp, G[g_Wout], H, dslot(DW_dlogits), tyi)) return 1;
-    colsum(t, s, t.dlogits, (long long)Vp, TB, V, G[g_bout]);
+    colsum(s, t.scratch, t.dlogits, (long long)Vp, TB, V, G[g_bout]);
     {   // embedding: dx = dpre1 . [W_ih1 ; W_is ; W_ig][:, x columns], summed onto the rows that were looked up (ordered, no atomics)
         SegSpec sg[3] = {{t.dpre1, 6 * H, t.wT_ih1 + (size_t)xoff * 4 * H, 4 * H, 4 * H, sP1},
                          {t.dpre1 + 4 * H, 6 * H, t.wT_is + (size_t)xoff * H, H, H, sP1},
@@ -893,7 +894,7 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(4 * H, 256)), dim3(256), 0, s, t.scratch, 6 * H, 0, 4 * H, G[g_bih1], G[g_bhh1]);
     hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(H, 256)), dim3(256), 0, s, t.scratch, 6 * H, 4 * H, H, G[g_bis], G[g_bhs]);
     hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(H, 256)), dim3(256), 0, s, t.scratch, 6 * H, 5 * H, H, G[g_big], G[g_bhg]);
-    colsum(t, s, t.dsent_all, (long long)D, TB, D, G[g_bsfc]);
+    colsum(s, t.scratch, t.dsent_all, (long long)D, TB, D, G[g_bsfc]);
     // att_va: dP^T (A, NV) x regions^T (D, NV) over the non-padding rows
     if (NV > 0) {
         if (gemm_to1(h, t, s, A, D, NVp, t.tY_dP, NVp, t.tX_reg, NVp, G[g_Wva], D, dslot(DW_dP), tyiP)) return 1;
@@ -909,9 +910,9 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
                             GProb{A, H, TBp, t.tY_dga, TBp, t.tX_gt, TBp, G[g_Wga], H, dslot(DW_step + DY_dga), tyi}};
         if (gemm_group(h, t, s, a, 4)) return 1;
     }
-    colsum(t, s, t.dwa_rows, (long long)A, TB, A, G[g_wa]);
-    colsum(t, s, t.dws_rows, (long long)A, TB, A, G[g_ws]);
-    colsum(t, s, t.dwg_rows, (long long)A, TB, A, G[g_wg]);
+    colsum(s, t.scratch, t.dwa_rows, (long long)A, TB, A, G[g_wa]);
+    colsum(s, t.scratch, t.dws_rows, (long long)A, TB, A, G[g_ws]);
+    colsum(s, t.scratch, t.dwg_rows, (long long)A, TB, A, G[g_wg]);
     HIPCHK(hipEventRecord(h->bucket_ev[4], s));
     h->buckets_recorded = true;
     LAUNCHCHK();
