@@ -381,6 +381,35 @@ int vsr_rank_captions(vsr_ssp* e, const int32_t* control_verb, const int32_t* de
                       int32_t MV, int32_t MS, int32_t N_sink, int64_t n_verbs, const float* seqs_perm, int32_t max_items, int32_t* rank,
                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- training batches of the ordering models on the device ----------------------------
+ * coco_scripts/train_region_sort.py:133-179 and coco_scripts/train_sinkhorn.py:144-205 (and their Flickr twins) for the N caption rows
+ * of a loader batch: from the loader's integer annotations to the inputs of vsr_ssp_train_forward and vsr_sinkhorn_loc_loss, as launches
+ * on the caller's stream - no read-back, no allocation.  The logic is csrc/train_batch_logic.h, the training twin of the ranking above:
+ * the same jobs, the same scan, the same limits (L == 10, 1 <= MV <= 8, MS >= MV, 2 <= N_sink <= 16; Lg >= 1).
+ *   control_verb, det_seqs_v, det_seqs_sr, n_verbs as for vsr_rank_plan; gt_seqs_v (N, Lg, MV) and gt_seqs_sr (N, Lg, MS) int32, or both
+ *   NULL (gt_roles is then zero filled if given); idx_list (N, L) int32 - the ground-truth position of each slot - or NULL (no items; the
+ *   four item tables may then be NULL too).  max_items = 0 is the static maximum N MV 10.
+ * vsr_train_batch_plan writes, compacted in the reference's loop order (captions, verb columns, ascending role id):
+ *   verbs (N MV) int64 - raw ids, vsr_ssp_train_forward takes them % 10000 -, det_roles and gt_roles (N MV, 10) int32: one row per ACTIVE
+ *     job; rows beyond counts[0] are zeros
+ *   item_gather (max_items, N_sink) int32 = n L + slot, -1 beyond the item's length; tr_locs / gt_locs (max_items, N_sink) fp32, 10.0
+ *     beyond the item's length (gt_locs from the STABLE argsort of the slots' idx_list values padded with 10); item_key (max_items, 3)
+ *     int32 = (caption, verb column, role id): one item per repeated role; items beyond counts[1] are zeros, -1 in item_gather
+ *   counts (4) int32 = {rows, items written, OR of all status words, items dropped beyond max_items}
+ *   status (N) int32, a bit set:  4 a matched det or gt role id outside [0, 26)   8 a negative verb, or verb % 10000 outside [0, n_verbs)
+ *     32 an item cut to N_sink slots   64 an idx_list value outside [0, 10) at a used slot.  A caption with bit 4 or 8 emits no rows and
+ *     no items.
+ *   plan: scratch of vsr_train_batch_plan_bytes(N, MV) bytes.
+ * vsr_gather_rows: out[i] = rows[gather[i]] (D floats, D a multiple of 4), a zero row where gather[i] < 0 or >= n_src_rows: the items'
+ *   feature rows seq (items, N_sink, 2352) from seqs_perm (N L, 2352) and item_gather. */
+size_t vsr_train_batch_plan_bytes(int32_t N, int32_t MV);
+int vsr_train_batch_plan(const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, const int32_t* gt_seqs_v,
+                         const int32_t* gt_seqs_sr, int32_t Lg, const int32_t* idx_list, int32_t N, int32_t L, int32_t MV, int32_t MS,
+                         int32_t N_sink, int64_t n_verbs, int32_t max_items, int64_t* verbs, int32_t* det_roles, int32_t* gt_roles,
+                         int32_t* item_gather, float* tr_locs, float* gt_locs, int32_t* item_key, int32_t* counts, int32_t* status,
+                         void* plan, size_t plan_bytes, void* stream);
+int vsr_gather_rows(const float* rows, int64_t n_src_rows, int32_t D, const int32_t* gather, int64_t n_out_rows, float* out, void* stream);
+
 /* ---- SinkhornNet training (coco_scripts/train_sinkhorn.py:137-215) -----------------------------------
  * The reference calls the net once per (image, caption, verb, repeated role) at batch size 1 and adds MSE losses on the host.
  * Here one forward, one fused loss and one backward serve all Q items of a loader batch; exact fp32 products throughout.

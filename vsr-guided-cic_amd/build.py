@@ -23,6 +23,10 @@ TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "gemm_bench")
 RANK_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "rank_logic_host.cpp")
 RANK_TOOL_DEPS = [RANK_TOOL_SRC, os.path.join(HERE, "csrc", "rank_logic.h")]
 RANK_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "rank_logic_host")
+# the training-batch logic (csrc/train_batch_logic.h) on the CPU, likewise; driven by tests/test_train_batch_logic.py
+TB_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "train_batch_host.cpp")
+TB_TOOL_DEPS = [TB_TOOL_SRC, os.path.join(HERE, "csrc", "train_batch_logic.h"), os.path.join(HERE, "csrc", "rank_logic.h")]
+TB_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "train_batch_host")
 
 
 STAMP = OUT + ".flags"      # the extra hipcc flags the library on disk was built with
@@ -78,8 +82,19 @@ def build_rank_tool(out=RANK_TOOL_OUT, force=False, extra_flags=()):
     return out
 
 
+def build_train_batch_tool(out=TB_TOOL_OUT, force=False, extra_flags=()):
+    """tools/train_batch_host with the host compiler ($CXX, default c++); extra_flags e.g. ("-fsanitize=address,undefined", "-g")"""
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in TB_TOOL_DEPS):
+        return out
+    cxx = os.environ.get("CXX", "c++")
+    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-Wextra", *extra_flags, "-o", out + ".tmp", TB_TOOL_SRC], check=True)
+    os.replace(out + ".tmp", out)
+    return out
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))
     if "--tool" in sys.argv:
         print(build_tool(force="--force" in sys.argv))
         print(build_rank_tool(force="--force" in sys.argv))
+        print(build_train_batch_tool(force="--force" in sys.argv))

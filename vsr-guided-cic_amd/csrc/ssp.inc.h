@@ -6,6 +6,7 @@
 // vsrcap/evalbatch.py: rank_captions is the same flow with the integer bookkeeping on the host.
 #include "ssp_kernels.h"
 #include "rank_kernels.h"
+#include "train_batch_kernels.h"
 
 struct vsr_ssp {
     vsr_handle cfg;                  // GEMM launch configuration only (stream-K slots, tile choice); fp32
@@ -951,4 +952,60 @@ extern "C" int vsr_rank_captions(vsr_ssp* e, const int32_t* control_verb, const 
     hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Qpad), dim3(64), 0, s, w.fc, N_sink, e->sw.n_iters, e->sw.tau, (float*)nullptr, w.assign);
     LAUNCHCHK();
     return vsr_rank_finish(w.plan, w.plan_bytes, w.pred, w.assign, N, L, MV, N_sink, rank, status, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- training batches on the device
+// train_region_sort.py:133-179 and train_sinkhorn.py:144-205 for the N caption rows of a loader batch: integer
+// annotations in; the rows of S_SSP.forward and the item tables of SinkhornNet.loc_loss out, compacted in the reference's loop order
+// (captions, verb columns, ascending role), with their counts in a 16-byte tensor that is the caller's ONE read-back.  Two launches on
+// the caller's stream, no read-back and no allocation here.  The tables are integers and a few floats (under 300 KB at N MV 10 items),
+// so max_items = 0 - the static maximum - costs nothing worth a bound; the feature rows are gathered afterwards (vsr_gather_rows) for
+// the items that exist.
+static size_t carve_tb_plan(int N, int MV, char* base, TbPlan& p) {
+    const size_t S = (size_t)N * MV;
+    Bump b{base};
+    p.row_off = b.take<int32_t>(S); p.item_off = b.take<int32_t>(S); p.jobs = b.take<TbJob>(S);
+    return (b.off + 255) & ~size_t(255);
+}
+extern "C" size_t vsr_train_batch_plan_bytes(int32_t N, int32_t MV) {
+    if (N <= 0 || MV < 1 || MV > RANK_MAX_MV || (long long)N * MV * RANK_L > INT_MAX / 64) return 0;
+    TbPlan p;
+    return carve_tb_plan(N, MV, nullptr, p);
+}
+
+extern "C" int vsr_train_batch_plan(const int32_t* control_verb, const int32_t* det_seqs_v, const int32_t* det_seqs_sr, const int32_t* gt_seqs_v,
+                                    const int32_t* gt_seqs_sr, int32_t Lg, const int32_t* idx_list, int32_t N, int32_t L, int32_t MV, int32_t MS, int32_t N_sink,
+                                    int64_t n_verbs, int32_t max_items, int64_t* verbs, int32_t* det_roles, int32_t* gt_roles, int32_t* item_gather, float* tr_locs,
+                                    float* gt_locs, int32_t* item_key, int32_t* counts, int32_t* status, void* plan, size_t plan_bytes, void* stream) {
+    if (!control_verb || !det_seqs_v || !det_seqs_sr || !verbs || !det_roles || !counts || !status || !plan || n_verbs <= 0)
+        return fail("vsr_train_batch_plan: bad arguments");
+    if (!gt_seqs_v != !gt_seqs_sr || (gt_seqs_v && !gt_roles)) return fail("vsr_train_batch_plan: gt_seqs_v, gt_seqs_sr and gt_roles go together");
+    if (idx_list && (!item_gather || !tr_locs || !gt_locs || !item_key)) return fail("vsr_train_batch_plan: idx_list needs the four item tables");
+    if (!!item_gather != !!tr_locs || !!item_gather != !!gt_locs || !!item_gather != !!item_key)
+        return fail("vsr_train_batch_plan: the four item tables go together");
+    if (rank_shape("vsr_train_batch_plan", N, L, MV, MS, N_sink, max_items)) return 1;
+    if (gt_seqs_v && Lg < 1) return fail("vsr_train_batch_plan: Lg %d < 1", Lg);
+    TbPlan p;
+    if (carve_tb_plan(N, MV, reinterpret_cast<char*>(plan), p) > plan_bytes) return fail("vsr_train_batch_plan: plan buffer too small");
+    const int S = N * MV, Qcap = rank_qcap(N, MV, max_items);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_tb_jobs, dim3(cdiv(S, 64)), dim3(64), 0, s, control_verb, det_seqs_v, det_seqs_sr, gt_seqs_v, gt_seqs_sr, idx_list, N, L, gt_seqs_v ? Lg : 1,
+                       MV, MS, N_sink, (long long)n_verbs, p);
+    TbOut o{verbs, det_roles, gt_roles, item_gather, tr_locs, gt_locs, item_key, counts, status};
+    hipLaunchKernelGGL(k_tb_compact, dim3(1), dim3(256), 0, s, p, idx_list, N, L, MV, N_sink, Qcap, o);
+    LAUNCHCHK();
+    return 0;
+}
+
+extern "C" int vsr_gather_rows(const float* rows, int64_t n_src_rows, int32_t D, const int32_t* gather, int64_t n_out_rows, float* out, void* stream) {
+    if (!rows || !gather || !out || n_src_rows <= 0 || n_out_rows < 0 || n_src_rows > INT_MAX || n_out_rows > INT_MAX) return fail("vsr_gather_rows: bad arguments");
+    if (D < 4 || D % 4) return fail("vsr_gather_rows: D %d must be a positive multiple of 4", D);
+    if (n_out_rows == 0) return 0;
+    const dim3 grid((int)std::min<long long>(2048, cdiv((long long)n_out_rows, 4LL)));
+    if (D == SH_ROW)
+        hipLaunchKernelGGL(k_rank_gather, grid, dim3(256), 0, (hipStream_t)stream, rows, gather, (long long)n_out_rows, (long long)n_src_rows, out);
+    else
+        hipLaunchKernelGGL(k_tb_gather, grid, dim3(256), 0, (hipStream_t)stream, rows, gather, (long long)n_out_rows, (long long)n_src_rows, D / 4, out);
+    LAUNCHCHK();
+    return 0;
 }

@@ -129,6 +129,9 @@ SIGNATURES = {
     "vsr_rank_plan": (I32, [P, P, P, I32, I32, I32, I32, I32, I64, I32, P, P, P, P, SZ, P]),
     "vsr_rank_finish": (I32, [P, SZ, P, P, I32, I32, I32, I32, P, P, P]),
     "vsr_rank_captions": (I32, [P, P, P, P, I32, I32, I32, I32, I32, I64, P, I32, P, P, P, SZ, P]),
+    "vsr_train_batch_plan_bytes": (SZ, [I32, I32]),
+    "vsr_train_batch_plan": (I32, [P, P, P, P, P, I32, P, I32, I32, I32, I32, I32, I64, I32, P, P, P, P, P, P, P, P, P, P, SZ, P]),
+    "vsr_gather_rows": (I32, [P, I64, I32, P, I64, P, P]),
     "vsr_sinkhorn_tape_bytes": (SZ, [I32, I32]),
     "vsr_sinkhorn_train_workspace_bytes": (SZ, [I32, I32]),
     "vsr_sinkhorn_train_forward": (I32, [P, P, I32, P, P, SZ, P, SZ, P]),

@@ -9,7 +9,8 @@ buffer (ssp_mask_layout, ssp_dropout_masks) that the forward and the backward bo
 
 rank_captions is the eval loop's ranking (eval_coco.py:141-221) for a loader batch as one stream of launches (vsr_rank_captions): integer
 annotations in, the (N, L) rank tensor and a per-caption status out, both on the device, nothing read back; rank_plan / rank_finish are
-its two integer stages on their own."""
+its two integer stages on their own.  train_batch_plan / gather_rows are the training twin (vsr_train_batch_plan, vsr_gather_rows): the
+same annotations in, the inputs of the two training calls out; vsrcap/trainbatch.py builds a batch from them."""
 import ctypes as C
 
 import numpy as np
@@ -176,28 +177,31 @@ class SspEngine:
     # ---- caption ranking on the device (include/vsrcap.h: vsr_rank_*)
     RANK_L = 10
 
-    def _annotations(self, control_verb, det_seqs_v, det_seqs_sr):
-        """the three integer arrays as contiguous int32 GPU tensors.  Host arrays travel together in ONE non-blocking upload from pinned
-        memory; tensors are converted where they live.  Only shapes are checked: the values are judged on the device (status)."""
-        xs = [control_verb, det_seqs_v, det_seqs_sr]
+    def _upload_ints(self, xs):
+        """integer arrays as contiguous int32 GPU tensors.  Host arrays travel together in ONE non-blocking upload from pinned memory;
+        tensors are converted where they live."""
         if all(isinstance(x, torch.Tensor) for x in xs):
-            xs = [x.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous() for x in xs]
-        else:
-            host = [x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in xs]
-            stage = torch.empty(sum(h.size for h in host), dtype=torch.int32, pin_memory=True)
-            view, lo = stage.numpy(), 0
-            for h in host:
-                view[lo:lo + h.size] = h.reshape(-1)
-                lo += h.size
-            dev, lo, xs = stage.to(self.device, non_blocking=True), 0, []
-            for h in host:
-                xs.append(dev[lo:lo + h.size].view(h.shape))
-                lo += h.size
-        cv, dv, dsr = xs
+            return [x.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous() for x in xs]
+        host = [x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in xs]
+        stage = torch.empty(sum(h.size for h in host), dtype=torch.int32, pin_memory=True)
+        view, lo = stage.numpy(), 0
+        for h in host:
+            view[lo:lo + h.size] = h.reshape(-1)
+            lo += h.size
+        dev, lo, out = stage.to(self.device, non_blocking=True), 0, []
+        for h in host:
+            out.append(dev[lo:lo + h.size].view(h.shape))
+            lo += h.size
+        return out
+
+    def _annotations(self, control_verb, det_seqs_v, det_seqs_sr, *more):
+        """the three integer arrays (and any further ones, returned after them) as contiguous int32 GPU tensors (_upload_ints).  Only
+        shapes are checked: the values are judged on the device (status)."""
+        cv, dv, dsr, *more = self._upload_ints([control_verb, det_seqs_v, det_seqs_sr, *more])
         if cv.dim() != 2 or dv.dim() != 3 or dsr.dim() != 3 or dv.size(0) != cv.size(0) or dv.size(2) != cv.size(1) or tuple(dsr.shape[:2]) != tuple(dv.shape[:2]) or cv.size(0) == 0:
             raise RuntimeError("expected control_verb (N, MV), det_seqs_v (N, L, MV), det_seqs_sr (N, L, MS); got %s, %s, %s"
                                % (tuple(cv.shape), tuple(dv.shape), tuple(dsr.shape)))
-        return cv, dv, dsr
+        return (cv, dv, dsr, *more)
 
     def rank_plan(self, control_verb, det_seqs_v, det_seqs_sr, n_sink=None, n_verbs=None, max_items=None):
         """the scan of vsr_rank_plan -> (plan, job_verbs (S,) int64, job_roles (S,10) int32, item_gather (max_items, n_sink) int32) with
@@ -262,6 +266,59 @@ class SspEngine:
             _lib.check(self.lib.vsr_rank_captions(self.h, _ptr(cv), _ptr(dv), _ptr(dsr), N, L, MV, MS, self.N, self._keep["ssp"]["v_embed_layer.weight"].shape[0],
                                                   _ptr(seqs_perm), max_items, _ptr(rank), _ptr(status), _ptr(ws), need, self._stream()))
         return rank, status
+
+    # ---- training batches on the device (include/vsrcap.h: vsr_train_batch_plan, vsr_gather_rows)
+    def train_batch_plan(self, control_verb, det_seqs_v, det_seqs_sr, gt_seqs_v=None, gt_seqs_sr=None, idx_list=None, n_sink=10, n_verbs=None, max_items=None):
+        """vsr_train_batch_plan: the annotations (host arrays or tensors; gt_seqs_v (N, Lg, MV) / gt_seqs_sr (N, Lg, MS) and idx_list (N, L)
+        optional) -> a dict of GPU tensors at their padded sizes: verbs (N MV,) int64, det_roles / gt_roles (N MV, 10) int32 (gt_roles None
+        without gt), item_gather (Q, n_sink) int32, tr_locs / gt_locs (Q, n_sink) fp32, item_key (Q, 3) int32 (all four None without
+        idx_list; Q = max_items or N MV 10), counts (4,) int32, status (N,) int32.  Launches only: nothing is read back."""
+        if (gt_seqs_v is None) != (gt_seqs_sr is None):
+            raise RuntimeError("gt_seqs_v and gt_seqs_sr go together")
+        more = ([gt_seqs_v, gt_seqs_sr] if gt_seqs_v is not None else []) + ([idx_list] if idx_list is not None else [])
+        cv, dv, dsr, *more = self._annotations(control_verb, det_seqs_v, det_seqs_sr, *more)
+        gv, gsr = more[:2] if gt_seqs_v is not None else (None, None)
+        idx = more[-1] if idx_list is not None else None
+        N, L, MV, MS = dv.size(0), dv.size(1), dv.size(2), dsr.size(2)
+        if gv is not None and (gv.dim() != 3 or gsr.dim() != 3 or gv.size(0) != N or gv.size(2) != MV or tuple(gsr.shape) != (N, gv.size(1), MS)):
+            raise RuntimeError("expected gt_seqs_v (%d, Lg, %d) and gt_seqs_sr (%d, Lg, %d); got %s, %s" % (N, MV, N, MS, tuple(gv.shape), tuple(gsr.shape)))
+        if idx is not None:
+            idx = idx.reshape(N, -1)
+            if idx.size(1) != L:
+                raise RuntimeError("expected idx_list (%d, %d); got %s" % (N, L, tuple(idx.shape)))
+        Lg = gv.size(1) if gv is not None else 0
+        if n_verbs is None:
+            n_verbs = self._keep["ssp"]["v_embed_layer.weight"].shape[0]
+        max_items = int(max_items or 0)
+        S, Q = N * MV, max_items if max_items > 0 else N * MV * self.RANK_L
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        with torch.cuda.device(self.device):
+            out = dict(verbs=new(S, torch.int64), det_roles=new((S, self.RANK_L), torch.int32), gt_roles=new((S, self.RANK_L), torch.int32) if gv is not None else None,
+                       item_gather=None, tr_locs=None, gt_locs=None, item_key=None, counts=new(4, torch.int32), status=new(N, torch.int32))
+            if idx is not None:
+                out.update(item_gather=new((Q, int(n_sink)), torch.int32), tr_locs=new((Q, int(n_sink)), torch.float32), gt_locs=new((Q, int(n_sink)), torch.float32),
+                           item_key=new((Q, 3), torch.int32))
+            plan = torch.empty(max(1, self.lib.vsr_train_batch_plan_bytes(N, MV)), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.vsr_train_batch_plan(_ptr(cv), _ptr(dv), _ptr(dsr), _ptr(gv), _ptr(gsr), Lg, _ptr(idx), N, L, MV, MS, int(n_sink), int(n_verbs), max_items,
+                                                     _ptr(out["verbs"]), _ptr(out["det_roles"]), _ptr(out["gt_roles"]), _ptr(out["item_gather"]), _ptr(out["tr_locs"]),
+                                                     _ptr(out["gt_locs"]), _ptr(out["item_key"]), _ptr(out["counts"]), _ptr(out["status"]), _ptr(plan), plan.numel(),
+                                                     self._stream()))
+        return out
+
+    def gather_rows(self, rows, gather):
+        """vsr_gather_rows: rows (n_src, D) fp32 (D a multiple of 4), gather (...) int32, both on the GPU -> (..., D) fp32 with a zero row
+        where gather < 0"""
+        _need_gpu(rows, "rows")
+        _need_gpu(gather, "gather")
+        if rows.dim() != 2 or rows.dtype != torch.float32 or gather.dtype != torch.int32:
+            raise RuntimeError("expected rows (n_src, D) fp32 and gather int32; got %s %s, %s" % (tuple(rows.shape), rows.dtype, gather.dtype))
+        rows, gather = rows.contiguous(), gather.contiguous()
+        out = torch.empty(tuple(gather.shape) + (rows.size(1),), dtype=torch.float32, device=self.device)
+        if gather.numel() == 0:
+            return out
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.vsr_gather_rows(_ptr(rows), rows.size(0), rows.size(1), _ptr(gather), gather.numel(), _ptr(out), self._stream()))
+        return out
 
     # ---- SinkhornNet training (include/vsrcap.h: vsr_sinkhorn_train_*, vsr_sinkhorn_loc_loss)
     def _check_seq(self, seq):
