@@ -275,6 +275,21 @@ int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, const int64_t*
  * pair of buffers (the round-1..5 contract) sees the old behaviour: the next vsr_prepare*() voids the saved forward. */
 int64_t vsr_train_generation(const vsr_handle* h);
 int vsr_train_select(vsr_handle* h, int64_t generation, void* stream);
+/* A forward taken ONE STEP PER CALL (ControllableCaptioningModel.step under autograd, :117-190: a caller's own unroll from init_state - scheduled
+ * sampling, a loss on some steps only).  A tape is a saved forward like any other: one pair of buffers, one generation, differentiated by ONE
+ * vsr_train_backward through the recurrence.  One row per image, zero initial state, no verb forcing.
+ *   begin   after vsr_prepare*(beam = 1) over the region tensor the steps read; train_workspace of vsr_train_workspace_bytes(h, B, max_steps)
+ *           bytes, 1 <= max_steps <= seq_len.  Files a forward of 0 steps; vsr_train_generation() names it.
+ *   step    step n = the steps taken so far: word_in / slots (B) int64 are the word fed and the slot read (clamped and counted like
+ *           vsr_train_forward's); writes logp_words (B,V), logp_gates (B,2) and the new state h1/c1/h2/c2 (B,H).  Makes the tape current
+ *           first (vsr_train_select), so decodes and other forwards may come between two steps as long as they get other buffers.
+ *   seal    logp_words (B,T,V) / logp_gates (B,T,2): the caller's stack of the T step outputs, which must stay untouched until the
+ *           backward.  From here vsr_train_select + vsr_train_backward treat the tape as a forward of T steps; no further step.
+ * step / seal of a tape whose buffers were handed out again fail like vsr_train_select of a stale generation.  No float atomics. */
+int vsr_train_tape_begin(vsr_handle* h, int32_t max_steps, void* train_workspace, size_t train_workspace_bytes, void* stream);
+int vsr_train_tape_step(vsr_handle* h, int64_t generation, const int64_t* word_in, const int64_t* slots, float* logp_words,
+                        float* logp_gates, float* h1_out, float* c1_out, float* h2_out, float* c2_out, void* stream);
+int vsr_train_tape_seal(vsr_handle* h, int64_t generation, const float* logp_words, const float* logp_gates, void* stream);
 /* Data-parallel hook (the reference is single-device, coco_scripts/train.py:22): vsr_train_backward finishes the
  * 28 gradients in buckets, largest first, and records a HIP event after each.  bucket_of[i] = bucket of gradient i (field
  * order of vsr_weights), static.  vsr_train_wait_bucket() makes `stream` wait on the device for one bucket of the LAST

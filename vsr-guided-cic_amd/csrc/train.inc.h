@@ -21,6 +21,10 @@ struct TrainCtx {                      // (plain data + two vectors: copied into
     long long generation = 0;          // bumped by every vsr_train_forward: identifies the saved forward a backward belongs to
     int B = 0, T = 0, TB = 0, TBp = 0, Bp = 0, RLp = 0;       // B: decoder ROWS (= images x rpi); Bp: the IMAGES, padded (K of the v-bar products)
     int rpi = 1;                       // rows per image (vsr_train_forward_rows): rows b rpi .. b rpi + rpi - 1 share image b's statics
+    // a TAPE (vsr_train_tape_begin): a forward taken one step per call.  tape_max = the steps its workspace was carved for (0: a whole
+    // forward), tape_steps = the steps taken; T / TB / TBp and logp_w / logp_g are those of the steps taken once it is sealed
+    int tape_max = 0, tape_steps = 0;
+    bool sealed = false;
     float* dP_rows = nullptr;          // rpi > 1: the rows' (R, A) contributions to dP of the current step (k_attend_bwd -> k_dP_rows_sum)
     const float* logp_w = nullptr;     // caller's (B,T,V) output of the forward, needed by the backward
     const float* logp_g = nullptr;     // (B,T,2)
@@ -357,6 +361,85 @@ extern "C" size_t vsr_train_workspace_bytes_rows(const vsr_handle* h, int32_t B,
 extern "C" size_t vsr_train_workspace_bytes(const vsr_handle* h, int32_t B, int32_t T) { return vsr_train_workspace_bytes_rows(h, B, 1, T); }
 
 // ---------------------------------------------------------------------------------------------- forward with saves
+// f16x2 flavour: fp16-pair images of the A operands (all-DMA kernel); BH elements of 4 bytes per state slot
+static bool train_a_images(const vsr_handle* h, const TrainCtx& t) {
+    return h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg && t.h1s16 && (t.B * h->d.rnn_size) % 8 == 0;
+}
+// Step tt of the unroll: state slot tt -> slot tt + 1, the step's saves, its gate log-probs into lg_out (row stride lg_stride).  The body
+// of vsr_train_forward's loop over the steps; a tape (vsr_train_tape_step) takes the same step one call at a time.
+static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im, float* lg_out, long long lg_stride, hipStream_t s) {
+    Ctx& c = h->c;
+    const vsr_dims& d = h->d;
+    const vsr_weights& w = h->w;
+    const int B = t.B, H = d.rnn_size, A = d.att_size, D = d.det_feat_size;
+    const size_t BH = (size_t)B * H;
+    const float isc = im ? 32768.f : 0.f;                  // (2^15: the exponent of the unit-bounded class)
+    const int* att_exp = im ? h->h2_exps + H2A_ATT : nullptr;
+    const float *h1o = t.h1s + (size_t)tt * BH, *c1o = t.c1s + (size_t)tt * BH, *h2o = t.h2s + (size_t)tt * BH, *c2o = t.c2s + (size_t)tt * BH;
+    float *h1n = t.h1s + (size_t)(tt + 1) * BH, *c1n = t.c1s + (size_t)(tt + 1) * BH, *h2n = t.h2s + (size_t)(tt + 1) * BH, *c2n = t.c2s + (size_t)(tt + 1) * BH;
+    float* g1 = t.gates1 + (size_t)tt * B * 6 * H;
+    float* g2 = t.gates2 + (size_t)tt * B * 4 * H;
+    float *s_t = t.s_ts + (size_t)tt * BH, *g_t = t.g_ts + (size_t)tt * BH;
+    float *hA = t.hAs + (size_t)tt * B * A, *sa = t.sas + (size_t)tt * B * A, *ga = t.gas + (size_t)tt * B * A;
+    float *sent = t.sents + (size_t)tt * B * D, *att = t.atts + (size_t)tt * B * D, *alpha = t.alphas + (size_t)tt * B * (c.R + 1);
+    const int* slot = t.slot32 + (size_t)tt * B;
+    uint16_t *h1n16 = im ? t.h1s16 + (size_t)(tt + 1) * BH * 2 : nullptr, *h2n16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
+    uint16_t *s_t16 = im ? t.s_t16 : nullptr, *g_t16 = im ? t.g_t16 : nullptr, *att16 = im ? t.att16 : nullptr;
+    StepOperands o;
+    o.M = B;
+    o.h1_old = h1o; o.h2_old = h2o; o.h1_new = h1n; o.h2_new = h2n; o.s_t = s_t; o.g_t = g_t; o.att = att;
+    if (im) { o.h1_old16 = t.h1s16 + (size_t)tt * BH * 2; o.h2_old16 = t.h2s16 + (size_t)tt * BH * 2; }
+    o.h1_new16 = h1n16; o.h2_new16 = h2n16; o.s_t16 = s_t16; o.g_t16 = g_t16; o.att16 = att16;
+    {   // S1: the recurrent parts only (h2, h1 of the previous step); nothing to multiply at step 0
+        int ns = 0;
+        const long long stride = (long long)B * 6 * H;
+        if (tt > 0) {
+            GemmBuilder g;
+            add_lstm1(g, d, w, o, c.scratch, L1_H2 | L1_H1);
+            ns = g.finish(h);
+            for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
+            if (g.launch(s, h)) return fail("train S1 gemm launch failed");
+        }
+        const int nblk = d.h2_first_lstm ? 6 : 5;      // without h2 in the input the shift-gate block has no recurrent part
+        if (K > 1) hipLaunchKernelGGL(k_lstm1_train<true>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
+                           t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, K);
+        else hipLaunchKernelGGL(k_lstm1_train<false>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
+                           t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, 1);
+    }
+    {   // S2
+        GemmBuilder g;
+        add_s2(g, d, w, o, c.scratch);
+        const int ns = g.finish(h);
+        const S2Layout l = place_s2(g, d, B, c.scratch, ns);
+        if (g.launch(s, h)) return fail("train S2 gemm launch failed");
+        // (Round 5: k_gate2's work inside the attention kernel's row blocks, as in decoding, with the sentinel / s_a / the shift gate stored
+        // on the way for the backward pass: measured at no gain - 10.99-11.06 k against 10.85-11.10 k samples/s, profiles/r05_h_* - and not kept.)
+        const long long n = (long long)B * (H + A + D + A);
+        hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias,
+                           B, H, A, D, g_t, hA, sent, sa, g1, g_t16, isc);
+    }
+    launch_attend(h, s, Gate2Args{}, B, K, slot, 0, hA, sa, sent, att, alpha, att16, att_exp);
+    {   // S5
+        GemmBuilder g;
+        add_s5(g, d, w, o, c.scratch, tt > 0);
+        const int ns = g.finish(h);
+        const long long stride = (long long)B * 4 * H, stride_g = (long long)B * A;
+        float* gas = c.scratch + stride * ns;
+        g.a.p[0].slab_stride = stride;
+        g.a.p[1].C = gas; g.a.p[1].slab_stride = stride_g;
+        if (g.launch(s, h)) return fail("train S5 gemm launch failed");
+        GateLogitArgs gl{gas, ns, stride_g, hA, w.att_g_weight, c.zsum, nullptr, slot, K, c.L, B, A,
+                         lg_out, lg_stride};
+        gl.ga_out = ga;
+        const int gblocks = B;
+        if (K > 1) hipLaunchKernelGGL(k_fwd_tail<true>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
+                           w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, K);
+        else hipLaunchKernelGGL(k_fwd_tail<false>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
+                           w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, 1);
+    }
+    LAUNCHCHK();
+    return 0;
+}
 // K = rows per image: M = B K decoder rows, rows b K .. b K + K - 1 are image b's (the order of repeat_interleave(K, 0)).  Whatever is
 // per image - the hoisted projections, P, the region rows, masks and index lists - is read through row / K, as the beams of the decode
 // path do; K = 1 launches the kernels of the one-row-per-image path (the <false> instantiations).
@@ -374,10 +457,11 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
-    const int B = c.B * K, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;      // (B: decoder rows)
+    const int B = c.B * K, H = d.rnn_size, E = d.input_encoding_size, V = d.vocab_size;      // (B: decoder rows)
     TrainCtx& t = *h->tc;
     t.valid = false;
     t.rpi = K; t.B = B; t.T = T;
+    t.tape_max = t.tape_steps = 0; t.sealed = false;
     const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
     if (need > train_ws_bytes) return fail("vsr_train_forward: training workspace too small (%zu < %zu)", train_ws_bytes, need);
     drop_saved_forwards_in(h->saved, train_ws, need);       // forwards filed in THIS buffer are overwritten now
@@ -385,10 +469,7 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
     register_train_images(h, t);                           // the bf16 twins / fp16-pair images of this workspace's transposed operands
     const int TB = T * B;
     const size_t BH = (size_t)B * H;
-    // f16x2 flavour: fp16-pair images of the A operands (all-DMA kernel); BH elements of 4 bytes per state slot
-    const bool im = h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg && t.h1s16 && (B * H) % 8 == 0;
-    const float isc = im ? 32768.f : 0.f;                  // (2^15: the exponent of the unit-bounded class)
-    const int* att_exp = im ? h->h2_exps + H2A_ATT : nullptr;
+    const bool im = train_a_images(h, t);
     {   // the zero states of step 0 (and their images): one launch
         ZeroList zl;
         zl.add(t.h1s, BH * sizeof(float)); zl.add(t.c1s, BH * sizeof(float)); zl.add(t.h2s, BH * sizeof(float)); zl.add(t.c2s, BH * sizeof(float));
@@ -415,71 +496,8 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         LAUNCHCHK();
     }
 
-    for (int tt = 0; tt < T; ++tt) {
-        const float *h1o = t.h1s + (size_t)tt * BH, *c1o = t.c1s + (size_t)tt * BH, *h2o = t.h2s + (size_t)tt * BH, *c2o = t.c2s + (size_t)tt * BH;
-        float *h1n = t.h1s + (size_t)(tt + 1) * BH, *c1n = t.c1s + (size_t)(tt + 1) * BH, *h2n = t.h2s + (size_t)(tt + 1) * BH, *c2n = t.c2s + (size_t)(tt + 1) * BH;
-        float* g1 = t.gates1 + (size_t)tt * B * 6 * H;
-        float* g2 = t.gates2 + (size_t)tt * B * 4 * H;
-        float *s_t = t.s_ts + (size_t)tt * BH, *g_t = t.g_ts + (size_t)tt * BH;
-        float *hA = t.hAs + (size_t)tt * B * A, *sa = t.sas + (size_t)tt * B * A, *ga = t.gas + (size_t)tt * B * A;
-        float *sent = t.sents + (size_t)tt * B * D, *att = t.atts + (size_t)tt * B * D, *alpha = t.alphas + (size_t)tt * B * (c.R + 1);
-        const int* slot = t.slot32 + (size_t)tt * B;
-        uint16_t *h1n16 = im ? t.h1s16 + (size_t)(tt + 1) * BH * 2 : nullptr, *h2n16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
-        uint16_t *s_t16 = im ? t.s_t16 : nullptr, *g_t16 = im ? t.g_t16 : nullptr, *att16 = im ? t.att16 : nullptr;
-        StepOperands o;
-        o.M = B;
-        o.h1_old = h1o; o.h2_old = h2o; o.h1_new = h1n; o.h2_new = h2n; o.s_t = s_t; o.g_t = g_t; o.att = att;
-        if (im) { o.h1_old16 = t.h1s16 + (size_t)tt * BH * 2; o.h2_old16 = t.h2s16 + (size_t)tt * BH * 2; }
-        o.h1_new16 = h1n16; o.h2_new16 = h2n16; o.s_t16 = s_t16; o.g_t16 = g_t16; o.att16 = att16;
-        {   // S1: the recurrent parts only (h2, h1 of the previous step); nothing to multiply at step 0
-            int ns = 0;
-            const long long stride = (long long)B * 6 * H;
-            if (tt > 0) {
-                GemmBuilder g;
-                add_lstm1(g, d, w, o, c.scratch, L1_H2 | L1_H1);
-                ns = g.finish(h);
-                for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
-                if (g.launch(s, h)) return fail("train S1 gemm launch failed");
-            }
-            const int nblk = d.h2_first_lstm ? 6 : 5;      // without h2 in the input the shift-gate block has no recurrent part
-            if (K > 1) hipLaunchKernelGGL(k_lstm1_train<true>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
-                               t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, K);
-            else hipLaunchKernelGGL(k_lstm1_train<false>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
-                               t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, 1);
-        }
-        {   // S2
-            GemmBuilder g;
-            add_s2(g, d, w, o, c.scratch);
-            const int ns = g.finish(h);
-            const S2Layout l = place_s2(g, d, B, c.scratch, ns);
-            if (g.launch(s, h)) return fail("train S2 gemm launch failed");
-            // (Round 5: k_gate2's work inside the attention kernel's row blocks, as in decoding, with the sentinel / s_a / the shift gate stored
-            // on the way for the backward pass: measured at no gain - 10.99-11.06 k against 10.85-11.10 k samples/s, profiles/r05_h_* - and not kept.)
-            const long long n = (long long)B * (H + A + D + A);
-            hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias,
-                               B, H, A, D, g_t, hA, sent, sa, g1, g_t16, isc);
-        }
-        launch_attend(h, s, Gate2Args{}, B, K, slot, 0, hA, sa, sent, att, alpha, att16, att_exp);
-        {   // S5
-            GemmBuilder g;
-            add_s5(g, d, w, o, c.scratch, tt > 0);
-            const int ns = g.finish(h);
-            const long long stride = (long long)B * 4 * H, stride_g = (long long)B * A;
-            float* gas = c.scratch + stride * ns;
-            g.a.p[0].slab_stride = stride;
-            g.a.p[1].C = gas; g.a.p[1].slab_stride = stride_g;
-            if (g.launch(s, h)) return fail("train S5 gemm launch failed");
-            GateLogitArgs gl{gas, ns, stride_g, hA, w.att_g_weight, c.zsum, nullptr, slot, K, c.L, B, A,
-                             logp_gates + (size_t)tt * 2, (long long)T * 2};
-            gl.ga_out = ga;
-            const int gblocks = B;
-            if (K > 1) hipLaunchKernelGGL(k_fwd_tail<true>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
-                               w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, K);
-            else hipLaunchKernelGGL(k_fwd_tail<false>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
-                               w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, 1);
-        }
-        LAUNCHCHK();
-    }
+    for (int tt = 0; tt < T; ++tt)
+        if (train_forward_step(h, t, K, tt, im, logp_gates + (size_t)tt * 2, (long long)T * 2, s)) return 1;
     {   // S6 for all steps at once: logits = h2[(b, t)] . out_fc^T (M = T B rows gathered in (b, t) order, so that the
         // (B, T, V) log-prob tensor is written row by row), then one log_softmax launch
         GemmBuilder g;
@@ -512,6 +530,156 @@ extern "C" int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, con
                                       float* logp_words, float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
     if (rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, %d]", rows_per_image, VSR_MAX_BEAM);
     return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_words, logp_gates, train_ws, train_ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- tape: the forward, one step per call
+// ControllableCaptioningModel.step under autograd (controllable_captioning.py:117-190) is the unroll of CaptioningModel.forward (:22-36)
+// taken by the caller one step at a time.  A tape is that unroll saved as a training forward: begin carves the workspace for max_steps and
+// files a forward of 0 steps, every step appends what train_forward_step saves for it, seal sets T to the steps taken and points the
+// saved forward at the caller's stacked (B, T, .) log-probs.  vsr_train_select / vsr_train_backward then see an ordinary forward.
+// One row per image (K = 1), zero initial state.
+
+// one step's (B) int64 word / slot ids -> the step's rows of the (T, B) int32 copies (counted and clamped like k_train_indices)
+__global__ void k_tape_indices(const int64_t* __restrict__ word_in, const int64_t* __restrict__ slots, int B, int V, int L,
+                               int* __restrict__ word32, int* __restrict__ slot32, int* __restrict__ bad) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    long long w = word_in[b], k = slots[b];
+    if (w < 0 || w >= V) { atomicAdd(bad, 1); w = w < 0 ? 0 : V - 1; }
+    if (k < 0 || k >= L) { atomicAdd(bad, 1); k = k < 0 ? 0 : L - 1; }
+    word32[b] = (int)w;
+    slot32[b] = (int)k;
+}
+// the (b, t)-ordered list of the saved state rows for the T steps taken (what k_train_indices lays out for a whole forward)
+__global__ void k_tape_rows_bt(int T, int B, int* __restrict__ rows_bt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * B) return;
+    const int tt = i / B, b = i - tt * B;
+    rows_bt[b * T + tt] = (tt + 1) * B + b;
+}
+
+// makes the tape of `generation` the handle's current forward (as vsr_train_select does for a backward) and checks that it is one
+static int tape_current(vsr_handle* h, int64_t generation, const char* who, void* stream) {
+    if (!h || !h->tc) return fail("%s: null handle", who);
+    if (!h->bound) return fail("%s: weights not bound", who);
+    if (vsr_train_select(h, generation, stream)) return 1;         // (fails when the tape's buffers were handed out again)
+    if (!h->tc->tape_max) return fail("%s: generation %lld is a whole forward, not a tape", who, (long long)generation);
+    return 0;
+}
+static void tape_refile(vsr_handle* h, const TrainCtx& t) {
+    for (SavedForward& sf : h->saved->v)
+        if (sf.t.generation == t.generation) sf.t = t;
+}
+
+extern "C" int vsr_train_tape_begin(vsr_handle* h, int32_t max_steps, void* train_ws, size_t train_ws_bytes, void* stream) {
+    if (check_ready(h, "vsr_train_tape_begin")) return 1;
+    if (!train_ws) return fail("vsr_train_tape_begin: null workspace");
+    Ctx& c = h->c;
+    if (c.beam != 1 && c.Mmax != c.B) return fail("vsr_train_tape_begin: prepare() must be called with beam = 1 (a tape has one row per image)");
+    if (c.ridx && !c.rows_are_images) return fail("vsr_train_tape_begin: index-list regions with a row -> image map (row_img) are a decode-side format; training needs one row per image (row_img = NULL)");
+    if (max_steps < 1 || max_steps > h->d.seq_len) return fail("vsr_train_tape_begin: max_steps %d not in [1, seq_len %d]", max_steps, h->d.seq_len);
+    hipStream_t s = (hipStream_t)stream;
+    TrainCtx& t = *h->tc;
+    t.valid = false;
+    t.rpi = 1; t.B = c.B; t.T = max_steps;
+    const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
+    if (need > train_ws_bytes) return fail("vsr_train_tape_begin: training workspace too small (%zu < %zu)", train_ws_bytes, need);
+    drop_saved_forwards_in(h->saved, train_ws, need);
+    t.tws_lo = reinterpret_cast<const char*>(train_ws); t.tws_bytes = need;
+    register_train_images(h, t);
+    const size_t BH = (size_t)t.B * h->d.rnn_size;
+    {   // the zero states of step 0 (and their images), as in vsr_train_forward
+        ZeroList zl;
+        zl.add(t.h1s, BH * sizeof(float)); zl.add(t.c1s, BH * sizeof(float)); zl.add(t.h2s, BH * sizeof(float)); zl.add(t.c2s, BH * sizeof(float));
+        if (train_a_images(h, t)) { zl.add(t.h1s16, BH * 2 * sizeof(uint16_t)); zl.add(t.h2s16, BH * 2 * sizeof(uint16_t)); }
+        if (zl.launch(s)) return fail("vsr_train_tape_begin: zero launch failed");
+    }
+    t.tape_max = max_steps; t.tape_steps = 0; t.sealed = false;
+    t.logp_w = t.logp_g = nullptr;
+    t.valid = true;
+    t.generation = ++h->gen_counter;
+    // (stashed now, not only at the seal: a vsr_prepare*() of another batch may come between two steps, and vsr_train_select restores from here)
+    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
+    LAUNCHCHK();
+    h->saved->v.push_back(SavedForward{c, t, h->ws_lo, h->ws_bytes});
+    return 0;
+}
+
+extern "C" int vsr_train_tape_step(vsr_handle* h, int64_t generation, const int64_t* word_in, const int64_t* slots, float* logp_words,
+                                   float* logp_gates, float* h1_out, float* c1_out, float* h2_out, float* c2_out, void* stream) {
+    if (tape_current(h, generation, "vsr_train_tape_step", stream)) return 1;
+    if (!word_in || !slots || !logp_words || !logp_gates || !h1_out || !c1_out || !h2_out || !c2_out) return fail("vsr_train_tape_step: null tensor");
+    TrainCtx& t = *h->tc;
+    if (t.sealed) return fail("vsr_train_tape_step: the tape of generation %lld has been sealed", (long long)generation);
+    if (t.tape_steps >= t.tape_max) return fail("vsr_train_tape_step: the tape already holds the %d steps it was begun for", t.tape_max);
+    hipStream_t s = (hipStream_t)stream;
+    Ctx& c = h->c;
+    const vsr_dims& d = h->d;
+    const vsr_weights& w = h->w;
+    const int B = t.B, H = d.rnn_size, E = d.input_encoding_size, V = d.vocab_size, tt = t.tape_steps;
+    const size_t BH = (size_t)B * H;
+    const bool im = train_a_images(h, t);
+    int* word32 = t.word32 + (size_t)tt * B;
+    float* x = t.x_all + (size_t)tt * B * E;               // (the weight-gradient phase reads the rows of every step)
+    hipLaunchKernelGGL(k_tape_indices, dim3(cdiv(B, 256)), dim3(256), 0, s, word_in, slots, B, V, c.L, word32, t.slot32 + (size_t)tt * B, c.nvalid_dev + 2);
+    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((long long)B * E, 256)), dim3(256), 0, s, w.embed_weight, word32, B, E, x);
+    LAUNCHCHK();
+    {   // the x part of this step's LSTM1 / gate pre-activations: M = B rows into the step's rows of xproj_all
+        StepOperands xo;
+        xo.M = B;
+        xo.x = im ? w.embed_weight : x; xo.word = im ? word32 : nullptr;
+        GemmBuilder g;
+        add_lstm1(g, d, w, xo, t.scratch, L1_X);
+        const int ns = g.finish(h);
+        const long long stride = (long long)B * 6 * H;
+        if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
+        for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
+        if (g.launch(s, h)) return fail("tape x-projection gemm launch failed");
+        hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch, ns, stride, stride, t.xproj_all + (size_t)tt * B * 6 * H);
+        LAUNCHCHK();
+    }
+    if (train_forward_step(h, t, 1, tt, im, logp_gates, 2, s)) return 1;
+    {   // S6 of this step: the new h2 (state slot tt + 1) -> the caller's (B, V) log-probs
+        StepOperands vo;
+        vo.M = B;
+        vo.h2_new = t.h2s + (size_t)(tt + 1) * BH; vo.h2_new16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
+        GemmBuilder g;
+        add_vocab(g, d, w, vo, t.scratch);
+        const int ns = g.finish(h);
+        const long long stride = (long long)B * V;
+        if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns);
+        g.a.p[0].slab_stride = stride;
+        if (g.launch(s, h)) return fail("tape S6 gemm launch failed");
+        const GateLogitArgs no_gate{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr, 0};
+        StepIO io;
+        io.M = B; io.vmode = VM_FULL; io.full_out = logp_words; io.full_stride = V;
+        launch_vocab(h, s, io, t.scratch, ns, stride, no_gate);
+        LAUNCHCHK();
+    }
+    const float* src[4] = {t.h1s, t.c1s, t.h2s, t.c2s};
+    float* dst[4] = {h1_out, c1_out, h2_out, c2_out};
+    for (int j = 0; j < 4; ++j) HIPCHK(hipMemcpyAsync(dst[j], src[j] + (size_t)(tt + 1) * BH, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
+    t.tape_steps = tt + 1;
+    tape_refile(h, t);
+    return 0;
+}
+
+extern "C" int vsr_train_tape_seal(vsr_handle* h, int64_t generation, const float* logp_words, const float* logp_gates, void* stream) {
+    if (tape_current(h, generation, "vsr_train_tape_seal", stream)) return 1;
+    if (!logp_words || !logp_gates) return fail("vsr_train_tape_seal: null tensor");
+    TrainCtx& t = *h->tc;
+    if (t.tape_steps < 1) return fail("vsr_train_tape_seal: the tape holds no step");
+    hipStream_t s = (hipStream_t)stream;
+    const int T = t.tape_steps, TB = T * t.B;
+    t.T = T; t.TB = TB; t.TBp = (int)up4((size_t)TB);       // (<= what the workspace was carved for: tape_steps <= tape_max)
+    hipLaunchKernelGGL(k_tape_rows_bt, dim3(cdiv(TB, 256)), dim3(256), 0, s, T, t.B, t.rows_bt);
+    t.logp_w = logp_words;
+    t.logp_g = logp_gates;
+    t.sealed = true;
+    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
+    LAUNCHCHK();
+    tape_refile(h, t);
+    return 0;
 }
 
 // Identity of the saved forward pass (0 = none).  The training workspace holds ONE forward at a time: a caller that keeps
@@ -586,6 +754,7 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     if (check_ready(h, "vsr_train_backward")) return 1;
     TrainCtx& t = *h->tc;
     if (!t.valid) return fail("vsr_train_backward: no saved forward (call vsr_train_forward first)");
+    if (t.tape_max && !t.sealed) return fail("vsr_train_backward: the current forward is a tape of %d steps that has not been sealed (vsr_train_tape_seal)", t.tape_steps);
     if (!grad_logp_words || !grad_logp_gates || !grads) return fail("vsr_train_backward: null tensor");
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;

@@ -120,6 +120,8 @@ class ControllableCaptioningModel(CaptioningModel):
         self._eng = None
         self._verb_dev = None
         self._wgen = 0                   # the weights' generation (module comment above)
+        from vsrcap.steptape import Lineage
+        self._lineage = Lineage()        # which manual step() loop a grad-enabled step belongs to
         _count_optimizer_steps()
         # prepare() caches the hoisted per-image tensors keyed on (data_ptr, tensor._version, shapes, weights generation);
         # set force_prepare = True when inputs / weights are rewritten in ways that do not bump _version
@@ -189,7 +191,8 @@ class ControllableCaptioningModel(CaptioningModel):
 
     def init_state(self, b_s, device):
         z = lambda: torch.zeros((b_s, self.rnn_size), dtype=torch.float32, device=device)
-        return (z(), z()), (z(), z()), torch.zeros((b_s,), dtype=torch.long, device=device)
+        # (recorded: a grad-enabled step() on this state opens a tape - vsrcap/steptape.py)
+        return self._lineage.note_init(((z(), z()), (z(), z()), torch.zeros((b_s,), dtype=torch.long, device=device)))
 
     # ------------------------------------------------------------------ engine plumbing
     def _engine(self, device, weights_may_have_moved=False):
@@ -333,6 +336,8 @@ class ControllableCaptioningModel(CaptioningModel):
 
     def _step(self, t, state, prev_outputs, statics, seqs, mode, with_verbs, gt):
         assert (mode in ['teacher_forcing', 'feedback'])
+        if self._builds_graph():
+            return self._step_taped(t, state, prev_outputs, statics, seqs, mode, with_verbs)
         det = statics[0]
         eng = self._engine(det.device)
         if mode == 'teacher_forcing':
@@ -347,6 +352,55 @@ class ControllableCaptioningModel(CaptioningModel):
         B = self._prepare(eng, det, statics[1], 1)
         v = self._verbs(eng, statics[2], det.device, B, self._n_slots(statics[1])) if with_verbs else None
         return eng.step(t, 1, prev_outputs, state, v, gt)
+
+    def _step_taped(self, t, state, prev_outputs, statics, seqs, mode, with_verbs):
+        """step() with a graph: the call appends to a tape, a training forward saved one step at a time which ONE hand-written backward
+        differentiates through the recurrence (vsrcap/steptape.py has the rules, vsrcap/train.py the autograd nodes).  What a tape
+        cannot express raises; nothing returns tensors without a grad_fn."""
+        from vsrcap import steptape, train
+        from vsrcap.regions import IndexedRegions
+        if with_verbs:
+            raise steptape.TapeError("step_v (verb forcing) is not differentiable here")
+        det = statics[0]
+        teacher = mode == 'teacher_forcing'
+        regions = seqs[1] if teacher else statics[1]
+        tape = self._lineage.resolve(state)
+        n = 0 if tape is None else tape.steps
+        if t != n:
+            raise steptape.TapeError("step(t=%d) on a state that has taken %d steps from init_state() (step n of a loop is called with t = n)" % (t, n))
+        key = (det.data_ptr(), regions.data_ptr() if torch.is_tensor(regions) else id(regions))      # the statics the loop was opened on
+        if tape is None:
+            if isinstance(regions, IndexedRegions) and regions.row_img is not None:
+                raise RuntimeError("training on IndexedRegions needs one decoder row per image (row_img=None), as the reference's "
+                                   "training batches have; with a row -> image map train on regions.dense()")
+            eng = self._engine(det.device, weights_may_have_moved=True)
+            B = self._prepare(eng, det, regions, 1, for_training=True)        # once per loop: step n reads slot n of it (teacher forcing)
+            limit = min(self.seq_len, self._n_slots(regions)) if teacher else self.seq_len
+            tape, token = train.tape_open(self, eng, det.device, B, limit, key)
+            self._lineage.register(tape)
+        else:
+            if key != tape.statics_key:
+                raise steptape.TapeError("the detections / region sequences differ from those of the loop's first step (the hoisted "
+                                         "projections are computed once per loop)")
+            self._engine(det.device)
+            token = None
+        (h1, c1), (h2, c2), slot = state
+        B, L = h1.size(0), self._n_slots(regions)
+        if teacher:
+            # word of step t, slot t (controllable_captioning.py:131-133)
+            word, slot_in, slot_out = seqs[0][:, t], torch.full((B,), t, dtype=torch.int64, device=det.device), slot
+        elif t == 0:
+            word, slot_in = torch.full((B,), self.bos_idx, dtype=torch.int64, device=det.device), slot
+            slot_out = slot_in
+        else:
+            # previous word; the slot pointer moves by the previous gate, clamped (:134-142)
+            word = prev_outputs[0]
+            slot_in = torch.clamp(slot + prev_outputs[1].to(slot.dtype), 0, L - 1)
+            slot_out = slot_in
+        out, gate, n1, m1, n2, m2 = train.tape_step(tape, word, slot_in, token, (h1, c1, h2, c2))
+        new_state = ((n1, m1), (n2, m2), slot_out)
+        tape.advance(new_state)
+        return (out, gate), new_state
 
     def test(self, detections, ctrl_det_seqs_test):
         return super().test((detections, ctrl_det_seqs_test))

@@ -415,20 +415,7 @@ class Engine:
         into: optional list of 28 caller tensors (e.g. views of ONE flat buffer, parallel.FlatGrads) the library writes
         the gradients to instead of fresh allocations."""
         if generation is not None:
-            # several forwards may be alive (each in its own slot): make this one the handle's current forward again
-            if self.lib.vsr_train_select(self.h, int(generation), self._stream(device)) != 0:
-                raise RuntimeError(
-                    "backward of a forward pass whose saved activations are gone (%s). A forward stays differentiable until its "
-                    "buffers are reused: that happens once it HAS been differentiated (a second backward needs a new forward - "
-                    "retain_graph=True is not supported across a later forward), when more than %d forwards are alive, or when "
-                    "the compute dtype / the parameters' storage changed in between."
-                    % (self.lib.vsr_last_error().decode(), MAX_LIVE_FORWARDS))
-            if self._slot.generation != generation:
-                for sl in self._slots:
-                    if sl.generation == generation:
-                        self._slot = sl
-                        self._prep_key = None           # the handle's hoisted state is this slot's now
-                        break
+            self._make_current(device, generation, "backward of a forward pass")
             self._slot.differentiated = True
         grad_out = _f32(grad_out, "grad of word log-probs")
         grad_gate = _f32(grad_gate, "grad of gate log-probs")
@@ -442,6 +429,61 @@ class Engine:
         g = _lib.VsrWeights(*[t.data_ptr() for t in grads])
         _lib.check(self.lib.vsr_train_backward(self.h, _ptr(grad_out), _ptr(grad_gate), C.byref(g), self._stream(device)))
         return grads
+
+    def _make_current(self, device, generation, who):
+        """several forwards may be alive (each in its own slot): make this one the handle's current forward again"""
+        if self.lib.vsr_train_select(self.h, int(generation), self._stream(device)) != 0:
+            raise RuntimeError(
+                "%s whose saved activations are gone (%s). A forward stays differentiable until its "
+                "buffers are reused: that happens once it HAS been differentiated (a second backward needs a new forward - "
+                "retain_graph=True is not supported across a later forward), when more than %d forwards are alive, or when "
+                "the compute dtype / the parameters' storage changed in between."
+                % (who, self.lib.vsr_last_error().decode(), MAX_LIVE_FORWARDS))
+        if self._slot.generation != generation:
+            for sl in self._slots:
+                if sl.generation == generation:
+                    self._slot = sl
+                    self._prep_key = None           # the handle's hoisted state is this slot's now
+                    break
+
+    # ------------------------------------------------------------------ tape: a training forward taken one step per call (vsrcap/steptape.py)
+    @_on_device
+    def tape_begin(self, B, device, max_steps):
+        """after prepare(beam = 1, for_training=True): files a forward of 0 steps in the current slot; returns (generation, token) - the
+        token keeps the slot's buffers reserved exactly as a forward's does (note_forward)"""
+        need = self.lib.vsr_train_workspace_bytes(self.h, B, int(max_steps))
+        if need == 0:
+            raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
+        if self._slot.live():
+            raise RuntimeError("internal: tape into a slot that holds a live forward (prepare(for_training=True) first)")
+        if self._tws is None or self._tws.numel() < need or self._tws.device != device:
+            self._tws = torch.empty(need, dtype=torch.uint8, device=device)
+        _lib.check(self.lib.vsr_train_tape_begin(self.h, int(max_steps), _ptr(self._tws), self._tws.numel(), self._stream(device)))
+        self._slot.generation = self.train_generation()
+        return self._slot.generation, self.note_forward()
+
+    @_on_device
+    def tape_step(self, device, generation, B, word, slot):
+        """word / slot (B) ids of this step -> (logp_words (B,V), logp_gates (B,2), (h1, c1, h2, c2)), all fresh tensors; B: the tape's rows"""
+        self._make_current(device, generation, "step of a manual loop")
+        word = word.to(device=device, dtype=torch.int64).contiguous()
+        slot = slot.to(device=device, dtype=torch.int64).contiguous()
+        H, V = self.dims.rnn_size, self.dims.vocab_size
+        if tuple(word.shape) != (B,) or tuple(slot.shape) != (B,):
+            raise RuntimeError("step of a manual loop of %d rows: got word ids %s and slots %s" % (B, tuple(word.shape), tuple(slot.shape)))
+        lw = torch.empty(B, V, dtype=torch.float32, device=device)
+        lg = torch.empty(B, 2, dtype=torch.float32, device=device)
+        st = tuple(torch.empty(B, H, dtype=torch.float32, device=device) for _ in range(4))
+        _lib.check(self.lib.vsr_train_tape_step(self.h, int(generation), _ptr(word), _ptr(slot), _ptr(lw), _ptr(lg), _ptr(st[0]),
+                                                _ptr(st[1]), _ptr(st[2]), _ptr(st[3]), self._stream(device)))
+        self.raise_on_bad_ids(device, "step")
+        return lw, lg, st
+
+    @_on_device
+    def tape_seal(self, device, generation, out, gate):
+        """out (B,T,V) / gate (B,T,2): the stacked step outputs; the library reads them in train_backward(generation=...)"""
+        self._make_current(device, generation, "backward of a manual loop")
+        _lib.check(self.lib.vsr_train_tape_seal(self.h, int(generation), _ptr(out), _ptr(gate), self._stream(device)))
 
     def bucket_map(self):
         """(bucket_of[28] in WEIGHT_FIELDS order, n_buckets): completion order of the gradients in vsr_train_backward"""

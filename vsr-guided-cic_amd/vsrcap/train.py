@@ -9,6 +9,7 @@ Callers reproduced:
 import torch
 
 from . import _lib
+from . import steptape
 
 _PARAM_KEYS = [k for _, k in _lib.WEIGHT_FIELDS]
 
@@ -65,3 +66,98 @@ def sample_logprobs_with_grad(model, eng, det, ctrl, outs, lps, rows_per_image=1
     lp_w = out.gather(2, words.unsqueeze(-1)).squeeze(-1)
     lp_g = gate.gather(2, gates.unsqueeze(-1)).squeeze(-1)
     return lp_w, lp_g
+
+
+# ---------------------------------------------------------------------------------------------------- step() under autograd
+# A manual loop over step() (controllable_captioning.py:117-190 called as CaptioningModel.forward :22-36 calls it) is taped: ONE saved
+# forward that grows by a step per call (include/vsrcap.h, vsr_train_tape_begin) and ONE vsr_train_backward for the whole loop, the
+# recurrence differentiated inside the library as for forward().  torch sees:
+#   _TapeRootFn(28 parameters) -> token             its backward runs after every step's: stacks, seals, calls the BPTT, returns 28 gradients
+#   _TapeStepFn(token | state of the step before) -> (out, gate, h1, c1, h2, c2)       its backward only files the step's g_out / g_gate
+# Step 0 hangs on the root's token, step n on the state tensors step n - 1 returned, so the root is reached through the chain.  State
+# gradients are out of scope: a step returns None for them and raises when one arrives.
+class StepTape(steptape.Tape):
+    """one tape: the lineage record (steptape.Tape) plus what the library and the root's backward need"""
+
+    def __init__(self, eng, device, B, max_steps, statics_key):
+        super().__init__(max_steps)
+        self.eng, self.device, self.B = eng, device, B
+        self.statics_key = statics_key
+        self.generation, self.token = eng.tape_begin(B, device, max_steps)
+        self.outs, self.gates = [], []       # the steps' raw outputs (no grad_fn: the tape must not hold its own graph)
+        self.filed = {}                      # step -> (g_out, g_gate) of the backward in progress
+        self.stacked = None                  # the (B,T,.) tensors the sealed forward points at
+
+
+def _no_double_backward(what):
+    if torch.is_grad_enabled():
+        raise RuntimeError("%s: create_graph=True is not supported - the backward of a manual step() loop is hand-written and not itself "
+                           "differentiable. %s" % (what, steptape.ALTERNATIVE))
+
+
+class _TapeRootFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tape, *params):
+        ctx.tape = tape
+        ctx.shapes = [tuple(p.shape) for p in params]
+        token = torch.zeros((), dtype=torch.float32, device=tape.device)
+        ctx.save_for_backward(token)         # (a second backward without retain_graph fails in autograd, as for _DecoderFn)
+        return token
+
+    @staticmethod
+    def backward(ctx, g_token):
+        _no_double_backward("backward of a step() loop")
+        ctx.saved_tensors
+        tape = ctx.tape
+        eng, T = tape.eng, len(tape.outs)
+        out, gate = torch.stack(tape.outs, 1), torch.stack(tape.gates, 1)
+        g_out, g_gate = torch.zeros_like(out), torch.zeros_like(gate)          # steps that got no gradient: zeros
+        for tt, (go, gg) in tape.filed.items():
+            if go is not None:
+                g_out[:, tt] = go
+            if gg is not None:
+                g_gate[:, tt] = gg
+        tape.filed = {}
+        tape.stacked = (out, gate)
+        tape.closed = True
+        eng.tape_seal(tape.device, tape.generation, out, gate)
+        sink = eng.grad_sink
+        grads = eng.train_backward(tape.device, g_out, g_gate, ctx.shapes, tape.generation, into=sink)
+        if sink is not None:
+            return (None,) * (1 + len(grads))
+        return (None,) + tuple(grads)
+
+
+class _TapeStepFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tape, word, slot, token, h1, c1, h2, c2):
+        ctx.set_materialize_grads(False)
+        ctx.tape, ctx.tt = tape, tape.steps
+        ctx.has_token = token is not None
+        lw, lg, st = tape.eng.tape_step(tape.device, tape.generation, tape.B, word, slot)
+        tape.outs.append(lw)
+        tape.gates.append(lg)
+        return (lw.detach(), lg.detach()) + st
+
+    @staticmethod
+    def backward(ctx, g_out, g_gate, *g_state):
+        _no_double_backward("backward of a step() loop")
+        if any(g is not None for g in g_state):
+            raise RuntimeError("step() under autograd: a gradient arrived for a state tensor that step %d returned; gradients with "
+                               "respect to the recurrent state are not computed (the loss may use the steps' outputs only). %s"
+                               % (ctx.tt, steptape.ALTERNATIVE))
+        if g_out is not None or g_gate is not None:
+            ctx.tape.filed[ctx.tt] = (g_out, g_gate)
+        g_token = torch.zeros((), dtype=torch.float32, device=ctx.tape.device) if ctx.has_token else None
+        return (None, None, None, g_token, None, None, None, None)
+
+
+def tape_open(model, eng, device, B, max_steps, statics_key):
+    """prepare(for_training=True) has been called: begins a tape; returns (tape, token) - the token is the first step's anchor"""
+    tape = StepTape(eng, device, B, max_steps, statics_key)
+    return tape, _TapeRootFn.apply(tape, *_params_in_abi_order(model))
+
+
+def tape_step(tape, word, slot, token, state4):
+    """appends a step; token: the root's (step 0) or None (the state tensors carry the chain).  -> (out, gate, h1, c1, h2, c2)"""
+    return _TapeStepFn.apply(tape, word, slot, token, *state4)
