@@ -88,6 +88,14 @@ const char* vsr_last_error(void);
 /* replaces ControllableCaptioningModel.__init__ shape bookkeeping (:11-70) */
 int vsr_create(const vsr_dims* dims, vsr_handle** out);
 void vsr_destroy(vsr_handle* h);
+/* borrows the 28 tensors.  What the handle derives from them forms one chain: bound pointers -> flavour (bf16 copies | vsr_set_gemm_mode
+ * | fp16-pair images) -> decode cache -> the statics of vsr_prepare*().  Two rules hold for every call that moves a link:
+ *   a flavour TRANSITION (bf16 on <-> off, f16x2 on <-> off, a change of vsr_set_gemm_mode, new weight pointers here) voids the decode
+ *   cache, every saved training forward and the prepared statics;
+ *   a REFRESH while the flavour is already on (vsr_refresh_bf16_weights / vsr_refresh_h2_weights again) voids the decode cache and the
+ *   prepared statics and keeps the saved forwards (a training step refreshes, then differentiates).
+ * Voided statics: vsr_prepare*() again, or the next decode / training call fails with a message.  Binding also switches the bf16 and
+ * f16x2 flavours off until their refresh is called again. */
 int vsr_bind_weights(vsr_handle* h, const vsr_weights* w);
 /* verb_2_vob_all table of step_v (:25-34, :283-292) as CSR: ids of verb v are
  * vocab_ids[row_ptr[v] .. row_ptr[v+1]); verbs >= n_verbs have no entry.  DEVICE pointers, borrowed. */
@@ -96,8 +104,9 @@ int vsr_set_verb_table(vsr_handle* h, const int32_t* row_ptr, const int32_t* voc
 /* ---- decode cache (optional, inference) ----------------------------------------------------------------
  * (V, 6H) projection of the embedding table through the x columns of lstm_cell_1.weight_ih / W1_is / W1_ig
  * (step :147-152, :181): weight-only work, so it is hoisted out of the call.  The buffer is caller-owned and must
- * outlive its use; vsr_bind_weights() or vsr_build_decode_cache(h, NULL, ...) drops it.  Rebuild after the
- * weights change (the training calls never use it). */
+ * outlive its use.  Dropped by vsr_build_decode_cache(h, NULL, ...) (no launch) and by every flavour transition and every refresh
+ * (vsr_bind_weights has the rules): build it last, in the final flavour.  A write to the weights that no such call follows (the fp32
+ * flavours have no refresh) leaves it stale: drop or rebuild it (the training calls never use it). */
 size_t vsr_decode_cache_floats(const vsr_handle* h);
 int vsr_build_decode_cache(vsr_handle* h, float* buffer, size_t n_floats, void* stream);
 
@@ -107,7 +116,8 @@ int vsr_build_decode_cache(vsr_handle* h, float* buffer, size_t n_floats, void* 
  * (v_mfma_f32_32x32x16_bf16) with fp32 accumulation; states, activations, reductions, losses, gradients and the master
  * weights stay fp32.  vsr_refresh_bf16_weights(h, buffer, ...) converts the 14 weight matrices into the caller's buffer
  * (vsr_bf16_weight_bytes) and switches the handle to bf16; call it again after every weight update (the copies are not
- * borrowed views).  buffer = NULL switches back to fp32.  Sizes must be multiples of 8 in this mode. */
+ * borrowed views).  buffer = NULL switches back to fp32.  Sizes must be multiples of 8 in this mode.  Switching on or off is a flavour
+ * transition, a further call while on a refresh (vsr_bind_weights has what each voids): vsr_prepare*() again after either. */
 size_t vsr_bf16_weight_bytes(const vsr_handle* h);
 int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t bytes, void* stream);
 
@@ -117,8 +127,8 @@ int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t bytes, void* st
  * fp32 rounding of the product.  Operands stay fp32 in memory (no copies).  Routing by the rows of a launch (csrc/vsrcap.hip,
  * GemmBuilder::finish): at most 80 rows (VSR_X3S_MAX) the weight-streaming kernel of gemm_x3s.h; up to 128 rows the 128 x 128 tile of
  * gemm_x3.h; 129 .. 192 rows the exact kernels of gemm_f32.h; from 193 rows (VSR_X3_MIN_ROWS) the 128 x 256 tile.  The flavours are
- * not bit-identical (different summation orders); every parity test runs in each of them (tests/conftest.py).  A change of mode voids
- * the decode cache, a saved training forward and the hoisted projections: call vsr_prepare*() again. */
+ * not bit-identical (different summation orders); every parity test runs in each of them (tests/conftest.py).  A change of mode is a
+ * flavour transition (vsr_bind_weights has what it voids): call vsr_prepare*() again. */
 int vsr_set_gemm_mode(vsr_handle* h, int32_t mode);
 
 /* ---- "f16x2": the fp32 flavour with three MFMAs per product and weights that are never split in a kernel (csrc/gemm_h2.h) ------
@@ -134,7 +144,8 @@ int vsr_set_gemm_mode(vsr_handle* h, int32_t mode);
  * and the gradients of the backward pass are scaled and split inside the kernel (csrc/gemm_h2.h), the gradients by bounds the
  * kernels that write them measure on the device.  Error against fp64 (tests/test_gpu_h2.py, next to the fma chain and f32x3): the
  * accumulation's, not the split's.  Call it again after every weight update (the images are not views); buffer = NULL: back to
- * mode 1 everywhere.  Sizes must be multiples of 8.  Turning it on or off voids what a change of mode voids.
+ * mode 1 everywhere.  Sizes must be multiples of 8.  Turning it on or off is a flavour transition, a further call while on a refresh
+ * (vsr_bind_weights has what each voids; the refresh also resets the bounds vsr_prepare*() measures): vsr_prepare*() again after either.
  * Limits: (1) a state handed to vsr_step by the caller is taken as unit-bounded (|h| < 1, what sigmoid x tanh produces; scale 2^15):
  * values of |h| >= 2 overflow fp16 - they are counted into vsr_bad_ids()'s count; the f32x3 / f32 flavours accept any state.  (2) The backward pass keeps the measured bounds of its
  * gradient operands in 8 slots per timestep of a 512-slot device table: up to T = 62 timesteps it runs on the f16x2 kernels, from

@@ -147,6 +147,79 @@ def test_bf16_mode_refreshes_its_copies_under_a_fused_optimizer(gemm_flavour):
     np.testing.assert_allclose(runs[0], runs[1], atol=5e-6, rtol=2e-5)      # (1-ulp differences of the two Adam kernels, amplified by the bf16 rounding of the copies)
 
 
+def _decode(m, det, ctrl):
+    """greedy ids, and the ids and log-probs of a seeded sample, without a graph and in whatever mode the model is in"""
+    with torch.no_grad():
+        words, gates = m.test(det, ctrl)
+        (sw, sg), (lw, lg) = m.sample_rl(det, ctrl, seed=7)
+    return words, gates, sw, sg, lw, lg
+
+
+def _fresh_like(m, cfg):
+    """a new model of m's current weights, in m's mode and compute dtype"""
+    fresh = helpers.build_model(cfg, {k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}, DEV)
+    return fresh.set_compute_dtype(m.compute_dtype).train(m.training)
+
+
+def test_train_mode_decode_after_an_eval_mode_decode_reads_the_trained_weights():
+    """The reference's training script alternates eval and train epochs: an eval-mode decode builds the decode cache, then train() and an
+    optimizer step move the weights, then sample_rl (the SCST caller) / test() decode in train mode.  That decode must read the stepped
+    weights, not embedding projections cached before the step: ids equal to and log-probs bitwise those of a fresh model of the final
+    weights in the same mode."""
+    cfg, w, det, ctrl_seq, caps, gts = _fixture()
+    ctrl = ctrl_seq[:, :cfg["L"]].contiguous()
+    m = helpers.build_model(cfg, w, DEV)          # eval mode
+    with torch.no_grad():
+        w0, g0 = m.test(det, ctrl)                # builds the cache
+        lp0 = m.sample_rl(det, ctrl, seed=7, forced=(w0, g0))[1]
+    _train(m, OPTS["adam"](fused=True), det, ctrl_seq, caps, gts, 1)
+    assert m.training
+    got = _decode(m, det, ctrl)
+    fresh = _fresh_like(m, cfg)
+    want = _decode(fresh, det, ctrl)
+    with torch.no_grad():
+        lp1 = fresh.sample_rl(det, ctrl, seed=7, forced=(w0, g0))[1]
+    moved = max((a - b).abs().max().item() for a, b in zip(lp0, lp1))
+    print("log-probs of the first greedy path moved by %.3e" % moved)
+    assert moved > 1e-3, "the step must move the log-probs of the greedy path, or the comparison below cannot fail"
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+
+
+def test_train_mode_decode_after_invalidate_cache_reads_the_edited_weights():
+    """the same through the documented call: eval-mode decode, a p.data edit, invalidate_cache(), train(), decode"""
+    cfg, w, det, ctrl_seq, caps, gts = _fixture()
+    ctrl = ctrl_seq[:, :cfg["L"]].contiguous()
+    m = helpers.build_model(cfg, w, DEV)
+    _decode(m, det, ctrl)
+    for p in m.parameters():
+        p.data.mul_(1.05)
+    m.invalidate_cache()
+    m.train()
+    got = _decode(m, det, ctrl)
+    want = _decode(_fresh_like(m, cfg), det, ctrl)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+
+
+def test_compute_dtype_switch_between_two_eval_decodes(gemm_flavour):
+    """every decode after set_compute_dtype() == a fresh model constructed in that dtype: flavour, images / copies and the decode cache
+    are redone in the chain's order (vsrcap/derived.py)"""
+    if gemm_flavour not in (None, "f16x2"):
+        pytest.skip("picks its own compute dtypes: run once")
+    cfg, w, det, ctrl_seq, caps, gts = _fixture()
+    ctrl = ctrl_seq[:, :cfg["L"]].contiguous()
+    want = {}
+    for chain in (("f16x2", "bf16", "f16x2"), ("f32", "f32x3")):
+        m = helpers.build_model(cfg, w, DEV)
+        for dtype in chain:
+            m.set_compute_dtype(dtype)
+            if dtype not in want:
+                want[dtype] = _decode(_fresh_like(m, cfg), det, ctrl)
+            for a, b in zip(_decode(m, det, ctrl), want[dtype]):
+                assert torch.equal(a, b), (chain, dtype)
+
+
 def test_inputs_created_under_inference_mode():
     """tensors made under torch.inference_mode() track no version counter: prepare() must not read it (it raised in round 5), and such
     inputs are never served from the prepare cache (an in-place rewrite would be invisible)"""

@@ -311,6 +311,16 @@ extern "C" int vsr_profile_end(vsr_handle* h, void* stream, double* gemm_ms, int
     return 0;
 }
 
+// ---- derived from the weights: bound pointers -> flavour (bf16 copies | x3 switch | fp16-pair images) -> decode cache -> prepared statics.
+// VOID_REFRESH: copies / images rebuilt in the same flavour: cache and statics are of older weights; the saved forwards stay (a training
+// step refreshes, then differentiates).  VOID_FLAVOUR: flavour or weight pointers changed: a saved forward is not differentiated in another.
+enum VoidLevel { VOID_REFRESH, VOID_FLAVOUR };
+static void void_derived(vsr_handle* h, VoidLevel level) {
+    h->xproj = nullptr;
+    h->prepared = false;              // vsr_prepare*() again (check_ready says so)
+    if (level == VOID_FLAVOUR) { invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved); }
+}
+
 extern "C" int vsr_bind_weights(vsr_handle* h, const vsr_weights* w) {
     if (!h || !w) return fail("vsr_bind_weights: null argument");
     const float* const* p = reinterpret_cast<const float* const*>(w);
@@ -318,9 +328,8 @@ extern "C" int vsr_bind_weights(vsr_handle* h, const vsr_weights* w) {
         if (!p[i]) return fail("vsr_bind_weights: weight pointer %zu is null", i);
     h->w = *w;
     h->bound = true;
-    invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved);     // saved forwards were taken with the old tensors
-    h->xproj = nullptr;               // a cache built for other weight pointers is void
-    if (h->bf16_on) {                 // ... and so are the bf16 copies: back to fp32 until vsr_refresh_bf16_weights is called again
+    void_derived(h, VOID_FLAVOUR);    // cache, statics and saved forwards were taken with the old tensors
+    if (h->bf16_on) {                 // ... and so were the bf16 copies: back to fp32 until vsr_refresh_bf16_weights is called again
         h->bf16_on = false;
         h->b16.erase(h->b16.begin(), h->b16.begin() + h->b16_weights);
         h->b16_weights = 0;
@@ -328,7 +337,6 @@ extern "C" int vsr_bind_weights(vsr_handle* h, const vsr_weights* w) {
     if (h->h2_on) {                   // ... and the fp16-pair images (vsr_refresh_h2_weights)
         h->h2_on = false;
         h->h2.clear(); h->h2t.clear();
-        h->prepared = false;
     }
     return 0;
 }
@@ -395,11 +403,10 @@ extern "C" size_t vsr_bf16_weight_bytes(const vsr_handle* h) {
 extern "C" int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t bytes, void* stream) {
     if (!h) return fail("vsr_refresh_bf16_weights: null handle");
     if (!buffer) {                                          // back to the fp32 parity mode
+        if (h->bf16_on) void_derived(h, VOID_FLAVOUR);
         h->bf16_on = false;
         h->b16.erase(h->b16.begin(), h->b16.begin() + h->b16_weights);     // the weight copies only: the training workspace's twins stay registered
         h->b16_weights = 0;
-        h->xproj = nullptr;                                 // a decode cache built in the other precision is void
-        invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved);      // a saved forward of the other precision cannot be differentiated in this one
         return 0;
     }
     if (!h->bound) return fail("vsr_refresh_bf16_weights: weights not bound");
@@ -423,10 +430,7 @@ extern "C" int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t byte
     h->b16_weights = h->b16.size();
     h->b16.insert(h->b16.end(), keep.begin(), keep.end());
     LAUNCHCHK();
-    if (!h->bf16_on) {
-        h->xproj = nullptr;
-        invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved);      // (as above: the GEMM precision of a saved forward and its backward must match)
-    }
+    void_derived(h, h->bf16_on ? VOID_REFRESH : VOID_FLAVOUR);
     h->bf16_on = true;
     return 0;
 }
@@ -468,7 +472,7 @@ __global__ void k_h2_prepare_exps(const unsigned* __restrict__ bounds, int R0, i
 extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes, void* stream) {
     if (!h) return fail("vsr_refresh_h2_weights: null handle");
     if (!buffer) {                                          // back to f32x3 for every launch
-        if (h->h2_on) { h->xproj = nullptr; invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved); h->prepared = false; }
+        if (h->h2_on) void_derived(h, VOID_FLAVOUR);
         h->h2_on = false;
         h->h2.clear(); h->h2t.clear();
         return 0;
@@ -532,8 +536,7 @@ extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes,
     hipLaunchKernelGGL(k_f32_to_h2_multi, dim3(blocks), dim3(256), 0, s, mc, reinterpret_cast<uint32_t*>(out), exps);
     LAUNCHCHK();
     h->h2_exps = exps; h->h2_bounds = bounds;
-    if (!h->h2_on) { h->xproj = nullptr; invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved); }
-    h->prepared = false;              // the bounds of the region / detection operands are measured by vsr_prepare*()
+    void_derived(h, h->h2_on ? VOID_REFRESH : VOID_FLAVOUR);      // (the bounds of the region / detection operands are measured by vsr_prepare*())
     h->h2_on = true;
     return 0;
 }
@@ -544,11 +547,7 @@ extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes,
 extern "C" int vsr_set_gemm_mode(vsr_handle* h, int32_t mode) {
     if (!h) return fail("vsr_set_gemm_mode: null handle");
     if (mode != 0 && mode != 1) return fail("vsr_set_gemm_mode: mode %d not in {0, 1}", mode);
-    if (h->x3_on != (mode == 1)) {
-        h->xproj = nullptr;                                // the decode cache is rebuilt in the new flavour,
-        invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved);     // a saved forward of the other flavour is not differentiated in this one,
-        h->prepared = false;                               // and the hoisted projections are redone: call vsr_prepare*() after a switch
-    }
+    if (h->x3_on != (mode == 1)) void_derived(h, VOID_FLAVOUR);
     h->x3_on = mode == 1;
     return 0;
 }

@@ -15,7 +15,9 @@ import torch
 from torch import nn
 
 from .CaptioningModel import CaptioningModel
+from vsrcap import _lib
 from vsrcap.engine import Engine
+from vsrcap.regions import IndexedRegions
 
 
 # GEMM flavour a new model starts in (all three keep fp32 operands in memory and accumulate in fp32):
@@ -32,7 +34,8 @@ COMPUTE_DTYPES = ('f32', 'f32x3', 'f16x2', 'bf16')
 # ---- the weights' GENERATION ------------------------------------------------------------------------------------------------
 # The reference reads its parameters live at every step (controllable_captioning.py:151-152,177-178; coco_scripts/train.py:112-113 steps
 # the optimizer and the next model(...) at :103 sees the new weights).  Here three things are DERIVED from the weights and have to be
-# redone when they move: the fp16-pair images (f16x2), the bf16 copies (bf16) and the decode cache (inference).  What says "they moved":
+# redone when they move: the fp16-pair images (f16x2), the bf16 copies (bf16) and the decode cache (inference); vsrcap/derived.py keeps
+# their books.  What says "they moved":
 #   (1) model._wgen, bumped by invalidate_cache(), train() / eval(), load_state_dict(), attach_optimizer()'s hook - and by EVERY forward
 #       that builds a graph (training: the weights are expected to move between two such calls, whoever moves them);
 #   (2) _OPT_STEPS, a process-wide count of torch.optim.Optimizer.step() calls (a global post-step hook): any optimizer stepping
@@ -58,11 +61,6 @@ def _count_optimizer_steps():
     _OPT_HOOK.append(register_optimizer_step_post_hook(_after_step))
 
 
-def _lib_max_beam():
-    from vsrcap import _lib
-    return _lib.MAX_BEAM
-
-
 def set_default_compute_dtype(dtype):
     """compute dtype of models constructed from now on ('f32' = exact fma chain everywhere, 'f32x3', 'f16x2', 'bf16'); returns the old one"""
     global DEFAULT_COMPUTE_DTYPE
@@ -73,6 +71,8 @@ def set_default_compute_dtype(dtype):
 
 
 class ControllableCaptioningModel(CaptioningModel):
+    _wgen = 0                            # the weights' generation (module comment above)
+
     def __init__(self, seq_len, vocab_size, bos_idx, det_feat_size=2048, input_encoding_size=1000, rnn_size=1000,
                  att_size=512, h2_first_lstm=True, img_second_lstm=False, dataset='coco', *, verb_2_vob_all=None):
         super().__init__(seq_len)
@@ -119,7 +119,6 @@ class ControllableCaptioningModel(CaptioningModel):
         self.init_weights()
         self._eng = None
         self._verb_dev = None
-        self._wgen = 0                   # the weights' generation (module comment above)
         from vsrcap.steptape import Lineage
         self._lineage = Lineage()        # which manual step() loop a grad-enabled step belongs to
         _count_optimizer_steps()
@@ -173,11 +172,11 @@ class ControllableCaptioningModel(CaptioningModel):
     def train(self, mode=True):
         # a mode switch redoes the derived state: eval() after a training run must decode with the FINAL weights whatever moved them
         if mode != self.training:
-            self._wgen = getattr(self, "_wgen", 0) + 1
+            self._wgen += 1
         return super().train(mode)
 
     def load_state_dict(self, *a, **kw):
-        self._wgen = getattr(self, "_wgen", 0) + 1
+        self._wgen += 1
         return super().load_state_dict(*a, **kw)
 
     def init_weights(self):
@@ -222,13 +221,8 @@ class ControllableCaptioningModel(CaptioningModel):
         pdev = next(iter(params.values())).device
         if pdev.type != 'cuda' or (device.index is not None and pdev.index != device.index):
             raise RuntimeError("model parameters are on %s but the inputs are on %s" % (pdev, device))
-        self._eng.bind(params)
-        self._eng.set_bf16(pdev, self._weights_version(), self.compute_dtype == 'bf16')
-        self._eng.set_gemm_mode(self.compute_dtype in ('f32x3', 'f16x2'))
-        dims8 = all(v % 8 == 0 for v in (self.det_feat_size, self.input_encoding_size, self.rnn_size, self.att_size))
-        self._eng.set_h2(pdev, self._weights_version(), self.compute_dtype == 'f16x2' and dims8)      # (other sizes: plain f32x3)
         # inference keeps a weight-only cache (embedding projection); while training the weights move every step
-        self._eng.decode_cache(pdev, self._weights_version(), enable=not self.training)
+        self._eng.sync_weights(params, self._weights_version(), self.compute_dtype, self.training)
         return self._eng
 
     def _weights_version(self):
@@ -247,13 +241,11 @@ class ControllableCaptioningModel(CaptioningModel):
 
     @staticmethod
     def _n_slots(regions):
-        from vsrcap.regions import IndexedRegions
         return regions.slot_idx.size(1) if isinstance(regions, IndexedRegions) else regions.size(1)
 
     def _prepare(self, eng, det, regions, beam, for_training=False):
         """Hoisted per-image work for either region format: the reference's dense (B,L,R,D) tensor, or
         vsrcap.regions.IndexedRegions (index lists into the image's feature bank; training too when every row is its own image)."""
-        from vsrcap.regions import IndexedRegions
         if isinstance(regions, IndexedRegions):
             return eng.prepare_indexed(det, regions.bank, regions.slot_idx, regions.row_img, beam, self._weights_version(), self.valid_rows_bound,
                                        for_training=for_training)
@@ -266,7 +258,6 @@ class ControllableCaptioningModel(CaptioningModel):
         eng = self._engine(det.device, weights_may_have_moved=with_grad)
         if captions.size(1) > self.seq_len:
             raise RuntimeError("captions longer than seq_len")
-        from vsrcap.regions import IndexedRegions
         if with_grad:
             if isinstance(ctrl_seq, IndexedRegions) and ctrl_seq.row_img is not None:
                 raise RuntimeError("training on IndexedRegions needs one decoder row per image (row_img=None), as the reference's "
@@ -294,13 +285,12 @@ class ControllableCaptioningModel(CaptioningModel):
         samples of every image in ONE call, rows b * K + j = sample j of image b (the order of repeat_interleave(K, 0)).  The image's
         statics - region rows, att_va(regions), the pooled descriptor's projections - exist once, forward and backward."""
         K = int(samples_per_image)
-        if not 1 <= K <= _lib_max_beam():
+        if not 1 <= K <= _lib.MAX_BEAM:
             raise ValueError("samples_per_image must be in [1, %d] (the rows of an image share the beam workspace), got %r"
-                             % (_lib_max_beam(), samples_per_image))
+                             % (_lib.MAX_BEAM, samples_per_image))
         det, ctrl = statics[0], statics[1]
         with_grad = self._builds_graph()
         eng = self._engine(det.device, weights_may_have_moved=with_grad)
-        from vsrcap.regions import IndexedRegions
         if with_grad and isinstance(ctrl, IndexedRegions) and ctrl.row_img is not None:
             raise RuntimeError("sample_rl with gradients on IndexedRegions needs one decoder row per image (row_img=None)")
         B = self._prepare(eng, det, ctrl, K, for_training=with_grad)
@@ -358,7 +348,6 @@ class ControllableCaptioningModel(CaptioningModel):
         differentiates through the recurrence (vsrcap/steptape.py has the rules, vsrcap/train.py the autograd nodes).  What a tape
         cannot express raises; nothing returns tensors without a grad_fn."""
         from vsrcap import steptape, train
-        from vsrcap.regions import IndexedRegions
         if with_verbs:
             raise steptape.TapeError("step_v (verb forcing) is not differentiable here")
         det = statics[0]

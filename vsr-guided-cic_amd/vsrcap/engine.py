@@ -2,6 +2,7 @@
 workspace and enqueues everything on torch's current HIP stream.  PyTorch is plumbing here (device memory,
 streams); all arithmetic happens in libvsrcap.so.
 """
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -10,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .derived import Derived
 
 
 def _on_device(fn):
@@ -17,9 +19,7 @@ def _on_device(fn):
     wants that stream's device to be the current one (a model on cuda:1 used without torch.cuda.set_device(1))."""
     @functools.wraps(fn)
     def wrapped(self, *a, **kw):
-        if self.device is None:
-            return fn(self, *a, **kw)
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(self.device) if self.device is not None else contextlib.nullcontext():
             return fn(self, *a, **kw)
     return wrapped
 
@@ -51,12 +51,11 @@ def _ver(t):
         return ("unversioned", _UNVERSIONED[0])
 
 
-class _Null:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+def _grown(buf, n, dtype, device):
+    """buf when it holds n elements on device, a fresh buffer otherwise"""
+    if buf is None or buf.numel() < n or buf.device != device:
+        return torch.empty(n, dtype=dtype, device=device)
+    return buf
 
 
 class ForwardToken:
@@ -95,12 +94,14 @@ class Engine:
         self.device = torch.device(device) if device is not None else None
         if self.device is not None and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        with torch.cuda.device(self.device) if self.device is not None else _Null():
+        with torch.cuda.device(self.device) if self.device is not None else contextlib.nullcontext():
             _lib.check(self.lib.vsr_create(C.byref(self.dims), C.byref(self.h)))
         # VSR_CHECK_IDS=1 (or eng.check_ids = True): after every call that takes word / slot / verb ids, read back the
         # library's count of out-of-range ids and raise like nn.Embedding would (costs one stream synchronisation per call)
         self.check_ids = os.environ.get("VSR_CHECK_IDS", "0") not in ("", "0")
-        self._bound_ptrs = None
+        self._derived = Derived()        # the state derived from the weights (vsrcap/derived.py); this engine is its backend
+        self._wbuf = {"bf16": None, "h2": None, "cache": None}      # ... the buffers its products live in
+        self._wdev = None                # ... and the device of the weights last handed to sync_weights()
         self._slots = [_Slot()]          # buffer pairs; more than one only while several training forwards are alive
         self._slot = self._slots[0]
         self._prep_key = None
@@ -113,15 +114,14 @@ class Engine:
     _keep = property(lambda self: self._slot.keep, lambda self, v: setattr(self._slot, "keep", v))
 
     def _claim_slot(self):
-        """Called before a vsr_prepare*() that will overwrite the current slot's workspace: if a live forward is saved there, move to
-        a free slot (one whose forward is gone or already differentiated), or open a new one.  The reference has no such limit at
-        all (eager autograd); MAX_LIVE_FORWARDS pairs of buffers is where this build stops."""
+        """Called before a vsr_prepare*() that will overwrite the current slot's workspace (_prepare_in_slot: the prepare key is already
+        void): if a live forward is saved there, move to a free slot (one whose forward is gone or already differentiated), or open
+        a new one.  The reference has no such limit at all (eager autograd); MAX_LIVE_FORWARDS pairs of buffers is where this build stops."""
         if not self._slot.live():
             return
         for sl in self._slots:
             if not sl.live():
                 self._slot = sl
-                self._prep_key = None
                 return
         if len(self._slots) >= MAX_LIVE_FORWARDS:
             raise RuntimeError("%d training forwards of this model are alive and not yet differentiated: each holds its own workspaces "
@@ -129,7 +129,6 @@ class Engine:
                                % len(self._slots))
         self._slot = _Slot()
         self._slots.append(self._slot)
-        self._prep_key = None
 
     def live_forwards(self):
         return sum(1 for sl in self._slots if sl.live())
@@ -142,34 +141,53 @@ class Engine:
         except Exception:
             pass
 
-    # ------------------------------------------------------------------ weights / tables
-    def bind(self, params):
-        """params: dict state_dict key -> fp32 CUDA tensor (borrowed, not copied)."""
+    # ------------------------------------------------------------------ weights and what is derived from them
+    @_on_device
+    def sync_weights(self, params, weights_version, compute_dtype, training):
+        """params: dict state_dict key -> fp32 CUDA tensor (borrowed, not copied).  Brings what the handle derives from them (GEMM flavour,
+        bf16 copies / fp16-pair images, decode cache) to weights_version: vsrcap/derived.py owns the chain, this engine is its backend."""
         ptrs = []
         for _, key in _lib.WEIGHT_FIELDS:
             t = params[key]
             if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
                 raise RuntimeError("weight %s must be a contiguous fp32 GPU tensor (got %s %s)" % (key, t.dtype, t.device))
             ptrs.append(t.data_ptr())
-        ptrs = tuple(ptrs)
-        if ptrs != self._bound_ptrs:
-            w = _lib.VsrWeights(*ptrs)
-            _lib.check(self.lib.vsr_bind_weights(self.h, C.byref(w)))
-            self._bound_ptrs = ptrs
+        dims8 = all(getattr(self.dims, k) % 8 == 0 for k in ("det_feat_size", "input_encoding_size", "rnn_size", "att_size"))
+        self._wdev = t.device
+        if self._derived.sync((tuple(ptrs), weights_version, compute_dtype, dims8, training), self):
             self._prep_key = None
-            self._cache_key = None
-        return ptrs
 
     def invalidate(self):
-        """Forget the cached prepare() / decode cache.  prepare() keys its cache on (data_ptr, tensor._version, shapes,
-        weights generation): writes that do not bump _version (t.data.copy_, DLPack / custom-kernel writes into the same
-        buffer, p.data edits of the weights) are invisible to it - call this after such a write."""
-        self._prep_key = None
-        self._cache_key = None
-        if getattr(self, "_bf16_key", None) is not None:
-            self._bf16_key = ("stale",)          # bf16 mode stays on; the copies are rebuilt by the next set_bf16()
-        if getattr(self, "_h2_key", None) is not None:
-            self._h2_key = ("stale",)            # ... and so are the fp16-pair images
+        """Forget the cached prepare() and everything derived from the weights.  prepare() keys its cache on (data_ptr,
+        tensor._version, shapes, weights generation): writes that do not bump _version (t.data.copy_, DLPack / custom-kernel writes
+        into the same buffer, p.data edits of the weights) are invisible to it - call this after such a write."""
+        self._derived.invalidate(self)
+
+    # the backend of vsrcap/derived.py, one method per library call (include/vsrcap.h says what each of them voids in the handle)
+    def bind(self, ptrs):
+        _lib.check(self.lib.vsr_bind_weights(self.h, C.byref(_lib.VsrWeights(*ptrs))))
+
+    def set_gemm_mode(self, x3):
+        _lib.check(self.lib.vsr_set_gemm_mode(self.h, 1 if x3 else 0))
+
+    def refresh_bf16(self, on):
+        self._derive("bf16", on, self.lib.vsr_bf16_weight_bytes, self.lib.vsr_refresh_bf16_weights)
+
+    def refresh_h2(self, on):
+        self._derive("h2", on, self.lib.vsr_h2_weight_bytes, self.lib.vsr_refresh_h2_weights)      # (torch allocations are 512-byte aligned)
+
+    def build_cache(self):
+        self._derive("cache", True, self.lib.vsr_decode_cache_floats, self.lib.vsr_build_decode_cache, torch.float32)
+
+    def drop_cache(self):
+        self._derive("cache", False, self.lib.vsr_decode_cache_floats, self.lib.vsr_build_decode_cache, torch.float32)
+
+    def _derive(self, kind, on, size, call, dtype=torch.uint8):
+        """one derived product: (re)built in a buffer this engine owns, or switched off (NULL buffer)"""
+        buf = None
+        if on:
+            buf = self._wbuf[kind] = _grown(self._wbuf[kind], size(self.h), dtype, self._wdev)
+        _lib.check(call(self.h, _ptr(buf), buf.numel() if on else 0, self._stream(self._wdev)))
 
     def raise_on_bad_ids(self, device, who):
         if not self.check_ids:
@@ -196,72 +214,6 @@ class Engine:
         self._verb_dev = (rp, fl)
         _lib.check(self.lib.vsr_set_verb_table(self.h, _ptr(rp), _ptr(fl), n))
 
-    def set_gemm_mode(self, x3):
-        """True (the library's default): "f32x3" - three bf16 terms per fp32 operand, six MFMAs per product; which kernel a launch
-        takes depends on its rows (include/vsrcap.h, vsr_set_gemm_mode); False: the exact fp32 fma chain for every launch"""
-        x3 = bool(x3)
-        if x3 != getattr(self, "_x3", True):
-            _lib.check(self.lib.vsr_set_gemm_mode(self.h, 1 if x3 else 0))
-            self._x3 = x3
-            self._cache_key = None
-            self._prep_key = None
-
-    # ------------------------------------------------------------------ f16x2: fp16-pair weight images on top of f32x3
-    @_on_device
-    def set_h2(self, device, weights_version, enable):
-        """enable: (re)build the fp16-pair images of the weight matrices when the bound weights or their version changed
-        (include/vsrcap.h, vsr_refresh_h2_weights); disable: back to plain f32x3."""
-        key = (self._bound_ptrs, weights_version) if enable else None
-        if key == getattr(self, "_h2_key", None):
-            return
-        if not enable:
-            _lib.check(self.lib.vsr_refresh_h2_weights(self.h, C.c_void_p(0), 0, self._stream(device)))
-        else:
-            n = self.lib.vsr_h2_weight_bytes(self.h)
-            if getattr(self, "_h2_buf", None) is None or self._h2_buf.numel() < n or self._h2_buf.device != device:
-                self._h2_buf = torch.empty(n, dtype=torch.uint8, device=device)      # (torch allocations are 512-byte aligned)
-            _lib.check(self.lib.vsr_refresh_h2_weights(self.h, _ptr(self._h2_buf), self._h2_buf.numel(), self._stream(device)))
-        self._cache_key = None                   # the library voids the decode cache and the hoisted tensors on every refresh
-        self._prep_key = None
-        self._h2_key = key
-
-    # ------------------------------------------------------------------ bf16 throughput mode
-    @_on_device
-    def set_bf16(self, device, weights_version, enable):
-        """enable: (re)build the bf16 copies of the weight matrices when the bound weights or their version changed and
-        switch the handle to bf16 GEMMs; disable: back to the fp32 parity mode (include/vsrcap.h, vsr_refresh_bf16_weights)."""
-        key = (self._bound_ptrs, weights_version) if enable else None
-        if key == getattr(self, "_bf16_key", None):
-            return
-        if not enable:
-            _lib.check(self.lib.vsr_refresh_bf16_weights(self.h, C.c_void_p(0), 0, self._stream(device)))
-        else:
-            n = self.lib.vsr_bf16_weight_bytes(self.h)
-            if getattr(self, "_bf16_buf", None) is None or self._bf16_buf.numel() < n or self._bf16_buf.device != device:
-                self._bf16_buf = torch.empty(n, dtype=torch.uint8, device=device)
-            _lib.check(self.lib.vsr_refresh_bf16_weights(self.h, _ptr(self._bf16_buf), self._bf16_buf.numel(), self._stream(device)))
-        if (key is None) != (getattr(self, "_bf16_key", None) is None):
-            self._cache_key = None               # the decode cache was built in the other precision
-            self._prep_key = None                # ... and so were the hoisted projections
-        self._bf16_key = key
-
-    # ------------------------------------------------------------------ decode cache (inference only)
-    @_on_device
-    def decode_cache(self, device, weights_version, enable=True):
-        """(Re)build the embedding-projection cache when the weights changed; enable=False drops it (training)."""
-        key = (self._bound_ptrs, weights_version) if enable else None
-        if key == getattr(self, "_cache_key", None):
-            return
-        if not enable:
-            _lib.check(self.lib.vsr_build_decode_cache(self.h, C.c_void_p(0), 0, self._stream(device)))
-            self._cache_key = None
-            return
-        n = self.lib.vsr_decode_cache_floats(self.h)
-        if getattr(self, "_cache_buf", None) is None or self._cache_buf.numel() < n or self._cache_buf.device != device:
-            self._cache_buf = torch.empty(n, dtype=torch.float32, device=device)
-        _lib.check(self.lib.vsr_build_decode_cache(self.h, _ptr(self._cache_buf), self._cache_buf.numel(), self._stream(device)))
-        self._cache_key = key
-
     # ------------------------------------------------------------------ hoisted statics
     @_on_device
     def prepare(self, det, regions, beam, weights_version=None, rows_bound=None, for_training=False):
@@ -273,27 +225,32 @@ class Engine:
         regions = _f32(regions, "region sequences")
         if det.dim() != 3 or regions.dim() != 4 or det.size(0) != regions.size(0) or det.size(2) != regions.size(3):
             raise RuntimeError("expected detections (B,R0,D) and regions (B,L,R,D); got %s and %s" % (tuple(det.shape), tuple(regions.shape)))
-        if det.size(2) != self.dims.det_feat_size:
-            raise RuntimeError("feature size %d != det_feat_size %d" % (det.size(2), self.dims.det_feat_size))
         B, R0, _ = det.shape
         _, L, R, _ = regions.shape
         key = (det.data_ptr(), _ver(det), regions.data_ptr(), _ver(regions), B, R0, L, R, beam,
-               self._bound_ptrs, weights_version, rows_bound)
+               self._derived.ptrs, weights_version, rows_bound)
+        self._prepare_in_slot(key, for_training, rows_bound, (det, regions), self.lib.vsr_workspace_bytes, (B, R0, L, R, beam),
+                              self.lib.vsr_prepare, (_ptr(det), B, R0, _ptr(regions), L, R, beam))
+        return B
+
+    def _prepare_in_slot(self, key, for_training, rows_bound, keep, size, size_args, call, args):
+        """The tail prepare() and prepare_indexed() share: served from the cache when the key matches; else the library call into the
+        workspace of a slot that holds no live forward.  keep: the inputs, borrowed by the library until the next prepare."""
+        if keep[0].size(2) != self.dims.det_feat_size:
+            raise RuntimeError("feature size %d != det_feat_size %d" % (keep[0].size(2), self.dims.det_feat_size))
         if key == self._prep_key and not (for_training and self._slot.live()):
-            return B
+            return
+        self._prep_key = None                # from here on the handle's statics are in flux: a call that raises leaves no key behind
         self._claim_slot()
         _lib.check(self.lib.vsr_set_valid_rows_bound(self.h, int(rows_bound or 0)))
-        need = self.lib.vsr_workspace_bytes(self.h, B, R0, L, R, beam)
+        need = size(self.h, *size_args)
         if need == 0:
-            raise RuntimeError("vsr_workspace_bytes rejected the shapes")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != det.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=det.device)
-        stream = torch.cuda.current_stream(det.device).cuda_stream
-        _lib.check(self.lib.vsr_prepare(self.h, _ptr(det), B, R0, _ptr(regions), L, R, beam, _ptr(self._ws),
-                                        self._ws.numel(), C.c_void_p(stream)))
-        self._keep = (det, regions)          # borrowed by the library until the next prepare
+            raise RuntimeError("%s rejected the shapes" % size.__name__)
+        dev = keep[0].device
+        self._ws = _grown(self._ws, need, torch.uint8, dev)
+        _lib.check(call(self.h, *args, _ptr(self._ws), self._ws.numel(), self._stream(dev)))
+        self._keep = keep
         self._prep_key = key
-        return B
 
     @_on_device
     def prepare_indexed(self, det, bank, slot_idx, row_img, beam, weights_version=None, rows_bound=None, for_training=False):
@@ -304,8 +261,6 @@ class Engine:
         if det.dim() != 3 or bank.dim() != 3 or slot_idx.dim() != 3 or det.size(0) != bank.size(0) or det.size(2) != bank.size(2):
             raise RuntimeError("expected detections (n_img,R0,D), bank (n_img,Rb,D), slot_idx (B,L,R); got %s, %s, %s"
                                % (tuple(det.shape), tuple(bank.shape), tuple(slot_idx.shape)))
-        if det.size(2) != self.dims.det_feat_size:
-            raise RuntimeError("feature size %d != det_feat_size %d" % (det.size(2), self.dims.det_feat_size))
         if not slot_idx.is_cuda or slot_idx.dtype != torch.int32:
             raise RuntimeError("slot_idx must be an int32 GPU tensor (got %s on %s)" % (slot_idx.dtype, slot_idx.device))
         slot_idx = slot_idx.contiguous()
@@ -321,21 +276,10 @@ class Engine:
             row_img = row_img.contiguous()
         key = ("idx", det.data_ptr(), _ver(det), bank.data_ptr(), _ver(bank), slot_idx.data_ptr(), _ver(slot_idx),
                None if row_img is None else (row_img.data_ptr(), _ver(row_img)), B, n_img, R0, Rb, L, R, beam,
-               self._bound_ptrs, weights_version, rows_bound)
-        if key == self._prep_key and not (for_training and self._slot.live()):
-            return B
-        self._claim_slot()
-        _lib.check(self.lib.vsr_set_valid_rows_bound(self.h, int(rows_bound or 0)))
-        need = self.lib.vsr_workspace_bytes_indexed(self.h, B, R0, n_img, Rb, L, R, beam)
-        if need == 0:
-            raise RuntimeError("vsr_workspace_bytes_indexed rejected the shapes")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != det.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=det.device)
-        self._prep_key = None
-        _lib.check(self.lib.vsr_prepare_indexed(self.h, _ptr(det), n_img, R0, _ptr(bank), Rb, _ptr(row_img), B, _ptr(slot_idx),
-                                                L, R, beam, _ptr(self._ws), self._ws.numel(), self._stream(det.device)))
-        self._keep = (det, bank, slot_idx, row_img)      # borrowed by the library until the next prepare
-        self._prep_key = key
+               self._derived.ptrs, weights_version, rows_bound)
+        self._prepare_in_slot(key, for_training, rows_bound, (det, bank, slot_idx, row_img),
+                              self.lib.vsr_workspace_bytes_indexed, (B, R0, n_img, Rb, L, R, beam),
+                              self.lib.vsr_prepare_indexed, (_ptr(det), n_img, R0, _ptr(bank), Rb, _ptr(row_img), B, _ptr(slot_idx), L, R, beam))
         return B
 
     @_on_device
@@ -378,8 +322,7 @@ class Engine:
                 self.lib.vsr_train_workspace_bytes_rows(self.h, n_img, K, T))
         if need == 0:
             raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
-        if getattr(self, "_tws", None) is None or self._tws.numel() < need or self._tws.device != device:
-            self._tws = torch.empty(need, dtype=torch.uint8, device=device)
+        self._tws = _grown(self._tws, need, torch.uint8, device)
         out = torch.empty(B, T, V, dtype=torch.float32, device=device)
         gate = torch.empty(B, T, 2, dtype=torch.float32, device=device)
         if self._slot.live():
@@ -456,8 +399,7 @@ class Engine:
             raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
         if self._slot.live():
             raise RuntimeError("internal: tape into a slot that holds a live forward (prepare(for_training=True) first)")
-        if self._tws is None or self._tws.numel() < need or self._tws.device != device:
-            self._tws = torch.empty(need, dtype=torch.uint8, device=device)
+        self._tws = _grown(self._tws, need, torch.uint8, device)
         _lib.check(self.lib.vsr_train_tape_begin(self.h, int(max_steps), _ptr(self._tws), self._tws.numel(), self._stream(device)))
         self._slot.generation = self.train_generation()
         return self._slot.generation, self.note_forward()
