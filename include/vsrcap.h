@@ -275,6 +275,22 @@ int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, const float*
 size_t vsr_train_workspace_bytes_rows(const vsr_handle* h, int32_t B, int32_t rows_per_image, int32_t T);
 int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots, int32_t T,
                            float* logp_words, float* logp_gates, void* train_workspace, size_t train_workspace_bytes, void* stream);
+/* The sparse vocabulary head: every training caller needs ONE log-prob per (row, step) - NLLLoss(out[:, :-1], captions[:, 1:]) (train.py:106),
+ * the sampled word's (train.py:174) - so no (rows,T,V) tensor is written and none is read back.  rows = B * rows_per_image; preconditions,
+ * workspace size (vsr_train_workspace_bytes[_rows]) and the handling of word_in / slots are those of vsr_train_forward_rows.
+ *   targets (rows,T) int64: the word whose log-prob is wanted at (row, step), or -1 = not selected: logp_sel is 0.0f exactly there and the
+ *           entry carries no gradient into the vocabulary head, whatever grad_logp_sel holds.  Any other value is counted into
+ *           vsr_bad_ids()'s count and taken as -1.
+ *   logp_sel (rows,T), logp_gates (rows,T,2): outputs (the gate head stays dense); logp_gates and the workspace stay untouched until the backward.
+ * The log_softmax rows stay in the training workspace and vsr_train_backward_selected turns them into their gradient IN PLACE: a forward
+ * can be differentiated ONCE - a second vsr_train_backward_selected of it fails.  The two kinds of forward do not mix: vsr_train_backward
+ * on a sparse forward fails, as does vsr_train_backward_selected on a dense forward or a tape; vsr_train_select serves both.  The
+ * gradients are those vsr_train_backward computes from the dense gradient with grad_logp_sel scattered to the targets. */
+int vsr_train_forward_selected(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots, const int64_t* targets,
+                               int32_t T, float* logp_sel, float* logp_gates, void* train_workspace, size_t train_workspace_bytes,
+                               void* stream);
+int vsr_train_backward_selected(vsr_handle* h, const float* grad_logp_sel, const float* grad_logp_gates, const vsr_weights* grads,
+                                void* stream);
 /* More than one live forward (the reference runs under eager autograd: two forwards then (l1 + l2).backward(), micro-batches, a decode
  * call between a forward and its backward all just work, CaptioningModel.py:22-36).  A forward's saved state lives in the TWO caller
  * buffers it was given - the vsr_prepare*() workspace and the training workspace - and stays differentiable for as long as no later

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""The XE and the SCST training step with the dense and with the sparse vocabulary head, alternating inside ONE process.
+
+    python tools/head_bench.py [--steps 20] [--warmup 5] [--dtype f16x2] [--workloads xe,scst] [--blocks] [--out profiles/NAME.json]
+
+Workloads are bench.py's: the XE step at B = 100, T = 20, V = 10 000 and the SCST step at 100 images x 5 samples (greedy baseline,
+samples_per_image = 5, CIDEr-D rewards on the device), resident synthetic batches, torch.optim.Adam(fused=True), both through
+parallel.DataParallelStep - with sparse_head off ("dense": a (rows, T, V) log-prob tensor and its gradient) and on ("sparse":
+vsr_train_forward_selected / vsr_train_backward_selected).  Each setting has its own model and optimizer (same initial weights).
+
+Timing: --warmup untimed steps per setting, then --steps timed steps that ALTERNATE dense / sparse so that clock and temperature drift
+hit both alike; every step is timed with a device synchronisation on both sides.  Reported per setting: median, min, max of the step
+times.  Memory: torch.cuda.max_memory_allocated of the setting's warm-up steps after a reset, as the peak above what was allocated
+before those steps (the setting's Adam state, workspaces and the transients of a step; the other setting's are resident and cancel).
+
+Conditions printed with the figures: peak lower by at least 2 rows T V 4 bytes (the dense output and its gradient), and the sparse
+median not above the dense median by more than the min-max spread of the dense samples of the same run.
+
+--blocks: no alternation - each setting runs its warm-up and its timed steps in one block.  For a kernel trace
+(rocprofv3 --kernel-trace --stats -- python tools/head_bench.py --blocks ...): tools/head_trace_count.py then counts the launches per
+step of each setting from the trace."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "vsr-guided-cic_amd"), ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+NS = 5
+SETTINGS = ("dense", "sparse")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dtype", default="f16x2")
+    ap.add_argument("--workloads", default="xe,scst")
+    ap.add_argument("--blocks", action="store_true")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import bench
+    from vsrcap import parallel, synth
+    from vsrcap.reward import CiderD, clean_ids
+    c, EOS = bench.CFG, bench.EOS
+    dev = torch.device("cuda", 0)
+
+    def sync_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    res = {"dtype": args.dtype, "steps": args.steps, "warmup": args.warmup, "alternating": not args.blocks,
+           "device": torch.cuda.get_device_name(0), "workloads": {}}
+    for wl in args.workloads.split(","):
+        xe = wl == "xe"
+        L = c["T"] if xe else c["L"]
+        batches = []
+        for i in range(2):
+            seed = 2000 + i
+            batches.append(tuple(torch.from_numpy(x).contiguous().to(dev) for x in (
+                synth.make_detections(c["B"], c["R0"], c["D"], seed=seed), synth.make_ctrl(c["B"], L, c["R"], c["D"], seed=seed),
+                synth.make_captions(c["B"], c["T"], c["V"], seed=seed), synth.make_gate_gts(c["B"], c["T"], seed=seed))))
+        if not xe:
+            corpus = [[clean_ids(cap, eos=EOS)] for cap in synth.make_captions(2000, c["T"], c["V"], seed=77)]
+            cider = CiderD(corpus, c["V"])
+            refs = [b[2].unsqueeze(1).contiguous() for b in batches]
+            refs5 = [r.repeat_interleave(NS, 0).contiguous() for r in refs]
+        forms = {}
+        for name in SETTINGS:
+            m, _ = bench.make_model(torch, synth, dev, True, args.dtype)
+            opt = torch.optim.Adam(m.parameters(), lr=5e-4, fused=True)
+            forms[name] = (m, parallel.DataParallelStep(m, opt, forward_fn=lambda d, cp, sq, _m=m: _m((d,), (cp, sq)),
+                                                        sample_fn=lambda d, ct, _m=m, **kw: _m.sample_rl(d, ct, **kw),
+                                                        sparse_head=name == "sparse"))
+
+        def one_step(name, i):
+            m, step = forms[name]
+            det, reg, caps, gts = batches[i & 1]
+            if xe:
+                return step.xe_step(det, caps, reg, gts)
+            with torch.no_grad():
+                m.eval()
+                base_words, _ = m.test(det, reg)
+                m.train()
+            r_base = cider.rewards(base_words, refs[i & 1], EOS).repeat_interleave(NS, 0)
+            return step.scst_step(det, reg, lambda words: (cider.rewards(words, refs5[i & 1], EOS), r_base), samples_per_image=NS)
+
+        times, peak, last = {n: [] for n in SETTINGS}, {}, {}
+
+        def warm(n):
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            for i in range(args.warmup):
+                one_step(n, i)
+            torch.cuda.synchronize()
+            peak[n] = (torch.cuda.max_memory_allocated() - before, torch.cuda.max_memory_allocated())
+
+        if args.blocks:
+            for n in SETTINGS:
+                warm(n)
+                for i in range(args.steps):
+                    times[n].append(sync_ms(lambda: last.__setitem__(n, one_step(n, i))))
+        else:
+            for n in SETTINGS:
+                warm(n)
+            for i in range(args.steps):
+                for n in SETTINGS:
+                    times[n].append(sync_ms(lambda: last.__setitem__(n, one_step(n, i))))
+        rows = c["B"] * (1 if xe else NS)
+        out = {"rows": rows, "T": c["T"], "V": c["V"], "settings": {}}
+        for n, t in times.items():
+            a = np.sort(np.array(t))
+            out["settings"][n] = {"median_ms": float(np.median(a)), "min_ms": float(a[0]), "max_ms": float(a[-1]),
+                                  "peak_over_resident_bytes": int(peak[n][0]), "max_memory_allocated_bytes": int(peak[n][1]),
+                                  "last_step_stats": [float(x) for x in last[n].reshape(-1).tolist()], "ms": [round(x, 3) for x in t]}
+        d, s = out["settings"]["dense"], out["settings"]["sparse"]
+        need = 2 * rows * c["T"] * c["V"] * 4
+        out["dense_output_plus_gradient_bytes"] = need
+        out["peak_saved_bytes"] = d["peak_over_resident_bytes"] - s["peak_over_resident_bytes"]
+        out["peak_lower_by_output_plus_gradient"] = bool(out["peak_saved_bytes"] >= need)
+        out["sparse_minus_dense_median_ms"] = s["median_ms"] - d["median_ms"]
+        out["dense_spread_ms"] = d["max_ms"] - d["min_ms"]
+        out["sparse_not_slower_beyond_dense_spread"] = bool(s["median_ms"] <= d["median_ms"] + out["dense_spread_ms"])
+        res["workloads"][wl] = out
+        for n in SETTINGS:
+            forms[n][1].close()
+        del forms, batches
+        torch.cuda.empty_cache()
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -25,6 +25,11 @@ struct TrainCtx {                      // (plain data + two vectors: copied into
     // forward), tape_steps = the steps taken; T / TB / TBp and logp_w / logp_g are those of the steps taken once it is sealed
     int tape_max = 0, tape_steps = 0;
     bool sealed = false;
+    // a SPARSE forward (vsr_train_forward_selected): no (B,T,V) tensor exists - the (t, b) log_softmax rows are in `dlogits` (stride
+    // up8(V)), the validated targets in tgt32 (the storage of rows_bt, which such a forward does not gather through), logp_w is null.
+    // vsr_train_backward_selected turns the rows into dlogits in place and marks the forward consumed: it cannot be differentiated twice
+    bool sparse = false, consumed = false;
+    int* tgt32 = nullptr;
     float* dP_rows = nullptr;          // rpi > 1: the rows' (R, A) contributions to dP of the current step (k_attend_bwd -> k_dP_rows_sum)
     const float* logp_w = nullptr;     // caller's (B,T,V) output of the forward, needed by the backward
     const float* logp_g = nullptr;     // (B,T,2)
@@ -443,10 +448,11 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
 // K = rows per image: M = B K decoder rows, rows b K .. b K + K - 1 are image b's (the order of repeat_interleave(K, 0)).  Whatever is
 // per image - the hoisted projections, P, the region rows, masks and index lists - is read through row / K, as the beams of the decode
 // path do; K = 1 launches the kernels of the one-row-per-image path (the <false> instantiations).
+// targets != null: the sparse head (vsr_train_forward_selected) - logp_words is then the (rows, T) tensor of the targets' log-probs
 static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, const int64_t* slots, int32_t T, float* logp_words,
-                              float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
-    if (check_ready(h, "vsr_train_forward")) return 1;
-    if (!word_in || !logp_words || !logp_gates || !train_ws) return fail("vsr_train_forward: null tensor");
+                              float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream, const int64_t* targets = nullptr) {
+    if (check_ready(h, targets ? "vsr_train_forward_selected" : "vsr_train_forward")) return 1;
+    if (!word_in || !logp_words || !logp_gates || !train_ws) return fail("%s: null tensor", targets ? "vsr_train_forward_selected" : "vsr_train_forward");
     Ctx& c = h->c;
     if (K == 1 && c.beam != 1 && c.Mmax != c.B) return fail("vsr_train_forward: prepare() must be called with beam = 1");
     if (K < 1 || K > c.beam) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, the prepared beam %d] (the workspace of vsr_prepare*() is sized by the beam)", K, c.beam);
@@ -462,7 +468,9 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
     t.valid = false;
     t.rpi = K; t.B = B; t.T = T;
     t.tape_max = t.tape_steps = 0; t.sealed = false;
+    t.sparse = targets != nullptr; t.consumed = false;
     const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
+    t.tgt32 = t.sparse ? t.rows_bt : nullptr;
     if (need > train_ws_bytes) return fail("vsr_train_forward: training workspace too small (%zu < %zu)", train_ws_bytes, need);
     drop_saved_forwards_in(h->saved, train_ws, need);       // forwards filed in THIS buffer are overwritten now
     t.tws_lo = reinterpret_cast<const char*>(train_ws); t.tws_bytes = need;
@@ -498,7 +506,26 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
 
     for (int tt = 0; tt < T; ++tt)
         if (train_forward_step(h, t, K, tt, im, logp_gates + (size_t)tt * 2, (long long)T * 2, s)) return 1;
-    {   // S6 for all steps at once: logits = h2[(b, t)] . out_fc^T (M = T B rows gathered in (b, t) order, so that the
+    if (t.sparse) {
+        // S6 for all steps at once, sparse head: the rows in their natural (t, b) order (state slots 1 .. T: nothing to gather), then
+        // k_vocab_select: the log_softmax rows stay in t.dlogits, the targets' entries go to the caller's (rows, T) tensor
+        all.h2_new = t.h2s + BH; all.h2_new16 = im ? t.h2s16 + BH * 2 : nullptr;
+        GemmBuilder g;
+        add_vocab(g, d, w, all, t.scratch);
+        const int ns = g.finish(h);
+        const long long stride = (long long)TB * V;
+        if (ns > 8 || (size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns);
+        g.a.p[0].slab_stride = stride;
+        if (g.launch(s, h)) return fail("train S6 gemm launch failed");
+        const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;
+        const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
+        const int Vp = (int)up4(V);
+        if (V >= 4096) hipLaunchKernelGGL(k_vocab_select<512>, dim3(TB), dim3(512), vsm, s, t.scratch, ns, stride, w.out_fc_bias, B, T, V, Vp, lds_row,
+                                          targets, t.dlogits, logp_words, t.tgt32, c.nvalid_dev + 2);
+        else hipLaunchKernelGGL(k_vocab_select<256>, dim3(TB), dim3(256), vsm, s, t.scratch, ns, stride, w.out_fc_bias, B, T, V, Vp, lds_row,
+                                targets, t.dlogits, logp_words, t.tgt32, c.nvalid_dev + 2);
+        LAUNCHCHK();
+    } else {   // S6 for all steps at once: logits = h2[(b, t)] . out_fc^T (M = T B rows gathered in (b, t) order, so that the
         // (B, T, V) log-prob tensor is written row by row), then one log_softmax launch
         GemmBuilder g;
         add_vocab(g, d, w, all, t.scratch, t.rows_bt);
@@ -513,7 +540,7 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         launch_vocab(h, s, io, t.scratch, ns, stride, no_gate);
         LAUNCHCHK();
     }
-    t.logp_w = logp_words;
+    t.logp_w = t.sparse ? nullptr : logp_words;
     t.logp_g = logp_gates;
     t.valid = true;
     t.generation = ++h->gen_counter;
@@ -530,6 +557,14 @@ extern "C" int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, con
                                       float* logp_words, float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
     if (rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, %d]", rows_per_image, VSR_MAX_BEAM);
     return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_words, logp_gates, train_ws, train_ws_bytes, stream);
+}
+// The sparse head: targets (rows, T) int64 (a word id, or -1 = not selected) -> logp_sel (rows, T); the gate head stays dense
+extern "C" int vsr_train_forward_selected(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots,
+                                          const int64_t* targets, int32_t T, float* logp_sel, float* logp_gates, void* train_ws,
+                                          size_t train_ws_bytes, void* stream) {
+    if (rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return fail("vsr_train_forward_selected: rows_per_image %d not in [1, %d]", rows_per_image, VSR_MAX_BEAM);
+    if (!targets) return fail("vsr_train_forward_selected: null targets (the dense head is vsr_train_forward / vsr_train_forward_rows)");
+    return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_sel, logp_gates, train_ws, train_ws_bytes, stream, targets);
 }
 
 // ---------------------------------------------------------------------------------------------- tape: the forward, one step per call
@@ -595,6 +630,7 @@ extern "C" int vsr_train_tape_begin(vsr_handle* h, int32_t max_steps, void* trai
         if (zl.launch(s)) return fail("vsr_train_tape_begin: zero launch failed");
     }
     t.tape_max = max_steps; t.tape_steps = 0; t.sealed = false;
+    t.sparse = t.consumed = false; t.tgt32 = nullptr;
     t.logp_w = t.logp_g = nullptr;
     t.valid = true;
     t.generation = ++h->gen_counter;
@@ -749,13 +785,23 @@ __global__ void k_sum_over_t_rows(const float* __restrict__ X, int T, int K, int
 }
 
 // ---------------------------------------------------------------------------------------------- backward
-extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
-                                  void* stream) {
-    if (check_ready(h, "vsr_train_backward")) return 1;
+// sel: vsr_train_backward_selected - grad_logp_words is then the (rows, T) gradient of the targets' log-probs
+static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
+                               void* stream) {
+    const char* who = sel ? "vsr_train_backward_selected" : "vsr_train_backward";
+    if (check_ready(h, who)) return 1;
     TrainCtx& t = *h->tc;
-    if (!t.valid) return fail("vsr_train_backward: no saved forward (call vsr_train_forward first)");
+    if (!t.valid) return fail("%s: no saved forward (call vsr_train_forward%s first)", who, sel ? "_selected" : "");
+    if (sel && t.tape_max) return fail("vsr_train_backward_selected: the current forward is a tape (a manual step() loop keeps the dense head): call vsr_train_backward");
     if (t.tape_max && !t.sealed) return fail("vsr_train_backward: the current forward is a tape of %d steps that has not been sealed (vsr_train_tape_seal)", t.tape_steps);
-    if (!grad_logp_words || !grad_logp_gates || !grads) return fail("vsr_train_backward: null tensor");
+    if (sel && !t.sparse) return fail("vsr_train_backward_selected: the current forward was taken by vsr_train_forward / vsr_train_forward_rows (dense head, a (B,T,V) "
+                                      "log-prob tensor): call vsr_train_backward with the dense gradient");
+    if (!sel && t.sparse) return fail("vsr_train_backward: the current forward was taken by vsr_train_forward_selected (sparse head: no (B,T,V) log-prob tensor "
+                                      "exists): call vsr_train_backward_selected with the (rows, T) gradient");
+    if (t.sparse && t.consumed) return fail("vsr_train_backward_selected: the forward of generation %lld has already been differentiated and is consumed - the "
+                                            "backward of the sparse head turns the saved log-prob rows into their gradient in place, so a second backward "
+                                            "needs a new vsr_train_forward_selected", (long long)t.generation);
+    if (!grad_logp_words || !grad_logp_gates || !grads) return fail("%s: null tensor", who);
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
@@ -770,7 +816,12 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     enum { g_embed, g_Wis, g_bis, g_Whs, g_bhs, g_Wva, g_Wha, g_wa, g_Wsa, g_ws, g_Wih1, g_Whh1, g_bih1, g_bhh1, g_Wih2, g_Whh2, g_bih2,
            g_bhh2, g_Wout, g_bout, g_Wsfc, g_bsfc, g_Wig, g_big, g_Whg, g_bhg, g_Wga, g_wg };
     for (int i = 0; i < 28; ++i)
-        if (!G[i]) return fail("vsr_train_backward: gradient pointer %d is null", i);
+        if (!G[i]) return fail("%s: gradient pointer %d is null", who, i);
+    if (t.sparse) {                        // from here on the saved rows are (about to be) overwritten: in the handle's copy and in the filed one
+        t.consumed = true;
+        for (SavedForward& sf : h->saved->v)
+            if (sf.t.generation == t.generation) sf.t.consumed = true;
+    }
 
     // f16x2 flavour: the W operands of the backward GEMMs - transposed weights here, transposed activations in phase B - are written as
     // fp16-pair images by the transposing kernel itself; the A operands are gradients: their producers fold max |x| into "dynamic" slots
@@ -820,7 +871,8 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     // (the K padding of the transposed operands - TBp, Bp, NVp columns - is zero-filled by the transposing kernel itself)
 
     // ---- phase 0: dlogits (t,b) and the vocabulary part of dh2 for every step
-    hipLaunchKernelGGL(k_dlogits_tb, dim3(TB), dim3(256), 0, s, t.logp_w, grad_logp_words, B, T, V, Vp, t.dlogits, dptr(DW_dlogits));
+    if (t.sparse) hipLaunchKernelGGL(k_dlogits_sel, dim3(TB), dim3(256), 0, s, grad_logp_words, t.tgt32, B, T, V, Vp, t.dlogits, dptr(DW_dlogits));
+    else hipLaunchKernelGGL(k_dlogits_tb, dim3(TB), dim3(256), 0, s, t.logp_w, grad_logp_words, B, T, V, Vp, t.dlogits, dptr(DW_dlogits));
     if (gemm_to1(h, t, s, TB, H, Vp, t.dlogits, Vp, t.wT_out, Vp, t.dh2_voc, H, dslot(DW_dlogits))) return 1;
     LAUNCHCHK();
 
@@ -1086,6 +1138,14 @@ extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, c
     h->buckets_recorded = true;
     LAUNCHCHK();
     return 0;
+}
+extern "C" int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
+                                  void* stream) {
+    return train_backward_impl(h, false, grad_logp_words, grad_logp_gates, grads, stream);
+}
+extern "C" int vsr_train_backward_selected(vsr_handle* h, const float* grad_logp_sel, const float* grad_logp_gates, const vsr_weights* grads,
+                                           void* stream) {
+    return train_backward_impl(h, true, grad_logp_sel, grad_logp_gates, grads, stream);
 }
 
 // Completion order of the 28 gradients inside vsr_train_backward: bucket_of[i] (field order of vsr_weights) in

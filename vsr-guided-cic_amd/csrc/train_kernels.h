@@ -735,4 +735,145 @@ __global__ void k_train_indices(const int64_t* __restrict__ word_in, const int64
     rows_bt[b * T + tt] = (tt + 1) * B + b;
 }
 
+// ---------------------------------------------------------------------------------------------- sparse vocabulary head
+// Every training caller wants ONE log-prob per (row, step) of the vocabulary head (coco_scripts/train.py:106 NLLLoss(out[:, :-1],
+// captions[:, 1:]); :174 the sampled word's).  vsr_train_forward_selected keeps the (T B, V) log_softmax rows INSIDE the training workspace
+// - the rows of t.dlogits, (t, b) order, stride Vp = up8(V), idle during the forward - and hands out logp_sel (rows, T) only;
+// vsr_train_backward_selected turns the rows into dlogits in place.  No (B, T, V) tensor exists on either side.
+
+// sum of up to 8 slabs + bias, four columns at once: every slab's load is issued before the first add (as slab_sum)
+__device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, int nslab, long long stride, const float* __restrict__ bias) {
+    float4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 s = *reinterpret_cast<const float4*>(bias);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < nslab) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
+    return s;
+}
+
+// Forward: one workgroup per (t, b) row of the S6 slabs (natural row order: no gather).  x = bias + slabs (<= 8), staged in LDS when the
+// launch passes V floats of dynamic LDS (lds_row) and re-summed from the slabs by the later passes otherwise; lse = max + log sum exp;
+// x - lse -> columns [0, V) of the row of `rows`; logp_sel[b T + t] = the target's entry.  targets (rows, T) int64: a word id, or -1 = not
+// selected (logp_sel = 0.0f exactly); anything else is counted into *bad and taken as -1.  tgt32 (T B): the validated targets in (t, b)
+// order for the backward.  16-byte accesses when V % 4 == 0 (every slab row, the bias and the output row are then 16-byte aligned).
+template <int NT>
+__global__ __launch_bounds__(NT) void k_vocab_select(const float* __restrict__ logits, int nsplit, long long stride, const float* __restrict__ bias,
+                                                      int B, int T, int V, int Vp, int lds_row, const int64_t* __restrict__ targets,
+                                                      float* __restrict__ rows, float* __restrict__ logp_sel, int* __restrict__ tgt32,
+                                                      int* __restrict__ bad) {
+    constexpr int NW = NT / 64;
+    __shared__ float red[2 * NW];
+    extern __shared__ float lrow[];
+    const int row = blockIdx.x, tt = row / B, b = row - tt * B;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* src = logits + (long long)row * V;
+    float* dst = rows + (long long)row * Vp;
+    const bool use_lds = lds_row != 0, vec = (V & 3) == 0;
+    long long tg = targets[(long long)b * T + tt];
+    if (tg < -1 || tg >= V) {
+        if (tid == 0) atomicAdd(bad, 1);
+        tg = -1;
+    }
+    const int tgt = (int)tg;
+    auto x1 = [&](int v) { return slab_sum(src + v, nsplit, stride, bias[v]); };
+
+    // ---- pass 1: the combined row (-> LDS) and its maximum
+    float mx = -INFINITY;
+    if (vec) {
+#pragma unroll 2
+        for (int v0 = tid * 4; v0 < V; v0 += 4 * NT) {
+            const float4 a = slab_sum4(src + v0, nsplit, stride, bias + v0);
+            if (use_lds) *reinterpret_cast<float4*>(lrow + v0) = a;
+            mx = fmaxf(fmaxf(mx, fmaxf(a.x, a.y)), fmaxf(a.z, a.w));
+        }
+    } else {
+        for (int v = tid; v < V; v += NT) {
+            const float x = x1(v);
+            if (use_lds) lrow[v] = x;
+            mx = fmaxf(mx, x);
+        }
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();                                       // (also: the LDS row is complete)
+    mx = red[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, red[w]);
+
+    // ---- pass 2: sum of exp
+    float se = 0.f;
+    if (vec) {
+#pragma unroll 2
+        for (int v0 = tid * 4; v0 < V; v0 += 4 * NT) {
+            const float4 a = use_lds ? *reinterpret_cast<const float4*>(lrow + v0) : slab_sum4(src + v0, nsplit, stride, bias + v0);
+            se += expf(a.x - mx); se += expf(a.y - mx); se += expf(a.z - mx); se += expf(a.w - mx);
+        }
+    } else {
+        for (int v = tid; v < V; v += NT) se += expf((use_lds ? lrow[v] : x1(v)) - mx);
+    }
+    se = wave_sum(se);
+    if (lane == 0) red[NW + wave] = se;
+    __syncthreads();
+    float se_all = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) se_all += red[NW + w];
+    const float lse = mx + logf(se_all);
+
+    // ---- pass 3: the log_softmax row, and the one entry that leaves
+    if (vec) {
+#pragma unroll 2
+        for (int v0 = tid * 4; v0 < V; v0 += 4 * NT) {
+            float4 a = use_lds ? *reinterpret_cast<const float4*>(lrow + v0) : slab_sum4(src + v0, nsplit, stride, bias + v0);
+            a.x -= lse; a.y -= lse; a.z -= lse; a.w -= lse;
+            *reinterpret_cast<float4*>(dst + v0) = a;
+            const int e = tgt - v0;
+            if (e >= 0 && e < 4) logp_sel[(long long)b * T + tt] = e == 0 ? a.x : e == 1 ? a.y : e == 2 ? a.z : a.w;
+        }
+    } else {
+        for (int v = tid; v < V; v += NT) {
+            const float l = (use_lds ? lrow[v] : x1(v)) - lse;
+            dst[v] = l;
+            if (v == tgt) logp_sel[(long long)b * T + tt] = l;
+        }
+    }
+    if (tid == 0) {
+        tgt32[row] = tgt;
+        if (tgt < 0) logp_sel[(long long)b * T + tt] = 0.f;
+    }
+}
+
+// Backward, phase 0 of vsr_train_backward_selected: the rows k_vocab_select left in t.dlogits become dlogits IN PLACE.  With a one-hot
+// upstream gradient of weight c = grad_logp_sel[b T + t] (0 when the target is -1) log_softmax backward is c [v == target] - exp(l) c: one
+// pass, no reduction (k_dlogits_tb's first pass only recovers c as a row sum of the dense gradient) and the same arithmetic per element.
+// The pad columns [V, Vp) get zeros; max |o| is folded into the f16x2 flavour's bound slot as k_dlogits_tb does.
+__global__ __launch_bounds__(256) void k_dlogits_sel(const float* __restrict__ grad_sel, const int* __restrict__ tgt32, int B, int T, int V,
+                                                     int Vp, float* __restrict__ dlogits, int* bm) {
+    const int tt = blockIdx.x / B, b = blockIdx.x % B, tid = threadIdx.x;
+    const int tgt = tgt32[blockIdx.x];
+    const float c = tgt >= 0 ? grad_sel[(long long)b * T + tt] : 0.f;
+    float* row = dlogits + (long long)blockIdx.x * Vp;
+    float mx = 0.f;
+    if ((V & 3) == 0) {
+        for (int v = tid * 4; v < Vp; v += 1024) {
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (v < V && c != 0.f) {                       // (c == 0: exp(l) 0 = 0 for every finite l <= 0 - the row is not read)
+                const float4 l = *reinterpret_cast<const float4*>(row + v);
+                o = make_float4((v == tgt ? c : 0.f) - expf(l.x) * c, (v + 1 == tgt ? c : 0.f) - expf(l.y) * c,
+                                (v + 2 == tgt ? c : 0.f) - expf(l.z) * c, (v + 3 == tgt ? c : 0.f) - expf(l.w) * c);
+            }
+            *reinterpret_cast<float4*>(row + v) = o;
+            mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        }
+    } else {
+        for (int v = tid; v < Vp; v += 256) {
+            const float o = (v < V && c != 0.f) ? (v == tgt ? c : 0.f) - expf(row[v]) * c : 0.f;
+            row[v] = o;
+            mx = fmaxf(mx, fabsf(o));
+        }
+    }
+    if (bm) block_absmax_to(mx, bm);
+}
+
 }  // namespace vsr

@@ -280,10 +280,38 @@ class ControllableCaptioningModel(CaptioningModel):
         v = self._verbs(eng, statics[2], det.device, B, self._n_slots(ctrl)) if len(statics) > 2 and statics[2] is not None else None
         return eng.greedy(B, det.device, v, False)
 
-    def _run_sample(self, statics, seed=None, forced=None, samples_per_image=1):
+    def forward_selected(self, statics, seqs, targets):
+        """Extension: forward() for callers that need ONE log-prob per (row, step) of the vocabulary head (every loss of
+        coco_scripts/train.py does).  statics / seqs as forward(); targets (B, T) int64: the word scored at each step, -1 = none
+        (vsrcap.train.xe_targets builds the XE ones).  -> (logp_sel (B, T), logp_gates (B, T, 2)): logp_sel[b, t] =
+        forward()[0][b, t, targets[b, t]], 0.0 where the target is -1.  No (B, T, V) tensor is written, saved or given a gradient.
+        Under no_grad / eval() the same values come back without a graph (validation loss)."""
+        det, (captions, ctrl_seq) = statics[0], seqs
+        with_grad = self._builds_graph()
+        eng = self._engine(det.device, weights_may_have_moved=with_grad)
+        if captions.size(1) > self.seq_len:
+            raise RuntimeError("captions longer than seq_len")
+        if isinstance(ctrl_seq, IndexedRegions) and ctrl_seq.row_img is not None:
+            raise RuntimeError("forward_selected on IndexedRegions needs one decoder row per image (row_img=None), as the reference's "
+                               "training batches have; with a row -> image map use regions.dense()")
+        B = self._prepare(eng, det, ctrl_seq, 1, for_training=True)
+        if with_grad:
+            from vsrcap.train import selected_forward_with_grad
+            return selected_forward_with_grad(self, eng, det, captions, targets, None, 1)
+        return eng.train_forward_selected(B, det.device, captions, targets)
+
+    def xe_loss(self, detections, captions, ctrl_det_seqs, ctrl_det_gts, gate_weight=4.0):
+        """Extension: the XE loss of coco_scripts/train.py:103-110 in one call, through the sparse head -> (loss, loss_cap, loss_gate)"""
+        from vsrcap.train import xe_targets, xe_loss_from_selected
+        targets = xe_targets(captions)
+        lp_sel, gate = self.forward_selected((detections,), (captions, ctrl_det_seqs), targets)
+        return xe_loss_from_selected(lp_sel, gate, targets, ctrl_det_gts, gate_weight)
+
+    def _run_sample(self, statics, seed=None, forced=None, samples_per_image=1, sparse_head=False):
         """samples_per_image = K (extension; the reference draws one sample per image and its SCST caller repeats every image): K
         samples of every image in ONE call, rows b * K + j = sample j of image b (the order of repeat_interleave(K, 0)).  The image's
-        statics - region rows, att_va(regions), the pooled descriptor's projections - exist once, forward and backward."""
+        statics - region rows, att_va(regions), the pooled descriptor's projections - exist once, forward and backward.
+        sparse_head (extension): the graph of the returned log-probs goes through the sparse vocabulary head (forward_selected's)."""
         K = int(samples_per_image)
         if not 1 <= K <= _lib.MAX_BEAM:
             raise ValueError("samples_per_image must be in [1, %d] (the rows of an image share the beam workspace), got %r"
@@ -304,7 +332,7 @@ class ControllableCaptioningModel(CaptioningModel):
         outs, lps = eng.sample(B, det.device, seed, forced, K)
         if with_grad:
             from vsrcap.train import sample_logprobs_with_grad
-            lps = sample_logprobs_with_grad(self, eng, det, ctrl, outs, lps, K)
+            lps = sample_logprobs_with_grad(self, eng, det, ctrl, outs, lps, K, sparse_head=bool(sparse_head))
         return outs, lps
 
     def _run_beam(self, statics, eos_idxs, beam_size, out_size, with_verbs, gt):

@@ -109,6 +109,8 @@ SIGNATURES = {
     "vsr_train_backward": (I32, [P, P, P, C.POINTER(VsrWeights), P]),
     "vsr_train_workspace_bytes_rows": (SZ, [P, I32, I32, I32]),
     "vsr_train_forward_rows": (I32, [P, I32, P, P, I32, P, P, P, SZ, P]),
+    "vsr_train_forward_selected": (I32, [P, I32, P, P, P, I32, P, P, P, SZ, P]),
+    "vsr_train_backward_selected": (I32, [P, P, P, C.POINTER(VsrWeights), P]),
     "vsr_train_generation": (I64, [P]),
     "vsr_train_select": (I32, [P, I64, P]),
     "vsr_train_tape_begin": (I32, [P, I32, P, SZ, P]),

@@ -339,6 +339,39 @@ class Engine:
         self.raise_on_bad_ids(device, "train_forward")
         return out, gate
 
+    @_on_device
+    def train_forward_selected(self, B, device, word_in, targets, slots=None, rows_per_image=1):
+        """train_forward with the sparse vocabulary head (vsr_train_forward_selected): targets (rows, T) int64, a word id or -1 = not
+        selected -> (logp_sel (rows, T), gate (rows, T, 2)).  No (rows, T, V) tensor is allocated; the log_softmax rows stay in the
+        training workspace until train_backward_selected consumes them."""
+        K, n_img = int(rows_per_image), B
+        B = n_img * K
+        if word_in.size(0) != B:
+            raise RuntimeError("train_forward_selected: %d rows of word ids for %d images x %d rows per image" % (word_in.size(0), n_img, K))
+        T = word_in.size(1)
+        if tuple(targets.shape) != (B, T):
+            raise RuntimeError("train_forward_selected: targets must be (%d, %d) like the word ids, got %s" % (B, T, tuple(targets.shape)))
+        word_in = word_in.to(device=device, dtype=torch.int64).contiguous()
+        targets = targets.to(device=device, dtype=torch.int64).contiguous()
+        if slots is not None:
+            slots = slots.to(device=device, dtype=torch.int64).contiguous()
+        need = (self.lib.vsr_train_workspace_bytes(self.h, B, T) if K == 1 else
+                self.lib.vsr_train_workspace_bytes_rows(self.h, n_img, K, T))
+        if need == 0:
+            raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
+        self._tws = _grown(self._tws, need, torch.uint8, device)
+        lp_sel = torch.empty(B, T, dtype=torch.float32, device=device)
+        gate = torch.empty(B, T, 2, dtype=torch.float32, device=device)
+        if self._slot.live():
+            raise RuntimeError("internal: training forward into a slot that holds a live forward (prepare(for_training=True) first)")
+        _lib.check(self.lib.vsr_train_forward_selected(self.h, K, _ptr(word_in), _ptr(slots), _ptr(targets), T, _ptr(lp_sel), _ptr(gate),
+                                                       _ptr(self._tws), self._tws.numel(), self._stream(device)))
+        self._slot.generation = self.train_generation()
+        self._slot.token = None
+        self._slot.differentiated = True      # (until train.py attaches the autograd node's token: note_forward)
+        self.raise_on_bad_ids(device, "train_forward_selected")
+        return lp_sel, gate
+
     def note_forward(self):
         """the autograd node of the forward just taken: returns the token that keeps its buffers reserved"""
         import weakref
@@ -352,11 +385,12 @@ class Engine:
         return int(self.lib.vsr_train_generation(self.h))
 
     @_on_device
-    def train_backward(self, device, grad_out, grad_gate, shapes, generation=None, into=None):
+    def train_backward(self, device, grad_out, grad_gate, shapes, generation=None, into=None, selected=False):
         """shapes: list of the 28 parameter shapes in WEIGHT_FIELDS order -> list of gradient tensors.
         generation: train_generation() recorded right after the forward this backward belongs to.
         into: optional list of 28 caller tensors (e.g. views of ONE flat buffer, parallel.FlatGrads) the library writes
-        the gradients to instead of fresh allocations."""
+        the gradients to instead of fresh allocations.
+        selected: the forward was train_forward_selected and grad_out is the (rows, T) gradient of its log-probs (train_backward_selected)."""
         if generation is not None:
             self._make_current(device, generation, "backward of a forward pass")
             self._slot.differentiated = True
@@ -370,8 +404,14 @@ class Engine:
         else:
             grads = [torch.empty(s, dtype=torch.float32, device=device) for s in shapes]
         g = _lib.VsrWeights(*[t.data_ptr() for t in grads])
-        _lib.check(self.lib.vsr_train_backward(self.h, _ptr(grad_out), _ptr(grad_gate), C.byref(g), self._stream(device)))
+        call = self.lib.vsr_train_backward_selected if selected else self.lib.vsr_train_backward
+        _lib.check(call(self.h, _ptr(grad_out), _ptr(grad_gate), C.byref(g), self._stream(device)))
         return grads
+
+    def train_backward_selected(self, device, grad_sel, grad_gate, shapes, generation=None, into=None):
+        """the backward of train_forward_selected: grad_sel (rows, T), grad_gate (rows, T, 2); everything else as train_backward.  It
+        consumes the forward's saved log-prob rows in place: a second backward of the same forward raises."""
+        return self.train_backward(device, grad_sel, grad_gate, shapes, generation, into, selected=True)
 
     def _make_current(self, device, generation, who):
         """several forwards may be alive (each in its own slot): make this one the handle's current forward again"""

@@ -89,10 +89,13 @@ class DataParallelStep:
     exchange_dtype: torch.float32 (default) or torch.bfloat16 - the wire format of the gradient exchange (BASELINE configs[3] names
     bf16: 142 MB instead of 285 MB per step over xGMI).  With bf16 every bucket is rounded to a bf16 image, the images are exchanged
     shard-wise (all-to-all), summed in fp32 by the shard's owner, rounded once more and all-gathered into the fp32 flat buffer the
-    optimizer reads: gradients, Adam state and master weights stay fp32, an exchanged value is rounded twice whatever the world size."""
+    optimizer reads: gradients, Adam state and master weights stay fp32, an exchanged value is rounded twice whatever the world size.
+    sparse_head: True sends both steps through the sparse vocabulary head (model.forward_selected / sample_rl(sparse_head=True)): one
+    log-prob per (row, step) leaves the library, no (b,T,V) tensor or gradient exists.  Needs the HIP model; forward_fn is then not
+    called, and sample_fn is called with sparse_head=True.  Losses, denominators and returned statistics are the dense path's."""
 
     def __init__(self, model_or_params, optimizer, forward_fn=None, sample_fn=None, group=None, all_reduce_fn=None,
-                 exchange_dtype=torch.float32):
+                 exchange_dtype=torch.float32, sparse_head=False):
         self.model = model_or_params if hasattr(model_or_params, "_engine") else None
         self.opt = optimizer
         self.forward_fn = forward_fn
@@ -105,6 +108,9 @@ class DataParallelStep:
         self._wire = None                  # bf16 image of the flat gradient buffer (exchange_dtype = bf16, caller-supplied SUM)
         self._cap_key, self._cap = None, 0
         self._wires = {}                   # shared bf16 staging (send, recv, out) + fp32 shard of the all-to-all exchange, sized for the largest bucket
+        self.sparse_head = bool(sparse_head)
+        if self.sparse_head and self.model is None:
+            raise ValueError("sparse_head=True needs the HIP model (the sparse vocabulary head lives in the library), not a parameter list")
         if self.model is not None:
             from . import _lib
             sd = dict(self.model.named_parameters())
@@ -240,7 +246,29 @@ class DataParallelStep:
             # next call - said explicitly, not inferred from Tensor._version (fused optimizers leave it untouched)
             self.model.invalidate_cache()
 
+    def _xe_step_selected(self, det, captions, ctrl_seq, gate_gts):
+        """xe_step through the sparse head: the same sums over the same global denominators, from (b,T) log-probs"""
+        from .train import xe_targets
+        targets = xe_targets(captions)
+        lp_sel, gate = self.model.forward_selected((det,), (captions, ctrl_seq), targets)
+        tgt_g = gate_gts.reshape(-1).long()
+        # global denominators (no gradient flows through them); every step but the last of a row has a target
+        counts = torch.tensor([float(captions.shape[0] * (captions.shape[1] - 1)), 0.0], dtype=torch.float64, device=lp_sel.device)
+        counts[1] = (tgt_g != -1).sum()
+        self._sum(counts)
+        nll_w = -lp_sel.sum()                                # (the library writes exactly 0.0 at the unselected entries: no mask)
+        nll_g = F.nll_loss(gate.reshape(-1, 2), tgt_g, ignore_index=-1, reduction="sum")
+        loss_cap = nll_w / counts[0].to(nll_w.dtype)
+        loss_gate = nll_g / counts[1].to(nll_g.dtype)
+        loss = loss_cap + 4 * loss_gate                      # this rank's share of the global loss
+        self._backward_and_exchange(loss)
+        self._optimizer_step()
+        stats = torch.stack([loss.detach(), loss_cap.detach(), loss_gate.detach()]).double()
+        return self._sum(stats)
+
     def xe_step(self, det, captions, ctrl_seq, gate_gts):
+        if self.sparse_head:
+            return self._xe_step_selected(det, captions, ctrl_seq, gate_gts)
         out, gate = self.forward_fn(det, captions, ctrl_seq)
         V = out.shape[-1]
         tgt_w = captions[:, 1:].reshape(-1)
@@ -264,10 +292,10 @@ class DataParallelStep:
         samples_per_image = K > 1: sample_fn(det, ctrl, samples_per_image=K) draws K samples of each of the b images in one call
         (model.sample_rl: statics shared); reward_fn then sees (b * K, T) words, row i * K + j = sample j of image i, and the global
         count is the number of samples."""
-        if samples_per_image == 1:
-            (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl)
-        else:
-            (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl, samples_per_image=samples_per_image)
+        kw = {"sparse_head": True} if self.sparse_head else {}
+        if samples_per_image != 1:
+            kw["samples_per_image"] = samples_per_image
+        (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl, **kw)
         reward, baseline = reward_fn(words)
         n = torch.tensor([float(words.shape[0])], dtype=torch.float64, device=lp_w.device)
         self._sum(n)

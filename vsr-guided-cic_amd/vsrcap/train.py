@@ -1,6 +1,7 @@
 """Autograd glue of the training path: ONE autograd.Function whose forward is vsr_train_forward (teacher-forced or
 sample-replayed unroll, activations saved by the library) and whose backward is the hand-written BPTT
 vsr_train_backward.  torch only sees (out, gate) -> 28 parameter gradients; nothing is differentiated by torch.
+_SelectedFn is the same with the sparse vocabulary head (opt-in): torch sees (logp_sel (rows, T), gate) and no (rows, T, V) tensor.
 
 Callers reproduced:
   coco_scripts/train.py:103-113   out, gate = model((det,), (captions, ctrl_det_seqs)); NLL losses; loss.backward()
@@ -52,18 +53,79 @@ def xe_forward_with_grad(model, eng, det, captions, ctrl_seq):
     return _DecoderFn.apply(eng, det.size(0), 1, det.device, captions, None, *_params_in_abi_order(model))
 
 
-def sample_logprobs_with_grad(model, eng, det, ctrl, outs, lps, rows_per_image=1):
+class _SelectedFn(torch.autograd.Function):
+    """_DecoderFn with the sparse vocabulary head: forward = vsr_train_forward_selected, backward = vsr_train_backward_selected.  torch
+    sees (logp_sel (rows, T), gate (rows, T, 2)) -> 28 parameter gradients; the (rows, T, V) log-probs never leave the library's
+    workspace, and nothing of that size is saved here or allocated for a gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, B, rows_per_image, device, word_in, targets, slots, *params):
+        lp_sel, gate = eng.train_forward_selected(B, device, word_in, targets, slots, rows_per_image)
+        ctx.generation = eng.train_generation()
+        ctx.token = eng.note_forward()
+        ctx.eng = eng
+        ctx.device = device
+        ctx.shapes = [tuple(p.shape) for p in params]
+        ctx.save_for_backward(lp_sel, gate)        # (the library reads the gate log-probs again in the backward pass)
+        return lp_sel, gate
+
+    @staticmethod
+    def backward(ctx, g_sel, g_gate):
+        lp_sel, gate = ctx.saved_tensors
+        if g_sel is None:
+            g_sel = torch.zeros_like(lp_sel)
+        if g_gate is None:
+            g_gate = torch.zeros_like(gate)
+        sink = ctx.eng.grad_sink
+        grads = ctx.eng.train_backward_selected(ctx.device, g_sel.contiguous(), g_gate.contiguous(), ctx.shapes, ctx.generation, into=sink)
+        if sink is not None:
+            return (None,) * (7 + len(grads))
+        return (None,) * 7 + tuple(grads)
+
+
+def selected_forward_with_grad(model, eng, det, word_in, targets, slots, rows_per_image=1):
+    """the training forward under autograd with the sparse head: prepare(for_training=True) has been called.  word_in / targets (rows, T),
+    targets = word id or -1 (not selected: log-prob 0.0, no gradient); slots None = step t reads slot t -> (logp_sel (rows, T), gate)."""
+    return _SelectedFn.apply(eng, word_in.size(0) // rows_per_image, rows_per_image, det.device, word_in, targets, slots,
+                             *_params_in_abi_order(model))
+
+
+def xe_targets(captions):
+    """(B, T) targets of the XE loss for the sparse head: step t is scored on captions[:, t + 1] (coco_scripts/train.py:106-108,
+    NLLLoss(out[:, :-1], captions[:, 1:])); the last step has no target: -1"""
+    last = torch.full_like(captions[:, :1], -1)
+    return torch.cat([captions[:, 1:], last], 1)
+
+
+def xe_loss_from_selected(lp_sel, gate, targets, gate_gts, gate_weight=4.0):
+    """coco_scripts/train.py:106-110 from the selected log-probs: loss_cap = the mean NLL over the selected entries (targets >= 0),
+    loss_gate = the mean NLL of the gate head over the ground truths that are not -1 (ignore_index).  -> (loss, loss_cap, loss_gate)"""
+    sel = targets >= 0
+    loss_cap = -torch.where(sel, lp_sel, torch.zeros_like(lp_sel)).sum() / sel.sum().to(lp_sel.dtype)
+    gts = gate_gts.reshape(-1).long()
+    keep = gts != -1
+    lp_g = gate.reshape(-1, 2).gather(1, gts.clamp(min=0).unsqueeze(-1)).squeeze(-1)
+    loss_gate = -torch.where(keep, lp_g, torch.zeros_like(lp_g)).sum() / keep.sum().to(lp_g.dtype)
+    return loss_cap + gate_weight * loss_gate, loss_cap, loss_gate
+
+
+def sample_logprobs_with_grad(model, eng, det, ctrl, outs, lps, rows_per_image=1, sparse_head=False):
     """log-probs of given samples WITH a graph: replays the sampled words / gates through the training forward
     (word fed at step t = previous sample, slot pointer = clamped running sum of the previous gates).
-    rows_per_image = K: the samples are (B * K, T), K adjacent rows per image; the forward shares the image's statics among them."""
+    rows_per_image = K: the samples are (B * K, T), K adjacent rows per image; the forward shares the image's statics among them.
+    sparse_head: the targets of the vocabulary head are the sampled words and lp_w is the library's output directly - no
+    (rows, T, V) tensor, no gather."""
     words, gates = outs
     B, T = words.shape                    # (decoder rows)
     L = ctrl.size(1)                      # (dense tensor or IndexedRegions: both answer size(1) with the slot count)
     bos = torch.full((B, 1), model.bos_idx, dtype=torch.int64, device=words.device)
     word_in = torch.cat([bos, words[:, :-1]], 1)
     slots = torch.cat([torch.zeros_like(bos), torch.clamp(torch.cumsum(gates[:, :-1], 1), max=L - 1)], 1)
-    out, gate = _DecoderFn.apply(eng, B // rows_per_image, rows_per_image, det.device, word_in, slots, *_params_in_abi_order(model))
-    lp_w = out.gather(2, words.unsqueeze(-1)).squeeze(-1)
+    if sparse_head:
+        lp_w, gate = selected_forward_with_grad(model, eng, det, word_in, words, slots, rows_per_image)
+    else:
+        out, gate = _DecoderFn.apply(eng, B // rows_per_image, rows_per_image, det.device, word_in, slots, *_params_in_abi_order(model))
+        lp_w = out.gather(2, words.unsqueeze(-1)).squeeze(-1)
     lp_g = gate.gather(2, gates.unsqueeze(-1)).squeeze(-1)
     return lp_w, lp_g
 
