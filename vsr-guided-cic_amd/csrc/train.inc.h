@@ -62,6 +62,44 @@ struct TrainCtx {                      // (plain data + two vectors: copied into
 
 static inline size_t up4(size_t x) { return (x + 7) & ~size_t(7); }   // K paddings: multiples of 8 (16-byte bf16 chunks; fp32 needs 4)
 
+// One transposed operand of the backward pass: buf (C, ld_out) = src (R, C; leading dimension ld_in) transposed.  THE description of the
+// buffer: carve_train takes it, its bf16 twin and its fp16-pair image (exponent slot `slot`) by size(), the backward transposes by R / C / ld.
+struct TOperand {
+    float* TrainCtx::* buf; const float* src; int R, C; long long ld_in, ld_out; int slot;
+    size_t size() const { return (size_t)C * (size_t)ld_out; }
+};
+constexpr int N_TW = 13, N_TX = 10, N_TOPS = N_TW + N_TX;
+// The 13 transposed weights, then the 10 transposed activations: the order of the workspace and of the two batched transposes.  Reads
+// B / rpi / TB / TBp / Bp / RLp of `t`: for a sealed tape those of the steps taken (its buffers were carved for tape_max).  The activations'
+// sources lie in the workspace: null while it is only being sized.  tX_reg, the last entry, is sized here (RLp) and transposed by a call
+// of its own, through the list of the non-padding rows (R = 0 here)
+static void train_operands(const vsr_handle* h, const TrainCtx& t, TOperand (&o)[N_TOPS]) {
+    const vsr_dims& d = h->d;
+    const vsr_weights& w = h->w;
+    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
+    const int in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0);
+    const size_t BH = (size_t)t.B * H;
+    int n = 0;
+    // (N, K) weight -> (K, ld_out >= N); the transposed matrix has the bound of the matrix: its slot (0..13, field order of b16_weight_list)
+    auto W = [&](float* TrainCtx::* buf, const float* src, int N, int K, long long ld_out) { o[n++] = TOperand{buf, src, N, K, K, ld_out, h->h2_slot_of(src)}; };
+    W(&TrainCtx::wT_ih1, w.lstm1_weight_ih, 4 * H, in1, 4 * H); W(&TrainCtx::wT_is, w.W1_is_weight, H, in1, H); W(&TrainCtx::wT_ig, w.W1_ig_weight, H, in1, H);
+    W(&TrainCtx::wT_hh1, w.lstm1_weight_hh, 4 * H, H, 4 * H); W(&TrainCtx::wT_hs, w.W1_hs_weight, H, H, H);
+    W(&TrainCtx::wT_ih2, w.lstm2_weight_ih, 4 * H, in2, 4 * H); W(&TrainCtx::wT_hh2, w.lstm2_weight_hh, 4 * H, H, 4 * H);
+    W(&TrainCtx::wT_hg, w.W1_hg_weight, H, H, H); W(&TrainCtx::wT_ha, w.att_ha_weight, A, H, A); W(&TrainCtx::wT_sfc, w.s_fc_weight, D, H, D);
+    W(&TrainCtx::wT_sa, w.att_sa_weight, A, H, A); W(&TrainCtx::wT_ga, w.att_ga_weight, A, H, A);
+    W(&TrainCtx::wT_out, w.out_fc_weight, V, H, (long long)up4(V));      // (K of the dh2_vocab GEMM: a multiple of 8)
+    // (rows, C) activation, rows (t, b) -> (C, rows padded); slot: the class of the activation
+    auto X = [&](float* TrainCtx::* buf, const float* src, size_t skip, int R, int C, long long ld_out, int slot) {
+        o[n++] = TOperand{buf, src ? src + skip : nullptr, R, C, C, ld_out, slot};
+    };
+    X(&TrainCtx::tX_h2prev, t.h2s, 0, t.TB, H, t.TBp, H2A_UNIT); X(&TrainCtx::tX_x, t.x_all, 0, t.TB, E, t.TBp, H2A_EMBED);   // state slots 0 .. T-1: entering step t
+    X(&TrainCtx::tX_h1prev, t.h1s, 0, t.TB, H, t.TBp, H2A_UNIT); X(&TrainCtx::tX_h1, t.h1s, BH, t.TB, H, t.TBp, H2A_UNIT);
+    X(&TrainCtx::tX_att, t.atts, 0, t.TB, D, t.TBp, H2A_ATT); X(&TrainCtx::tX_st, t.s_ts, 0, t.TB, H, t.TBp, H2A_UNIT);
+    X(&TrainCtx::tX_gt, t.g_ts, 0, t.TB, H, t.TBp, H2A_UNIT); X(&TrainCtx::tX_h2, t.h2s, BH, t.TB, H, t.TBp, H2A_UNIT);
+    X(&TrainCtx::tX_vbar, h->c.vbar, 0, t.B / t.rpi, D, t.Bp, H2A_DET);     // per IMAGE
+    X(&TrainCtx::tX_reg, h->c.regions, 0, 0, D, t.RLp, H2A_REGION);
+}
+
 static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     const vsr_dims& d = h->d;
     const Ctx& c = h->c;
@@ -94,42 +132,24 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     t.dh1_c = b.take<float>(B * H); t.dh2_c = b.take<float>(B * H);
     for (int i = 0; i < 2; ++i) { t.dc1_c[i] = b.take<float>(B * H); t.dc2_c[i] = b.take<float>(B * H); }
     t.dpre1sum = b.take<float>(Bi * 6 * H); t.dpre2sum = b.take<float>(Bi * 4 * H); t.dx_all = b.take<float>(TB * E); t.xproj_all = b.take<float>(TB * 6 * H);
-    t.wT_ih1 = b.take<float>(in1 * 4 * H); t.wT_is = b.take<float>(in1 * H); t.wT_ig = b.take<float>(in1 * H);
-    t.wT_hh1 = b.take<float>(H * 4 * H); t.wT_hs = b.take<float>(H * H);
-    t.wT_ih2 = b.take<float>(in2 * 4 * H); t.wT_hh2 = b.take<float>(H * 4 * H);
-    t.wT_hg = b.take<float>(H * H); t.wT_ha = b.take<float>(H * A); t.wT_sfc = b.take<float>(H * D);
-    t.wT_sa = b.take<float>(H * A); t.wT_ga = b.take<float>(H * A); t.wT_out = b.take<float>(H * up4(V));
+    // the transposed operands (train_operands): fp32 buffer, bf16 twin and fp16-pair image of each, all sized and slotted by its entry
+    TOperand ops[N_TOPS];
+    train_operands(h, t, ops);
     t.twins.clear();
-    auto twin = [&](const float* f, size_t n) { t.twins.push_back(TrainCtx::Twin{f, n, b.take<uint16_t>(n)}); };
-    twin(t.wT_ih1, in1 * 4 * H); twin(t.wT_is, in1 * H); twin(t.wT_ig, in1 * H); twin(t.wT_hh1, H * 4 * H); twin(t.wT_hs, H * H);
-    twin(t.wT_ih2, in2 * 4 * H); twin(t.wT_hh2, H * 4 * H); twin(t.wT_hg, H * H); twin(t.wT_ha, H * A); twin(t.wT_sfc, H * D);
-    twin(t.wT_sa, H * A); twin(t.wT_ga, H * A); twin(t.wT_out, H * up4(V));
+    auto take = [&](int lo, int hi) { for (int i = lo; i < hi; ++i) t.*ops[i].buf = b.take<float>(ops[i].size()); };
+    auto twins = [&](int lo, int hi) { for (int i = lo; i < hi; ++i) t.twins.push_back(TrainCtx::Twin{t.*ops[i].buf, ops[i].size(), b.take<uint16_t>(ops[i].size())}); };
+    take(0, N_TW);
+    twins(0, N_TW);
     b.off = (b.off + 255) & ~size_t(255);
-    t.tX_h2prev = b.take<float>(H * TBp); t.tX_x = b.take<float>(E * TBp); t.tX_h1prev = b.take<float>(H * TBp);
-    t.tX_h1 = b.take<float>(H * TBp); t.tX_att = b.take<float>(D * TBp); t.tX_st = b.take<float>(H * TBp);
-    t.tX_gt = b.take<float>(H * TBp); t.tX_h2 = b.take<float>(H * TBp); t.tX_vbar = b.take<float>(D * Bp);
-    t.tX_reg = b.take<float>(D * RLp);
+    take(N_TW, N_TOPS);
     t.tY_dpre1 = b.take<float>(6 * H * TBp); t.tY_dpre2 = b.take<float>(4 * H * TBp); t.tY_dlogits = b.take<float>(V * TBp);
     t.tY_dhA = b.take<float>(A * TBp); t.tY_dsent = b.take<float>(D * TBp); t.tY_dsa = b.take<float>(A * TBp); t.tY_dga = b.take<float>(A * TBp);
     t.tY_dpre1sum = b.take<float>(6 * H * Bp); t.tY_dpre2sum = b.take<float>(4 * H * Bp); t.tY_dP = b.take<float>(A * RLp);
-    twin(t.tX_h2prev, H * TBp); twin(t.tX_x, E * TBp); twin(t.tX_h1prev, H * TBp); twin(t.tX_h1, H * TBp); twin(t.tX_att, D * TBp);
-    twin(t.tX_st, H * TBp); twin(t.tX_gt, H * TBp); twin(t.tX_h2, H * TBp); twin(t.tX_vbar, D * Bp); twin(t.tX_reg, D * RLp);
+    twins(N_TW, N_TOPS);
     t.imgs.clear(); t.h2img = nullptr;
     if (h->h2_on && !h->bf16_on) {
         size_t off = 0;
-        auto img = [&](const float* f, size_t n, int slot) { t.imgs.push_back(TrainCtx::Img{f, n, off, slot}); off += up4(n); };
-        // (slots 0..13: field order of b16_weight_list - the transposed matrix has the bound of the matrix)
-        const vsr_weights& w = h->w;
-        img(t.wT_ih1, in1 * 4 * H, h->h2_slot_of(w.lstm1_weight_ih)); img(t.wT_is, in1 * H, h->h2_slot_of(w.W1_is_weight));
-        img(t.wT_ig, in1 * H, h->h2_slot_of(w.W1_ig_weight)); img(t.wT_hh1, H * 4 * H, h->h2_slot_of(w.lstm1_weight_hh));
-        img(t.wT_hs, H * H, h->h2_slot_of(w.W1_hs_weight)); img(t.wT_ih2, in2 * 4 * H, h->h2_slot_of(w.lstm2_weight_ih));
-        img(t.wT_hh2, H * 4 * H, h->h2_slot_of(w.lstm2_weight_hh)); img(t.wT_hg, H * H, h->h2_slot_of(w.W1_hg_weight));
-        img(t.wT_ha, H * A, h->h2_slot_of(w.att_ha_weight)); img(t.wT_sfc, H * D, h->h2_slot_of(w.s_fc_weight));
-        img(t.wT_sa, H * A, h->h2_slot_of(w.att_sa_weight)); img(t.wT_ga, H * A, h->h2_slot_of(w.att_ga_weight));
-        img(t.wT_out, H * up4(V), h->h2_slot_of(w.out_fc_weight));
-        img(t.tX_h2prev, H * TBp, H2A_UNIT); img(t.tX_x, E * TBp, H2A_EMBED); img(t.tX_h1prev, H * TBp, H2A_UNIT); img(t.tX_h1, H * TBp, H2A_UNIT);
-        img(t.tX_att, D * TBp, H2A_ATT); img(t.tX_st, H * TBp, H2A_UNIT); img(t.tX_gt, H * TBp, H2A_UNIT); img(t.tX_h2, H * TBp, H2A_UNIT);
-        img(t.tX_vbar, D * Bp, H2A_DET); img(t.tX_reg, D * RLp, H2A_REGION);
+        for (const TOperand& o : ops) { t.imgs.push_back(TrainCtx::Img{t.*o.buf, o.size(), off, o.slot}); off += up4(o.size()); }
         b.off = (b.off + 255) & ~size_t(255);
         t.h2img = b.take<float>(off);
         b.off = (b.off + 255) & ~size_t(255);
@@ -273,31 +293,31 @@ struct TransBatch {
         m.blk[i + 1] = blocks;
     }
 };
+// where a transpose's output goes: kind 0 = the fp32 buffer, 1 = its bf16 twin, 2 = an fp16-pair image scaled by exps[slot] - the registered
+// one of a W operand (h2img), else `out` itself when the caller names a slot (self_slot >= 0) and the buffer can hold an image in place
+struct TransDst { int kind; uint16_t* img; int slot; const int* exps; };
+static TransDst trans_dst(const vsr_handle* h, float* out, long long ld_out, bool h2img, int self_slot) {
+    if (uint16_t* tw = h->bf16_on ? const_cast<uint16_t*>(h->map16(out)) : nullptr) return TransDst{1, tw, 0, nullptr};
+    if (h2img) {
+        if (const H2Range* r2 = h->map_h2(out)) return TransDst{2, reinterpret_cast<uint16_t*>(const_cast<float*>(r2->img + (out - r2->lo))), r2->slot, h->h2_exps};
+        if (self_slot >= 0 && ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 31) == 0) return TransDst{2, reinterpret_cast<uint16_t*>(out), self_slot, h->h2_exps};
+    }
+    return TransDst{0, nullptr, 0, nullptr};
+}
 static void transpose(vsr_handle* h, hipStream_t s, const float* in, long long ld_in, int R, int C, float* out, long long ld_out,
                       const int* list = nullptr, bool h2img = false, int self_slot = -1, const int* rlimit = nullptr, TransBatch* tb = nullptr) {
-    uint16_t* tw = h->bf16_on ? const_cast<uint16_t*>(h->map16(out)) : nullptr;
-    const dim3 grid(cdiv(C, 64), cdiv(R, 64)), block(256);
-    const H2Range* r2 = (h2img && !tw) ? h->map_h2(out) : nullptr;
-    if (tb && !list) {
-        if (h2img && !tw && !r2 && self_slot >= 0 && ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 31) == 0)
-            tb->add(s, 2, h->h2_exps, in, ld_in, R, C, out, ld_out, reinterpret_cast<uint16_t*>(out), self_slot);
-        else if (r2) tb->add(s, 2, h->h2_exps, in, ld_in, R, C, out, ld_out, reinterpret_cast<uint16_t*>(const_cast<float*>(r2->img + (out - r2->lo))), r2->slot);
-        else if (tw) tb->add(s, 1, nullptr, in, ld_in, R, C, out, ld_out, tw, 0);
-        else tb->add(s, 0, nullptr, in, ld_in, R, C, out, ld_out, nullptr, 0);
-        return;
-    }
-    if (h2img && !tw && !r2 && self_slot >= 0 && ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 31) == 0) {
-        uint16_t* img = reinterpret_cast<uint16_t*>(out);
-        if (list) hipLaunchKernelGGL((k_transpose_t<true, 2>), grid, block, 0, s, in, ld_in, list, R, C, out, ld_out, img, h->h2_exps, self_slot, rlimit);
-        else hipLaunchKernelGGL((k_transpose_t<false, 2>), grid, block, 0, s, in, ld_in, (const int*)nullptr, R, C, out, ld_out, img, h->h2_exps, self_slot);
-    } else if (r2) {
-        uint16_t* img = reinterpret_cast<uint16_t*>(const_cast<float*>(r2->img + (out - r2->lo)));
-        if (list) hipLaunchKernelGGL((k_transpose_t<true, 2>), grid, block, 0, s, in, ld_in, list, R, C, out, ld_out, img, h->h2_exps, r2->slot, rlimit);
-        else hipLaunchKernelGGL((k_transpose_t<false, 2>), grid, block, 0, s, in, ld_in, (const int*)nullptr, R, C, out, ld_out, img, h->h2_exps, r2->slot);
-    } else if (list && tw) hipLaunchKernelGGL((k_transpose_t<true, 1>), grid, block, 0, s, in, ld_in, list, R, C, out, ld_out, tw, (const int*)nullptr, 0, rlimit);
-    else if (list) hipLaunchKernelGGL((k_transpose_t<true, 0>), grid, block, 0, s, in, ld_in, list, R, C, out, ld_out, (uint16_t*)nullptr, (const int*)nullptr, 0, rlimit);
-    else if (tw) hipLaunchKernelGGL((k_transpose_t<false, 1>), grid, block, 0, s, in, ld_in, (const int*)nullptr, R, C, out, ld_out, tw);
-    else hipLaunchKernelGGL((k_transpose_t<false, 0>), grid, block, 0, s, in, ld_in, (const int*)nullptr, R, C, out, ld_out, (uint16_t*)nullptr);
+    const TransDst d = trans_dst(h, out, ld_out, h2img, self_slot);
+    if (tb && !list) { tb->add(s, d.kind, d.exps, in, ld_in, R, C, out, ld_out, d.img, d.slot); return; }
+    auto go = [&](auto GATHER, auto IMG) {
+        hipLaunchKernelGGL((k_transpose_t<decltype(GATHER)::value, decltype(IMG)::value>), dim3(cdiv(C, 64), cdiv(R, 64)), dim3(256), 0, s, in, ld_in, list, R, C,
+                           out, ld_out, d.img, d.exps, d.slot, list ? rlimit : (const int*)nullptr);
+    };
+    auto kind = [&](auto GATHER) {
+        if (d.kind == 2) go(GATHER, std::integral_constant<int, 2>{});
+        else if (d.kind == 1) go(GATHER, std::integral_constant<int, 1>{});
+        else go(GATHER, std::integral_constant<int, 0>{});
+    };
+    if (list) kind(std::true_type{}); else kind(std::false_type{});
 }
 
 // ---------------------------------------------------------------------------------------------- more than one live forward
@@ -369,6 +389,72 @@ extern "C" size_t vsr_train_workspace_bytes(const vsr_handle* h, int32_t B, int3
 // f16x2 flavour: fp16-pair images of the A operands (all-DMA kernel); BH elements of 4 bytes per state slot
 static bool train_a_images(const vsr_handle* h, const TrainCtx& t) {
     return h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg && t.h1s16 && (t.B * h->d.rnn_size) % 8 == 0;
+}
+// Begins a saved forward of K rows per image and T steps in the caller's buffer: carves it, drops the forwards filed in it, registers the
+// images of its transposed operands and zeroes the states of step 0.  `who`: the public function, for the messages
+static int train_begin(vsr_handle* h, TrainCtx& t, int K, int T, void* train_ws, size_t bytes, const char* who, hipStream_t s) {
+    t.valid = false;
+    t.rpi = K; t.B = h->c.B * K; t.T = T;
+    const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
+    if (need > bytes) return fail("%s: training workspace too small (%zu < %zu)", who, bytes, need);
+    drop_saved_forwards_in(h->saved, train_ws, need);       // forwards filed in THIS buffer are overwritten now
+    t.tws_lo = reinterpret_cast<const char*>(train_ws); t.tws_bytes = need;
+    register_train_images(h, t);                           // the bf16 twins / fp16-pair images of this workspace's transposed operands
+    const size_t BH = (size_t)t.B * h->d.rnn_size;
+    ZeroList zl;                                           // the zero states of step 0 (and their images): one launch
+    zl.add(t.h1s, BH * sizeof(float)); zl.add(t.c1s, BH * sizeof(float)); zl.add(t.h2s, BH * sizeof(float)); zl.add(t.c2s, BH * sizeof(float));
+    if (train_a_images(h, t)) { zl.add(t.h1s16, BH * 2 * sizeof(uint16_t)); zl.add(t.h2s16, BH * 2 * sizeof(uint16_t)); }
+    if (zl.launch(s)) return fail("%s: zero launch failed", who);
+    return 0;
+}
+// the per-batch rows of the f16x2 exponent table as they are now -> the forward's stash (vsr_train_select restores from there)
+static void train_stash(vsr_handle* h, TrainCtx& t, hipStream_t s) {
+    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
+}
+// Files the forward under a new generation: from here on vsr_train_select can make it the handle's current one again
+static int train_file(vsr_handle* h, TrainCtx& t, hipStream_t s) {
+    t.valid = true;
+    t.generation = ++h->gen_counter;
+    train_stash(h, t, s);
+    LAUNCHCHK();
+    h->saved->v.push_back(SavedForward{h->c, t, h->ws_lo, h->ws_bytes});
+    return 0;
+}
+// The x part of the LSTM1 / gate pre-activations of o.M rows does not depend on the recurrence: one GEMM -> dst (o.M, 6H)
+static int train_xproj(vsr_handle* h, TrainCtx& t, const StepOperands& o, float* dst, hipStream_t s) {
+    GemmBuilder g;
+    add_lstm1(g, h->d, h->w, o, t.scratch, L1_X);
+    const int ns = g.finish(h);
+    const long long stride = (long long)o.M * 6 * h->d.rnn_size;
+    if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
+    for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
+    if (g.launch(s, h)) return fail("train x-projection gemm launch failed");
+    hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch, ns, stride, stride, dst);
+    LAUNCHCHK();
+    return 0;
+}
+// S6 of o.M rows (gathered through `rows` when given): logits = h2 . out_fc^T as slabs of stride o.M V in t.scratch.  Returns their
+// number (at most ns_max when that is given), 0 after a failure; the caller's head kernel (launch_vocab, k_vocab_select) sums them
+static int train_vocab_gemm(vsr_handle* h, TrainCtx& t, const StepOperands& o, const int* rows, int ns_max, hipStream_t s) {
+    GemmBuilder g;
+    add_vocab(g, h->d, h->w, o, t.scratch, rows);
+    const int ns = g.finish(h);
+    const long long stride = (long long)o.M * h->d.vocab_size;
+    if ((ns_max && ns > ns_max) || (size_t)stride * ns > t.scratch_floats) { fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns); return 0; }
+    g.a.p[0].slab_stride = stride;
+    if (g.launch(s, h)) { fail("train S6 gemm launch failed"); return 0; }
+    return ns;
+}
+// ... and the dense head over them: whole log_softmax rows -> out (o.M, V)
+static int train_vocab_full(vsr_handle* h, TrainCtx& t, const StepOperands& o, const int* rows, float* out, hipStream_t s) {
+    const int ns = train_vocab_gemm(h, t, o, rows, 0, s);
+    if (!ns) return 1;
+    const GateLogitArgs no_gate{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr, 0};
+    StepIO io;                                         // (K = 1, no gate logits)
+    io.M = o.M; io.vmode = VM_FULL; io.full_out = out; io.full_stride = h->d.vocab_size;
+    launch_vocab(h, s, io, t.scratch, ns, (long long)o.M * h->d.vocab_size, no_gate);
+    LAUNCHCHK();
+    return 0;
 }
 // Step tt of the unroll: state slot tt -> slot tt + 1, the step's saves, its gate log-probs into lg_out (row stride lg_stride).  The body
 // of vsr_train_forward's loop over the steps; a tape (vsr_train_tape_step) takes the same step one call at a time.
@@ -465,26 +551,14 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
     const vsr_weights& w = h->w;
     const int B = c.B * K, H = d.rnn_size, E = d.input_encoding_size, V = d.vocab_size;      // (B: decoder rows)
     TrainCtx& t = *h->tc;
-    t.valid = false;
-    t.rpi = K; t.B = B; t.T = T;
     t.tape_max = t.tape_steps = 0; t.sealed = false;
     t.sparse = targets != nullptr; t.consumed = false;
-    const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
+    if (train_begin(h, t, K, T, train_ws, train_ws_bytes, "vsr_train_forward", s)) return 1;
     t.tgt32 = t.sparse ? t.rows_bt : nullptr;
-    if (need > train_ws_bytes) return fail("vsr_train_forward: training workspace too small (%zu < %zu)", train_ws_bytes, need);
-    drop_saved_forwards_in(h->saved, train_ws, need);       // forwards filed in THIS buffer are overwritten now
-    t.tws_lo = reinterpret_cast<const char*>(train_ws); t.tws_bytes = need;
-    register_train_images(h, t);                           // the bf16 twins / fp16-pair images of this workspace's transposed operands
     const int TB = T * B;
     const size_t BH = (size_t)B * H;
     const bool im = train_a_images(h, t);
-    {   // the zero states of step 0 (and their images): one launch
-        ZeroList zl;
-        zl.add(t.h1s, BH * sizeof(float)); zl.add(t.c1s, BH * sizeof(float)); zl.add(t.h2s, BH * sizeof(float)); zl.add(t.c2s, BH * sizeof(float));
-        if (im) { zl.add(t.h1s16, BH * 2 * sizeof(uint16_t)); zl.add(t.h2s16, BH * 2 * sizeof(uint16_t)); }
-        if (zl.launch(s)) return fail("vsr_train_forward: zero launch failed");
-    }
-    StepOperands all;                                      // the operands of the two launches over all T B rows (step_gemms.h)
+    StepOperands all;                                     // the operands of the two launches over all T B rows (step_gemms.h)
     all.M = TB;
     // (with images: the rows are gathered from the embedding table's image by the GEMM itself)
     all.x = im ? w.embed_weight : t.x_all; all.word = im ? t.word32 : nullptr;
@@ -492,17 +566,7 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
     hipLaunchKernelGGL(k_train_indices, dim3(cdiv(TB, 256)), dim3(256), 0, s, word_in, slots, T, B, V, c.L, t.word32, t.slot32, t.rows_bt, c.nvalid_dev + 2);
     hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((long long)TB * E, 256)), dim3(256), 0, s, w.embed_weight, t.word32, TB, E, t.x_all);
     LAUNCHCHK();
-    {   // the x part of every step's LSTM1 / gate pre-activations does not depend on the recurrence: one GEMM with M = T B
-        GemmBuilder g;
-        add_lstm1(g, d, w, all, t.scratch, L1_X);
-        const int ns = g.finish(h);
-        const long long stride = (long long)TB * 6 * H;
-        if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
-        for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-        if (g.launch(s, h)) return fail("train x-projection gemm launch failed");
-        hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch, ns, stride, stride, t.xproj_all);
-        LAUNCHCHK();
-    }
+    if (train_xproj(h, t, all, t.xproj_all, s)) return 1;      // every step's x part at once: M = T B
 
     for (int tt = 0; tt < T; ++tt)
         if (train_forward_step(h, t, K, tt, im, logp_gates + (size_t)tt * 2, (long long)T * 2, s)) return 1;
@@ -510,13 +574,9 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         // S6 for all steps at once, sparse head: the rows in their natural (t, b) order (state slots 1 .. T: nothing to gather), then
         // k_vocab_select: the log_softmax rows stay in t.dlogits, the targets' entries go to the caller's (rows, T) tensor
         all.h2_new = t.h2s + BH; all.h2_new16 = im ? t.h2s16 + BH * 2 : nullptr;
-        GemmBuilder g;
-        add_vocab(g, d, w, all, t.scratch);
-        const int ns = g.finish(h);
+        const int ns = train_vocab_gemm(h, t, all, nullptr, 8, s);           // (k_vocab_select sums at most 8 slabs: slab_sum4)
+        if (!ns) return 1;
         const long long stride = (long long)TB * V;
-        if (ns > 8 || (size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns);
-        g.a.p[0].slab_stride = stride;
-        if (g.launch(s, h)) return fail("train S6 gemm launch failed");
         const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;
         const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
         const int Vp = (int)up4(V);
@@ -527,27 +587,11 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         LAUNCHCHK();
     } else {   // S6 for all steps at once: logits = h2[(b, t)] . out_fc^T (M = T B rows gathered in (b, t) order, so that the
         // (B, T, V) log-prob tensor is written row by row), then one log_softmax launch
-        GemmBuilder g;
-        add_vocab(g, d, w, all, t.scratch, t.rows_bt);
-        const int ns = g.finish(h);
-        const long long stride = (long long)TB * V;
-        if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns);
-        g.a.p[0].slab_stride = stride;
-        if (g.launch(s, h)) return fail("train S6 gemm launch failed");
-        const GateLogitArgs no_gate{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr, 0};
-        StepIO io;                                         // (K = 1, no gate logits: the whole log_softmax rows)
-        io.M = TB; io.vmode = VM_FULL; io.full_out = logp_words; io.full_stride = V;
-        launch_vocab(h, s, io, t.scratch, ns, stride, no_gate);
-        LAUNCHCHK();
+        if (train_vocab_full(h, t, all, t.rows_bt, logp_words, s)) return 1;
     }
     t.logp_w = t.sparse ? nullptr : logp_words;
     t.logp_g = logp_gates;
-    t.valid = true;
-    t.generation = ++h->gen_counter;
-    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
-    LAUNCHCHK();
-    h->saved->v.push_back(SavedForward{c, t, h->ws_lo, h->ws_bytes});
-    return 0;
+    return train_file(h, t, s);
 }
 extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const int64_t* slots, int32_t T, float* logp_words,
                                  float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
@@ -574,17 +618,6 @@ extern "C" int vsr_train_forward_selected(vsr_handle* h, int32_t rows_per_image,
 // saved forward at the caller's stacked (B, T, .) log-probs.  vsr_train_select / vsr_train_backward then see an ordinary forward.
 // One row per image (K = 1), zero initial state.
 
-// one step's (B) int64 word / slot ids -> the step's rows of the (T, B) int32 copies (counted and clamped like k_train_indices)
-__global__ void k_tape_indices(const int64_t* __restrict__ word_in, const int64_t* __restrict__ slots, int B, int V, int L,
-                               int* __restrict__ word32, int* __restrict__ slot32, int* __restrict__ bad) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    long long w = word_in[b], k = slots[b];
-    if (w < 0 || w >= V) { atomicAdd(bad, 1); w = w < 0 ? 0 : V - 1; }
-    if (k < 0 || k >= L) { atomicAdd(bad, 1); k = k < 0 ? 0 : L - 1; }
-    word32[b] = (int)w;
-    slot32[b] = (int)k;
-}
 // the (b, t)-ordered list of the saved state rows for the T steps taken (what k_train_indices lays out for a whole forward)
 __global__ void k_tape_rows_bt(int T, int B, int* __restrict__ rows_bt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -615,30 +648,13 @@ extern "C" int vsr_train_tape_begin(vsr_handle* h, int32_t max_steps, void* trai
     if (max_steps < 1 || max_steps > h->d.seq_len) return fail("vsr_train_tape_begin: max_steps %d not in [1, seq_len %d]", max_steps, h->d.seq_len);
     hipStream_t s = (hipStream_t)stream;
     TrainCtx& t = *h->tc;
-    t.valid = false;
-    t.rpi = 1; t.B = c.B; t.T = max_steps;
-    const size_t need = carve_train(h, t, reinterpret_cast<char*>(train_ws));
-    if (need > train_ws_bytes) return fail("vsr_train_tape_begin: training workspace too small (%zu < %zu)", train_ws_bytes, need);
-    drop_saved_forwards_in(h->saved, train_ws, need);
-    t.tws_lo = reinterpret_cast<const char*>(train_ws); t.tws_bytes = need;
-    register_train_images(h, t);
-    const size_t BH = (size_t)t.B * h->d.rnn_size;
-    {   // the zero states of step 0 (and their images), as in vsr_train_forward
-        ZeroList zl;
-        zl.add(t.h1s, BH * sizeof(float)); zl.add(t.c1s, BH * sizeof(float)); zl.add(t.h2s, BH * sizeof(float)); zl.add(t.c2s, BH * sizeof(float));
-        if (train_a_images(h, t)) { zl.add(t.h1s16, BH * 2 * sizeof(uint16_t)); zl.add(t.h2s16, BH * 2 * sizeof(uint16_t)); }
-        if (zl.launch(s)) return fail("vsr_train_tape_begin: zero launch failed");
-    }
+    if (train_begin(h, t, 1, max_steps, train_ws, train_ws_bytes, "vsr_train_tape_begin", s)) return 1;
     t.tape_max = max_steps; t.tape_steps = 0; t.sealed = false;
     t.sparse = t.consumed = false; t.tgt32 = nullptr;
     t.logp_w = t.logp_g = nullptr;
-    t.valid = true;
-    t.generation = ++h->gen_counter;
-    // (stashed now, not only at the seal: a vsr_prepare*() of another batch may come between two steps, and vsr_train_select restores from here)
-    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
-    LAUNCHCHK();
-    h->saved->v.push_back(SavedForward{c, t, h->ws_lo, h->ws_bytes});
-    return 0;
+    // (filed - and the exponent rows stashed - now, not only at the seal: a vsr_prepare*() of another batch may come between two steps,
+    // and vsr_train_select restores from here)
+    return train_file(h, t, s);
 }
 
 extern "C" int vsr_train_tape_step(vsr_handle* h, int64_t generation, const int64_t* word_in, const int64_t* slots, float* logp_words,
@@ -657,41 +673,17 @@ extern "C" int vsr_train_tape_step(vsr_handle* h, int64_t generation, const int6
     const bool im = train_a_images(h, t);
     int* word32 = t.word32 + (size_t)tt * B;
     float* x = t.x_all + (size_t)tt * B * E;               // (the weight-gradient phase reads the rows of every step)
-    hipLaunchKernelGGL(k_tape_indices, dim3(cdiv(B, 256)), dim3(256), 0, s, word_in, slots, B, V, c.L, word32, t.slot32 + (size_t)tt * B, c.nvalid_dev + 2);
+    // (T = 1, no row list: the step's (B) ids -> the step's rows of the (T, B) int32 copies, counted and clamped as for a whole forward)
+    hipLaunchKernelGGL(k_train_indices, dim3(cdiv(B, 256)), dim3(256), 0, s, word_in, slots, 1, B, V, c.L, word32, t.slot32 + (size_t)tt * B, (int*)nullptr, c.nvalid_dev + 2);
     hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((long long)B * E, 256)), dim3(256), 0, s, w.embed_weight, word32, B, E, x);
     LAUNCHCHK();
-    {   // the x part of this step's LSTM1 / gate pre-activations: M = B rows into the step's rows of xproj_all
-        StepOperands xo;
-        xo.M = B;
-        xo.x = im ? w.embed_weight : x; xo.word = im ? word32 : nullptr;
-        GemmBuilder g;
-        add_lstm1(g, d, w, xo, t.scratch, L1_X);
-        const int ns = g.finish(h);
-        const long long stride = (long long)B * 6 * H;
-        if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
-        for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-        if (g.launch(s, h)) return fail("tape x-projection gemm launch failed");
-        hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch, ns, stride, stride, t.xproj_all + (size_t)tt * B * 6 * H);
-        LAUNCHCHK();
-    }
+    StepOperands o;                                        // this step's M = B rows of the two launches a whole forward makes over all T B
+    o.M = B;
+    o.x = im ? w.embed_weight : x; o.word = im ? word32 : nullptr;
+    o.h2_new = t.h2s + (size_t)(tt + 1) * BH; o.h2_new16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
+    if (train_xproj(h, t, o, t.xproj_all + (size_t)tt * B * 6 * H, s)) return 1;
     if (train_forward_step(h, t, 1, tt, im, logp_gates, 2, s)) return 1;
-    {   // S6 of this step: the new h2 (state slot tt + 1) -> the caller's (B, V) log-probs
-        StepOperands vo;
-        vo.M = B;
-        vo.h2_new = t.h2s + (size_t)(tt + 1) * BH; vo.h2_new16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
-        GemmBuilder g;
-        add_vocab(g, d, w, vo, t.scratch);
-        const int ns = g.finish(h);
-        const long long stride = (long long)B * V;
-        if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns);
-        g.a.p[0].slab_stride = stride;
-        if (g.launch(s, h)) return fail("tape S6 gemm launch failed");
-        const GateLogitArgs no_gate{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr, 0};
-        StepIO io;
-        io.M = B; io.vmode = VM_FULL; io.full_out = logp_words; io.full_stride = V;
-        launch_vocab(h, s, io, t.scratch, ns, stride, no_gate);
-        LAUNCHCHK();
-    }
+    if (train_vocab_full(h, t, o, nullptr, logp_words, s)) return 1;      // the new h2 (state slot tt + 1) -> the caller's (B, V) log-probs
     const float* src[4] = {t.h1s, t.c1s, t.h2s, t.c2s};
     float* dst[4] = {h1_out, c1_out, h2_out, c2_out};
     for (int j = 0; j < 4; ++j) HIPCHK(hipMemcpyAsync(dst[j], src[j] + (size_t)(tt + 1) * BH, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -712,7 +704,7 @@ extern "C" int vsr_train_tape_seal(vsr_handle* h, int64_t generation, const floa
     t.logp_w = logp_words;
     t.logp_g = logp_gates;
     t.sealed = true;
-    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
+    train_stash(h, t, s);
     LAUNCHCHK();
     tape_refile(h, t);
     return 0;
@@ -785,6 +777,9 @@ __global__ void k_sum_over_t_rows(const float* __restrict__ X, int T, int K, int
 }
 
 // ---------------------------------------------------------------------------------------------- backward
+// the 28 gradients, in the field order of vsr_weights
+enum { g_embed, g_Wis, g_bis, g_Whs, g_bhs, g_Wva, g_Wha, g_wa, g_Wsa, g_ws, g_Wih1, g_Whh1, g_bih1, g_bhh1, g_Wih2, g_Whh2, g_bih2,
+       g_bhh2, g_Wout, g_bout, g_Wsfc, g_bsfc, g_Wig, g_big, g_Whg, g_bhg, g_Wga, g_wg };
 // sel: vsr_train_backward_selected - grad_logp_words is then the (rows, T) gradient of the targets' log-probs
 static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
                                void* stream) {
@@ -813,8 +808,6 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     const int RL = c.B * c.L * c.R, R1 = c.R + 1;
     const size_t BH = (size_t)B * H;
     float* const* G = reinterpret_cast<float* const*>(grads);     // same field order as vsr_weights
-    enum { g_embed, g_Wis, g_bis, g_Whs, g_bhs, g_Wva, g_Wha, g_wa, g_Wsa, g_ws, g_Wih1, g_Whh1, g_bih1, g_bhh1, g_Wih2, g_Whh2, g_bih2,
-           g_bhh2, g_Wout, g_bout, g_Wsfc, g_bsfc, g_Wig, g_big, g_Whg, g_bhg, g_Wga, g_wg };
     for (int i = 0; i < 28; ++i)
         if (!G[i]) return fail("%s: gradient pointer %d is null", who, i);
     if (t.sparse) {                        // from here on the saved rows are (about to be) overwritten: in the handle's copy and in the filed one
@@ -837,27 +830,20 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     auto dptr = [&](int i) { return h2b ? dyn + i : (int*)nullptr; };
     if (h2b) HIPCHK(hipMemsetAsync(dyn, 0, H2_NDYN * sizeof(int), s));
     // ---- transposed weights (the optimizer may have changed them since the last call): one batched launch (TransBatch)
-    TransBatch tbw;
-    transpose(h, s, w.lstm1_weight_ih, in1, 4 * H, in1, t.wT_ih1, 4 * H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.W1_is_weight, in1, H, in1, t.wT_is, H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.W1_ig_weight, in1, H, in1, t.wT_ig, H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.lstm1_weight_hh, H, 4 * H, H, t.wT_hh1, 4 * H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.W1_hs_weight, H, H, H, t.wT_hs, H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.lstm2_weight_ih, in2, 4 * H, in2, t.wT_ih2, 4 * H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.lstm2_weight_hh, H, 4 * H, H, t.wT_hh2, 4 * H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.W1_hg_weight, H, H, H, t.wT_hg, H, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.att_ha_weight, H, A, H, t.wT_ha, A, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.s_fc_weight, H, D, H, t.wT_sfc, D, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.att_sa_weight, H, A, H, t.wT_sa, A, nullptr, h2b, -1, nullptr, &tbw);
-    transpose(h, s, w.att_ga_weight, H, A, H, t.wT_ga, A, nullptr, h2b, -1, nullptr, &tbw);
+    TOperand ops[N_TOPS];              // (a sealed tape: with the T / TB / TBp of the steps taken)
+    train_operands(h, t, ops);
+    auto transpose_ops = [&](int lo, int hi) {          // entries [lo, hi) of the table in one batched launch (TransBatch), in table order
+        TransBatch tb;
+        for (int i = lo; i < hi; ++i) transpose(h, s, ops[i].src, ops[i].ld_in, ops[i].R, ops[i].C, t.*ops[i].buf, ops[i].ld_out, nullptr, h2b, -1, nullptr, &tb);
+        tb.flush(s);
+    };
     const int Vp = (int)up4(V);        // K of the dh2_vocab GEMM must be a multiple of 8: zero-padded columns
     if (Vp != V) {
         HIPCHK(hipMemsetAsync(t.wT_out, 0, (size_t)H * Vp * sizeof(float), s));
         if (uint16_t* tw = h->bf16_on ? const_cast<uint16_t*>(h->map16(t.wT_out)) : nullptr) HIPCHK(hipMemsetAsync(tw, 0, (size_t)H * Vp * sizeof(uint16_t), s));
         if (const H2Range* r2 = h2b ? h->map_h2(t.wT_out) : nullptr) HIPCHK(hipMemsetAsync(const_cast<float*>(r2->img), 0, (size_t)H * Vp * sizeof(float), s));
     }
-    transpose(h, s, w.out_fc_weight, H, V, H, t.wT_out, Vp, nullptr, h2b, -1, nullptr, &tbw);
-    tbw.flush(s);
+    transpose_ops(0, N_TW);
     {   // dP, the carries of the last step: one launch
         ZeroList zl;
         zl.add(t.dP, (size_t)RL * A * sizeof(float));
@@ -997,22 +983,10 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     }
 
     // ---- phase B: weight gradients, reduction over all T*B rows
-    const float* h1prev = t.h1s;              // rows (t,b): state entering step t
-    const float* h1cur = t.h1s + BH;
-    const float* h2prev = t.h2s;
-    const float* h2cur = t.h2s + BH;
-    TransBatch tbx, tby;
-    transpose(h, s, h2prev, H, TB, H, t.tX_h2prev, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, t.x_all, E, TB, E, t.tX_x, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, h1prev, H, TB, H, t.tX_h1prev, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, h1cur, H, TB, H, t.tX_h1, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, t.atts, D, TB, D, t.tX_att, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, t.s_ts, H, TB, H, t.tX_st, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, t.g_ts, H, TB, H, t.tX_gt, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, h2cur, H, TB, H, t.tX_h2, TBp, nullptr, h2b, -1, nullptr, &tbx);
-    transpose(h, s, c.vbar, D, Bi, D, t.tX_vbar, Bp, nullptr, h2b, -1, nullptr, &tbx);
-    tbx.flush(s);
-    if (NV > 0) transpose(h, s, c.regions, (long long)D, NV, D, t.tX_reg, (long long)NVp, c.vlist, h2b, -1, nv_dev);
+    TransBatch tby;
+    transpose_ops(N_TW, N_TOPS - 1);          // the activations, rows (t, b); tX_reg through the list of the non-padding rows:
+    const TOperand& reg = ops[N_TOPS - 1];
+    if (NV > 0) transpose(h, s, reg.src, reg.ld_in, NV, reg.C, t.*reg.buf, (long long)NVp, c.vlist, h2b, -1, nv_dev);
     if (h2b) hipLaunchKernelGGL(k_h2_dyn_fold, dim3(1), dim3(64), 0, s, dyn, T, T * K);
     const int sP1 = dslot(DW_step + DY_dpre1), sQ = dslot(DW_step + DY_dq), sP2 = dslot(DW_step + DY_dpre2);
     // the transposed gradients are the A operands of the weight-gradient GEMMs: with the whole-pass bounds known (k_h2_dyn_fold) they are
@@ -1152,8 +1126,6 @@ extern "C" int vsr_train_backward_selected(vsr_handle* h, const float* grad_logp
 // [0, VSR_GRAD_BUCKETS); bucket b is complete when its event has fired.  Static (does not depend on the shapes).
 extern "C" int vsr_train_bucket_map(int32_t* bucket_of, int32_t* n_buckets) {
     if (!bucket_of || !n_buckets) return fail("vsr_train_bucket_map: null argument");
-    enum { g_embed, g_Wis, g_bis, g_Whs, g_bhs, g_Wva, g_Wha, g_wa, g_Wsa, g_ws, g_Wih1, g_Whh1, g_bih1, g_bhh1, g_Wih2, g_Whh2, g_bih2,
-           g_bhh2, g_Wout, g_bout, g_Wsfc, g_bsfc, g_Wig, g_big, g_Whg, g_bhg, g_Wga, g_wg };
     const int b0[] = {g_Wih1, g_Wis, g_Wig}, b1[] = {g_Wih2, g_Whh2, g_bih2, g_bhh2}, b2[] = {g_Wout, g_bout, g_embed},
               b3[] = {g_Whh1, g_Whs, g_bih1, g_bhh1, g_bis, g_bhs, g_big, g_bhg, g_Wsfc, g_bsfc, g_Wva},
               b4[] = {g_Whg, g_Wha, g_Wsa, g_Wga, g_wa, g_ws, g_wg};

@@ -721,6 +721,7 @@ __global__ __launch_bounds__(256) void k_bwd_tail(const float* __restrict__ Ca, 
 
 // (B, T) int64 captions / slot traces -> (T, B) int32 step-major copies, plus the (b, t)-ordered row list of the saved
 // states (row (t + 1) * B + b) that the batched vocabulary projection gathers through.  slots == null: slot = step.
+// rows_bt == null: no row list (a tape step: T = 1, the (B) ids of one step; k_tape_rows_bt lists the rows at the seal)
 __global__ void k_train_indices(const int64_t* __restrict__ word_in, const int64_t* __restrict__ slots, int T, int B, int V, int L,
                                 int* __restrict__ word32, int* __restrict__ slot32, int* __restrict__ rows_bt, int* __restrict__ bad) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -732,7 +733,7 @@ __global__ void k_train_indices(const int64_t* __restrict__ word_in, const int64
     if (k < 0 || k >= L) { atomicAdd(bad, 1); k = k < 0 ? 0 : L - 1; }
     word32[i] = (int)w;
     slot32[i] = (int)k;
-    rows_bt[b * T + tt] = (tt + 1) * B + b;
+    if (rows_bt) rows_bt[b * T + tt] = (tt + 1) * B + b;
 }
 
 // ---------------------------------------------------------------------------------------------- sparse vocabulary head

@@ -306,16 +306,20 @@ class Engine:
 
     # ------------------------------------------------------------------ training (forward with saves + BPTT backward)
     @_on_device
-    def train_forward(self, B, device, word_in, slots=None, rows_per_image=1):
+    def train_forward(self, B, device, word_in, slots=None, rows_per_image=1, targets=None, who="train_forward"):
         """B images, rows_per_image decoder rows each (word_in / slots and the outputs have B * rows_per_image rows, an image's rows
-        adjacent); prepare() must have been called with beam >= rows_per_image"""
+        adjacent); prepare() must have been called with beam >= rows_per_image -> (out (rows, T, V), gate (rows, T, 2)).
+        targets: the sparse vocabulary head (train_forward_selected) -> (logp_sel (rows, T), gate)"""
         K, n_img = int(rows_per_image), B
         B = n_img * K
         if word_in.size(0) != B:
-            raise RuntimeError("train_forward: %d rows of word ids for %d images x %d rows per image" % (word_in.size(0), n_img, K))
+            raise RuntimeError("%s: %d rows of word ids for %d images x %d rows per image" % (who, word_in.size(0), n_img, K))
         T = word_in.size(1)
-        V = self.dims.vocab_size
+        if targets is not None and tuple(targets.shape) != (B, T):
+            raise RuntimeError("%s: targets must be (%d, %d) like the word ids, got %s" % (who, B, T, tuple(targets.shape)))
         word_in = word_in.to(device=device, dtype=torch.int64).contiguous()
+        if targets is not None:
+            targets = targets.to(device=device, dtype=torch.int64).contiguous()
         if slots is not None:
             slots = slots.to(device=device, dtype=torch.int64).contiguous()
         need = (self.lib.vsr_train_workspace_bytes(self.h, B, T) if K == 1 else
@@ -323,54 +327,30 @@ class Engine:
         if need == 0:
             raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
         self._tws = _grown(self._tws, need, torch.uint8, device)
-        out = torch.empty(B, T, V, dtype=torch.float32, device=device)
+        out = torch.empty((B, T) if targets is not None else (B, T, self.dims.vocab_size), dtype=torch.float32, device=device)
         gate = torch.empty(B, T, 2, dtype=torch.float32, device=device)
         if self._slot.live():
             raise RuntimeError("internal: training forward into a slot that holds a live forward (prepare(for_training=True) first)")
-        if K == 1:
-            _lib.check(self.lib.vsr_train_forward(self.h, _ptr(word_in), _ptr(slots), T, _ptr(out), _ptr(gate), _ptr(self._tws),
-                                                  self._tws.numel(), self._stream(device)))
+        tail = (T, _ptr(out), _ptr(gate), _ptr(self._tws), self._tws.numel(), self._stream(device))
+        if targets is not None:
+            _lib.check(self.lib.vsr_train_forward_selected(self.h, K, _ptr(word_in), _ptr(slots), _ptr(targets), *tail))
+        elif K == 1:
+            _lib.check(self.lib.vsr_train_forward(self.h, _ptr(word_in), _ptr(slots), *tail))
         else:
-            _lib.check(self.lib.vsr_train_forward_rows(self.h, K, _ptr(word_in), _ptr(slots), T, _ptr(out), _ptr(gate), _ptr(self._tws),
-                                                       self._tws.numel(), self._stream(device)))
+            _lib.check(self.lib.vsr_train_forward_rows(self.h, K, _ptr(word_in), _ptr(slots), *tail))
         self._slot.generation = self.train_generation()
         self._slot.token = None
         self._slot.differentiated = True      # (until train.py attaches the autograd node's token: note_forward)
-        self.raise_on_bad_ids(device, "train_forward")
+        self.raise_on_bad_ids(device, who)
         return out, gate
 
-    @_on_device
     def train_forward_selected(self, B, device, word_in, targets, slots=None, rows_per_image=1):
         """train_forward with the sparse vocabulary head (vsr_train_forward_selected): targets (rows, T) int64, a word id or -1 = not
         selected -> (logp_sel (rows, T), gate (rows, T, 2)).  No (rows, T, V) tensor is allocated; the log_softmax rows stay in the
         training workspace until train_backward_selected consumes them."""
-        K, n_img = int(rows_per_image), B
-        B = n_img * K
-        if word_in.size(0) != B:
-            raise RuntimeError("train_forward_selected: %d rows of word ids for %d images x %d rows per image" % (word_in.size(0), n_img, K))
-        T = word_in.size(1)
-        if tuple(targets.shape) != (B, T):
-            raise RuntimeError("train_forward_selected: targets must be (%d, %d) like the word ids, got %s" % (B, T, tuple(targets.shape)))
-        word_in = word_in.to(device=device, dtype=torch.int64).contiguous()
-        targets = targets.to(device=device, dtype=torch.int64).contiguous()
-        if slots is not None:
-            slots = slots.to(device=device, dtype=torch.int64).contiguous()
-        need = (self.lib.vsr_train_workspace_bytes(self.h, B, T) if K == 1 else
-                self.lib.vsr_train_workspace_bytes_rows(self.h, n_img, K, T))
-        if need == 0:
-            raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
-        self._tws = _grown(self._tws, need, torch.uint8, device)
-        lp_sel = torch.empty(B, T, dtype=torch.float32, device=device)
-        gate = torch.empty(B, T, 2, dtype=torch.float32, device=device)
-        if self._slot.live():
-            raise RuntimeError("internal: training forward into a slot that holds a live forward (prepare(for_training=True) first)")
-        _lib.check(self.lib.vsr_train_forward_selected(self.h, K, _ptr(word_in), _ptr(slots), _ptr(targets), T, _ptr(lp_sel), _ptr(gate),
-                                                       _ptr(self._tws), self._tws.numel(), self._stream(device)))
-        self._slot.generation = self.train_generation()
-        self._slot.token = None
-        self._slot.differentiated = True      # (until train.py attaches the autograd node's token: note_forward)
-        self.raise_on_bad_ids(device, "train_forward_selected")
-        return lp_sel, gate
+        if targets is None:
+            raise RuntimeError("train_forward_selected: targets is None (the dense head is train_forward)")
+        return self.train_forward(B, device, word_in, slots, rows_per_image, targets, "train_forward_selected")
 
     def note_forward(self):
         """the autograd node of the forward just taken: returns the token that keeps its buffers reserved"""

@@ -1,7 +1,7 @@
 """Autograd glue of the training path: ONE autograd.Function whose forward is vsr_train_forward (teacher-forced or
 sample-replayed unroll, activations saved by the library) and whose backward is the hand-written BPTT
 vsr_train_backward.  torch only sees (out, gate) -> 28 parameter gradients; nothing is differentiated by torch.
-_SelectedFn is the same with the sparse vocabulary head (opt-in): torch sees (logp_sel (rows, T), gate) and no (rows, T, V) tensor.
+With targets it takes the sparse vocabulary head (opt-in): torch sees (logp_sel (rows, T), gate) and no (rows, T, V) tensor.
 
 Callers reproduced:
   coco_scripts/train.py:103-113   out, gate = model((det,), (captions, ctrl_det_seqs)); NLL losses; loss.backward()
@@ -16,15 +16,23 @@ _PARAM_KEYS = [k for _, k in _lib.WEIGHT_FIELDS]
 
 
 class _DecoderFn(torch.autograd.Function):
+    """targets None: the dense head, torch sees (out (rows, T, V), gate (rows, T, 2)) -> 28 parameter gradients.  targets given: the sparse
+    head (forward = vsr_train_forward_selected, backward = vsr_train_backward_selected), torch sees (logp_sel (rows, T), gate); the
+    (rows, T, V) log-probs never leave the library's workspace, and nothing of that size is saved here or allocated for a gradient."""
+
     @staticmethod
-    def forward(ctx, eng, B, rows_per_image, device, word_in, slots, *params):
-        out, gate = eng.train_forward(B, device, word_in, slots, rows_per_image)
+    def forward(ctx, eng, B, rows_per_image, device, word_in, targets, slots, *params):
+        if targets is None:
+            out, gate = eng.train_forward(B, device, word_in, slots, rows_per_image)
+        else:
+            out, gate = eng.train_forward_selected(B, device, word_in, targets, slots, rows_per_image)
+        ctx.selected = targets is not None
         ctx.generation = eng.train_generation()    # identifies this forward among the live ones (include/vsrcap.h, vsr_train_select)
         ctx.token = eng.note_forward()             # while this node is alive and not differentiated, its buffers are not reused
         ctx.eng = eng
         ctx.device = device
         ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.save_for_backward(out, gate)           # the library reads them again in the backward pass
+        ctx.save_for_backward(out, gate)           # the library reads them again in the backward pass (sparse head: the gate log-probs)
         return out, gate
 
     @staticmethod
@@ -35,12 +43,13 @@ class _DecoderFn(torch.autograd.Function):
         if g_gate is None:
             g_gate = torch.zeros_like(gate)
         sink = ctx.eng.grad_sink
-        grads = ctx.eng.train_backward(ctx.device, g_out.contiguous(), g_gate.contiguous(), ctx.shapes, ctx.generation, into=sink)
+        grads = ctx.eng.train_backward(ctx.device, g_out.contiguous(), g_gate.contiguous(), ctx.shapes, ctx.generation, into=sink,
+                                       selected=ctx.selected)
         if sink is not None:
             # training-loop mode (parallel.FlatGrads): the gradients went straight into the caller's flat buffer, whose views
             # ARE the parameters' .grad - nothing for autograd to accumulate (and no 285 MB of fresh tensors per step)
-            return (None,) * (6 + len(grads))
-        return (None, None, None, None, None, None) + tuple(grads)
+            return (None,) * (7 + len(grads))
+        return (None,) * 7 + tuple(grads)
 
 
 def _params_in_abi_order(model):
@@ -50,43 +59,13 @@ def _params_in_abi_order(model):
 
 def xe_forward_with_grad(model, eng, det, captions, ctrl_seq):
     """forward() under autograd: prepare() has been called with ctrl_seq (one slot per step)."""
-    return _DecoderFn.apply(eng, det.size(0), 1, det.device, captions, None, *_params_in_abi_order(model))
-
-
-class _SelectedFn(torch.autograd.Function):
-    """_DecoderFn with the sparse vocabulary head: forward = vsr_train_forward_selected, backward = vsr_train_backward_selected.  torch
-    sees (logp_sel (rows, T), gate (rows, T, 2)) -> 28 parameter gradients; the (rows, T, V) log-probs never leave the library's
-    workspace, and nothing of that size is saved here or allocated for a gradient."""
-
-    @staticmethod
-    def forward(ctx, eng, B, rows_per_image, device, word_in, targets, slots, *params):
-        lp_sel, gate = eng.train_forward_selected(B, device, word_in, targets, slots, rows_per_image)
-        ctx.generation = eng.train_generation()
-        ctx.token = eng.note_forward()
-        ctx.eng = eng
-        ctx.device = device
-        ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.save_for_backward(lp_sel, gate)        # (the library reads the gate log-probs again in the backward pass)
-        return lp_sel, gate
-
-    @staticmethod
-    def backward(ctx, g_sel, g_gate):
-        lp_sel, gate = ctx.saved_tensors
-        if g_sel is None:
-            g_sel = torch.zeros_like(lp_sel)
-        if g_gate is None:
-            g_gate = torch.zeros_like(gate)
-        sink = ctx.eng.grad_sink
-        grads = ctx.eng.train_backward_selected(ctx.device, g_sel.contiguous(), g_gate.contiguous(), ctx.shapes, ctx.generation, into=sink)
-        if sink is not None:
-            return (None,) * (7 + len(grads))
-        return (None,) * 7 + tuple(grads)
+    return _DecoderFn.apply(eng, det.size(0), 1, det.device, captions, None, None, *_params_in_abi_order(model))
 
 
 def selected_forward_with_grad(model, eng, det, word_in, targets, slots, rows_per_image=1):
     """the training forward under autograd with the sparse head: prepare(for_training=True) has been called.  word_in / targets (rows, T),
     targets = word id or -1 (not selected: log-prob 0.0, no gradient); slots None = step t reads slot t -> (logp_sel (rows, T), gate)."""
-    return _SelectedFn.apply(eng, word_in.size(0) // rows_per_image, rows_per_image, det.device, word_in, targets, slots,
+    return _DecoderFn.apply(eng, word_in.size(0) // rows_per_image, rows_per_image, det.device, word_in, targets, slots,
                              *_params_in_abi_order(model))
 
 
@@ -124,7 +103,7 @@ def sample_logprobs_with_grad(model, eng, det, ctrl, outs, lps, rows_per_image=1
     if sparse_head:
         lp_w, gate = selected_forward_with_grad(model, eng, det, word_in, words, slots, rows_per_image)
     else:
-        out, gate = _DecoderFn.apply(eng, B // rows_per_image, rows_per_image, det.device, word_in, slots, *_params_in_abi_order(model))
+        out, gate = _DecoderFn.apply(eng, B // rows_per_image, rows_per_image, det.device, word_in, None, slots, *_params_in_abi_order(model))
         lp_w = out.gather(2, words.unsqueeze(-1)).squeeze(-1)
     lp_g = gate.gather(2, gates.unsqueeze(-1)).squeeze(-1)
     return lp_w, lp_g
