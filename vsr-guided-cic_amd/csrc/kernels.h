@@ -24,6 +24,29 @@ __device__ __forceinline__ float slab_sum(const float* __restrict__ p, int nslab
     return s;
 }
 
+// slab_sum at two / four consecutive offsets (one 8- / 16-byte load per slab; p + k * stride aligned accordingly): every component is
+// slab_sum's chain of adds
+__device__ __forceinline__ float2 slab_sum2(const float* __restrict__ p, int nslab, long long stride) {
+    float2 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? *reinterpret_cast<const float2*>(p + k * stride) : make_float2(0.f, 0.f);
+    float2 s = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < nslab) { s.x += v[k].x; s.y += v[k].y; }
+    return s;
+}
+__device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, int nslab, long long stride) {
+    float4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < nslab) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
+    return s;
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // bf16 image (round-to-nearest-even) of a value / of four consecutive values: the bf16 GEMM mode lets the producers of its A
@@ -53,6 +76,15 @@ __device__ __forceinline__ void img_store(uint16_t* __restrict__ img, long long 
     uint16_t* g = img + ((idx >> 3) << 4) + (idx & 7);
     g[0] = __builtin_bit_cast(uint16_t, hi);
     g[8] = __builtin_bit_cast(uint16_t, lo);
+}
+__device__ __forceinline__ void img_store2(uint16_t* __restrict__ img, long long idx /* even; img 4-byte aligned */, float v0, float v1, float isc) {
+    if (isc == 0.f) { *reinterpret_cast<uint32_t*>(img + idx) = (uint32_t)bf16_bits(v0) | ((uint32_t)bf16_bits(v1) << 16); return; }
+    const float x0 = v0 * isc, x1 = v1 * isc;
+    const _Float16 hi0 = (_Float16)x0, hi1 = (_Float16)x1;
+    const _Float16 lo0 = (_Float16)(x0 - (float)hi0), lo1 = (_Float16)(x1 - (float)hi1);
+    uint16_t* g = img + ((idx >> 3) << 4) + (idx & 7);
+    *reinterpret_cast<uint32_t*>(g) = (uint32_t)__builtin_bit_cast(uint16_t, hi0) | ((uint32_t)__builtin_bit_cast(uint16_t, hi1) << 16);
+    *reinterpret_cast<uint32_t*>(g + 8) = (uint32_t)__builtin_bit_cast(uint16_t, lo0) | ((uint32_t)__builtin_bit_cast(uint16_t, lo1) << 16);
 }
 __device__ __forceinline__ void img_store4(uint16_t* __restrict__ img, long long idx /* a multiple of 4 */, float4 v, float isc) {
     if (isc == 0.f) { *reinterpret_cast<uint2*>(img + idx) = bf16_bits4(v); return; }
@@ -88,11 +120,11 @@ __device__ __forceinline__ int xcd_item(int n) {
 
 // ---------------------------------------------------------------------------------------------- prepare
 // pooled descriptor vbar[b] = sum_r det[b,r,:] / #(rows with non-zero sum)           (step :126-128)
-// dmask = k_rowmask over the (n_img * R0) detection rows; one block per (decoder row, 1024-column chunk), rows summed in
+// dmask = k_rowmask over the (n_img * R0) detection rows; one block per (decoder row, chunk of 4 x blockDim columns), rows summed in
 // order r = 0..R0-1.  row_img (optional): decoder row b pools the detections of image row_img[b].
 __global__ __launch_bounds__(256) void k_pool(const float* __restrict__ det, const int* __restrict__ row_img,
                                               const float* __restrict__ dmask, int R0, int D, float* __restrict__ vbar) {
-    const int b = blockIdx.x, d = (blockIdx.y * 256 + threadIdx.x) * 4;
+    const int b = blockIdx.x, d = (blockIdx.y * blockDim.x + threadIdx.x) * 4;
     const int img = row_img ? row_img[b] : b;
     const float* X = det + (long long)img * R0 * D;
     const float* mk = dmask + (long long)img * R0;
@@ -100,41 +132,59 @@ __global__ __launch_bounds__(256) void k_pool(const float* __restrict__ det, con
     for (int r = 0; r < R0; ++r) n += mk[r];
     if (d >= D) return;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r = 0; r < R0; ++r) {
-        const float4 v = *reinterpret_cast<const float4*>(X + (long long)r * D + d);
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    // eight rows' loads are issued before the first add (a plain loop keeps one load in flight per lane); the adds keep the order of r
+    for (int r0 = 0; r0 < R0; r0 += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (r0 + k < R0) v[k] = *reinterpret_cast<const float4*>(X + (long long)(r0 + k) * D + d);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (r0 + k < R0) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
     }
     *reinterpret_cast<float4*>(vbar + (long long)b * D + d) = make_float4(s.x / n, s.y / n, s.z / n, s.w / n);
 }
 
 // region-row masks m[row] = (sum_d regions[row,:] != 0), one wave per row                 (step :159)
 // blockmax (optional): max |x| over the block's four rows, one float per block (the f16x2 GEMM flavour scales the region / detection
-// operands by a bound measured here, in the pass that reads them anyway; k_max_reduce folds the per-block values)
-__global__ __launch_bounds__(256) void k_rowmask(const float* __restrict__ X, long long rows, int D, float* __restrict__ mask,
-                                                 float* __restrict__ blockmax = nullptr) {
-    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+// operands by a bound measured here, in the pass that reads them anyway; k_h2_prepare_exps folds the per-block values)
+// One launch covers two row sets of the same width (prepare(): region rows, then detection rows) as two block ranges: blocks
+// [0, nblk0) take set 0, the rest set 1.  zero4 (optional): four ints that block 0 clears (prepare()'s device counters, whose first
+// reader and writer are launched behind this kernel).
+struct RowMaskArgs {
+    const float* X[2]; long long rows[2]; float* mask[2]; float* blockmax[2];
+    int nblk0; int* zero4;
+};
+__global__ __launch_bounds__(256) void k_rowmask(const RowMaskArgs a, int D) {
+    const int set = (int)blockIdx.x >= a.nblk0 ? 1 : 0;
+    const int blk = (int)blockIdx.x - (set ? a.nblk0 : 0);
+    const float* __restrict__ X = a.X[set];
+    float* __restrict__ blockmax = a.blockmax[set];
+    const long long rows = a.rows[set], row = (long long)blk * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
+    if (a.zero4 && blockIdx.x == 0 && threadIdx.x < 4) a.zero4[threadIdx.x] = 0;
     float s = 0.f, mx = 0.f;
     if (row < rows) {
+        // (the order of the adds is part of the result: the mask is (rounded sum != 0).  Issuing a lane's eight loads of a 2048-wide row
+        // before the first add was measured and bought nothing: at 100 x 360 rows the pass already runs at 5.3 TB/s, profiles/r20_c_*)
         for (int d = lane * 4; d < D; d += 256) {
             float4 v = *reinterpret_cast<const float4*>(X + row * D + d);
             s += (v.x + v.y) + (v.z + v.w);
             if (blockmax) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
         }
         s = wave_sum(s);
-        if (lane == 0) mask[row] = (s != 0.f) ? 1.f : 0.f;
+        if (lane == 0) a.mask[set][row] = (s != 0.f) ? 1.f : 0.f;
     }
     if (blockmax) {                                       // (block-uniform)
         __shared__ float wm[4];
         mx = wave_max(mx);
         if (lane == 0) wm[threadIdx.x >> 6] = mx;
         __syncthreads();
-        if (threadIdx.x == 0) blockmax[blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+        if (threadIdx.x == 0) blockmax[blk] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
     }
 }
-// *out = max(v[0 .. n)) as the bit pattern of a non-negative float (a NaN counts as +inf); one block
-__global__ __launch_bounds__(1024) void k_max_reduce(const float* __restrict__ v, long long n, unsigned* __restrict__ out) {
-    __shared__ float wm[16];
+// max(v[0 .. n)) of non-negative floats (a NaN counts as +inf) over one 1024-thread block; the result is thread 0's
+__device__ __forceinline__ float block_max_1024(const float* __restrict__ v, long long n, float* wm /* LDS, 16 */) {
     float m = 0.f;
     bool nan = false;
     for (long long i = threadIdx.x; i < n; i += 1024) { const float x = v[i]; nan |= !(x == x); m = fmaxf(m, x); }
@@ -142,14 +192,13 @@ __global__ __launch_bounds__(1024) void k_max_reduce(const float* __restrict__ v
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0)
         for (int w = 1; w < 16; ++w) m = fmaxf(m, wm[w]);
-        *out = __float_as_uint(m);
-    }
+    return m;
 }
 
 // list of the non-padding region rows (ascending) and their count: att_va(0) = 0 (no bias), so the hoisted region
-// projection only has to run over these rows.  (k_compact_count / k_compact_scan / k_compact_write below.)
+// projection only has to run over these rows.  (k_compact_count / k_compact_write below.)
 // Index-list region format: slot entry (b, l, r) names row slot_idx[b,l,r] of image row_img[b]'s feature
 // bank (-1 = padding).  ridx = absolute bank row (or -1), rmask = the reference's row mask of the dense tensor the list
 // stands for (an all-zero bank row is masked exactly as its dense copy would be).  bad counts out-of-range indices.
@@ -208,7 +257,9 @@ __global__ __launch_bounds__(64) void k_reorder_slots(const int* __restrict__ sl
         }
 }
 
-// Three small launches (a single 1024-thread block walking its rows serially took 42-100 us): per-256-row counts, an exclusive scan of the (<= 4096 x 1024) block counts, ordered writes.
+// Two small launches (a single 1024-thread block walking its rows serially took 42-100 us): per-256-row counts, then ordered writes in
+// which every block adds up the counts in front of it itself (a scan launch of its own in between was one more launch latency in
+// prepare()'s dependent chain; the counts are a few hundred ints that stay in L2) and the last block stores the total.
 __global__ __launch_bounds__(256) void k_compact_count(const float* __restrict__ mask, int rows, int* __restrict__ bcount) {
     __shared__ int wsum[4];
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -219,35 +270,20 @@ __global__ __launch_bounds__(256) void k_compact_count(const float* __restrict__
     if (threadIdx.x == 0) bcount[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-__global__ __launch_bounds__(1024) void k_compact_scan(int* __restrict__ bcount, int nblocks, int* __restrict__ total) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (nblocks + 1023) / 1024;
-    const int b0 = tid * per, b1 = min(nblocks, b0 + per);
-    int n = 0;
-    for (int b = b0; b < b1; ++b) n += bcount[b];
-    part[tid] = n;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - n;                       // exclusive prefix of this thread's blocks
-    for (int b = b0; b < b1; ++b) { const int c = bcount[b]; bcount[b] = run; run += c; }
-    if (tid == 1023) *total = part[1023];
-}
-
-__global__ __launch_bounds__(256) void k_compact_write(const float* __restrict__ mask, int rows, const int* __restrict__ boffset,
-                                                       int* __restrict__ vlist) {
-    __shared__ int wsum[4];
+__global__ __launch_bounds__(256) void k_compact_write(const float* __restrict__ mask, int rows, const int* __restrict__ bcount,
+                                                       int* __restrict__ vlist, int* __restrict__ total) {
+    __shared__ int wsum[4], wpre[4];
     const int r = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool v = r < rows && mask[r] != 0.f;
     const unsigned long long bal = __ballot(v);
-    if (lane == 0) wsum[wave] = __popcll(bal);
+    int pre = 0;                                   // this thread's share of the counts of blocks [0, blockIdx.x)
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) pre += bcount[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
+    if (lane == 0) { wsum[wave] = __popcll(bal); wpre[wave] = pre; }
     __syncthreads();
-    int base = boffset[blockIdx.x];
+    int base = wpre[0] + wpre[1] + wpre[2] + wpre[3];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = base + wsum[0] + wsum[1] + wsum[2] + wsum[3];
     for (int w = 0; w < wave; ++w) base += wsum[w];
     if (v) vlist[base + __popcll(bal & ((1ull << lane) - 1ull))] = r;
 }
@@ -278,12 +314,14 @@ __global__ void k_zero_rows_beyond(const int* __restrict__ vlist, const int* __r
 // rows_dev (optional): the number of real rows lives on the device (the launch covers `rows` = the caller's bound)
 __global__ void k_slab_reduce_scatter(const float* __restrict__ slabs, int nslab, long long stride, int rows, int A,
                                       const int* __restrict__ vlist, float* __restrict__ P, const int* __restrict__ rows_dev = nullptr) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    // four consecutive elements per thread: A % 4 == 0 (vsr_create) and the slabs and P are 16-byte aligned (workspace carve), so they
+    // are one row's and every slab is one 16-byte load
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (rows_dev && *rows_dev < rows) rows = *rows_dev;
     if (i >= (long long)rows * A) return;
     const int m = (int)(i / A), a = (int)(i % A);
-    float s = slab_sum(slabs + i, nslab, stride);
-    P[(long long)vlist[m] * A + a] = s;
+    const float4 s = slab_sum4(slabs + i, nslab, stride);
+    *reinterpret_cast<float4*>(P + (long long)vlist[m] * A + a) = s;
 }
 
 // hoisted image part of the LSTM1 / gate pre-activations: sum the split-K slabs and fold in all biases.
@@ -310,10 +348,22 @@ __global__ void k_slab_reduce(const float* __restrict__ slabs, int nsplit, long 
     out[i] = s;
 }
 
-// decode state at t = 0: slot pointer 0, previous word = bos (init_state :109-115; the h/c states are one memset)
-__global__ void k_init_rows(int* __restrict__ slot, int* __restrict__ word, int bos, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { slot[i] = 0; word[i] = bos; }
+// decode state at t = 0: zero h / c states (one range of n_st 4-byte words) and their two 16-bit images (n_img words each), slot
+// pointer 0, previous word = bos (init_state :109-115).  One launch (three memsets and a kernel were four launch latencies in a row).
+// The ranges are 16-byte aligned (workspace carve).
+__global__ __launch_bounds__(256) void k_zero_state(uint32_t* __restrict__ st, size_t n_st, uint32_t* __restrict__ img0,
+                                                    uint32_t* __restrict__ img1, size_t n_img, int* __restrict__ slot,
+                                                    int* __restrict__ word, int bos, int n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
+    auto zero = [&](uint32_t* p, size_t nw) {
+        uint4* p4 = reinterpret_cast<uint4*>(p);
+        for (size_t k = i; k < (nw >> 2); k += nt) p4[k] = make_uint4(0u, 0u, 0u, 0u);
+        for (size_t k = (nw & ~size_t(3)) + i; k < nw; k += nt) p[k] = 0u;
+    };
+    zero(st, n_st);
+    zero(img0, n_img);
+    zero(img1, n_img);
+    for (size_t k = i; k < (size_t)n; k += nt) { slot[k] = 0; word[k] = bos; }
 }
 
 // f16x2 flavour: a state handed to vsr_step by the caller is an A operand of class "unit" (|x| < 2 at the fixed scale 2^15: what
@@ -354,17 +404,35 @@ __global__ void k_i32_to_i64(const int* src, int64_t* dst, int n) {
 // xproj (optional): (V, 6H) cached projection of every embedding row (decode cache), gathered by word[row];
 // nblk: number of leading gate blocks (of 6) that the GEMM produced (the rest only has hoisted terms).
 // the cell itself: q = [i, f, g, o, s-gate, g-gate image part] pre-activations of one (row, unit)
+__device__ __forceinline__ void lstm1_cell(const float (&q)[6], float c_old, float& c, float& h1v, float& stv) {
+    c = sigmoidf_(q[1]) * c_old + sigmoidf_(q[0]) * tanhf(q[2]);
+    const float tc = tanhf(c);
+    h1v = sigmoidf_(q[3]) * tc;
+    stv = sigmoidf_(q[4]) * tc;
+}
 __device__ __forceinline__ void lstm1_point(const float (&q)[6], float c_old, long long i, float* __restrict__ h1n, float* __restrict__ c1n,
                                             float* __restrict__ s_t, float* __restrict__ gpre, uint16_t* __restrict__ h1n16,
                                             uint16_t* __restrict__ s_t16, float isc) {
-    const float c = sigmoidf_(q[1]) * c_old + sigmoidf_(q[0]) * tanhf(q[2]);
-    const float tc = tanhf(c);
-    const float h1v = sigmoidf_(q[3]) * tc, stv = sigmoidf_(q[4]) * tc;
+    float c, h1v, stv;
+    lstm1_cell(q, c_old, c, h1v, stv);
     h1n[i] = h1v;
     c1n[i] = c;
     s_t[i] = stv;
     gpre[i] = q[5];
     if (h1n16) { img_store(h1n16, i, h1v, isc); img_store(s_t16, i, stv, isc); }
+}
+// ... of the two units i (even), i + 1 of a row: the same cell twice, 8-byte stores (all bases 8-byte aligned, the images 4-byte)
+__device__ __forceinline__ void lstm1_point2(const float (&qa)[6], const float (&qb)[6], float2 c_old, long long i, float* __restrict__ h1n,
+                                             float* __restrict__ c1n, float* __restrict__ s_t, float* __restrict__ gpre,
+                                             uint16_t* __restrict__ h1n16, uint16_t* __restrict__ s_t16, float isc) {
+    float ca, ha, sa, cb, hb, sb;
+    lstm1_cell(qa, c_old.x, ca, ha, sa);
+    lstm1_cell(qb, c_old.y, cb, hb, sb);
+    *reinterpret_cast<float2*>(h1n + i) = make_float2(ha, hb);
+    *reinterpret_cast<float2*>(c1n + i) = make_float2(ca, cb);
+    *reinterpret_cast<float2*>(s_t + i) = make_float2(sa, sb);
+    *reinterpret_cast<float2*>(gpre + i) = make_float2(qa[5], qb[5]);
+    if (h1n16) { img_store2(h1n16, i, ha, hb, isc); img_store2(s_t16, i, sa, sb, isc); }
 }
 
 __global__ void k_lstm1(const float* __restrict__ pre, int nsplit, long long stride, const float* __restrict__ vproj,
@@ -1335,6 +1403,56 @@ __global__ __launch_bounds__((K + 1) * 64) void k_select_lstm1(const SelBeamArgs
         q[g] = s + vp[g];
     }
     lstm1_point(q, sums[(pl * 7 + 6) * SL_UB + u], (long long)row * H + j, h1n, c1n, s_t, gpre, h1n16, s_t16, isc);
+}
+// The same kernel with TWO adjacent hidden units per lane, i.e. a slice of 128 units per workgroup: 8-byte loads and stores, half the
+// workgroups.  At 100 images x beam 5 x H = 1000 the one-unit launch is 1 600 workgroups of 6 waves, of which 256 CUs x 5 hold 1 280: the
+// last 320 ran the whole dependent chain (loads, selection, barrier, gather, cell, stores) a second time on a fifth of the chip.  These
+// are 800 and resident at once.  Every (row, unit) element is still the expressions above in their order - a lane just carries two of
+// them.  Needs an even H and 8-byte aligned bases (4-byte for the images): run_step chooses, the one-unit kernel takes the rest.
+template <int K>
+__global__ __launch_bounds__((K + 1) * 64) void k_select_lstm1_x2(const SelBeamArgs sel, const float* __restrict__ pre, int nsplit, long long stride,
+                                                                  const float* __restrict__ vproj, const float* __restrict__ c1_old, int H, int nslice,
+                                                                  float* __restrict__ h1n, float* __restrict__ c1n, float* __restrict__ s_t,
+                                                                  float* __restrict__ gpre, const float* __restrict__ xproj, int nblk,
+                                                                  uint16_t* __restrict__ h1n16, uint16_t* __restrict__ s_t16, float isc, int skip5) {
+    __shared__ float2 sums[K * 7 * SL_UB];                 // per parent: six gate sums and its old cell state, of the lane's two units
+    __shared__ int sel_s[2 * KMAX];
+    const int b = blockIdx.x / nslice, slice = blockIdx.x % nslice;
+    const int wave = threadIdx.x >> 6, u = threadIdx.x & 63, cb = sel.cb;
+    const int j = (slice * SL_UB + u) * 2;
+    float2 vp[6];
+#pragma unroll
+    for (int g = 0; g < 6; ++g) vp[g] = make_float2(0.f, 0.f);
+    if (wave == K) {
+        select_beam_wave<K>(sel, b, u, slice == 0, sel_s);
+    } else if (j < H) {
+#pragma unroll
+        for (int g = 0; g < 6; ++g) vp[g] = *reinterpret_cast<const float2*>(vproj + (long long)b * 6 * H + (long long)g * H + j);
+        if (wave < cb) {
+            const long long base = (long long)(b * cb + wave) * 6 * H + j;
+            const float2 co = *reinterpret_cast<const float2*>(c1_old + (long long)(b * cb + wave) * H + j);
+#pragma unroll
+            for (int g = 0; g < 6; ++g) {
+                const int sk = g == 5 ? skip5 : 0;
+                sums[(wave * 7 + g) * SL_UB + u] = g < nblk ? slab_sum2(pre + base + (long long)g * H + sk * stride, nsplit - sk, stride) : make_float2(0.f, 0.f);
+            }
+            sums[(wave * 7 + 6) * SL_UB + u] = co;
+        }
+    }
+    __syncthreads();
+    if (wave == K || j >= H) return;
+    const int pl = sel_s[wave], w = sel_s[KMAX + wave];
+    const int row = b * K + wave;
+    const float* xp = xproj + (long long)w * 6 * H + j;
+    float qa[6], qb[6];
+#pragma unroll
+    for (int g = 0; g < 6; ++g) {
+        float2 s = sums[(pl * 7 + g) * SL_UB + u];
+        const float2 x = *reinterpret_cast<const float2*>(xp + (long long)g * H);
+        s.x += x.x; s.y += x.y;
+        qa[g] = s.x + vp[g].x; qb[g] = s.y + vp[g].y;
+    }
+    lstm1_point2(qa, qb, sums[(pl * 7 + 6) * SL_UB + u], (long long)row * H + j, h1n, c1n, s_t, gpre, h1n16, s_t16, isc);
 }
 
 // final ordering by sequence log-prob + back-tracking through the parent pointers      (:182-194)

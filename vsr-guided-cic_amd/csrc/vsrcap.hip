@@ -60,7 +60,7 @@ struct Ctx {
     float* dmask = nullptr;      // row masks of the detection rows (pooled descriptor)
     float *vbar, *vproj, *vproj2, *P, *rmask;
     int *vlist, *nvalid_dev;     // non-padding region rows (ascending) and their number
-    int* bcount;                 // per-256-row counts / offsets of the compaction
+    int* bcount;                 // per-256-row counts of the compaction
     int nvalid = 0;
     bool bounded = false;        // nvalid is the caller's row bound (vsr_set_valid_rows_bound), the real count lives in nvalid_dev[0]
     float* st[2][4];   // h1, c1, h2, c2 double-buffered
@@ -462,9 +462,16 @@ __global__ void k_h2_head_init(int* exps, unsigned* bounds, int* idx) {
 // exponents of the operands vsr_prepare*() measures: region rows (their max); the pooled descriptor (sum of <= R0 detection rows over a
 // count >= 1, step :126-128: R0 x the detections' max - loose bounds cost nothing, fp16 subnormals are honoured); the attended vector
 // (a convex combination of the sentinel and region rows, step :167-171): max(region max, sentinel bound)
-__global__ void k_h2_prepare_exps(const unsigned* __restrict__ bounds, int R0, int* __restrict__ exps) {
+// One 1024-thread block: it first folds the per-block maxima k_rowmask left (bm_regions, bm_det) into the two bounds (stored as the bit
+// patterns of non-negative floats; a NaN counts as +inf).
+__global__ __launch_bounds__(1024) void k_h2_prepare_exps(const float* __restrict__ bm_regions, long long n_regions, const float* __restrict__ bm_det,
+                                                          long long n_det, unsigned* __restrict__ bounds, int R0, int* __restrict__ exps) {
+    __shared__ float wm[2][16];
+    const float r = block_max_1024(bm_regions, n_regions, wm[0]), dt = block_max_1024(bm_det, n_det, wm[1]);
     if (threadIdx.x != 0) return;
-    const float r = __uint_as_float(bounds[H2A_REGION]), dt = __uint_as_float(bounds[H2A_DET]), sn = __uint_as_float(bounds[H2B_SENT]);
+    bounds[H2A_REGION] = __float_as_uint(r);
+    bounds[H2A_DET] = __float_as_uint(dt);
+    const float sn = __uint_as_float(bounds[H2B_SENT]);
     exps[H2A_REGION] = h2_exp_of(r);
     exps[H2A_DET] = h2_exp_of(dt * (float)R0);
     exps[H2A_ATT] = h2_exp_of(fmaxf(r, sn));
@@ -626,8 +633,16 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     float* bm_regions = h2b ? c.scratch : nullptr;
     float* bm_det = h2b ? c.scratch + cdiv(prows, 4) : nullptr;
     if (h2b && (size_t)(cdiv(prows, 4) + cdiv((long long)(indexed ? n_img : B) * R0, 4)) > c.scratch_floats) return fail("%s: scratch too small for the operand bounds", who);
-    hipLaunchKernelGGL(k_rowmask, dim3(cdiv(prows, 4)), dim3(256), 0, s, regions, prows, D, c.bmask, bm_regions);
-    HIPCHK(hipMemsetAsync(c.nvalid_dev, 0, 4 * sizeof(int), s));      // [0] row count, [1] bad slot indices, [2] bad word / slot / verb ids
+    // one launch masks the region rows and the detection rows (the pooled descriptor's, below) and clears the device counters:
+    // [0] row count, [1] bad slot indices, [2] bad word / slot / verb ids, [3] rows beyond a caller's bound
+    const long long drows = (long long)(indexed ? n_img : B) * R0;
+    {
+        RowMaskArgs a;
+        a.X[0] = regions; a.rows[0] = prows; a.mask[0] = c.bmask; a.blockmax[0] = bm_regions;
+        a.X[1] = det; a.rows[1] = drows; a.mask[1] = c.dmask; a.blockmax[1] = bm_det;
+        a.nblk0 = (int)cdiv(prows, 4); a.zero4 = c.nvalid_dev;
+        hipLaunchKernelGGL(k_rowmask, dim3(cdiv(prows, 4) + cdiv(drows, 4)), dim3(256), 0, s, a, D);
+    }
     if (indexed) {
         hipLaunchKernelGGL(k_index_rows, dim3(cdiv(rows, 256)), dim3(256), 0, s, slot_idx, row_img, c.bmask, B, L * R, Rb, n_img,
                            c.ridx_buf, c.rmask, c.nvalid_dev + 1);
@@ -635,8 +650,7 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     {
         const int nb = (int)cdiv(prows, 256);
         hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(256), 0, s, c.bmask, (int)prows, c.bcount);
-        hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, s, c.bcount, nb, c.nvalid_dev);
-        hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(256), 0, s, c.bmask, (int)prows, c.bcount, c.vlist);
+        hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(256), 0, s, c.bmask, (int)prows, c.bcount, c.vlist, c.nvalid_dev);
     }
     LAUNCHCHK();
     // A caller that knows an upper bound on the non-padding rows (vsr_set_valid_rows_bound: the eval script builds its region tensors on
@@ -655,14 +669,11 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     }
 
     // pooled descriptor
-    const long long drows = (long long)(indexed ? n_img : B) * R0;
-    hipLaunchKernelGGL(k_rowmask, dim3(cdiv(drows, 4)), dim3(256), 0, s, det, drows, D, c.dmask, bm_det);
-    if (h2b) {
-        hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, s, bm_regions, (long long)cdiv(prows, 4), h->h2_bounds + H2A_REGION);
-        hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, s, bm_det, (long long)cdiv(drows, 4), h->h2_bounds + H2A_DET);
-        hipLaunchKernelGGL(k_h2_prepare_exps, dim3(1), dim3(64), 0, s, h->h2_bounds, R0, h->h2_exps);
-    }
-    hipLaunchKernelGGL(k_pool, dim3(B, cdiv(D, 1024)), dim3(256), 0, s, det, indexed ? row_img : nullptr, c.dmask, R0, D, c.vbar);
+    if (h2b)
+        hipLaunchKernelGGL(k_h2_prepare_exps, dim3(1), dim3(1024), 0, s, bm_regions, (long long)cdiv(prows, 4), bm_det, (long long)cdiv(drows, 4),
+                           h->h2_bounds, R0, h->h2_exps);
+    // (one wave per block: B x D / 256 blocks, enough of them to fill the chip at 100 images)
+    hipLaunchKernelGGL(k_pool, dim3(B, cdiv(D, 256)), dim3(64), 0, s, det, indexed ? row_img : nullptr, c.dmask, R0, D, c.vbar);
     LAUNCHCHK();
 
     // hoisted vbar projections: columns [voff, voff + D) of the LSTM1 / gate input weights
@@ -720,7 +731,7 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
             return fail("%s: att_va slabs (%lld x %d floats) exceed the workspace scratch (%zu)", who, stride, ns, c.scratch_floats);
         g.a.p[0].slab_stride = stride;
         if (g.launch(s, h)) return fail("att_va gemm launch failed");
-        hipLaunchKernelGGL(k_slab_reduce_scatter, dim3(cdiv(stride, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.nvalid, A, c.vlist, c.P,
+        hipLaunchKernelGGL(k_slab_reduce_scatter, dim3(cdiv(stride, 4 * 256)), dim3(256), 0, s, c.scratch, ns, stride, c.nvalid, A, c.vlist, c.P,
                            bound > 0 ? c.nvalid_dev : (const int*)nullptr);
         LAUNCHCHK();
     }
@@ -743,7 +754,10 @@ extern "C" int vsr_prepare_indexed(vsr_handle* h, const float* det, int32_t n_im
 
 extern "C" int vsr_row_mask(const float* rows, int64_t n_rows, int32_t D, float* mask, void* stream) {
     if (!rows || !mask || n_rows <= 0 || D <= 0 || (D & 3)) return fail("vsr_row_mask: bad arguments");
-    hipLaunchKernelGGL(k_rowmask, dim3(cdiv(n_rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, (long long)n_rows, D, mask);
+    RowMaskArgs a;
+    memset(&a, 0, sizeof(a));
+    a.X[0] = rows; a.rows[0] = (long long)n_rows; a.mask[0] = mask; a.nblk0 = (int)cdiv(n_rows, 4);
+    hipLaunchKernelGGL(k_rowmask, dim3(cdiv(n_rows, 4)), dim3(256), 0, (hipStream_t)stream, a, D);
     LAUNCHCHK();
     return 0;
 }
@@ -849,9 +863,18 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     // ---- S1
     if (io.s1_from_prev && io.sel_beam) {
         const SelBeamArgs& sb = *io.sel_beam;
-        const int nslice = cdiv(H, SL_UB);
+        // two units per lane (8-byte accesses) wherever H is even and every base is 8-byte aligned (the images: 4-byte).  vsr_create
+        // admits only H % 4 == 0 and the workspace is carved at 256 bytes: what is left for the one-unit kernel is a caller's decode
+        // cache buffer (vsr_build_decode_cache) at an address that is only 4-byte aligned
+        uintptr_t al = 0, al16 = reinterpret_cast<uintptr_t>(h1n16) | reinterpret_cast<uintptr_t>(s_t16);
+        for (const void* p : {(const void*)c.pre1, (const void*)c.vproj, (const void*)c1o, (const void*)h1n, (const void*)c1n, (const void*)c.s_t,
+                              (const void*)c.gpre, (const void*)h->xproj})
+            al |= reinterpret_cast<uintptr_t>(p);
+        const bool x2 = H % 2 == 0 && (al & 7) == 0 && (al16 & 3) == 0;
+        const int nslice = cdiv(H, x2 ? 2 * SL_UB : SL_UB);
         with_const_1to8(sb.beam, [&](auto KK) {
-            hipLaunchKernelGGL((k_select_lstm1<decltype(KK)::value>), dim3(sb.B * nslice), dim3((decltype(KK)::value + 1) * 64), 0, s, sb, c.pre1, c.pre1_ns, c.pre1_stride,
+            constexpr int K = decltype(KK)::value;
+            hipLaunchKernelGGL(x2 ? k_select_lstm1_x2<K> : k_select_lstm1<K>, dim3(sb.B * nslice), dim3((K + 1) * 64), 0, s, sb, c.pre1, c.pre1_ns, c.pre1_stride,
                                c.vproj, c1o, H, nslice, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5);
         });
     } else if (io.s1_from_prev && io.sel_simple) {
@@ -964,13 +987,14 @@ static int check_ready(vsr_handle* h, const char* who) {
 static int zero_state(vsr_handle* h, int M, hipStream_t s) {
     Ctx& c = h->c;
     const size_t n = (size_t)M * h->d.rnn_size * sizeof(float);
-    // the four state arrays of buffer 0 are consecutive in the workspace (carve): one memset
-    HIPCHK(hipMemsetAsync(c.st[0][0], 0, (size_t)(reinterpret_cast<char*>(c.st[0][3]) - reinterpret_cast<char*>(c.st[0][0])) + n, s));
-    HIPCHK(hipMemsetAsync(c.st16[0][0], 0, (size_t)M * h->d.rnn_size * 2 * sizeof(uint16_t), s));     // images of the zero h1 / h2 (bf16 or fp16 pairs)
-    HIPCHK(hipMemsetAsync(c.st16[0][1], 0, (size_t)M * h->d.rnn_size * 2 * sizeof(uint16_t), s));
+    // the four state arrays of buffer 0 are consecutive in the workspace (carve): one range; the images of the zero h1 / h2 (bf16 or
+    // fp16 pairs: up to 4 bytes per element); the initial rows - one launch
+    const size_t n_st = ((size_t)(reinterpret_cast<char*>(c.st[0][3]) - reinterpret_cast<char*>(c.st[0][0])) + n) / 4;
+    hipLaunchKernelGGL(k_zero_state, dim3((unsigned)std::min<size_t>(cdiv((long long)n_st, 4 * 256), 2048)), dim3(256), 0, s,
+                       reinterpret_cast<uint32_t*>(c.st[0][0]), n_st, reinterpret_cast<uint32_t*>(c.st16[0][0]),
+                       reinterpret_cast<uint32_t*>(c.st16[0][1]), n / 4, c.slot[0], c.word[0], h->d.bos_idx, M);
     c.st16_ok[0] = true;
     c.st16_ok[1] = false;
-    hipLaunchKernelGGL(k_init_rows, dim3(cdiv(M, 256)), dim3(256), 0, s, c.slot[0], c.word[0], h->d.bos_idx, M);
     LAUNCHCHK();
     return 0;
 }
