@@ -47,8 +47,8 @@ typedef struct vsr_dims {
     int32_t img_second_lstm;      /* 1: LSTM2 input is [h1 | att | vbar] (:54-57)  */
 } vsr_dims;
 
-/* the 28 state_dict tensors, borrowed (no copy: optimizer updates stay visible); layout per
- * controllable_captioning.py:23-68, row-major [out, in] */
+/* the 28 state_dict tensors, borrowed (no copy: optimizer updates stay visible) and read only - except by vsr_adam_step, which
+ * writes the bound tensors; layout per controllable_captioning.py:23-68, row-major [out, in] */
 typedef struct vsr_weights {
     const float* embed_weight;          /* (V, E) */
     const float* W1_is_weight;          /* (H, in1)   in1 = [H +] D + E */
@@ -324,6 +324,30 @@ int vsr_train_tape_seal(vsr_handle* h, int64_t generation, const float* logp_wor
  * point into one flat caller buffer laid out in bucket order: each bucket is then one contiguous collective. */
 int vsr_train_bucket_map(int32_t* bucket_of, int32_t* n_buckets);
 int vsr_train_wait_bucket(vsr_handle* h, int32_t bucket, void* stream);
+
+/* ---- the optimizer step (coco_scripts/train.py:77,113: Adam(model.parameters(), lr), optim.step()) --------------------------------
+ * torch.optim.Adam semantics (amsgrad = maximize = false) on the 28 tensors in ONE launch that also leaves what the handle derives from
+ * the new weights, so no refresh call follows a step (csrc/optim_kernels.h).  Per element, in torch's fused kernel's order of operations:
+ *   g += weight_decay p  (L2, not AdamW);  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),   bc1 = 1 - beta1^step, bc2 = 1 - beta2^step formed on the host in double.
+ * The hyper-parameters are doubles, as torch keeps them; ONE set for all tensors (a caller with several parameter groups makes several
+ * optimizers or none: nothing here applies one group's values to another's tensors).
+ *   params      must be the 28 pointers bound to the handle (vsr_bind_weights), else the call fails.  The tensors are borrowed - and
+ *               WRITTEN: this is the one call that writes through the bound pointers, which is what it is for.
+ *   grads       fp32, any 4-byte alignment (views of one flat buffer); a NULL entry leaves that tensor and its two moments untouched
+ *               (it is still measured / converted).  Read only.
+ *   exp_avg, exp_avg_sq   the moments, fp32, shaped like the parameters, read and written.
+ * What it does to the handle is what a refresh does (rules at vsr_bind_weights).  f16x2 on: the max |p| of the 14 matrices and the
+ * embedding table is folded in the same pass and the refresh's own tail rebuilds exponents and images in the buffer the handle was last
+ * given (five launches); bf16 on: the bf16 copies are written in the same pass (one launch).  Either way the decode cache and the
+ * prepared statics are void, the saved forwards stay, and the bounds vsr_prepare*() measures are reset.  Neither on (f32 / f32x3):
+ * just the update, one launch; nothing is derived, and only the decode cache is dropped. */
+typedef struct vsr_adam_args {
+    double lr, beta1, beta2, eps, weight_decay;
+    int32_t step;                 /* 1-based count of THIS step */
+} vsr_adam_args;
+int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr_weights* grads, const vsr_weights* exp_avg,
+                  const vsr_weights* exp_avg_sq, const vsr_adam_args* a, void* stream);
 
 /* test hook: copy an internal buffer of the saved training pass ("dpre1", "dpre2", "dh2_voc", "gates1", ...) */
 int vsr_debug_copy(vsr_handle* h, const char* name, float* dst, size_t n_floats, void* stream);

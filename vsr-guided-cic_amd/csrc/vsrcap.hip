@@ -30,6 +30,7 @@
 #include "step_gemms.h"
 #include "kernels.h"
 #include "train_kernels.h"
+#include "optim_kernels.h"
 
 using namespace vsr;
 
@@ -115,6 +116,7 @@ struct vsr_handle : GemmState {         // (gemm_route.h: the GEMM flavours swit
     const float* xproj = nullptr;     // decode cache: (V, 6H) projection of the embedding table, valid for the bound weights
     long long rows_bound = 0;    // vsr_set_valid_rows_bound: > 0 = the caller's upper bound on the non-padding region rows; vsr_prepare*() then never waits for the host
     int attend_parts = 2, attend_limit = 256;        // workgroups per row of k_attend in launches of <= attend_limit / parts rows (VSR_ATTEND_PARTS, VSR_ATTEND_LIMIT)
+    int adam_blocks = 0;         // grid budget of vsr_adam_step: the workgroups the device holds at once (set at its first call)
     int split_pre1 = 1;          // the h1 part of the next step's LSTM1 sums in the S5 launch, the h2 part with the vocabulary (run_step; VSR_SPLIT_PRE1=0: all of it with the vocabulary, as in rounds 2-5)
     Ctx c;
     // measurement
@@ -476,25 +478,13 @@ __global__ __launch_bounds__(1024) void k_h2_prepare_exps(const float* __restric
     exps[H2A_DET] = h2_exp_of(dt * (float)R0);
     exps[H2A_ATT] = h2_exp_of(fmaxf(r, sn));
 }
-extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes, void* stream) {
-    if (!h) return fail("vsr_refresh_h2_weights: null handle");
-    if (!buffer) {                                          // back to f32x3 for every launch
-        if (h->h2_on) void_derived(h, VOID_FLAVOUR);
-        h->h2_on = false;
-        h->h2.clear(); h->h2t.clear();
-        return 0;
-    }
-    if (!h->bound) return fail("vsr_refresh_h2_weights: weights not bound");
+// the launches of a refresh into the image buffer at `base`.  adam != null (vsr_adam_step): the optimizer's launch takes the place of the
+// bound pass - it measures the tensors it has just written - and everything after it is the refresh's own tail
+struct AdamLaunch { AdamMulti t; AdamHyper hy; };
+static int h2_refresh_launches(vsr_handle* h, char* base, hipStream_t s, const AdamLaunch* adam) {
     const vsr_dims& d = h->d;
-    if (d.det_feat_size % 8 || d.input_encoding_size % 8 || d.rnn_size % 8 || d.att_size % 8)
-        return fail("vsr_refresh_h2_weights: the f16x2 flavour needs det_feat_size, input_encoding_size, rnn_size and att_size to be "
-                    "multiples of 8 (whole 8-element groups of the fp16-pair images); got %d %d %d %d", d.det_feat_size, d.input_encoding_size, d.rnn_size, d.att_size);
-    if (bytes < vsr_h2_weight_bytes(h)) return fail("vsr_refresh_h2_weights: buffer too small");
-    if (reinterpret_cast<uintptr_t>(buffer) & 255) return fail("vsr_refresh_h2_weights: buffer must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
     const float* p[B16_NW]; size_t n[B16_NW];
     b16_weight_list(h->d, h->w, p, n);
-    char* base = reinterpret_cast<char*>(buffer);
     int* exps = reinterpret_cast<int*>(base);
     unsigned* bounds = reinterpret_cast<unsigned*>(base + 128);
     int* idx = reinterpret_cast<int*>(base + 256);          // 3 x H2_NSLOT ints of index lists for k_h2_exps
@@ -514,7 +504,8 @@ extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes,
     }
     mt.blk[B16_NW + 1] = blocks;
     mt.nt = B16_NW + 1;
-    hipLaunchKernelGGL(k_absmax_multi, dim3(blocks), dim3(256), 0, s, mt, bounds);
+    if (adam) hipLaunchKernelGGL(k_adam_multi, dim3(adam->t.blk[ADAM_NT]), dim3(256), 0, s, adam->t, adam->hy, bounds);
+    else hipLaunchKernelGGL(k_absmax_multi, dim3(blocks), dim3(256), 0, s, mt, bounds);
     // |sentinel| = |s_fc s_t + b| <= max_d (sum_j |W_dj| + |b_d|) since |s_t| < 1                                   (step :155)
     hipLaunchKernelGGL(k_row_l1_max, dim3(cdiv(d.det_feat_size, L1MAX_ROWS)), dim3(256), 0, s, h->w.s_fc_weight, h->w.s_fc_bias, d.det_feat_size, d.rnn_size, bounds + H2B_SENT);
     hipLaunchKernelGGL(k_h2_exps, dim3(1), dim3(64), 0, s, bounds, idx, idx + H2_NSLOT, idx + 2 * H2_NSLOT, (int)H2A_REGION, exps);   // slots 0 .. 15
@@ -543,8 +534,100 @@ extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes,
     hipLaunchKernelGGL(k_f32_to_h2_multi, dim3(blocks), dim3(256), 0, s, mc, reinterpret_cast<uint32_t*>(out), exps);
     LAUNCHCHK();
     h->h2_exps = exps; h->h2_bounds = bounds;
+    return 0;
+}
+extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes, void* stream) {
+    if (!h) return fail("vsr_refresh_h2_weights: null handle");
+    if (!buffer) {                                          // back to f32x3 for every launch
+        if (h->h2_on) void_derived(h, VOID_FLAVOUR);
+        h->h2_on = false;
+        h->h2.clear(); h->h2t.clear();
+        return 0;
+    }
+    if (!h->bound) return fail("vsr_refresh_h2_weights: weights not bound");
+    const vsr_dims& d = h->d;
+    if (d.det_feat_size % 8 || d.input_encoding_size % 8 || d.rnn_size % 8 || d.att_size % 8)
+        return fail("vsr_refresh_h2_weights: the f16x2 flavour needs det_feat_size, input_encoding_size, rnn_size and att_size to be "
+                    "multiples of 8 (whole 8-element groups of the fp16-pair images); got %d %d %d %d", d.det_feat_size, d.input_encoding_size, d.rnn_size, d.att_size);
+    if (bytes < vsr_h2_weight_bytes(h)) return fail("vsr_refresh_h2_weights: buffer too small");
+    if (reinterpret_cast<uintptr_t>(buffer) & 255) return fail("vsr_refresh_h2_weights: buffer must be 256-byte aligned");
+    if (h2_refresh_launches(h, reinterpret_cast<char*>(buffer), (hipStream_t)stream, nullptr)) return 1;
     void_derived(h, h->h2_on ? VOID_REFRESH : VOID_FLAVOUR);      // (the bounds of the region / detection operands are measured by vsr_prepare*())
     h->h2_on = true;
+    return 0;
+}
+
+// ---- the optimizer step (optim_kernels.h): Adam on the 28 bound tensors and, in the same pass, what the flavour derives from them
+static void weight_sizes(const vsr_dims& d, size_t (&n)[ADAM_NT]) {          // elements of the 28 tensors, in the order of vsr_weights
+    const size_t H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
+    const size_t in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0);
+    const size_t c[ADAM_NT] = {V * E, H * in1, H, H * H, H, A * D, A * H, A, A * H, A, 4 * H * in1, 4 * H * H, 4 * H, 4 * H,
+                               4 * H * in2, 4 * H * H, 4 * H, 4 * H, V * H, V, D * H, D, H * in1, H, H * H, H, A * H, A};
+    for (int i = 0; i < ADAM_NT; ++i) n[i] = c[i];
+}
+static_assert(sizeof(vsr_weights) == ADAM_NT * sizeof(float*), "one table entry per tensor of vsr_weights");
+extern "C" int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr_weights* grads, const vsr_weights* exp_avg,
+                             const vsr_weights* exp_avg_sq, const vsr_adam_args* a, void* stream) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !a) return fail("vsr_adam_step: null argument");
+    if (!h->bound) return fail("vsr_adam_step: weights not bound");
+    if (memcmp(params, &h->w, sizeof(vsr_weights)) != 0)
+        return fail("vsr_adam_step: params are not the 28 tensors bound to this handle (vsr_bind_weights): the step writes through the bound pointers and rebuilds what the handle derives from them");
+    if (a->step < 1) return fail("vsr_adam_step: step is the 1-based count of this step, got %d", a->step);
+    if (!(a->lr >= 0) || !(a->eps >= 0) || !(a->weight_decay >= 0) || !(a->beta1 >= 0 && a->beta1 < 1) || !(a->beta2 >= 0 && a->beta2 < 1))
+        return fail("vsr_adam_step: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)");
+    float* const* P = reinterpret_cast<float* const*>(params);
+    const float* const* G = reinterpret_cast<const float* const*>(grads);
+    float* const* M = reinterpret_cast<float* const*>(exp_avg);
+    float* const* V = reinterpret_cast<float* const*>(exp_avg_sq);
+    size_t n[ADAM_NT];
+    weight_sizes(h->d, n);
+    const float* wp[B16_NW]; size_t wn[B16_NW];
+    b16_weight_list(h->d, h->w, wp, wn);
+    if (!h->adam_blocks) {               // one resident round of workgroups: a second, partial round would be the tail of the launch
+        int per_cu = 0, dev = 0, cus = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_adam_multi, 256, 0));
+        HIPCHK(hipGetDevice(&dev));
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        h->adam_blocks = std::max(ADAM_NT, std::min(ADAM_MAX_BLOCKS, per_cu * cus));
+    }
+    AdamLaunch L;
+    memset(&L, 0, sizeof(L));
+    size_t total = 0;
+    for (int i = 0; i < ADAM_NT; ++i) total += n[i];
+    int blocks = 0;
+    for (int i = 0; i < ADAM_NT; ++i) {
+        if (!M[i] || !V[i]) return fail("vsr_adam_step: moment pointer %d is null", i);
+        L.t.p[i] = P[i]; L.t.g[i] = G[i]; L.t.m[i] = M[i]; L.t.v[i] = V[i]; L.t.n[i] = (long long)n[i];
+        L.t.slot[i] = -1;
+        int mat = -1;                                  // index among the 14 matrices the GEMMs multiply by
+        for (int j = 0; j < B16_NW; ++j) if (wp[j] == P[i]) mat = j;
+        if (h->h2_on) L.t.slot[i] = mat >= 0 ? mat : (P[i] == h->w.embed_weight ? (int)H2A_EMBED : -1);
+        if (h->bf16_on && mat >= 0) {
+            if ((size_t)mat >= h->b16_weights || h->b16[mat].lo != wp[mat]) return fail("vsr_adam_step: internal: bf16 copy %d is not registered", mat);
+            L.t.b16[i] = const_cast<uint16_t*>(h->b16[mat].b);
+        }
+        // blocks by the tensor's share of the elements, at least one, no more than it has 16-byte groups for; grid-stride covers the rest
+        L.t.blk[i] = blocks;
+        const long long share = (long long)((double)n[i] / (double)total * h->adam_blocks);
+        blocks += (int)std::max<long long>(1, std::min<long long>(share, cdiv((long long)n[i], 4 * 256)));
+    }
+    L.t.blk[ADAM_NT] = blocks;
+    // torch's: both corrections in double, handed to the kernel as fp32; the step size a double quotient rounded once
+    const float bc1 = (float)(1.0 - std::pow(a->beta1, (double)a->step));
+    L.hy.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(a->beta2, (double)a->step));
+    L.hy.step_size = (float)(a->lr / (double)bc1);
+    L.hy.beta1 = a->beta1; L.hy.beta2 = a->beta2; L.hy.eps = a->eps; L.hy.wd = a->weight_decay;
+    hipStream_t s = (hipStream_t)stream;
+    if (h->h2_on) {
+        if (h2_refresh_launches(h, reinterpret_cast<char*>(h->h2_exps), s, &L)) return 1;      // (the exponent table is the head of the image buffer)
+    } else {
+        hipLaunchKernelGGL(k_adam_multi, dim3(blocks), dim3(256), 0, s, L.t, L.hy, (unsigned*)nullptr);
+        LAUNCHCHK();
+    }
+    // what a refresh voids (vsr_bind_weights has the rules); with no flavour product the fp32 kernels read the weights live: only the
+    // decode cache is of the old weights
+    if (h->h2_on || h->bf16_on) void_derived(h, VOID_REFRESH);
+    else h->xproj = nullptr;
     return 0;
 }
 

@@ -43,6 +43,13 @@ COMPUTE_DTYPES = ('f32', 'f32x3', 'f16x2', 'bf16')
 #   (3) sum(p._version) - in-place edits through torch ops.  NOT sufficient on its own: fused optimizers (Adam / SGD(fused=True))
 #       update the parameters in place and leave _version untouched on this torch build (round-5 review).
 # Writes none of these sees (p.data edits, DLPack / custom kernels into the same storage) in eval mode: call invalidate_cache().
+# The library's own optimizer (vsrcap/optim.py, one vsr_adam_step per step) is the one writer that does not leave the derived state
+# behind: the call that moves the weights rebuilds the images / copies from them.  For its own model it is taken out of (2) again
+# (_own_opt_steps; a twin that shares the parameters sees the count move as for any optimizer); it bumps (1) itself and files the
+# rebuilt state under the new version (optimizer_step), and the next graph-building forward, finding the version exactly
+# where that step left it, does not bump (1) again: no refresh call in the training loop.  Anything else in between - (1), (2) or (3)
+# moving, set_compute_dtype() - and that forward refreshes as it always did.  What none of the counters sees is then the caller's to
+# announce in TRAINING mode as well: a p.data edit between such a step and the next training forward needs invalidate_cache().
 _OPT_STEPS = [0]
 _OPT_HOOK = []
 
@@ -58,6 +65,8 @@ def _count_optimizer_steps():
 
     def _after_step(opt, args, kwargs):
         _OPT_STEPS[0] += 1
+        if getattr(opt, "rebuilds_derived_state", False):       # vsrcap.optim.Adam: every OTHER model is voided as by any optimizer;
+            opt.model._own_opt_steps += 1                       # its own was told, and served, by the step itself (optimizer_step)
     _OPT_HOOK.append(register_optimizer_step_post_hook(_after_step))
 
 
@@ -72,6 +81,8 @@ def set_default_compute_dtype(dtype):
 
 class ControllableCaptioningModel(CaptioningModel):
     _wgen = 0                            # the weights' generation (module comment above)
+    _own_opt_steps = 0                   # steps of a vsrcap.optim.Adam built on this model, as counted into _OPT_STEPS
+    _stepped_at = None                   # the weights' version the library's own optimizer left them - and the derived state - at
 
     def __init__(self, seq_len, vocab_size, bos_idx, det_feat_size=2048, input_encoding_size=1000, rnn_size=1000,
                  att_size=512, h2_first_lstm=True, img_second_lstm=False, dataset='coco', *, verb_2_vob_all=None):
@@ -142,6 +153,7 @@ class ControllableCaptioningModel(CaptioningModel):
         if dtype not in COMPUTE_DTYPES:
             raise ValueError("compute dtype must be one of %s" % (COMPUTE_DTYPES,))
         self.compute_dtype = dtype
+        self._stepped_at = None
         return self
 
     def set_valid_rows_bound(self, n):
@@ -168,6 +180,21 @@ class ControllableCaptioningModel(CaptioningModel):
         if reg is None:
             return None
         return reg(lambda opt, args, kwargs: self.invalidate_cache())
+
+    def optimizer_step(self, params, grads, exp_avg, exp_avg_sq, **hyper):
+        """The hook of vsrcap.optim.Adam: ONE library call updates the 28 parameters (given, with their gradients and moments, in
+        _lib.WEIGHT_FIELDS order; a gradient may be None) and rebuilds the state the engine derives from them (the module comment
+        above).  hyper: lr, beta1, beta2, eps, weight_decay, step of Engine.adam_step."""
+        dev = params[0].device
+        if dev.type != 'cuda':
+            raise RuntimeError("vsrcap.optim.Adam steps on the GPU only: the model's parameters are on %s" % dev)
+        if self._eng is None or self._eng.device != dev or self._eng._derived.ptrs != tuple(p.data_ptr() for p in params):
+            self._engine(dev)                # a first step before any forward, or parameters in new storage: bind
+        self._wgen += 1                      # the weights move ...
+        version = self._weights_version()
+        self._stepped_at = None
+        self._eng.adam_step([p.data for p in params], grads, exp_avg, exp_avg_sq, weights_version=version, **hyper)
+        self._stepped_at = version           # ... and what is derived from them has moved along
 
     def train(self, mode=True):
         # a mode switch redoes the derived state: eval() after a training run must decode with the FINAL weights whatever moved them
@@ -197,7 +224,9 @@ class ControllableCaptioningModel(CaptioningModel):
     def _engine(self, device, weights_may_have_moved=False):
         """weights_may_have_moved: the caller builds an autograd graph (a training forward): the derived weight state is redone"""
         if weights_may_have_moved:
-            self._wgen += 1
+            if self._stepped_at is None or self._stepped_at != self._weights_version():
+                self._wgen += 1
+            self._stepped_at = None
         if device.type != 'cuda':
             raise RuntimeError("ControllableCaptioningModel (MI355X build) computes only on the GPU: move the model and "
                                "its inputs to 'cuda'. There is no CPU fallback.")
@@ -226,7 +255,7 @@ class ControllableCaptioningModel(CaptioningModel):
         return self._eng
 
     def _weights_version(self):
-        return (self._wgen, _OPT_STEPS[0], sum(p._version for p in self.parameters()))
+        return (self._wgen, _OPT_STEPS[0] - self._own_opt_steps, sum(p._version for p in self.parameters()))
 
     def _builds_graph(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())

@@ -38,6 +38,10 @@ class VsrWeights(C.Structure):
     _fields_ = [(f, C.c_void_p) for f, _ in WEIGHT_FIELDS]
 
 
+class VsrAdamArgs(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("step", C.c_int32)]
+
+
 MAX_BEAM = 8          # VSR_MAX_BEAM of include/vsrcap.h: beams, and rows (samples) per image
 
 P = C.c_void_p
@@ -118,6 +122,7 @@ SIGNATURES = {
     "vsr_train_tape_seal": (I32, [P, I64, P, P, P]),
     "vsr_train_bucket_map": (I32, [C.POINTER(I32), C.POINTER(I32)]),
     "vsr_train_wait_bucket": (I32, [P, I32, P]),
+    "vsr_adam_step": (I32, [P, C.POINTER(VsrWeights), C.POINTER(VsrWeights), C.POINTER(VsrWeights), C.POINTER(VsrWeights), C.POINTER(VsrAdamArgs), P]),
     "vsr_bad_ids": (I32, [P, C.POINTER(I32), P]),
     "vsr_set_valid_rows_bound": (I32, [P, I64]),
     "vsr_debug_copy": (I32, [P, C.c_char_p, P, SZ, P]),

@@ -7,6 +7,8 @@ voids the decode cache, the saved forwards and the prepared statics; a refresh w
 issues the calls that bring a handle to a target in the chain's order - the decode cache last, in the final flavour.  The calls go
 through a backend (vsrcap/engine.py: buffers, ctypes, device and stream) with one method per library call: bind(ptrs),
 refresh_bf16(on), set_gemm_mode(x3), refresh_h2(on), build_cache(), drop_cache().
+One event comes from outside the chain: stepped(), after the optimizer of vsrcap/optim.py has rewritten the weights AND their flavour
+product in one library call - the product is current, everything to its right is void.
 No torch, no ctypes: tests/test_derived_logic.py enumerates event sequences against a fake handle."""
 
 # compute dtype -> (bf16 copies, x3 switch, fp16-pair images); f16x2 needs sizes that are multiples of 8 and is plain f32x3 otherwise
@@ -36,6 +38,17 @@ class Derived:
         self.bf16 = self.h2 = None
         self._drop_cache(backend)
         self.statics_void = True
+
+    def stepped(self, ptrs, version):
+        """the library's own optimizer step (vsr_adam_step) wrote the bound weights and, in the same call, rebuilt the flavour product
+        that is on from them: that product is of (ptrs, version) - the weights as they are now - and, as after any refresh, the
+        library dropped its cache pointer and the statics are void.  The caller vouches for ptrs == self.ptrs (the call fails otherwise)."""
+        key = (ptrs, version)
+        if self.bf16_on:
+            self.bf16 = key
+        if self.h2_on:
+            self.h2 = key
+        self._library_voided()
 
     def sync(self, target, backend):
         """target: (bound_ptrs, weights_version, compute_dtype, dims_multiple_of_8, training).  Returns whether the prepared statics are

@@ -163,6 +163,29 @@ class Engine:
         into the same buffer, p.data edits of the weights) are invisible to it - call this after such a write."""
         self._derived.invalidate(self)
 
+    @_on_device
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, weights_version):
+        """One vsr_adam_step on the current stream (vsrcap/optim.py).  The four lists hold 28 fp32 GPU tensors in WEIGHT_FIELDS order; an
+        entry of grads may be None.  params must be the tensors this handle has bound.  weights_version: the model's version of the
+        weights AFTER this step - what the rebuilt flavour product is filed under (Derived.stepped)."""
+        ptrs = tuple(t.data_ptr() for t in params)
+        if ptrs != self._derived.ptrs:
+            raise RuntimeError("adam_step: the parameters are not the tensors bound to this engine (sync_weights first)")
+        for p, g, m, v in zip(params, grads, exp_avg, exp_avg_sq):
+            for t in (g, m, v):
+                if t is not None and (t.dtype != torch.float32 or t.device != p.device or not t.is_contiguous() or t.numel() != p.numel()):
+                    raise RuntimeError("adam_step: gradients and moments must be contiguous fp32 tensors shaped like their parameter, on its device")
+        table = lambda ts: C.byref(_lib.VsrWeights(*[0 if t is None else t.data_ptr() for t in ts]))
+        args = _lib.VsrAdamArgs(lr, beta1, beta2, eps, weight_decay, step)
+        try:
+            _lib.check(self.lib.vsr_adam_step(self.h, table(params), table(grads), table(exp_avg), table(exp_avg_sq), C.byref(args),
+                                              self._stream(params[0].device)))
+        except Exception:
+            self._derived.invalidate(self)       # launches may have gone out: nothing derived is known to be current
+            raise
+        self._derived.stepped(ptrs, weights_version)
+        self._prep_key = None
+
     # the backend of vsrcap/derived.py, one method per library call (include/vsrcap.h says what each of them voids in the handle)
     def bind(self, ptrs):
         _lib.check(self.lib.vsr_bind_weights(self.h, C.byref(_lib.VsrWeights(*ptrs))))

@@ -241,9 +241,10 @@ class DataParallelStep:
 
     def _optimizer_step(self):
         self.opt.step()
-        if self.model is not None:
+        if self.model is not None and not getattr(self.opt, "rebuilds_derived_state", False):
             # the weights moved: whatever the library derived from them (fp16-pair images, bf16 copies, decode cache) is redone by the
-            # next call - said explicitly, not inferred from Tensor._version (fused optimizers leave it untouched)
+            # next call - said explicitly, not inferred from Tensor._version (fused optimizers leave it untouched).  vsrcap.optim.Adam
+            # is the exception: its step has rebuilt that state already
             self.model.invalidate_cache()
 
     def _xe_step_selected(self, det, captions, ctrl_seq, gate_gts):
