@@ -535,6 +535,9 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
     float* z_s = sent_s + D;      // R + 1  (then alpha)
     float* red = z_s + R + 1;     // 8
     int* ri_s = reinterpret_cast<int*>(red + 8);   // R: row of P / regions behind slot entry r (dense: its own row)
+    // R: the row's region mask.  The score loop's projection loads depend on it and the softmax reads it again: from global memory it
+    // was a dependent round trip in front of every pass of the score loop (33.2 -> 29.4 us per launch at 500 rows: profiles/r22_c_*_kernel_stats.csv)
+    float* mk_s = reinterpret_cast<float*>(ri_s + R);
     const int item = xcd_item(M * nparts);
     if (item < 0) return;
     const int row = item / nparts, part = item - row * nparts;
@@ -624,12 +627,12 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
     for (int r = tid; r < R; r += NT) {
         const int e = ridx ? ridx[sl * R + r] : (int)(sl * R + r);
         ri_s[r] = e < 0 ? 0 : e;                   // padding entries are masked and never dereferenced
+        mk_s[r] = rmask[sl * R + r];
     }
     __syncthreads();
 
     // scores: wave w takes rows w, w+4, ... of [regions ; sentinel]; four rows per pass so that their projection
     // loads are all in flight before the first tanh (one L2 round trip per pass instead of one per row)
-    const float* mk_row = rmask + sl * R;
     constexpr int QN = NT == 512 ? 5 : 4;        // rows per wave and pass: 8 waves x 5 cover the 37 score rows of R = 36 at once
     for (int r0 = wave; r0 < R + 1; r0 += QN * NW) {
         float sc[QN];
@@ -642,7 +645,7 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
                 const int r = r0 + NW * q;
                 const float* src = (r < R) ? P + (long long)ri_s[r] * A : sa_row;
                 // padding rows were never projected (att_va(0) = 0): their P entry is not defined, use the exact zero
-                const bool live = r < R + 1 && (r >= R || mk_row[r] != 0.f);
+                const bool live = r < R + 1 && (r >= R || mk_s[r] != 0.f);
                 p[q] = live ? *reinterpret_cast<const float4*>(src + a) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             const float4 h = *reinterpret_cast<const float4*>(hA_s + a);
@@ -653,7 +656,7 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
                 const int r = r0 + NW * q;
                 // a padding row's score never reaches the output (alpha = mask * softmax = 0, and the shift logit sums
                 // mask * z): its 512 tanh are skipped (wave-uniform: a wave owns whole rows); its z stays 0
-                const bool live = r < R + 1 && (r >= R || mk_row[r] != 0.f);
+                const bool live = r < R + 1 && (r >= R || mk_s[r] != 0.f);
                 if (!live) continue;
                 const float4 w = (r < R) ? wa : ws;
                 sc[q] += w.x * tanhf(p[q].x + h.x);
@@ -683,7 +686,6 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
         float ssum = 0.f;
         for (int w = 0; w < NW; ++w) ssum += red[w];
         const float m0 = (ssum != 0.f) ? 1.f : 0.f;
-        const float* mk = rmask + sl * R;
         // R + 1 <= 64 handled by one pass per 64 entries
         float mx = -INFINITY;
         for (int j = lane; j < R + 1; j += 64) mx = fmaxf(mx, z_s[j]);
@@ -693,7 +695,7 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
         se = wave_sum(se);
         float s2 = 0.f;
         for (int j = lane; j < R + 1; j += 64) {
-            const float m = (j == 0) ? m0 : mk[j - 1];
+            const float m = (j == 0) ? m0 : mk_s[j - 1];
             const float z = z_s[j];
             if (j > 0) zs += m * z;
             s2 += (expf(z - mx) / se) * m;
@@ -701,7 +703,7 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
         s2 = wave_sum(s2);
         zs = wave_sum(zs);
         for (int j = lane; j < R + 1; j += 64) {
-            const float m = (j == 0) ? m0 : mk[j - 1];
+            const float m = (j == 0) ? m0 : mk_s[j - 1];
             const float al = ((expf(z_s[j] - mx) / se) * m) / s2;
             z_s[j] = al;
             if (alpha_out && first) alpha_out[(long long)row * (R + 1) + j] = al;

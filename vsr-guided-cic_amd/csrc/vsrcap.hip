@@ -893,7 +893,7 @@ static void launch_attend(vsr_handle* h, hipStream_t s, const Gate2Args& g2, int
                           const float* sa, const float* sent, float* att, float* alpha_out, uint16_t* att16, const int* att_exp) {
     const Ctx& c = h->c;
     const int A = h->d.att_size, D = h->d.det_feat_size, np = attend_parts(h, M);
-    const size_t smem = (size_t)(2 * A + D + c.R + 1 + 8 + c.R) * sizeof(float);
+    const size_t smem = (size_t)(2 * A + D + c.R + 1 + 8 + 2 * c.R) * sizeof(float);      // hA | sa | sentinel | z | red | region rows | region mask
     auto go = [&](auto NT) {
         hipLaunchKernelGGL(k_attend<decltype(NT)::value>, dim3(cdiv(M * np, 8) * 8), dim3(decltype(NT)::value), smem, s, g2, hA, sa, sent, c.P, c.regions,
                            c.rmask, c.ridx, slot, fixed_slot, rpi, M, c.L, c.R, A, D, h->w.att_a_weight, h->w.att_s_weight, att, c.zsum, alpha_out, att16, att_exp, np);
