@@ -41,6 +41,18 @@ def test_struct_layouts_match_header():
     assert fields == [f for f, _ in _lib.WEIGHT_FIELDS]
 
 
+def test_bucket_map_is_the_one_the_exchange_was_tuned_for():
+    """vsr_train_bucket_map is read off the backward's table of gradients (csrc/train.inc.h, train_grad_table): pinned here to the
+    assignment the five literal lists it replaced made, in the field order of vsr_weights."""
+    import ctypes as C
+    from vsrcap import _lib
+    lib = _lib.load()
+    bucket_of, n = (C.c_int32 * 28)(), C.c_int32()
+    assert lib.vsr_train_bucket_map(bucket_of, C.byref(n)) == 0
+    assert n.value == 5
+    assert list(bucket_of) == [2, 0, 3, 3, 3, 3, 4, 4, 4, 4, 0, 3, 3, 3, 1, 1, 1, 1, 2, 2, 3, 3, 0, 3, 4, 3, 4, 4]
+
+
 def test_create_rejects_bad_dims_or_reports_no_device():
     import ctypes as C
     from vsrcap import _lib

@@ -159,18 +159,25 @@ def test_optimizer_step_stays_visible_to_the_library():
     np.testing.assert_allclose(losses, ol, atol=2e-4, rtol=0)
 
 
-def test_bucketed_exchange_is_ordered_behind_the_gradients_it_carries(monkeypatch):
+@pytest.mark.parametrize("flags", [None, dict(h2_first_lstm=False), dict(img_second_lstm=True)], ids=["g1_xe_wide", "no_h2_first_lstm", "img_second_lstm"])
+def test_bucketed_exchange_is_ordered_behind_the_gradients_it_carries(monkeypatch, flags):
     """The overlapped exchange of DataParallelStep on ONE GPU (round-2 advisor finding): every gradient bucket is handed to an
     ASYNCHRONOUS device operation on the side stream behind the library's bucket event (vsr_train_wait_bucket).  With "all-reduce"
     = multiply by 2 (a stand-in with an exactly known result), every one of the 28 gradients must come out as exactly twice the
     gradient of a step without exchange: a bucket exchanged before one of its gradients was complete would leave that gradient
-    undoubled (or half-written); so would a gradient assigned to the wrong bucket.  Also: the same through the bf16 wire format."""
+    undoubled (or half-written); so would a gradient assigned to the wrong bucket.  Also: the same through the bf16 wire format.
+    The two flag cases (cfg and weights of test_xe_gradients_config_flags) run the rows of the backward's gradient table that exist
+    only without h2 in LSTM1's input / with the image in LSTM2's."""
     from vsrcap import parallel
-    meta, _ = load_golden("g1_xe_wide")
-    cfg = meta["cfg"]
-    w = helpers.weights_for(cfg, gains=meta["gains"])
-    det, ctrl_seq, caps, gts = (x.to(DEV) for x in helpers.train_inputs(cfg, meta["seed"]))
-    m = helpers.build_model(cfg, w, DEV).train()
+    if flags is None:
+        meta, _ = load_golden("g1_xe_wide")
+        cfg, seed, flags = meta["cfg"], meta["seed"], {}
+        w = helpers.weights_for(cfg, gains=meta["gains"])
+    else:
+        cfg, seed = dict(V=61, B=5, R0=6, R=7, D=128, L=4, T=7, E=32, H=48, A=16), 12
+        w = synth.make_weights(cfg["V"], cfg["D"], cfg["E"], cfg["H"], cfg["A"], seed=4, gains={k: 1.5 for k in synth.DEFAULT_GAINS}, **flags)
+    det, ctrl_seq, caps, gts = (x.to(DEV) for x in helpers.train_inputs(cfg, seed))
+    m = helpers.build_model(cfg, w, DEV, **flags).train()
     opt = torch.optim.SGD(m.parameters(), lr=0.0)                    # lr 0: the gradients stay inspectable, the weights fixed
 
     def grads_of(step):

@@ -1,5 +1,5 @@
 // What a decoder timestep multiplies: the problem lists of its grouped GEMM launches (S1 / S2 / S5 / S6 of vsrcap.hip's header), ONCE for
-// the decode step (run_step) and the training forward (vsr_train_forward, train.inc.h).  Host only: free functions that append problems to a
+// the decode step (run_step) and the training forward (vsr_train_forward, train.inc.h); at the end those of the training backward's step.  Host only: free functions that append problems to a
 // GemmBuilder (gemm_route.h).  The order of the problems numbers the tiles and the order of a problem's segments is the summation order:
 // both are part of the result's bits (tests/test_gpu_flip_rate.py has rejected a reorder).  Slab layout - tight counts, which buffer a
 // problem's slabs land in - is the caller's: finish() does not read C, so a caller patches C / slab_stride / nslab after planning.
@@ -88,6 +88,51 @@ inline void add_vocab(GemmBuilder& g, const vsr_dims& d, const vsr_weights& w, c
     const int H = d.rnn_size, V = d.vocab_size;
     GemmProb& p0 = g.prob(o.M, V, dst, V);
     GemmBuilder::seg(p0, o.h2_new, H, rows, w.out_fc_weight, H, H, o.h2_new16, H2A_UNIT);
+}
+
+// ---- the training backward's step: its three grouped data-gradient GEMMs against the TRANSPOSED weights (train.inc.h, train_backward_step).
+// The step's gradient rows, the transposed weights and the exponent slots of the gradients (H2A_NONE: the launch cannot take the f16x2
+// kernels).  C is left null: every problem's slabs are placed by the caller.  Problem order and segment order are part of the bits here too.
+struct BwdStepOperands {
+    int M = 0;
+    const float *dpre1 = nullptr, *dpre2 = nullptr;       // (M, 6H) [LSTM1 gates | sentinel gate | dq], (M, 4H)
+    const float *dhA = nullptr, *dsent = nullptr, *dsa = nullptr, *dga = nullptr;
+    const float *wT_ih1 = nullptr, *wT_is = nullptr, *wT_ig = nullptr, *wT_hh1 = nullptr, *wT_hs = nullptr, *wT_ih2 = nullptr, *wT_hh2 = nullptr;
+    const float *wT_hg = nullptr, *wT_ha = nullptr, *wT_sfc = nullptr, *wT_sa = nullptr, *wT_ga = nullptr;
+    int s_dpre1 = H2A_NONE, s_dpre2 = H2A_NONE, s_dq = H2A_NONE, s_dhA = H2A_NONE, s_dsent = H2A_NONE, s_dsa = H2A_NONE, s_dga = H2A_NONE;
+};
+// GEMM 1: dpre2 -> [dh1_a | datt (| dvbar)] (N = H + D: the first rows of W_ih2^T), dpre2 -> the hh part of the dh2 carry, dga -> dg_t
+inline void add_bwd1(GemmBuilder& g, const vsr_dims& d, const BwdStepOperands& o) {
+    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size;
+    GemmProb& p0 = g.prob(o.M, H + D, nullptr, H + D);
+    GemmBuilder::seg(p0, o.dpre2, 4 * H, nullptr, o.wT_ih2, 4 * H, 4 * H, nullptr, o.s_dpre2);
+    GemmProb& p1 = g.prob(o.M, H, nullptr, H);
+    GemmBuilder::seg(p1, o.dpre2, 4 * H, nullptr, o.wT_hh2, 4 * H, 4 * H, nullptr, o.s_dpre2);
+    GemmProb& p2 = g.prob(o.M, H, nullptr, H);
+    GemmBuilder::seg(p2, o.dga, A, nullptr, o.wT_ga, A, A, nullptr, o.s_dga);
+}
+// GEMM 2: [dq | dhA] -> dh1_b,  [dsent | dsa] -> ds_t
+inline void add_bwd2(GemmBuilder& g, const vsr_dims& d, const BwdStepOperands& o) {
+    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size;
+    GemmProb& p0 = g.prob(o.M, H, nullptr, H);
+    GemmBuilder::seg(p0, o.dpre1 + 5 * H, 6 * H, nullptr, o.wT_hg, H, H, nullptr, o.s_dq);
+    GemmBuilder::seg(p0, o.dhA, A, nullptr, o.wT_ha, A, A, nullptr, o.s_dhA);
+    GemmProb& p1 = g.prob(o.M, H, nullptr, H);
+    GemmBuilder::seg(p1, o.dsent, D, nullptr, o.wT_sfc, D, D, nullptr, o.s_dsent);
+    GemmBuilder::seg(p1, o.dsa, A, nullptr, o.wT_sa, A, A, nullptr, o.s_dsa);
+}
+// GEMM 3: dpre1 -> the dh1 carry, then (h2_first_lstm) the LSTM1-input part of the dh2 carry: rows 0 .. H-1 of W_ih1^T / W1_is^T / W1_ig^T = their h2 columns
+inline void add_bwd3(GemmBuilder& g, const vsr_dims& d, const BwdStepOperands& o) {
+    const int H = d.rnn_size;
+    GemmProb& p1 = g.prob(o.M, H, nullptr, H);
+    GemmBuilder::seg(p1, o.dpre1, 6 * H, nullptr, o.wT_hh1, 4 * H, 4 * H, nullptr, o.s_dpre1);
+    GemmBuilder::seg(p1, o.dpre1 + 4 * H, 6 * H, nullptr, o.wT_hs, H, H, nullptr, o.s_dpre1);
+    if (d.h2_first_lstm) {
+        GemmProb& p0 = g.prob(o.M, H, nullptr, H);
+        GemmBuilder::seg(p0, o.dpre1, 6 * H, nullptr, o.wT_ih1, 4 * H, 4 * H, nullptr, o.s_dpre1);
+        GemmBuilder::seg(p0, o.dpre1 + 4 * H, 6 * H, nullptr, o.wT_is, H, H, nullptr, o.s_dpre1);
+        GemmBuilder::seg(p0, o.dpre1 + 5 * H, 6 * H, nullptr, o.wT_ig, H, H, nullptr, o.s_dq);
+    }
 }
 
 }  // namespace vsr

@@ -11,8 +11,19 @@
 //   phase B  all weight gradients as big GEMMs with the reduction over the T*B rows:
 //            dW[n][k] = sum_rows dY^T[n][row] * X^T[k][row]   (both operands transposed once per call)
 // so every matrix product of the backward pass runs on the same stream-K fp32-MFMA kernel as the forward pass.
+// Stated once: the transposed operands (train_operands), a step's slices of the saved arrays (train_step_slices), the step's grouped
+// GEMMs (step_gemms.h), the 28 gradients with their producers and buckets (train_grad_table).
 
 constexpr int VSR_GRAD_BUCKETS = 5;
+// f16x2 backward: the "dynamic" slots of the exponent table (from H2_DYN0), where the producers of the gradient operands fold max |x|.
+// Block tt of DYN_PER_STEP slots belongs to step tt (DY_*); the last two blocks hold the whole-pass slots (DW_*): DW_step + DY_x is the
+// max over the steps of DY_x (k_h2_dyn_fold)
+constexpr int DYN_PER_STEP = 8, DYN_MAX_T = H2_NDYN / DYN_PER_STEP - 2;
+enum { DY_dpre2, DY_dga, DY_dq, DY_dhA, DY_dsent, DY_dsa, DY_dpre1, DY_N };
+enum { DW_dlogits = DYN_MAX_T * DYN_PER_STEP, DW_dP, DW_dpre1sum, DW_dpre2sum, DW_dpre1all, DW_N, DW_step = (DYN_MAX_T + 1) * DYN_PER_STEP };
+static_assert(DY_N <= DYN_PER_STEP && DW_N <= DW_step && DW_step + DYN_PER_STEP == H2_NDYN && DYN_MAX_T == 62,
+              "the per-step blocks, then one block of whole-pass slots, then the block of the per-step maxima: k_h2_dyn_fold");
+
 struct TrainCtx {                      // (plain data + two vectors: copied into SavedForwards)
     bool valid = false;
     const char* tws_lo = nullptr;      // the training workspace this forward was carved into
@@ -63,41 +74,55 @@ struct TrainCtx {                      // (plain data + two vectors: copied into
 static inline size_t up4(size_t x) { return (x + 7) & ~size_t(7); }   // K paddings: multiples of 8 (16-byte bf16 chunks; fp32 needs 4)
 
 // One transposed operand of the backward pass: buf (C, ld_out) = src (R, C; leading dimension ld_in) transposed.  THE description of the
-// buffer: carve_train takes it, its bf16 twin and its fp16-pair image (exponent slot `slot`) by size(), the backward transposes by R / C / ld.
+// buffer: carve_train takes it (and, for a W operand, its bf16 twin and its fp16-pair image with exponent slot `slot`) by size(), the
+// backward transposes by R / C / ld, the gradient table (train_grad_table) names its operands by entry.
 struct TOperand {
     float* TrainCtx::* buf; const float* src; int R, C; long long ld_in, ld_out; int slot;
     size_t size() const { return (size_t)C * (size_t)ld_out; }
 };
-constexpr int N_TW = 13, N_TX = 10, N_TOPS = N_TW + N_TX;
-// The 13 transposed weights, then the 10 transposed activations: the order of the workspace and of the two batched transposes.  Reads
-// B / rpi / TB / TBp / Bp / RLp of `t`: for a sealed tape those of the steps taken (its buffers were carved for tape_max).  The activations'
-// sources lie in the workspace: null while it is only being sized.  tX_reg, the last entry, is sized here (RLp) and transposed by a call
-// of its own, through the list of the non-padding rows (R = 0 here)
+// The 13 transposed weights, the 10 transposed activations (both W operands), then the 10 transposed gradients (the A operands of the
+// weight-gradient products): the order of the workspace and of the batched transposes.
+enum { TW_ih1, TW_is, TW_ig, TW_hh1, TW_hs, TW_ih2, TW_hh2, TW_hg, TW_ha, TW_sfc, TW_sa, TW_ga, TW_out,
+       TX_h2prev, TX_x, TX_h1prev, TX_h1, TX_att, TX_st, TX_gt, TX_h2, TX_vbar, TX_reg,
+       TY_dpre1, TY_dpre2, TY_dlogits, TY_dhA, TY_dsent, TY_dsa, TY_dga, TY_dpre1sum, TY_dpre2sum, TY_dP, N_TOPS };
+constexpr int N_TW = TX_h2prev, N_TWX = TY_dpre1;       // [0, N_TW) weights, [N_TW, N_TWX) activations, [N_TWX, N_TOPS) gradients
+// Reads B / rpi / TB / TBp / Bp / RLp of `t`: for a sealed tape those of the steps taken (its buffers were carved for tape_max).  The
+// sources in the workspace are null while it is only being sized.  TX_reg and TY_dP are sized here (RLp) and transposed through the list
+// of the non-padding rows (R = 0 here: the backward sets their R / ld_out to the rows it gathers).  A gradient's slot is its DYNAMIC
+// slot (DW_*: relative to H2_DYN0, and only while the backward runs on the f16x2 kernels)
 static void train_operands(const vsr_handle* h, const TrainCtx& t, TOperand (&o)[N_TOPS]) {
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
     const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
-    const int in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0);
+    const int in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0), Bi = t.B / t.rpi;
     const size_t BH = (size_t)t.B * H;
-    int n = 0;
     // (N, K) weight -> (K, ld_out >= N); the transposed matrix has the bound of the matrix: its slot (0..13, field order of b16_weight_list)
-    auto W = [&](float* TrainCtx::* buf, const float* src, int N, int K, long long ld_out) { o[n++] = TOperand{buf, src, N, K, K, ld_out, h->h2_slot_of(src)}; };
-    W(&TrainCtx::wT_ih1, w.lstm1_weight_ih, 4 * H, in1, 4 * H); W(&TrainCtx::wT_is, w.W1_is_weight, H, in1, H); W(&TrainCtx::wT_ig, w.W1_ig_weight, H, in1, H);
-    W(&TrainCtx::wT_hh1, w.lstm1_weight_hh, 4 * H, H, 4 * H); W(&TrainCtx::wT_hs, w.W1_hs_weight, H, H, H);
-    W(&TrainCtx::wT_ih2, w.lstm2_weight_ih, 4 * H, in2, 4 * H); W(&TrainCtx::wT_hh2, w.lstm2_weight_hh, 4 * H, H, 4 * H);
-    W(&TrainCtx::wT_hg, w.W1_hg_weight, H, H, H); W(&TrainCtx::wT_ha, w.att_ha_weight, A, H, A); W(&TrainCtx::wT_sfc, w.s_fc_weight, D, H, D);
-    W(&TrainCtx::wT_sa, w.att_sa_weight, A, H, A); W(&TrainCtx::wT_ga, w.att_ga_weight, A, H, A);
-    W(&TrainCtx::wT_out, w.out_fc_weight, V, H, (long long)up4(V));      // (K of the dh2_vocab GEMM: a multiple of 8)
-    // (rows, C) activation, rows (t, b) -> (C, rows padded); slot: the class of the activation
-    auto X = [&](float* TrainCtx::* buf, const float* src, size_t skip, int R, int C, long long ld_out, int slot) {
-        o[n++] = TOperand{buf, src ? src + skip : nullptr, R, C, C, ld_out, slot};
+    auto W = [&](int i, float* TrainCtx::* buf, const float* src, int N, int K, long long ld_out) { o[i] = TOperand{buf, src, N, K, K, ld_out, h->h2_slot_of(src)}; };
+    W(TW_ih1, &TrainCtx::wT_ih1, w.lstm1_weight_ih, 4 * H, in1, 4 * H); W(TW_is, &TrainCtx::wT_is, w.W1_is_weight, H, in1, H); W(TW_ig, &TrainCtx::wT_ig, w.W1_ig_weight, H, in1, H);
+    W(TW_hh1, &TrainCtx::wT_hh1, w.lstm1_weight_hh, 4 * H, H, 4 * H); W(TW_hs, &TrainCtx::wT_hs, w.W1_hs_weight, H, H, H);
+    W(TW_ih2, &TrainCtx::wT_ih2, w.lstm2_weight_ih, 4 * H, in2, 4 * H); W(TW_hh2, &TrainCtx::wT_hh2, w.lstm2_weight_hh, 4 * H, H, 4 * H);
+    W(TW_hg, &TrainCtx::wT_hg, w.W1_hg_weight, H, H, H); W(TW_ha, &TrainCtx::wT_ha, w.att_ha_weight, A, H, A); W(TW_sfc, &TrainCtx::wT_sfc, w.s_fc_weight, D, H, D);
+    W(TW_sa, &TrainCtx::wT_sa, w.att_sa_weight, A, H, A); W(TW_ga, &TrainCtx::wT_ga, w.att_ga_weight, A, H, A);
+    W(TW_out, &TrainCtx::wT_out, w.out_fc_weight, V, H, (long long)up4(V));      // (K of the dh2_vocab GEMM: a multiple of 8)
+    // (R, C) matrix, leading dimension ld_in -> (C, R padded); slot: the class of the activation / the dynamic slot of the gradient
+    auto X = [&](int i, float* TrainCtx::* buf, const float* src, size_t skip, int R, int C, long long ld_in, long long ld_out, int slot) {
+        o[i] = TOperand{buf, src ? src + skip : nullptr, R, C, ld_in, ld_out, slot};
     };
-    X(&TrainCtx::tX_h2prev, t.h2s, 0, t.TB, H, t.TBp, H2A_UNIT); X(&TrainCtx::tX_x, t.x_all, 0, t.TB, E, t.TBp, H2A_EMBED);   // state slots 0 .. T-1: entering step t
-    X(&TrainCtx::tX_h1prev, t.h1s, 0, t.TB, H, t.TBp, H2A_UNIT); X(&TrainCtx::tX_h1, t.h1s, BH, t.TB, H, t.TBp, H2A_UNIT);
-    X(&TrainCtx::tX_att, t.atts, 0, t.TB, D, t.TBp, H2A_ATT); X(&TrainCtx::tX_st, t.s_ts, 0, t.TB, H, t.TBp, H2A_UNIT);
-    X(&TrainCtx::tX_gt, t.g_ts, 0, t.TB, H, t.TBp, H2A_UNIT); X(&TrainCtx::tX_h2, t.h2s, BH, t.TB, H, t.TBp, H2A_UNIT);
-    X(&TrainCtx::tX_vbar, h->c.vbar, 0, t.B / t.rpi, D, t.Bp, H2A_DET);     // per IMAGE
-    X(&TrainCtx::tX_reg, h->c.regions, 0, 0, D, t.RLp, H2A_REGION);
+    X(TX_h2prev, &TrainCtx::tX_h2prev, t.h2s, 0, t.TB, H, H, t.TBp, H2A_UNIT); X(TX_x, &TrainCtx::tX_x, t.x_all, 0, t.TB, E, E, t.TBp, H2A_EMBED);   // state slots 0 .. T-1: entering step t
+    X(TX_h1prev, &TrainCtx::tX_h1prev, t.h1s, 0, t.TB, H, H, t.TBp, H2A_UNIT); X(TX_h1, &TrainCtx::tX_h1, t.h1s, BH, t.TB, H, H, t.TBp, H2A_UNIT);
+    X(TX_att, &TrainCtx::tX_att, t.atts, 0, t.TB, D, D, t.TBp, H2A_ATT); X(TX_st, &TrainCtx::tX_st, t.s_ts, 0, t.TB, H, H, t.TBp, H2A_UNIT);
+    X(TX_gt, &TrainCtx::tX_gt, t.g_ts, 0, t.TB, H, H, t.TBp, H2A_UNIT); X(TX_h2, &TrainCtx::tX_h2, t.h2s, BH, t.TB, H, H, t.TBp, H2A_UNIT);
+    X(TX_vbar, &TrainCtx::tX_vbar, h->c.vbar, 0, Bi, D, D, t.Bp, H2A_DET);     // per IMAGE
+    X(TX_reg, &TrainCtx::tX_reg, h->c.regions, 0, 0, D, D, t.RLp, H2A_REGION);
+    // rows (t, b) of every step; dpre1 is ONE image (all six column blocks), dlogits' rows are padded to up8(V)
+    X(TY_dpre1, &TrainCtx::tY_dpre1, t.dpre1, 0, t.TB, 6 * H, 6 * H, t.TBp, DW_dpre1all); X(TY_dpre2, &TrainCtx::tY_dpre2, t.dpre2, 0, t.TB, 4 * H, 4 * H, t.TBp, DW_step + DY_dpre2);
+    X(TY_dlogits, &TrainCtx::tY_dlogits, t.dlogits, 0, t.TB, V, (long long)up4(V), t.TBp, DW_dlogits);
+    X(TY_dhA, &TrainCtx::tY_dhA, t.dhA_all, 0, t.TB, A, A, t.TBp, DW_step + DY_dhA); X(TY_dsent, &TrainCtx::tY_dsent, t.dsent_all, 0, t.TB, D, D, t.TBp, DW_step + DY_dsent);
+    X(TY_dsa, &TrainCtx::tY_dsa, t.dsa_all, 0, t.TB, A, A, t.TBp, DW_step + DY_dsa); X(TY_dga, &TrainCtx::tY_dga, t.dga_all, 0, t.TB, A, A, t.TBp, DW_step + DY_dga);
+    // per IMAGE: the sums over an image's rows and steps (the gradients of the hoisted v-bar projections)
+    X(TY_dpre1sum, &TrainCtx::tY_dpre1sum, t.dpre1sum, 0, Bi, 6 * H, 6 * H, t.Bp, DW_dpre1sum); X(TY_dpre2sum, &TrainCtx::tY_dpre2sum, t.dpre2sum, 0, Bi, 4 * H, 4 * H, t.Bp, DW_dpre2sum);
+    // dP per slot entry, or (index lists) summed per bank row first
+    X(TY_dP, &TrainCtx::tY_dP, h->c.ridx ? t.dP_bank : t.dP, 0, 0, A, A, t.RLp, DW_dP);
 }
 
 static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
@@ -132,7 +157,7 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     t.dh1_c = b.take<float>(B * H); t.dh2_c = b.take<float>(B * H);
     for (int i = 0; i < 2; ++i) { t.dc1_c[i] = b.take<float>(B * H); t.dc2_c[i] = b.take<float>(B * H); }
     t.dpre1sum = b.take<float>(Bi * 6 * H); t.dpre2sum = b.take<float>(Bi * 4 * H); t.dx_all = b.take<float>(TB * E); t.xproj_all = b.take<float>(TB * 6 * H);
-    // the transposed operands (train_operands): fp32 buffer, bf16 twin and fp16-pair image of each, all sized and slotted by its entry
+    // the transposed operands (train_operands): the fp32 buffer of each, bf16 twin and fp16-pair image of a W operand, all sized and slotted by its entry
     TOperand ops[N_TOPS];
     train_operands(h, t, ops);
     t.twins.clear();
@@ -141,15 +166,12 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     take(0, N_TW);
     twins(0, N_TW);
     b.off = (b.off + 255) & ~size_t(255);
-    take(N_TW, N_TOPS);
-    t.tY_dpre1 = b.take<float>(6 * H * TBp); t.tY_dpre2 = b.take<float>(4 * H * TBp); t.tY_dlogits = b.take<float>(V * TBp);
-    t.tY_dhA = b.take<float>(A * TBp); t.tY_dsent = b.take<float>(D * TBp); t.tY_dsa = b.take<float>(A * TBp); t.tY_dga = b.take<float>(A * TBp);
-    t.tY_dpre1sum = b.take<float>(6 * H * Bp); t.tY_dpre2sum = b.take<float>(4 * H * Bp); t.tY_dP = b.take<float>(A * RLp);
-    twins(N_TW, N_TOPS);
+    take(N_TW, N_TOPS);               // (the gradients are A operands: no twins, no registered images)
+    twins(N_TW, N_TWX);
     t.imgs.clear(); t.h2img = nullptr;
     if (h->h2_on && !h->bf16_on) {
         size_t off = 0;
-        for (const TOperand& o : ops) { t.imgs.push_back(TrainCtx::Img{t.*o.buf, o.size(), off, o.slot}); off += up4(o.size()); }
+        for (int i = 0; i < N_TWX; ++i) { t.imgs.push_back(TrainCtx::Img{t.*ops[i].buf, ops[i].size(), off, ops[i].slot}); off += up4(ops[i].size()); }
         b.off = (b.off + 255) & ~size_t(255);
         t.h2img = b.take<float>(off);
         b.off = (b.off + 255) & ~size_t(255);
@@ -167,20 +189,20 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
 
 struct SegSpec { const float* A; int lda; const float* W; int ldw; int K; int a_cls = H2A_NONE; const uint16_t* A16 = nullptr; };
 
-// whole-pass bounds from the per-step ones (block 63: max over the steps; block 62 slots 2, 3: the sums over t of dpre1 / dpre2 rows)
+// whole-pass bounds from the per-step ones (DW_step + j: max over the steps; DW_dpre1sum / DW_dpre2sum: the sums over t of dpre1 / dpre2 rows)
 // (nsum: rows one sum runs over - the T steps of a row, times the rows of an image when several share its statics)
 __global__ void k_h2_dyn_fold(int* __restrict__ dyn, int T, int nsum) {
     const int j = threadIdx.x;
-    if (j >= 8) return;
+    if (j >= DYN_PER_STEP) return;
     int m = 0;
-    for (int tt = 0; tt < T; ++tt) m = max(m, dyn[tt * 8 + j]);
-    dyn[63 * 8 + j] = m;
-    if (j == 0) dyn[62 * 8 + 3] = __float_as_int(__int_as_float(m) * (float)nsum);
-    if (j == 6) {
+    for (int tt = 0; tt < T; ++tt) m = max(m, dyn[tt * DYN_PER_STEP + j]);
+    dyn[DW_step + j] = m;
+    if (j == DY_dpre2) dyn[DW_dpre2sum] = __float_as_int(__int_as_float(m) * (float)nsum);
+    if (j == DY_dpre1) {
         int m2 = 0;
-        for (int tt = 0; tt < T; ++tt) m2 = max(m2, dyn[tt * 8 + 2]);
-        dyn[62 * 8 + 2] = __float_as_int(fmaxf(__int_as_float(m), __int_as_float(m2)) * (float)nsum);
-        dyn[62 * 8 + 4] = max(m, m2);                                       // all six column blocks of dpre1 (its transpose is one image)
+        for (int tt = 0; tt < T; ++tt) m2 = max(m2, dyn[tt * DYN_PER_STEP + DY_dq]);
+        dyn[DW_dpre1sum] = __float_as_int(fmaxf(__int_as_float(m), __int_as_float(m2)) * (float)nsum);
+        dyn[DW_dpre1all] = max(m, m2);                                      // all six column blocks of dpre1 (its transpose is one image)
     }
 }
 
@@ -456,6 +478,40 @@ static int train_vocab_full(vsr_handle* h, TrainCtx& t, const StepOperands& o, c
     LAUNCHCHK();
     return 0;
 }
+// K rows per image -> the "rows share an image" template flag and the K the kernel is given: f(std::bool_constant<(K > 1)>, K).  K = 1
+// launches the kernels of the one-row-per-image path (the <false> instances) with 1
+template <class F> static inline void with_shared_rows(int K, F&& f) {
+    if (K > 1) f(std::true_type{}, K); else f(std::false_type{}, 1);
+}
+// Step tt's slices of the saved arrays (rows (t, b)) and of the backward's all-steps gradients: THE place that knows the layouts.
+// Shared by the forward step, the tape step and the backward step.  im: the forward keeps 16-bit images of its A operands (else null)
+struct StepSlices {
+    float *h1o, *c1o, *h2o, *c2o;          // state entering the step (slot tt) ...
+    float *h1n, *c1n, *h2n, *c2n;          // ... and leaving it (slot tt + 1)
+    float *g1, *g2, *s_t, *g_t, *hA, *sa, *ga, *sent, *att, *alpha, *x, *xproj;
+    int *word, *slot;
+    uint16_t *h1o16, *h2o16, *h1n16, *h2n16, *s_t16, *g_t16, *att16;
+    float *dh2_voc, *dpre1, *dpre2, *dhA, *dsent, *dsa, *dga, *dwa, *dws, *dwg;
+};
+static StepSlices train_step_slices(const vsr_handle* h, const TrainCtx& t, int tt, bool im = false) {
+    const vsr_dims& d = h->d;
+    const size_t B = t.B, BH = B * d.rnn_size, BA = B * d.att_size, BD = B * d.det_feat_size, BE = B * d.input_encoding_size, o = tt, n = tt + 1;
+    StepSlices q;
+    q.h1o = t.h1s + o * BH; q.c1o = t.c1s + o * BH; q.h2o = t.h2s + o * BH; q.c2o = t.c2s + o * BH;
+    q.h1n = t.h1s + n * BH; q.c1n = t.c1s + n * BH; q.h2n = t.h2s + n * BH; q.c2n = t.c2s + n * BH;
+    q.g1 = t.gates1 + o * BH * 6; q.g2 = t.gates2 + o * BH * 4; q.s_t = t.s_ts + o * BH; q.g_t = t.g_ts + o * BH;
+    q.hA = t.hAs + o * BA; q.sa = t.sas + o * BA; q.ga = t.gas + o * BA;
+    q.sent = t.sents + o * BD; q.att = t.atts + o * BD; q.alpha = t.alphas + o * B * (h->c.R + 1);
+    q.x = t.x_all + o * BE; q.xproj = t.xproj_all + o * BH * 6;
+    q.word = t.word32 + o * B; q.slot = t.slot32 + o * B;
+    q.h1o16 = im ? t.h1s16 + o * BH * 2 : nullptr; q.h2o16 = im ? t.h2s16 + o * BH * 2 : nullptr;
+    q.h1n16 = im ? t.h1s16 + n * BH * 2 : nullptr; q.h2n16 = im ? t.h2s16 + n * BH * 2 : nullptr;
+    q.s_t16 = im ? t.s_t16 : nullptr; q.g_t16 = im ? t.g_t16 : nullptr; q.att16 = im ? t.att16 : nullptr;     // (of the current step only)
+    q.dh2_voc = t.dh2_voc + o * BH; q.dpre1 = t.dpre1 + o * BH * 6; q.dpre2 = t.dpre2 + o * BH * 4;
+    q.dhA = t.dhA_all + o * BA; q.dsent = t.dsent_all + o * BD; q.dsa = t.dsa_all + o * BA; q.dga = t.dga_all + o * BA;
+    q.dwa = t.dwa_rows + o * BA; q.dws = t.dws_rows + o * BA; q.dwg = t.dwg_rows + o * BA;
+    return q;
+}
 // Step tt of the unroll: state slot tt -> slot tt + 1, the step's saves, its gate log-probs into lg_out (row stride lg_stride).  The body
 // of vsr_train_forward's loop over the steps; a tape (vsr_train_tape_step) takes the same step one call at a time.
 static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im, float* lg_out, long long lg_stride, hipStream_t s) {
@@ -463,24 +519,13 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
     const int B = t.B, H = d.rnn_size, A = d.att_size, D = d.det_feat_size;
-    const size_t BH = (size_t)B * H;
     const float isc = im ? 32768.f : 0.f;                  // (2^15: the exponent of the unit-bounded class)
     const int* att_exp = im ? h->h2_exps + H2A_ATT : nullptr;
-    const float *h1o = t.h1s + (size_t)tt * BH, *c1o = t.c1s + (size_t)tt * BH, *h2o = t.h2s + (size_t)tt * BH, *c2o = t.c2s + (size_t)tt * BH;
-    float *h1n = t.h1s + (size_t)(tt + 1) * BH, *c1n = t.c1s + (size_t)(tt + 1) * BH, *h2n = t.h2s + (size_t)(tt + 1) * BH, *c2n = t.c2s + (size_t)(tt + 1) * BH;
-    float* g1 = t.gates1 + (size_t)tt * B * 6 * H;
-    float* g2 = t.gates2 + (size_t)tt * B * 4 * H;
-    float *s_t = t.s_ts + (size_t)tt * BH, *g_t = t.g_ts + (size_t)tt * BH;
-    float *hA = t.hAs + (size_t)tt * B * A, *sa = t.sas + (size_t)tt * B * A, *ga = t.gas + (size_t)tt * B * A;
-    float *sent = t.sents + (size_t)tt * B * D, *att = t.atts + (size_t)tt * B * D, *alpha = t.alphas + (size_t)tt * B * (c.R + 1);
-    const int* slot = t.slot32 + (size_t)tt * B;
-    uint16_t *h1n16 = im ? t.h1s16 + (size_t)(tt + 1) * BH * 2 : nullptr, *h2n16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
-    uint16_t *s_t16 = im ? t.s_t16 : nullptr, *g_t16 = im ? t.g_t16 : nullptr, *att16 = im ? t.att16 : nullptr;
+    const StepSlices q = train_step_slices(h, t, tt, im);
     StepOperands o;
     o.M = B;
-    o.h1_old = h1o; o.h2_old = h2o; o.h1_new = h1n; o.h2_new = h2n; o.s_t = s_t; o.g_t = g_t; o.att = att;
-    if (im) { o.h1_old16 = t.h1s16 + (size_t)tt * BH * 2; o.h2_old16 = t.h2s16 + (size_t)tt * BH * 2; }
-    o.h1_new16 = h1n16; o.h2_new16 = h2n16; o.s_t16 = s_t16; o.g_t16 = g_t16; o.att16 = att16;
+    o.h1_old = q.h1o; o.h2_old = q.h2o; o.h1_new = q.h1n; o.h2_new = q.h2n; o.s_t = q.s_t; o.g_t = q.g_t; o.att = q.att;
+    o.h1_old16 = q.h1o16; o.h2_old16 = q.h2o16; o.h1_new16 = q.h1n16; o.h2_new16 = q.h2n16; o.s_t16 = q.s_t16; o.g_t16 = q.g_t16; o.att16 = q.att16;
     {   // S1: the recurrent parts only (h2, h1 of the previous step); nothing to multiply at step 0
         int ns = 0;
         const long long stride = (long long)B * 6 * H;
@@ -492,10 +537,10 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
             if (g.launch(s, h)) return fail("train S1 gemm launch failed");
         }
         const int nblk = d.h2_first_lstm ? 6 : 5;      // without h2 in the input the shift-gate block has no recurrent part
-        if (K > 1) hipLaunchKernelGGL(k_lstm1_train<true>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
-                           t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, K);
-        else hipLaunchKernelGGL(k_lstm1_train<false>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
-                           t.xproj_all + (size_t)tt * B * 6 * H, c1o, B, H, h1n, c1n, s_t, c.gpre, g1, nblk, h1n16, s_t16, isc, 1);
+        with_shared_rows(K, [&](auto SH, int k) {
+            hipLaunchKernelGGL(k_lstm1_train<decltype(SH)::value>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
+                               q.xproj, q.c1o, B, H, q.h1n, q.c1n, q.s_t, c.gpre, q.g1, nblk, q.h1n16, q.s_t16, isc, k);
+        });
     }
     {   // S2
         GemmBuilder g;
@@ -506,10 +551,10 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
         // (Round 5: k_gate2's work inside the attention kernel's row blocks, as in decoding, with the sentinel / s_a / the shift gate stored
         // on the way for the backward pass: measured at no gain - 10.99-11.06 k against 10.85-11.10 k samples/s, profiles/r05_h_* - and not kept.)
         const long long n = (long long)B * (H + A + D + A);
-        hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias,
-                           B, H, A, D, g_t, hA, sent, sa, g1, g_t16, isc);
+        hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, q.c1n, w.s_fc_bias,
+                           B, H, A, D, q.g_t, q.hA, q.sent, q.sa, q.g1, q.g_t16, isc);
     }
-    launch_attend(h, s, Gate2Args{}, B, K, slot, 0, hA, sa, sent, att, alpha, att16, att_exp);
+    launch_attend(h, s, Gate2Args{}, B, K, q.slot, 0, q.hA, q.sa, q.sent, q.att, q.alpha, q.att16, att_exp);
     {   // S5
         GemmBuilder g;
         add_s5(g, d, w, o, c.scratch, tt > 0);
@@ -519,14 +564,14 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
         g.a.p[0].slab_stride = stride;
         g.a.p[1].C = gas; g.a.p[1].slab_stride = stride_g;
         if (g.launch(s, h)) return fail("train S5 gemm launch failed");
-        GateLogitArgs gl{gas, ns, stride_g, hA, w.att_g_weight, c.zsum, nullptr, slot, K, c.L, B, A,
+        GateLogitArgs gl{gas, ns, stride_g, q.hA, w.att_g_weight, c.zsum, nullptr, q.slot, K, c.L, B, A,
                          lg_out, lg_stride};
-        gl.ga_out = ga;
+        gl.ga_out = q.ga;
         const int gblocks = B;
-        if (K > 1) hipLaunchKernelGGL(k_fwd_tail<true>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
-                           w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, K);
-        else hipLaunchKernelGGL(k_fwd_tail<false>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
-                           w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, c2o, B, H, h2n, c2n, g2, h2n16, isc, 1);
+        with_shared_rows(K, [&](auto SH, int k) {
+            hipLaunchKernelGGL(k_fwd_tail<decltype(SH)::value>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
+                               w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, q.c2o, B, H, q.h2n, q.c2n, q.g2, q.h2n16, isc, k);
+        });
     }
     LAUNCHCHK();
     return 0;
@@ -671,17 +716,16 @@ extern "C" int vsr_train_tape_step(vsr_handle* h, int64_t generation, const int6
     const int B = t.B, H = d.rnn_size, E = d.input_encoding_size, V = d.vocab_size, tt = t.tape_steps;
     const size_t BH = (size_t)B * H;
     const bool im = train_a_images(h, t);
-    int* word32 = t.word32 + (size_t)tt * B;
-    float* x = t.x_all + (size_t)tt * B * E;               // (the weight-gradient phase reads the rows of every step)
+    const StepSlices q = train_step_slices(h, t, tt, im);  // (x: the weight-gradient phase reads the rows of every step)
     // (T = 1, no row list: the step's (B) ids -> the step's rows of the (T, B) int32 copies, counted and clamped as for a whole forward)
-    hipLaunchKernelGGL(k_train_indices, dim3(cdiv(B, 256)), dim3(256), 0, s, word_in, slots, 1, B, V, c.L, word32, t.slot32 + (size_t)tt * B, (int*)nullptr, c.nvalid_dev + 2);
-    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((long long)B * E, 256)), dim3(256), 0, s, w.embed_weight, word32, B, E, x);
+    hipLaunchKernelGGL(k_train_indices, dim3(cdiv(B, 256)), dim3(256), 0, s, word_in, slots, 1, B, V, c.L, q.word, q.slot, (int*)nullptr, c.nvalid_dev + 2);
+    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv((long long)B * E, 256)), dim3(256), 0, s, w.embed_weight, q.word, B, E, q.x);
     LAUNCHCHK();
     StepOperands o;                                        // this step's M = B rows of the two launches a whole forward makes over all T B
     o.M = B;
-    o.x = im ? w.embed_weight : x; o.word = im ? word32 : nullptr;
-    o.h2_new = t.h2s + (size_t)(tt + 1) * BH; o.h2_new16 = im ? t.h2s16 + (size_t)(tt + 1) * BH * 2 : nullptr;
-    if (train_xproj(h, t, o, t.xproj_all + (size_t)tt * B * 6 * H, s)) return 1;
+    o.x = im ? w.embed_weight : q.x; o.word = im ? q.word : nullptr;
+    o.h2_new = q.h2n; o.h2_new16 = q.h2n16;
+    if (train_xproj(h, t, o, q.xproj, s)) return 1;
     if (train_forward_step(h, t, 1, tt, im, logp_gates, 2, s)) return 1;
     if (train_vocab_full(h, t, o, nullptr, logp_words, s)) return 1;      // the new h2 (state slot tt + 1) -> the caller's (B, V) log-probs
     const float* src[4] = {t.h1s, t.c1s, t.h2s, t.c2s};
@@ -779,7 +823,214 @@ __global__ void k_sum_over_t_rows(const float* __restrict__ X, int T, int K, int
 // ---------------------------------------------------------------------------------------------- backward
 // the 28 gradients, in the field order of vsr_weights
 enum { g_embed, g_Wis, g_bis, g_Whs, g_bhs, g_Wva, g_Wha, g_wa, g_Wsa, g_ws, g_Wih1, g_Whh1, g_bih1, g_bhh1, g_Wih2, g_Whh2, g_bih2,
-       g_bhh2, g_Wout, g_bout, g_Wsfc, g_bsfc, g_Wig, g_big, g_Whg, g_bhg, g_Wga, g_wg };
+       g_bhh2, g_Wout, g_bout, g_Wsfc, g_bsfc, g_Wig, g_big, g_Whg, g_bhg, g_Wga, g_wg, N_GRADS };
+static_assert(N_GRADS * sizeof(float*) == sizeof(vsr_weights), "one gradient per field of vsr_weights");
+
+// One row of THE table of the weight gradients (train_grad_table): what produces a gradient (or one column window of it) and in which
+// bucket.  Phase B of the backward walks the rows in order and records a bucket's event where the walk leaves the bucket;
+// vsr_train_bucket_map reads the buckets off the same rows.  Adding a gradient, or moving one to another bucket, is an edit of its rows.
+struct GradRow {
+    enum Kind { PROD, COLSUM, EMBED };
+    enum { ALONE = -1 };
+    enum Pre { PRE_NONE, PRE_DPRE2SUM, PRE_VA };
+    int kind, g, bucket;
+    bool on;                   // the configuration has this row (the bucket map counts it either way)
+    // PROD: G[g] + col (leading dimension ldd) = rows [r0, r0 + M) of the transposed gradient `ty` x the transposed activation `tx`
+    // (train_operands entries: K = their padded row count, N = tx's columns, exponent slot and image-in-place of A = ty's)
+    int ty, r0, M, tx, col, ldd;
+    int slot;                  // the dynamic slot of these rows where ty is NOT one image of one bound (-1: ty's own)
+    int launch;                // adjacent products with the same id share a gemm_group launch; ALONE: gemm_to1.  Which products share a
+                               // launch decides tiles and slabs, i.e. the bits
+    int pre;                   // code that stays code, run before the product: the sum over t and its transpose (PRE_DPRE2SUM); a memset
+                               // INSTEAD of the product when no region row is valid (PRE_VA)
+    // COLSUM: G[g] (and G[g2], the second bias of a pair; -1: none) = the sums of columns [c0, c0 + n) of src (T B rows, C columns,
+    // leading dimension ld).  Adjacent rows of one src share the partial-sum launch
+    int g2, ld, C, c0, n;
+    float* TrainCtx::* src;
+    // EMBED: the data-gradient GEMM dx, a memset and k_embed_grad_rows - code in the walk
+};
+// The rows, in the order phase B issues them.  Reads only the sizes and the two flags of `d`: buckets and order do not depend on them.
+static std::vector<GradRow> train_grad_table(const vsr_dims& d) {
+    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size, Vp = (int)up4((size_t)V);
+    const bool h2in = d.h2_first_lstm, img2 = d.img_second_lstm;
+    const int voff = h2in ? H : 0, xoff = voff + D, in1 = xoff + E, in2 = H + D + (img2 ? D : 0);
+    const int ALONE = GradRow::ALONE;
+    std::vector<GradRow> v;
+    v.reserve(40);
+    int b = 0;
+    auto prod = [&](int g, int col, int ldd, int ty, int r0, int M, int tx, int launch, int slot = -1, bool on = true, int pre = GradRow::PRE_NONE) {
+        GradRow r{};
+        r.kind = GradRow::PROD; r.g = g; r.g2 = -1; r.bucket = b; r.on = on;
+        r.ty = ty; r.r0 = r0; r.M = M; r.tx = tx; r.col = col; r.ldd = ldd; r.slot = slot; r.launch = launch; r.pre = pre;
+        v.push_back(r);
+    };
+    auto bias = [&](int g, int g2, float* TrainCtx::* src, int ld, int C, int c0, int n) {
+        GradRow r{};
+        r.kind = GradRow::COLSUM; r.g = g; r.g2 = g2; r.bucket = b; r.on = true; r.src = src; r.ld = ld; r.C = C; r.c0 = c0; r.n = n;
+        v.push_back(r);
+    };
+    // dpre1's column blocks [LSTM1 gates | sentinel gate] and [dq] have bounds of their own where its transpose is not one image
+    const int sP1 = DW_step + DY_dpre1, sQ = DW_step + DY_dq;
+    // ---- bucket 0: lstm_cell_1.weight_ih / W1_is / W1_ig: row blocks [0,4H), [4H,5H), [5H,6H) of dpre1^T against [h2_prev | vbar | x].
+    // (grouped launches, round 6: the two 4H-row products are 256 whole tiles together, the four H-row ones share a launch - without the
+    // h2 columns the three x parts share one; the three short-K image-constant parts share one)
+    b = 0;
+    const int gi[3] = {g_Wih1, g_Wis, g_Wig}, r0[3] = {0, 4 * H, 5 * H}, nr[3] = {4 * H, H, H}, sl[3] = {sP1, sP1, sQ};
+    for (int i = 0; i < 3; ++i) {
+        const int l = h2in && i > 0 ? 1 : 0;
+        prod(gi[i], 0, in1, TY_dpre1, r0[i], nr[i], TX_h2prev, l, sl[i], h2in);
+        prod(gi[i], xoff, in1, TY_dpre1, r0[i], nr[i], TX_x, l, sl[i]);
+    }
+    for (int i = 0; i < 3; ++i) prod(gi[i], voff, in1, TY_dpre1sum, r0[i], nr[i], TX_vbar, 2);
+    // ---- bucket 1: lstm_cell_2 (the attended-vector part is 256 whole tiles on its own; the h1 part and weight_hh are 256 together)
+    b = 1;
+    prod(g_Wih2, 0, in2, TY_dpre2, 0, 4 * H, TX_h1, 0);
+    prod(g_Whh2, 0, H, TY_dpre2, 0, 4 * H, TX_h2prev, 0);
+    prod(g_Wih2, H, in2, TY_dpre2, 0, 4 * H, TX_att, ALONE);
+    prod(g_Wih2, H + D, in2, TY_dpre2sum, 0, 4 * H, TX_vbar, ALONE, -1, img2, GradRow::PRE_DPRE2SUM);
+    bias(g_bih2, g_bhh2, &TrainCtx::dpre2, 4 * H, 4 * H, 0, 4 * H);
+    // ---- bucket 2: out_fc and the embedding
+    b = 2;
+    prod(g_Wout, 0, H, TY_dlogits, 0, V, TX_h2, ALONE);
+    bias(g_bout, -1, &TrainCtx::dlogits, Vp, V, 0, V);
+    { GradRow r{}; r.kind = GradRow::EMBED; r.g = g_embed; r.g2 = -1; r.bucket = b; r.on = true; v.push_back(r); }
+    // ---- bucket 3: the recurrent LSTM1 / sentinel-gate weights, all LSTM1 / gate biases, s_fc, att_va
+    b = 3;
+    prod(g_Whh1, 0, H, TY_dpre1, 0, 4 * H, TX_h1prev, 0, sP1);           // (with W1_hs and s_fc: 224 whole tiles in one launch)
+    prod(g_Whs, 0, H, TY_dpre1, 4 * H, H, TX_h1prev, 0, sP1);
+    prod(g_Wsfc, 0, H, TY_dsent, 0, D, TX_st, 0);
+    // the six LSTM1 / gate bias gradients are column sums of ONE matrix (dpre1, 6H columns): one partial-sum launch, three finishing launches
+    // that write both members of a pair (same per-column arithmetic as three separate sums: bit-identical)
+    bias(g_bih1, g_bhh1, &TrainCtx::dpre1, 6 * H, 6 * H, 0, 4 * H);
+    bias(g_bis, g_bhs, &TrainCtx::dpre1, 6 * H, 6 * H, 4 * H, H);
+    bias(g_big, g_bhg, &TrainCtx::dpre1, 6 * H, 6 * H, 5 * H, H);
+    bias(g_bsfc, -1, &TrainCtx::dsent_all, D, D, 0, D);
+    prod(g_Wva, 0, D, TY_dP, 0, A, TX_reg, ALONE, -1, true, GradRow::PRE_VA);      // dP^T (A, NV) x regions^T (D, NV) over the non-padding rows
+    // ---- bucket 4 (the tail, 3.5 M floats): W1_hg, att_ha, att_sa, att_ga and the three score vectors
+    b = 4;
+    prod(g_Whg, 0, H, TY_dpre1, 5 * H, H, TX_h1, 0, sQ);
+    prod(g_Wha, 0, H, TY_dhA, 0, A, TX_h1, 0);
+    prod(g_Wsa, 0, H, TY_dsa, 0, A, TX_st, 0);
+    prod(g_Wga, 0, H, TY_dga, 0, A, TX_gt, 0);
+    bias(g_wa, -1, &TrainCtx::dwa_rows, A, A, 0, A);
+    bias(g_ws, -1, &TrainCtx::dws_rows, A, A, 0, A);
+    bias(g_wg, -1, &TrainCtx::dwg_rows, A, A, 0, A);
+    return v;
+}
+
+// out (images, C) = the sum over t - and over an image's K rows, ascending - of X (T, B, C)
+static void sum_over_t(hipStream_t s, const float* X, int T, int K, int B, int C, float* out) {
+    const long long per_t = (long long)B * C, n_out = per_t / K;
+    if (K > 1) hipLaunchKernelGGL(k_sum_over_t_rows, dim3(cdiv(n_out, 256)), dim3(256), 0, s, X, T, K, C, per_t, n_out, out);
+    else hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv(per_t, 256)), dim3(256), 0, s, X, T, per_t, out);
+}
+
+// What the steps of one backward pass share
+struct BwdPass {
+    const float* dlg = nullptr;    // the gradient of the gate log-probs (B, T, 2)
+    int* dyn = nullptr;            // the dynamic slots of the exponent table when the pass runs on the f16x2 kernels, else null
+    int cb = 0;                    // which of the two cell-carry buffers holds the carries of step tt + 1
+    int ns3 = 0;                   // slabs of the later step's GEMM 3 waiting in t.scratch (consumed by k_bwd_head)
+    int slot(int i) const { return dyn ? H2_DYN0 + i : (int)H2A_NONE; }
+    int* ptr(int i) const { return dyn ? dyn + i : nullptr; }
+};
+// Step tt of the reverse-time loop: k_bwd_head, GEMM 1, k_bwd_mid, k_dalpha, k_attend_bwd, GEMM 2, k_bwd_tail, GEMM 3 (data gradients
+// only; the GEMMs' problem lists are step_gemms.h's).  Mirrors train_forward_step.
+static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, hipStream_t s) {
+    Ctx& c = h->c;
+    const vsr_dims& d = h->d;
+    const vsr_weights& w = h->w;
+    const int B = t.B, T = t.T, K = t.rpi, Bi = B / K, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, R1 = c.R + 1, cb = p.cb;
+    const size_t BH = (size_t)B * H;
+    const long long st3 = (long long)B * H;
+    const StepSlices q = train_step_slices(h, t, tt);
+    const int y = tt * DYN_PER_STEP;                   // the step's block of dynamic slots
+    BwdStepOperands o;
+    o.M = B;
+    o.dpre1 = q.dpre1; o.dpre2 = q.dpre2; o.dhA = q.dhA; o.dsent = q.dsent; o.dsa = q.dsa; o.dga = q.dga;
+    o.wT_ih1 = t.wT_ih1; o.wT_is = t.wT_is; o.wT_ig = t.wT_ig; o.wT_hh1 = t.wT_hh1; o.wT_hs = t.wT_hs; o.wT_ih2 = t.wT_ih2; o.wT_hh2 = t.wT_hh2;
+    o.wT_hg = t.wT_hg; o.wT_ha = t.wT_ha; o.wT_sfc = t.wT_sfc; o.wT_sa = t.wT_sa; o.wT_ga = t.wT_ga;
+    o.s_dpre1 = p.slot(y + DY_dpre1); o.s_dpre2 = p.slot(y + DY_dpre2); o.s_dq = p.slot(y + DY_dq); o.s_dhA = p.slot(y + DY_dhA);
+    o.s_dsent = p.slot(y + DY_dsent); o.s_dsa = p.slot(y + DY_dsa); o.s_dga = p.slot(y + DY_dga);
+    {   // gate log-probs -> dga, dhA (first writer), dzsum;  carries of step tt + 1 + vocabulary part -> LSTM2 backward
+        BwdHeadArgs a;
+        a.lg = t.logp_g + (size_t)tt * 2; a.dlg = p.dlg + (size_t)tt * 2; a.lg_stride = (long long)T * 2;
+        a.ga = q.ga; a.hA = q.hA; a.w_g = w.att_g_weight; a.A = A;
+        a.dga = q.dga; a.dhA = q.dhA; a.dzsum = t.dzsum; a.dwg_rows = q.dwg; a.gblocks = B;
+        a.s_h1 = t.scratch; a.s_h2 = d.h2_first_lstm ? t.scratch + st3 * p.ns3 : nullptr; a.nslab3 = p.ns3; a.stride3 = st3;
+        a.dh1_c = t.dh1_c; a.dh2_c = t.dh2_c; a.dh2_voc = q.dh2_voc;
+        a.dc_next = t.dc2_c[cb]; a.gates2 = q.g2; a.c2 = q.c2n; a.c2_prev = tt > 0 ? q.c2o : nullptr;
+        a.M = B; a.H = H; a.dpre2 = q.dpre2; a.dc_prev = t.dc2_c[cb ^ 1];
+        a.bm_dga = p.ptr(y + DY_dga); a.bm_dpre2 = p.ptr(y + DY_dpre2);
+        hipLaunchKernelGGL(k_bwd_head, dim3(a.gblocks + cdiv((long long)BH, 256)), dim3(256), 0, s, a);
+    }
+    {   // grouped GEMM 1: dpre2 -> [dh1_a | datt (| dvbar)] , dh2 carry (hh part);  dga -> dg_t
+        GemmBuilder g;
+        add_bwd1(g, d, o);
+        const int ns1 = g.finish(h);
+        BwdMidArgs a;
+        a.nslab = ns1; a.st0 = (long long)B * (H + D); a.st1 = (long long)B * H; a.st2 = (long long)B * H;
+        float *C0 = t.scratch, *C1 = C0 + a.st0 * ns1, *C2 = C1 + a.st1 * ns1;
+        g.a.p[0].C = C0; g.a.p[0].slab_stride = a.st0;
+        g.a.p[1].C = C1; g.a.p[1].slab_stride = a.st1;
+        g.a.p[2].C = C2; g.a.p[2].slab_stride = a.st2;
+        if (g.launch(s, h)) return fail("bwd gemm 1 launch failed");
+        // datt; dg_t -> shift-gate backward (dq into dpre1[:, 5H:6H], dtc); dh1 so far (= dh1_a + carry, into dh_tot) and the
+        // hh part of the new dh2 carry (the LSTM1-input part is added by the next k_bwd_head from GEMM 3's slabs)
+        a.C0 = C0; a.C1 = C1; a.C2 = C2; a.M = B; a.H = H; a.D = D;
+        a.datt = t.datt; a.dh1_c = t.dh1_c; a.dh_tot = t.dh_tot; a.dh2_c = t.dh2_c;
+        a.gates1 = q.g1; a.c1 = q.c1n; a.dq = q.dpre1 + 5 * H; a.dtc = t.dtc; a.bm_dq = p.ptr(y + DY_dq);
+        const int wmax = D > H ? D : H;
+        hipLaunchKernelGGL(k_bwd_mid, dim3(cdiv((long long)B * wmax, 256), 3), dim3(256), 0, s, a);
+    }
+    {   // attention
+        with_shared_rows(K, [&](auto SH, int k) {
+            hipLaunchKernelGGL(k_dalpha<decltype(SH)::value>, dim3(cdiv((long long)B * R1, 4)), dim3(256), 0, s, t.datt, q.sent, c.regions, c.rmask, c.ridx, q.slot, B, c.L, c.R, D,
+                               t.dalpha, k);
+        });
+        // two workgroups per row in launches of <= 128 rows (as k_attend): half the A columns each, its 512 threads = 256 columns x 2 row groups
+        const int NTb = A >= 512 ? 512 : 256;
+        const int np = attend_bwd_parts(h, B, NTb);
+        const int RG = np > 1 ? NTb / (A / np) : 1;
+        const size_t smem = (size_t)(R1 + 8 + (np > 1 ? (RG - 1) * (A / np) * 2 : 0)) * sizeof(float);
+        // K > 1: rows of an image may name the same slot: each row writes its (R, A) block, the blocks are added onto dP in row order
+        with_shared_rows(K, [&](auto SH, int) {
+            constexpr bool sh = decltype(SH)::value;
+            auto go = [&](auto NT) {
+                constexpr int nt = decltype(NT)::value;
+                hipLaunchKernelGGL((k_attend_bwd<nt, sh>), dim3(cdiv(B * np, 8) * 8), dim3(nt), smem, s, t.datt, t.dalpha, t.dzsum, q.alpha, q.hA, q.sa, q.sent, c.P, c.regions, c.rmask, c.ridx,
+                                   q.slot, 0, B, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, q.dsent, q.dsa, q.dhA, sh ? t.dP_rows : t.dP, q.dwa, q.dws,
+                                   p.ptr(y + DY_dhA), p.ptr(y + DY_dsent), p.ptr(y + DY_dsa), np, K);
+            };
+            if (A >= 512) go(std::integral_constant<int, 512>{}); else go(std::integral_constant<int, 256>{});
+        });
+        if (K > 1) hipLaunchKernelGGL(k_dP_rows_sum, dim3(cdiv((long long)Bi * c.R * (A / 4), 256)), dim3(256), 0, s, t.dP_rows, q.slot, c.rmask, Bi, K, c.L, c.R, A, t.dP);
+    }
+    {   // grouped GEMM 2: [dq | dhA] -> dh1_b ; [dsent | dsa] -> ds_t;  then the sentinel gate and LSTM1 pointwise backward
+        GemmBuilder g;
+        add_bwd2(g, d, o);
+        const int ns = g.finish(h);
+        const long long st = (long long)B * H;
+        float *Ca = t.scratch, *Cb = Ca + st * ns;
+        g.a.p[0].C = Ca; g.a.p[0].slab_stride = st;
+        g.a.p[1].C = Cb; g.a.p[1].slab_stride = st;
+        if (g.launch(s, h)) return fail("bwd gemm 2 launch failed");
+        hipLaunchKernelGGL(k_bwd_tail, dim3(cdiv((long long)BH, 256)), dim3(256), 0, s, Ca, Cb, ns, st, t.dh_tot, t.dtc, t.dc1_c[cb], q.g1, q.c1n,
+                           tt > 0 ? q.c1o : (float*)nullptr, B, H, q.dpre1, t.dc1_c[cb ^ 1], p.ptr(y + DY_dpre1));
+    }
+    // grouped GEMM 3: dpre1 -> dh1 carry, dh2 carry (LSTM1 input part); its slabs stay in t.scratch for the next k_bwd_head
+    p.ns3 = 0;
+    if (tt > 0) {
+        GemmBuilder g;
+        add_bwd3(g, d, o);
+        p.ns3 = g.finish(h);
+        g.a.p[0].C = t.scratch; g.a.p[0].slab_stride = st3;
+        if (d.h2_first_lstm) { g.a.p[1].C = t.scratch + st3 * p.ns3; g.a.p[1].slab_stride = st3; }
+        if (g.launch(s, h)) return fail("bwd gemm 3 launch failed");
+    }
+    LAUNCHCHK();
+    return 0;
+}
 // sel: vsr_train_backward_selected - grad_logp_words is then the (rows, T) gradient of the targets' log-probs
 static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
                                void* stream) {
@@ -799,16 +1050,14 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     if (!grad_logp_words || !grad_logp_gates || !grads) return fail("%s: null tensor", who);
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;
-    const vsr_weights& w = h->w;
     Ctx& c = h->c;
-    const int B = t.B, T = t.T, TB = t.TB, TBp = t.TBp, Bp = t.Bp, RLp = t.RLp;          // (B: decoder rows)
-    const int K = t.rpi, Bi = B / K;                                                      // rows per image of the saved forward; images
+    const int B = t.B, T = t.T, TB = t.TB, TBp = t.TBp;           // (B: decoder rows)
+    const int K = t.rpi;                                          // rows per image of the saved forward
     const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
-    const int in1 = (d.h2_first_lstm ? H : 0) + D + E, voff = d.h2_first_lstm ? H : 0, xoff = voff + D, in2 = H + D + (d.img_second_lstm ? D : 0);
-    const int RL = c.B * c.L * c.R, R1 = c.R + 1;
+    const int RL = c.B * c.L * c.R;
     const size_t BH = (size_t)B * H;
     float* const* G = reinterpret_cast<float* const*>(grads);     // same field order as vsr_weights
-    for (int i = 0; i < 28; ++i)
+    for (int i = 0; i < N_GRADS; ++i)
         if (!G[i]) return fail("%s: gradient pointer %d is null", who, i);
     if (t.sparse) {                        // from here on the saved rows are (about to be) overwritten: in the handle's copy and in the filed one
         t.consumed = true;
@@ -817,26 +1066,34 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     }
 
     // f16x2 flavour: the W operands of the backward GEMMs - transposed weights here, transposed activations in phase B - are written as
-    // fp16-pair images by the transposing kernel itself; the A operands are gradients: their producers fold max |x| into "dynamic" slots
-    // of the exponent table (block tt of 8 slots for step tt, blocks 62 / 63 for the whole-pass operands)
+    // fp16-pair images by the transposing kernel itself; the A operands are gradients: their producers fold max |x| into the dynamic slots
+    // of the exponent table (DY_* / DW_*)
     // (the same conditions GemmBuilder::finish(), gemm_route.h, routes a launch to the f16x2 kernels by: a backward pass that wrote only images for
     // launches that then fall through to the fp32-operand kernels would read unwritten buffers - finish() refuses such a launch too)
-    const bool h2b = h->h2_on && h->x3_on && h->gk.gemm_tile == 0 && !h->bf16_on && t.h2img && T <= H2_NDYN / 8 - 2;
+    const bool h2b = h->h2_on && h->x3_on && h->gk.gemm_tile == 0 && !h->bf16_on && t.h2img && T <= DYN_MAX_T;
     h->h2t_only = h2b;
-    int* dyn = h2b ? h->h2_exps + H2_DYN0 : nullptr;
-    enum { DY_dpre2, DY_dga, DY_dq, DY_dhA, DY_dsent, DY_dsa, DY_dpre1 };               // per-step block
-    enum { DW_dlogits = 62 * 8, DW_dP, DW_dpre1sum, DW_dpre2sum, DW_dpre1all, DW_step = 63 * 8 };      // whole-pass slots (DW_step + DY_x: max over the steps)
-    auto dslot = [&](int i) { return h2b ? H2_DYN0 + i : (int)H2A_NONE; };
-    auto dptr = [&](int i) { return h2b ? dyn + i : (int*)nullptr; };
-    if (h2b) HIPCHK(hipMemsetAsync(dyn, 0, H2_NDYN * sizeof(int), s));
-    // ---- transposed weights (the optimizer may have changed them since the last call): one batched launch (TransBatch)
+    BwdPass p;
+    p.dlg = grad_logp_gates;
+    p.dyn = h2b ? h->h2_exps + H2_DYN0 : nullptr;
+    if (h2b) HIPCHK(hipMemsetAsync(p.dyn, 0, H2_NDYN * sizeof(int), s));
+    const int NV = c.nvalid, NVp = (int)up4((size_t)NV);     // non-padding region rows: the only ones att_va saw
+    // under a caller's row bound (vsr_set_valid_rows_bound) NV is the BOUND and the list's tail [n, NV) repeats its first entry: the two
+    // gathers below read those rows as zeros (k_transpose_t's rlimit = the device-side count), so att_va's gradient sums over n rows
+    const int* nv_dev = c.bounded ? c.nvalid_dev : nullptr;
+    // (the K padding of the transposed operands - TBp, Bp, NVp columns - is zero-filled by the transposing kernel itself)
     TOperand ops[N_TOPS];              // (a sealed tape: with the T / TB / TBp of the steps taken)
     train_operands(h, t, ops);
-    auto transpose_ops = [&](int lo, int hi) {          // entries [lo, hi) of the table in one batched launch (TransBatch), in table order
+    for (int i : {(int)TX_reg, (int)TY_dP}) { ops[i].R = NV; ops[i].ld_out = NVp; }       // the pair gathered through the list of the non-padding rows
+    // entry i -> its buffer.  img: a W operand's registered image, or (self_slot >= 0) the buffer itself holds an image; tb: collected
+    auto tr = [&](int i, bool img, int self_slot, TransBatch* tb, const int* list = nullptr, const int* rlimit = nullptr) {
+        transpose(h, s, ops[i].src, ops[i].ld_in, ops[i].R, ops[i].C, t.*ops[i].buf, ops[i].ld_out, list, img, self_slot, rlimit, tb);
+    };
+    auto transpose_ops = [&](int lo, int hi) {          // W operands [lo, hi) of the table in one batched launch (TransBatch), in table order
         TransBatch tb;
-        for (int i = lo; i < hi; ++i) transpose(h, s, ops[i].src, ops[i].ld_in, ops[i].R, ops[i].C, t.*ops[i].buf, ops[i].ld_out, nullptr, h2b, -1, nullptr, &tb);
+        for (int i = lo; i < hi; ++i) tr(i, h2b, -1, &tb);
         tb.flush(s);
     };
+    // ---- transposed weights (the optimizer may have changed them since the last call)
     const int Vp = (int)up4(V);        // K of the dh2_vocab GEMM must be a multiple of 8: zero-padded columns
     if (Vp != V) {
         HIPCHK(hipMemsetAsync(t.wT_out, 0, (size_t)H * Vp * sizeof(float), s));
@@ -850,265 +1107,103 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
         zl.add(t.dh1_c, BH * sizeof(float)); zl.add(t.dh2_c, BH * sizeof(float)); zl.add(t.dc1_c[0], BH * sizeof(float)); zl.add(t.dc2_c[0], BH * sizeof(float));
         if (zl.launch(s)) return fail("vsr_train_backward: zero launch failed");
     }
-    const int NV = c.nvalid, NVp = (int)up4((size_t)NV);     // non-padding region rows: the only ones att_va saw
-    // under a caller's row bound (vsr_set_valid_rows_bound) NV is the BOUND and the list's tail [n, NV) repeats its first entry: the two
-    // gathers below read those rows as zeros (k_transpose_t's rlimit = the device-side count), so att_va's gradient sums over n rows
-    const int* nv_dev = c.bounded ? c.nvalid_dev : nullptr;
-    // (the K padding of the transposed operands - TBp, Bp, NVp columns - is zero-filled by the transposing kernel itself)
 
     // ---- phase 0: dlogits (t,b) and the vocabulary part of dh2 for every step
-    if (t.sparse) hipLaunchKernelGGL(k_dlogits_sel, dim3(TB), dim3(256), 0, s, grad_logp_words, t.tgt32, B, T, V, Vp, t.dlogits, dptr(DW_dlogits));
-    else hipLaunchKernelGGL(k_dlogits_tb, dim3(TB), dim3(256), 0, s, t.logp_w, grad_logp_words, B, T, V, Vp, t.dlogits, dptr(DW_dlogits));
-    if (gemm_to1(h, t, s, TB, H, Vp, t.dlogits, Vp, t.wT_out, Vp, t.dh2_voc, H, dslot(DW_dlogits))) return 1;
+    if (t.sparse) hipLaunchKernelGGL(k_dlogits_sel, dim3(TB), dim3(256), 0, s, grad_logp_words, t.tgt32, B, T, V, Vp, t.dlogits, p.ptr(DW_dlogits));
+    else hipLaunchKernelGGL(k_dlogits_tb, dim3(TB), dim3(256), 0, s, t.logp_w, grad_logp_words, B, T, V, Vp, t.dlogits, p.ptr(DW_dlogits));
+    if (gemm_to1(h, t, s, TB, H, Vp, t.dlogits, Vp, t.wT_out, Vp, t.dh2_voc, H, p.slot(DW_dlogits))) return 1;
     LAUNCHCHK();
 
-    // ---- phase A: reverse time.  Per step: k_bwd_head, GEMM 1, k_bwd_mid, k_dalpha, k_attend_bwd, GEMM 2, k_bwd_tail, GEMM 3
-    int cb = 0;
-    int ns3 = 0;                              // slabs of the later step's GEMM 3 waiting in t.scratch (consumed by k_bwd_head)
-    const long long st3 = (long long)B * H;
-    for (int tt = T - 1; tt >= 0; --tt, cb ^= 1) {
-        const float *c1 = t.c1s + (size_t)(tt + 1) * BH, *c1p = t.c1s + (size_t)tt * BH;
-        const float *c2 = t.c2s + (size_t)(tt + 1) * BH, *c2p = t.c2s + (size_t)tt * BH;
-        const float* g1 = t.gates1 + (size_t)tt * B * 6 * H;
-        const float* g2 = t.gates2 + (size_t)tt * B * 4 * H;
-        const float *hA = t.hAs + (size_t)tt * B * A, *sa = t.sas + (size_t)tt * B * A, *ga = t.gas + (size_t)tt * B * A;
-        const float *sent = t.sents + (size_t)tt * B * D, *alpha = t.alphas + (size_t)tt * B * R1;
-        const int* slot = t.slot32 + (size_t)tt * B;
-        float* dpre1 = t.dpre1 + (size_t)tt * B * 6 * H;
-        float* dpre2 = t.dpre2 + (size_t)tt * B * 4 * H;
-        float *dhA = t.dhA_all + (size_t)tt * B * A, *dsent = t.dsent_all + (size_t)tt * B * D, *dsa = t.dsa_all + (size_t)tt * B * A;
-        float* dga = t.dga_all + (size_t)tt * B * A;
-        float *dwa = t.dwa_rows + (size_t)tt * B * A, *dws = t.dws_rows + (size_t)tt * B * A, *dwg = t.dwg_rows + (size_t)tt * B * A;
+    // ---- phase A: reverse time (the cell-carry buffers alternate)
+    for (int tt = T - 1; tt >= 0; --tt, p.cb ^= 1)
+        if (train_backward_step(h, t, tt, p, s)) return 1;
 
-        {   // gate log-probs -> dga, dhA (first writer), dzsum;  carries of step tt + 1 + vocabulary part -> LSTM2 backward
-            BwdHeadArgs q;
-            q.lg = t.logp_g + (size_t)tt * 2; q.dlg = grad_logp_gates + (size_t)tt * 2; q.lg_stride = (long long)T * 2;
-            q.ga = ga; q.hA = hA; q.w_g = w.att_g_weight; q.A = A;
-            q.dga = dga; q.dhA = dhA; q.dzsum = t.dzsum; q.dwg_rows = dwg; q.gblocks = B;
-            q.s_h1 = t.scratch; q.s_h2 = d.h2_first_lstm ? t.scratch + st3 * ns3 : nullptr; q.nslab3 = ns3; q.stride3 = st3;
-            q.dh1_c = t.dh1_c; q.dh2_c = t.dh2_c; q.dh2_voc = t.dh2_voc + (size_t)tt * BH;
-            q.dc_next = t.dc2_c[cb]; q.gates2 = g2; q.c2 = c2; q.c2_prev = tt > 0 ? c2p : nullptr;
-            q.M = B; q.H = H; q.dpre2 = dpre2; q.dc_prev = t.dc2_c[cb ^ 1];
-            q.bm_dga = dptr(tt * 8 + DY_dga); q.bm_dpre2 = dptr(tt * 8 + DY_dpre2);
-            hipLaunchKernelGGL(k_bwd_head, dim3(q.gblocks + cdiv((long long)BH, 256)), dim3(256), 0, s, q);
-        }
-        {   // grouped GEMM 1: dpre2 -> [dh1_a | datt (| dvbar)] , dh2 carry (hh part);  dga -> dg_t
-            GemmBuilder g;
-            GemmProb& p0 = g.prob(B, H + D, nullptr, H + D);
-            GemmBuilder::seg(p0, dpre2, 4 * H, nullptr, t.wT_ih2, 4 * H, 4 * H, nullptr, dslot(tt * 8 + DY_dpre2));
-            GemmProb& p1 = g.prob(B, H, nullptr, H);
-            GemmBuilder::seg(p1, dpre2, 4 * H, nullptr, t.wT_hh2, 4 * H, 4 * H, nullptr, dslot(tt * 8 + DY_dpre2));
-            GemmProb& p2 = g.prob(B, H, nullptr, H);
-            GemmBuilder::seg(p2, dga, A, nullptr, t.wT_ga, A, A, nullptr, dslot(tt * 8 + DY_dga));
-            const int ns1 = g.finish(h);
-            BwdMidArgs q;
-            q.nslab = ns1; q.st0 = (long long)B * (H + D); q.st1 = (long long)B * H; q.st2 = (long long)B * H;
-            float *C0 = t.scratch, *C1 = C0 + q.st0 * ns1, *C2 = C1 + q.st1 * ns1;
-            g.a.p[0].C = C0; g.a.p[0].slab_stride = q.st0;
-            g.a.p[1].C = C1; g.a.p[1].slab_stride = q.st1;
-            g.a.p[2].C = C2; g.a.p[2].slab_stride = q.st2;
-            if (g.launch(s, h)) return fail("bwd gemm 1 launch failed");
-            // datt; dg_t -> shift-gate backward (dq into dpre1[:, 5H:6H], dtc); dh1 so far (= dh1_a + carry, into dh_tot) and the
-            // hh part of the new dh2 carry (the LSTM1-input part is added by the next k_bwd_head from GEMM 3's slabs)
-            q.C0 = C0; q.C1 = C1; q.C2 = C2; q.M = B; q.H = H; q.D = D;
-            q.datt = t.datt; q.dh1_c = t.dh1_c; q.dh_tot = t.dh_tot; q.dh2_c = t.dh2_c;
-            q.gates1 = g1; q.c1 = c1; q.dq = dpre1 + 5 * H; q.dtc = t.dtc; q.bm_dq = dptr(tt * 8 + DY_dq);
-            const int wmax = D > H ? D : H;
-            hipLaunchKernelGGL(k_bwd_mid, dim3(cdiv((long long)B * wmax, 256), 3), dim3(256), 0, s, q);
-        }
-        // attention
-        {
-            if (K > 1) hipLaunchKernelGGL(k_dalpha<true>, dim3(cdiv((long long)B * R1, 4)), dim3(256), 0, s, t.datt, sent, c.regions, c.rmask, c.ridx, slot, B, c.L, c.R, D,
-                               t.dalpha, K);
-            else hipLaunchKernelGGL(k_dalpha<false>, dim3(cdiv((long long)B * R1, 4)), dim3(256), 0, s, t.datt, sent, c.regions, c.rmask, c.ridx, slot, B, c.L, c.R, D,
-                               t.dalpha, 1);
-            // two workgroups per row in launches of <= 128 rows (as k_attend): half the A columns each, its 512 threads = 256 columns x 2 row groups
-            const int NTb = A >= 512 ? 512 : 256;
-            const int np = attend_bwd_parts(h, B, NTb);
-            const int RG = np > 1 ? NTb / (A / np) : 1;
-            const size_t smem = (size_t)(R1 + 8 + (np > 1 ? (RG - 1) * (A / np) * 2 : 0)) * sizeof(float);
-            // K > 1: rows of an image may name the same slot: each row writes its (R, A) block, the blocks are added onto dP in row order
-            auto go = [&](auto NT, auto SH) {
-                constexpr int nt = decltype(NT)::value;
-                constexpr bool sh = decltype(SH)::value;
-                hipLaunchKernelGGL((k_attend_bwd<nt, sh>), dim3(cdiv(B * np, 8) * 8), dim3(nt), smem, s, t.datt, t.dalpha, t.dzsum, alpha, hA, sa, sent, c.P, c.regions, c.rmask, c.ridx,
-                                   slot, 0, B, c.L, c.R, A, D, w.att_a_weight, w.att_s_weight, dsent, dsa, dhA, sh ? t.dP_rows : t.dP, dwa, dws,
-                                   dptr(tt * 8 + DY_dhA), dptr(tt * 8 + DY_dsent), dptr(tt * 8 + DY_dsa), np, K);
-            };
-            if (K > 1) {
-                if (A >= 512) go(std::integral_constant<int, 512>{}, std::true_type{}); else go(std::integral_constant<int, 256>{}, std::true_type{});
-                hipLaunchKernelGGL(k_dP_rows_sum, dim3(cdiv((long long)Bi * c.R * (A / 4), 256)), dim3(256), 0, s, t.dP_rows, slot, c.rmask, Bi, K, c.L, c.R, A, t.dP);
-            } else {
-                if (A >= 512) go(std::integral_constant<int, 512>{}, std::false_type{}); else go(std::integral_constant<int, 256>{}, std::false_type{});
-            }
-        }
-        // grouped GEMM 2: [dq | dhA] -> dh1_b ; [dsent | dsa] -> ds_t;  then the sentinel gate and LSTM1 pointwise backward
-        {
-            GemmBuilder g;
-            GemmProb& p0 = g.prob(B, H, nullptr, H);
-            GemmBuilder::seg(p0, dpre1 + 5 * H, 6 * H, nullptr, t.wT_hg, H, H, nullptr, dslot(tt * 8 + DY_dq));
-            GemmBuilder::seg(p0, dhA, A, nullptr, t.wT_ha, A, A, nullptr, dslot(tt * 8 + DY_dhA));
-            GemmProb& p1 = g.prob(B, H, nullptr, H);
-            GemmBuilder::seg(p1, dsent, D, nullptr, t.wT_sfc, D, D, nullptr, dslot(tt * 8 + DY_dsent));
-            GemmBuilder::seg(p1, dsa, A, nullptr, t.wT_sa, A, A, nullptr, dslot(tt * 8 + DY_dsa));
-            const int ns = g.finish(h);
-            const long long st = (long long)B * H;
-            float *Ca = t.scratch, *Cb = Ca + st * ns;
-            g.a.p[0].C = Ca; g.a.p[0].slab_stride = st;
-            g.a.p[1].C = Cb; g.a.p[1].slab_stride = st;
-            if (g.launch(s, h)) return fail("bwd gemm 2 launch failed");
-            hipLaunchKernelGGL(k_bwd_tail, dim3(cdiv((long long)BH, 256)), dim3(256), 0, s, Ca, Cb, ns, st, t.dh_tot, t.dtc, t.dc1_c[cb], g1, c1,
-                               tt > 0 ? c1p : (const float*)nullptr, B, H, dpre1, t.dc1_c[cb ^ 1], dptr(tt * 8 + DY_dpre1));
-        }
-        // grouped GEMM 3: dpre1 -> dh1 carry, dh2 carry (LSTM1 input part); its slabs stay in t.scratch for the next k_bwd_head
-        ns3 = 0;
-        if (tt > 0) {
-            GemmBuilder g;
-            GemmProb& p1 = g.prob(B, H, nullptr, H);
-            const int s1 = dslot(tt * 8 + DY_dpre1), sq = dslot(tt * 8 + DY_dq);
-            GemmBuilder::seg(p1, dpre1, 6 * H, nullptr, t.wT_hh1, 4 * H, 4 * H, nullptr, s1);
-            GemmBuilder::seg(p1, dpre1 + 4 * H, 6 * H, nullptr, t.wT_hs, H, H, nullptr, s1);
-            if (d.h2_first_lstm) {
-                GemmProb& p0 = g.prob(B, H, nullptr, H);
-                GemmBuilder::seg(p0, dpre1, 6 * H, nullptr, t.wT_ih1, 4 * H, 4 * H, nullptr, s1);          // rows 0..H-1 of W_ih1^T = h2 columns
-                GemmBuilder::seg(p0, dpre1 + 4 * H, 6 * H, nullptr, t.wT_is, H, H, nullptr, s1);
-                GemmBuilder::seg(p0, dpre1 + 5 * H, 6 * H, nullptr, t.wT_ig, H, H, nullptr, sq);
-            }
-            ns3 = g.finish(h);
-            g.a.p[0].C = t.scratch; g.a.p[0].slab_stride = st3;
-            if (d.h2_first_lstm) { g.a.p[1].C = t.scratch + st3 * ns3; g.a.p[1].slab_stride = st3; }
-            if (g.launch(s, h)) return fail("bwd gemm 3 launch failed");
-        }
-        LAUNCHCHK();
-    }
-
-    // ---- phase B: weight gradients, reduction over all T*B rows
-    TransBatch tby;
-    transpose_ops(N_TW, N_TOPS - 1);          // the activations, rows (t, b); tX_reg through the list of the non-padding rows:
-    const TOperand& reg = ops[N_TOPS - 1];
-    if (NV > 0) transpose(h, s, reg.src, reg.ld_in, NV, reg.C, t.*reg.buf, (long long)NVp, c.vlist, h2b, -1, nv_dev);
-    if (h2b) hipLaunchKernelGGL(k_h2_dyn_fold, dim3(1), dim3(64), 0, s, dyn, T, T * K);
-    const int sP1 = dslot(DW_step + DY_dpre1), sQ = dslot(DW_step + DY_dq), sP2 = dslot(DW_step + DY_dpre2);
+    // ---- phase B: weight gradients, reduction over all T*B rows.  First the operands (train_operands) ...
+    transpose_ops(N_TW, TX_reg);              // the activations, rows (t, b); TX_reg through the list of the non-padding rows:
+    if (NV > 0) tr(TX_reg, h2b, -1, nullptr, c.vlist, nv_dev);
+    if (h2b) hipLaunchKernelGGL(k_h2_dyn_fold, dim3(1), dim3(64), 0, s, p.dyn, T, T * K);
     // the transposed gradients are the A operands of the weight-gradient GEMMs: with the whole-pass bounds known (k_h2_dyn_fold) they are
-    // written as fp16-pair images IN PLACE of the fp32 values and those GEMMs take the all-DMA kernel (tyi: the buffer holds an image)
+    // written as fp16-pair images IN PLACE of the fp32 values and those GEMMs take the all-DMA kernel (a_img: the buffer holds an image)
+    bool a_img[N_TOPS] = {};
     const bool tyi = h2b && h->gk.h2_aimg && TBp % 8 == 0 && (reinterpret_cast<uintptr_t>(t.tY_dpre1) & 255) == 0;     // (every buffer of the workspace shares that alignment)
-    const int sY1 = dslot(DW_dpre1all);
-    transpose(h, s, t.dpre1, 6 * H, TB, 6 * H, t.tY_dpre1, TBp, nullptr, tyi, sY1, nullptr, &tby);
-    transpose(h, s, t.dpre2, 4 * H, TB, 4 * H, t.tY_dpre2, TBp, nullptr, tyi, sP2, nullptr, &tby);
-    transpose(h, s, t.dlogits, Vp, TB, V, t.tY_dlogits, TBp, nullptr, tyi, dslot(DW_dlogits), nullptr, &tby);
-    transpose(h, s, t.dhA_all, A, TB, A, t.tY_dhA, TBp, nullptr, tyi, dslot(DW_step + DY_dhA), nullptr, &tby);
-    transpose(h, s, t.dsent_all, D, TB, D, t.tY_dsent, TBp, nullptr, tyi, dslot(DW_step + DY_dsent), nullptr, &tby);
-    transpose(h, s, t.dsa_all, A, TB, A, t.tY_dsa, TBp, nullptr, tyi, dslot(DW_step + DY_dsa), nullptr, &tby);
-    transpose(h, s, t.dga_all, A, TB, A, t.tY_dga, TBp, nullptr, tyi, dslot(DW_step + DY_dga), nullptr, &tby);
-    tby.flush(s);
-    const float* dP_rows = t.dP;
-    if (c.ridx) {
-        // index lists: several slot entries of an image name the same bank row; att_va's gradient runs over bank rows, so the
-        // entry gradients are first summed per bank row, in ascending entry order (deterministic, like the embedding gradient)
-        hipLaunchKernelGGL(k_dP_to_bank, dim3(c.n_img * c.Rb), dim3(128), 0, s, t.dP, c.ridx, c.L * c.R, c.Rb, A, t.dP_bank);
-        dP_rows = t.dP_bank;
+    {
+        TransBatch tby;
+        for (int i = TY_dpre1; i < TY_dpre1sum; ++i) { a_img[i] = tyi; tr(i, tyi, p.slot(ops[i].slot), &tby); }
+        tby.flush(s);
     }
+    const TOperand& dP = ops[TY_dP];
+    // index lists: several slot entries of an image name the same bank row; att_va's gradient runs over bank rows, so the
+    // entry gradients are first summed per bank row, in ascending entry order (deterministic, like the embedding gradient)
+    if (c.ridx) hipLaunchKernelGGL(k_dP_to_bank, dim3(c.n_img * c.Rb), dim3(128), 0, s, t.dP, c.ridx, c.L * c.R, c.Rb, A, t.dP_bank);
     if (h2b && NV > 0) {
         const long long ndp = (long long)(c.ridx ? (size_t)c.n_img * c.Rb : (size_t)RL) * A;
-        hipLaunchKernelGGL(k_absmax, dim3((unsigned)std::min<long long>(1024, cdiv(ndp, 1024))), dim3(256), 0, s, dP_rows, ndp, reinterpret_cast<unsigned*>(dyn + DW_dP));
+        hipLaunchKernelGGL(k_absmax, dim3((unsigned)std::min<long long>(1024, cdiv(ndp, 1024))), dim3(256), 0, s, dP.src, ndp, reinterpret_cast<unsigned*>(p.dyn + DW_dP));
     }
-    const bool tyiP = tyi && NVp % 8 == 0;
-    if (NV > 0) transpose(h, s, dP_rows, (long long)A, NV, A, t.tY_dP, (long long)NVp, c.vlist, tyiP, dslot(DW_dP), nv_dev);
+    a_img[TY_dP] = tyi && NVp % 8 == 0;
+    if (NV > 0) tr(TY_dP, a_img[TY_dP], p.slot(dP.slot), nullptr, c.vlist, nv_dev);
     // the gradient of the hoisted v-bar projection: per IMAGE, the sum over its rows (ascending) and steps
-    if (K > 1) hipLaunchKernelGGL(k_sum_over_t_rows, dim3(cdiv((long long)Bi * 6 * H, 256)), dim3(256), 0, s, t.dpre1, T, K, 6 * H, (long long)B * 6 * H, (long long)Bi * 6 * H, t.dpre1sum);
-    else hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv((long long)B * 6 * H, 256)), dim3(256), 0, s, t.dpre1, T, (long long)B * 6 * H, t.dpre1sum);
-    transpose(h, s, t.dpre1sum, 6 * H, Bi, 6 * H, t.tY_dpre1sum, Bp);
+    sum_over_t(s, t.dpre1, T, K, B, 6 * H, t.dpre1sum);
+    tr(TY_dpre1sum, false, -1, nullptr);
     LAUNCHCHK();
 
-    // Gradients are finished bucket by bucket, largest first, and an event is recorded after each bucket
-    // (vsr_train_bucket_map / vsr_train_wait_bucket): a data-parallel caller starts the all-reduce of a finished bucket on
-    // a side stream while the remaining weight-gradient GEMMs run.  The last bucket is the smallest (14 MB).
+    // ... then the table of the gradients, row by row.  Gradients are finished bucket by bucket, largest first, and a bucket's event is
+    // recorded where the walk leaves it (vsr_train_bucket_map / vsr_train_wait_bucket): a data-parallel caller starts the all-reduce of a
+    // finished bucket on a side stream while the remaining weight-gradient GEMMs run.  The last bucket is the smallest (14 MB).
     if (!h->bucket_ev[0])
         for (int i = 0; i < VSR_GRAD_BUCKETS; ++i) HIPCHK(hipEventCreateWithFlags(&h->bucket_ev[i], hipEventDisableTiming));
-    // ---- bucket 0: lstm_cell_1.weight_ih / W1_is / W1_ig: row blocks [0,4H), [4H,5H), [5H,6H) of dpre1^T against [h2_prev | vbar | x]
-    {
-        float* Gw[3] = {G[g_Wih1], G[g_Wis], G[g_Wig]};
-        const int r0[3] = {0, 4 * H, 5 * H}, nr[3] = {4 * H, H, H};
-        auto dy = [&](int i) { return t.tY_dpre1 + (size_t)r0[i] * TBp; };
-        auto sa = [&](int i) { return tyi ? sY1 : (i == 2 ? sQ : sP1); };
-        auto h2part = [&](int i) { return GProb{nr[i], H, TBp, dy(i), TBp, t.tX_h2prev, TBp, Gw[i], in1, sa(i), tyi}; };
-        auto xpart = [&](int i) { return GProb{nr[i], E, TBp, dy(i), TBp, t.tX_x, TBp, Gw[i] + xoff, in1, sa(i), tyi}; };
-        auto vpart = [&](int i) { return GProb{nr[i], D, Bp, t.tY_dpre1sum + (size_t)r0[i] * Bp, Bp, t.tX_vbar, Bp, Gw[i] + voff, in1, dslot(DW_dpre1sum), false}; };
-        // (grouped launches, round 6: the two 4H-row products are 256 whole tiles together; the four H-row ones share a launch; the three
-        // short-K image-constant parts share one)
-        if (d.h2_first_lstm) {
-            const GProb a[2] = {h2part(0), xpart(0)};
-            if (gemm_group(h, t, s, a, 2)) return 1;
-            const GProb b[4] = {h2part(1), xpart(1), h2part(2), xpart(2)};
-            if (gemm_group(h, t, s, b, 4)) return 1;
-        } else {
-            const GProb a[3] = {xpart(0), xpart(1), xpart(2)};
-            if (gemm_group(h, t, s, a, 3)) return 1;
+    const std::vector<GradRow> rows = train_grad_table(d);
+    auto product = [&](const GradRow& r) {              // (the operands by entry: K = their padded rows)
+        const TOperand &Y = ops[r.ty], &X = ops[r.tx];
+        const int Kp = (int)Y.ld_out;
+        return GProb{r.M, X.C, Kp, t.*Y.buf + (size_t)r.r0 * Kp, Kp, t.*X.buf, (int)X.ld_out, G[r.g] + r.col, r.ldd,
+                     p.slot(a_img[r.ty] || r.slot < 0 ? Y.slot : r.slot), a_img[r.ty]};
+    };
+    int bucket = 0;
+    for (size_t i = 0; i < rows.size();) {
+        const GradRow& r = rows[i];
+        if (r.bucket != bucket) {
+            if (r.bucket != bucket + 1 || r.bucket >= VSR_GRAD_BUCKETS) return fail("%s: the gradient table's buckets are not 0 .. %d in order", who, VSR_GRAD_BUCKETS - 1);
+            HIPCHK(hipEventRecord(h->bucket_ev[bucket++], s));
         }
-        const GProb c3[3] = {vpart(0), vpart(1), vpart(2)};
-        if (gemm_group(h, t, s, c3, 3)) return 1;
+        if (!r.on) { ++i; continue; }
+        if (r.kind == GradRow::PROD && r.pre == GradRow::PRE_VA && NV == 0) {       // att_va saw no row
+            HIPCHK(hipMemsetAsync(G[r.g], 0, (size_t)r.M * ops[r.tx].C * sizeof(float), s));
+            ++i;
+        } else if (r.kind == GradRow::PROD && r.launch == GradRow::ALONE) {
+            if (r.pre == GradRow::PRE_DPRE2SUM) {       // the v-bar columns of lstm_cell_2.weight_ih: as dpre1sum above
+                sum_over_t(s, t.dpre2, T, K, B, 4 * H, t.dpre2sum);
+                tr(TY_dpre2sum, false, -1, nullptr);
+            }
+            const GProb P = product(r);
+            if (gemm_to1(h, t, s, P.M, P.N, P.K, P.A, P.lda, P.W, P.ldw, P.dst, P.ldd, P.a_cls, P.a_img)) return 1;
+            ++i;
+        } else if (r.kind == GradRow::PROD) {           // the run of products that share this launch
+            GProb P[4];
+            int n = 0;
+            for (; i < rows.size() && rows[i].kind == GradRow::PROD && rows[i].launch == r.launch && rows[i].bucket == r.bucket; ++i) {
+                if (!rows[i].on) continue;
+                if (n == 4) return fail("%s: more than four products in one launch of the gradient table", who);
+                P[n++] = product(rows[i]);
+            }
+            if (gemm_group(h, t, s, P, n)) return 1;
+        } else if (r.kind == GradRow::COLSUM) {         // (through the idle slab scratch, like colsum())
+            const bool shared = i > 0 && rows[i - 1].kind == GradRow::COLSUM && rows[i - 1].src == r.src && rows[i - 1].bucket == r.bucket;
+            if (!shared) hipLaunchKernelGGL(k_colsum, dim3(cdiv(r.C, 64), COLSUM_CHUNKS), dim3(256), 0, s, t.*r.src, (long long)r.ld, TB, r.C, t.scratch);
+            hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(r.n, 256)), dim3(256), 0, s, t.scratch, r.C, r.c0, r.n, G[r.g], r.g2 >= 0 ? G[r.g2] : (float*)nullptr);
+            ++i;
+        } else {   // EMBED: dx = dpre1 . [W_ih1 ; W_is ; W_ig][:, x columns], summed onto the rows that were looked up (ordered, no atomics)
+            const int xoff = (d.h2_first_lstm ? H : 0) + D, sP1 = p.slot(DW_step + DY_dpre1), sQ = p.slot(DW_step + DY_dq);
+            SegSpec sg[3] = {{t.dpre1, 6 * H, t.wT_ih1 + (size_t)xoff * 4 * H, 4 * H, 4 * H, sP1},
+                             {t.dpre1 + 4 * H, 6 * H, t.wT_is + (size_t)xoff * H, H, H, sP1},
+                             {t.dpre1 + 5 * H, 6 * H, t.wT_ig + (size_t)xoff * H, H, H, sQ}};
+            if (gemm_to(h, t, s, TB, E, sg, 3, t.dx_all, E)) return 1;
+            HIPCHK(hipMemsetAsync(G[r.g], 0, (size_t)V * E * sizeof(float), s));
+            hipLaunchKernelGGL(k_embed_grad_rows, dim3(TB), dim3(256), 0, s, t.dx_all, t.word32, TB, E, G[r.g]);
+            ++i;
+        }
     }
-    HIPCHK(hipEventRecord(h->bucket_ev[0], s));
-    // ---- bucket 1: lstm_cell_2
-    {   // (the attended-vector part is 256 whole tiles on its own; the h1 part and lstm_cell_2.weight_hh are 256 together)
-        const GProb a[2] = {GProb{4 * H, H, TBp, t.tY_dpre2, TBp, t.tX_h1, TBp, G[g_Wih2], in2, sP2, tyi},
-                            GProb{4 * H, H, TBp, t.tY_dpre2, TBp, t.tX_h2prev, TBp, G[g_Whh2], H, sP2, tyi}};
-        if (gemm_group(h, t, s, a, 2)) return 1;
-    }
-    if (gemm_to1(h, t, s, 4 * H, D, TBp, t.tY_dpre2, TBp, t.tX_att, TBp, G[g_Wih2] + H, in2, sP2, tyi)) return 1;
-    if (d.img_second_lstm) {
-        if (K > 1) hipLaunchKernelGGL(k_sum_over_t_rows, dim3(cdiv((long long)Bi * 4 * H, 256)), dim3(256), 0, s, t.dpre2, T, K, 4 * H, (long long)B * 4 * H, (long long)Bi * 4 * H, t.dpre2sum);
-        else hipLaunchKernelGGL(k_sum_over_t, dim3(cdiv((long long)B * 4 * H, 256)), dim3(256), 0, s, t.dpre2, T, (long long)B * 4 * H, t.dpre2sum);
-        transpose(h, s, t.dpre2sum, 4 * H, Bi, 4 * H, t.tY_dpre2sum, Bp);
-        if (gemm_to1(h, t, s, 4 * H, D, Bp, t.tY_dpre2sum, Bp, t.tX_vbar, Bp, G[g_Wih2] + H + D, in2, dslot(DW_dpre2sum))) return 1;
-    }
-    colsum(s, t.scratch, t.dpre2, (long long)4 * H, TB, 4 * H, G[g_bih2], G[g_bhh2]);
-    HIPCHK(hipEventRecord(h->bucket_ev[1], s));
-    // ---- bucket 2: out_fc and the embedding
-    if (gemm_to1(h, t, s, V, H, TBp, t.tY_dlogits, TBp, t.tX_h2, TBp, G[g_Wout], H, dslot(DW_dlogits), tyi)) return 1;
-    colsum(s, t.scratch, t.dlogits, (long long)Vp, TB, V, G[g_bout]);
-    {   // embedding: dx = dpre1 . [W_ih1 ; W_is ; W_ig][:, x columns], summed onto the rows that were looked up (ordered, no atomics)
-        SegSpec sg[3] = {{t.dpre1, 6 * H, t.wT_ih1 + (size_t)xoff * 4 * H, 4 * H, 4 * H, sP1},
-                         {t.dpre1 + 4 * H, 6 * H, t.wT_is + (size_t)xoff * H, H, H, sP1},
-                         {t.dpre1 + 5 * H, 6 * H, t.wT_ig + (size_t)xoff * H, H, H, sQ}};
-        if (gemm_to(h, t, s, TB, E, sg, 3, t.dx_all, E)) return 1;
-        HIPCHK(hipMemsetAsync(G[g_embed], 0, (size_t)V * E * sizeof(float), s));
-        hipLaunchKernelGGL(k_embed_grad_rows, dim3(TB), dim3(256), 0, s, t.dx_all, t.word32, TB, E, G[g_embed]);
-    }
-    HIPCHK(hipEventRecord(h->bucket_ev[2], s));
-    // ---- bucket 3: the recurrent LSTM1 / sentinel-gate weights, all LSTM1 / gate biases, s_fc, att_va
-    {   // lstm_cell_1.weight_hh, W1_hs and s_fc: 224 whole tiles in one launch
-        const GProb a[3] = {GProb{4 * H, H, TBp, t.tY_dpre1, TBp, t.tX_h1prev, TBp, G[g_Whh1], H, tyi ? sY1 : sP1, tyi},
-                            GProb{H, H, TBp, t.tY_dpre1 + (size_t)4 * H * TBp, TBp, t.tX_h1prev, TBp, G[g_Whs], H, tyi ? sY1 : sP1, tyi},
-                            GProb{D, H, TBp, t.tY_dsent, TBp, t.tX_st, TBp, G[g_Wsfc], H, dslot(DW_step + DY_dsent), tyi}};
-        if (gemm_group(h, t, s, a, 3)) return 1;
-    }
-    // the six LSTM1 / gate bias gradients are column sums of ONE matrix (dpre1, 6H columns): one partial-sum launch, three finishing launches
-    // that write both members of a pair (same per-column arithmetic as three separate sums: bit-identical)
-    hipLaunchKernelGGL(k_colsum, dim3(cdiv(6 * H, 64), COLSUM_CHUNKS), dim3(256), 0, s, t.dpre1, (long long)6 * H, TB, 6 * H, t.scratch);
-    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(4 * H, 256)), dim3(256), 0, s, t.scratch, 6 * H, 0, 4 * H, G[g_bih1], G[g_bhh1]);
-    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(H, 256)), dim3(256), 0, s, t.scratch, 6 * H, 4 * H, H, G[g_bis], G[g_bhs]);
-    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(H, 256)), dim3(256), 0, s, t.scratch, 6 * H, 5 * H, H, G[g_big], G[g_bhg]);
-    colsum(s, t.scratch, t.dsent_all, (long long)D, TB, D, G[g_bsfc]);
-    // att_va: dP^T (A, NV) x regions^T (D, NV) over the non-padding rows
-    if (NV > 0) {
-        if (gemm_to1(h, t, s, A, D, NVp, t.tY_dP, NVp, t.tX_reg, NVp, G[g_Wva], D, dslot(DW_dP), tyiP)) return 1;
-    } else {
-        HIPCHK(hipMemsetAsync(G[g_Wva], 0, (size_t)A * D * sizeof(float), s));
-    }
-    HIPCHK(hipEventRecord(h->bucket_ev[3], s));
-    // ---- bucket 4 (the tail, 3.5 M floats): W1_hg, att_ha, att_sa, att_ga and the three score vectors
-    {
-        const GProb a[4] = {GProb{H, H, TBp, t.tY_dpre1 + (size_t)5 * H * TBp, TBp, t.tX_h1, TBp, G[g_Whg], H, tyi ? sY1 : sQ, tyi},
-                            GProb{A, H, TBp, t.tY_dhA, TBp, t.tX_h1, TBp, G[g_Wha], H, dslot(DW_step + DY_dhA), tyi},
-                            GProb{A, H, TBp, t.tY_dsa, TBp, t.tX_st, TBp, G[g_Wsa], H, dslot(DW_step + DY_dsa), tyi},
-                            GProb{A, H, TBp, t.tY_dga, TBp, t.tX_gt, TBp, G[g_Wga], H, dslot(DW_step + DY_dga), tyi}};
-        if (gemm_group(h, t, s, a, 4)) return 1;
-    }
-    colsum(s, t.scratch, t.dwa_rows, (long long)A, TB, A, G[g_wa]);
-    colsum(s, t.scratch, t.dws_rows, (long long)A, TB, A, G[g_ws]);
-    colsum(s, t.scratch, t.dwg_rows, (long long)A, TB, A, G[g_wg]);
-    HIPCHK(hipEventRecord(h->bucket_ev[4], s));
+    if (bucket != VSR_GRAD_BUCKETS - 1) return fail("%s: the gradient table ends in bucket %d of %d", who, bucket, VSR_GRAD_BUCKETS);
+    HIPCHK(hipEventRecord(h->bucket_ev[bucket], s));
     h->buckets_recorded = true;
     LAUNCHCHK();
     return 0;
@@ -1126,16 +1221,14 @@ extern "C" int vsr_train_backward_selected(vsr_handle* h, const float* grad_logp
 // [0, VSR_GRAD_BUCKETS); bucket b is complete when its event has fired.  Static (does not depend on the shapes).
 extern "C" int vsr_train_bucket_map(int32_t* bucket_of, int32_t* n_buckets) {
     if (!bucket_of || !n_buckets) return fail("vsr_train_bucket_map: null argument");
-    const int b0[] = {g_Wih1, g_Wis, g_Wig}, b1[] = {g_Wih2, g_Whh2, g_bih2, g_bhh2}, b2[] = {g_Wout, g_bout, g_embed},
-              b3[] = {g_Whh1, g_Whs, g_bih1, g_bhh1, g_bis, g_bhs, g_big, g_bhg, g_Wsfc, g_bsfc, g_Wva},
-              b4[] = {g_Whg, g_Wha, g_Wsa, g_Wga, g_wa, g_ws, g_wg};
-    for (int i = 0; i < 28; ++i) bucket_of[i] = -1;
-    for (int i : b0) bucket_of[i] = 0;
-    for (int i : b1) bucket_of[i] = 1;
-    for (int i : b2) bucket_of[i] = 2;
-    for (int i : b3) bucket_of[i] = 3;
-    for (int i : b4) bucket_of[i] = 4;
-    for (int i = 0; i < 28; ++i)
+    for (int i = 0; i < N_GRADS; ++i) bucket_of[i] = -1;
+    for (const GradRow& r : train_grad_table(vsr_dims{}))        // (the rows of every configuration: sizes and flags do not move a bucket)
+        for (int g : {r.g, r.g2}) {
+            if (g < 0) continue;
+            if (bucket_of[g] >= 0 && bucket_of[g] != r.bucket) return fail("vsr_train_bucket_map: gradient %d has rows in buckets %d and %d", g, bucket_of[g], r.bucket);
+            bucket_of[g] = r.bucket;
+        }
+    for (int i = 0; i < N_GRADS; ++i)
         if (bucket_of[i] < 0) return fail("vsr_train_bucket_map: gradient %d has no bucket", i);
     *n_buckets = VSR_GRAD_BUCKETS;
     return 0;
