@@ -27,6 +27,11 @@ RANK_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "rank_logic_host")
 TB_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "train_batch_host.cpp")
 TB_TOOL_DEPS = [TB_TOOL_SRC, os.path.join(HERE, "csrc", "train_batch_logic.h"), os.path.join(HERE, "csrc", "rank_logic.h")]
 TB_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "train_batch_host")
+# the planning half of the dense-product path (csrc/products.h) on the CPU: host arithmetic, but the routing header pulls in the kernel
+# headers, so hipcc; driven by tests/test_products_logic.py
+PROD_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "products_host.hip")
+PROD_TOOL_DEPS = [PROD_TOOL_SRC, os.path.join(HERE, "csrc", "products.h"), os.path.join(HERE, "csrc", "kernels.h")] + GEMM_HEADERS
+PROD_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "products_host")
 
 
 STAMP = OUT + ".flags"      # the extra hipcc flags the library on disk was built with
@@ -92,9 +97,20 @@ def build_train_batch_tool(out=TB_TOOL_OUT, force=False, extra_flags=()):
     return out
 
 
+def build_products_tool(out=PROD_TOOL_OUT, force=False):
+    """tools/products_host with hipcc at -O1 (its kernels are never launched; it runs on a machine without a GPU)"""
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in PROD_TOOL_DEPS):
+        return out
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-O1", "--offload-arch=gfx950", "-std=c++17", "-o", out + ".tmp", PROD_TOOL_SRC], check=True)
+    os.replace(out + ".tmp", out)
+    return out
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))
     if "--tool" in sys.argv:
         print(build_tool(force="--force" in sys.argv))
         print(build_rank_tool(force="--force" in sys.argv))
         print(build_train_batch_tool(force="--force" in sys.argv))
+        print(build_products_tool(force="--force" in sys.argv))

@@ -31,6 +31,12 @@ namespace vsr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The limits of one grouped launch.  The planners cut no tile into more than GEMM_MAX_SLABS pieces; every consumer of slabs (slab_sum*,
+// k_attend's fused sums) holds that many loads in flight, and every slab workspace is sized by it.
+constexpr int GEMM_MAX_SLABS = 8;
+constexpr int GEMM_MAX_PROB = 4;     // problems per launch
+constexpr int GEMM_MAX_SEG = 3;      // K segments per problem
+
 struct GemmSeg {
     const float* A;      // (rows, lda) activations
     const int* a_idx;    // optional row gather: row m reads A + a_idx[m] * lda
@@ -43,7 +49,7 @@ struct GemmSeg {
 };
 
 struct GemmProb {
-    GemmSeg seg[3];
+    GemmSeg seg[GEMM_MAX_SEG];
     float* C;            // (nslab, M, ldc)
     long long slab_stride;
     int nseg;
@@ -60,7 +66,7 @@ struct GemmProb {
 };
 
 struct GemmArgs {
-    GemmProb p[4];
+    GemmProb p[GEMM_MAX_PROB];
     int nprob;
     int total_iters;
     int G;               // workgroups with a non-empty range (1 <= G <= total_iters); grid = 8 * ceil(G / 8)
@@ -676,13 +682,13 @@ inline int gemm_plan(GemmArgs& a, int slots, int min_iters = 8, int BM = 64, int
     a.total_iters = total;
     int G = total / min_iters;
     if (G > slots) G = slots;
-    const int L_min = (kt_max + 6) / 7;            // keep pieces per tile <= 8
+    const int L_min = (kt_max + GEMM_MAX_SLABS - 2) / (GEMM_MAX_SLABS - 1);            // keep pieces per tile <= GEMM_MAX_SLABS
     if (G > total / L_min) G = total / L_min;
     if (G < 1) G = 1;
     a.G = G;
     const int L = total / G;                       // shortest range
     a.nslab = G == 1 ? 1 : (kt_max + L - 1) / L + 1;
-    if (a.nslab > 8) a.nslab = 8;
+    if (a.nslab > GEMM_MAX_SLABS) a.nslab = GEMM_MAX_SLABS;
     for (int i = 0; i < a.nprob; ++i) a.p[i].nslab = a.nslab;      // (gemm_tight_slabs: fewer for a short-K problem of a merged launch)
     a.aligned = 0;
     a.xcd_chunk = 0;
@@ -695,10 +701,10 @@ inline int gemm_plan(GemmArgs& a, int slots, int min_iters = 8, int BM = 64, int
 // k-windows at the same time and share them in L2, where the stream-K ranges (k offsets shifted from tile to tile) send almost
 // every tile load to the Infinity Cache.  The slab count is exact (max split) and a tile writes exactly
 // split_p slabs.  Chooses the smallest critical path T = max_p ceil(ktiles_p / split_p) with sum_p tiles_p split_p <= slots,
-// pieces of at least min_iters k-tiles, split <= 8.  Returns 0 (and leaves the plan untouched) when the tiles alone exceed the
+// pieces of at least min_iters k-tiles, split <= GEMM_MAX_SLABS.  Returns 0 (and leaves the plan untouched) when the tiles alone exceed the
 // slots: the caller then uses gemm_plan.
 inline int gemm_plan_aligned(GemmArgs& a, int slots, int min_iters, int BM, int BN, int BK) {
-    int tiles[4], kt[4], kt_max = 1, sum_tiles = 0;
+    int tiles[GEMM_MAX_PROB], kt[GEMM_MAX_PROB], kt_max = 1, sum_tiles = 0;
     for (int i = 0; i < a.nprob; ++i) {
         const GemmProb& p = a.p[i];
         tiles[i] = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
@@ -714,7 +720,7 @@ inline int gemm_plan_aligned(GemmArgs& a, int slots, int min_iters, int BM, int 
         bool ok = true;
         for (int i = 0; i < a.nprob && ok; ++i) {
             const int s = (kt[i] + T - 1) / T;
-            ok = s <= 8 && (s == 1 || kt[i] / s >= min_iters);
+            ok = s <= GEMM_MAX_SLABS && (s == 1 || kt[i] / s >= min_iters);
             wgs += tiles[i] * s;
         }
         if (!ok || wgs > slots) break;

@@ -9,8 +9,6 @@
 
 #include "gemm_dispatch.h"
 
-struct vsr_handle;
-
 namespace vsr {
 
 struct Bf16Range { const float* lo; const float* hi; const uint16_t* b; };   // fp32 matrix [lo, hi) has a bf16 copy at b
@@ -139,6 +137,16 @@ struct GemmState {
             if (p >= b16[i].lo && p < b16[i].hi) return true;
         return false;
     }
+};
+
+// What vsr_profile_* measures.  GemmBuilder::launch times and counts a launch that is handed one (the decoder's); the ordering models hand none.
+struct GemmProfile {
+    bool on = false;
+    std::vector<hipEvent_t> ev;      // pool, pairs (start, stop)
+    size_t ev_used = 0;
+    double flops = 0, bytes = 0;
+    int every = 1;                   // time every every-th GEMM launch (1 = all of them)
+    long long seen = 0;              // GEMM launches since vsr_profile_begin*
 };
 
 // every segment of every problem of a launch
@@ -323,7 +331,7 @@ struct GemmBuilder {
         route.tn = (t == 128 || (by_m && maxM >= 1024)) ? 2 : 1;
         return gemm_plan(a, route.tm == 2 ? k.gemm_slots / 2 : k.gemm_slots_small, k.gemm_min_iters, 64 * route.tm, 64 * route.tn);
     }
-    int launch(hipStream_t s, vsr_handle* h);        // (vsrcap.hip: gemm_dispatch() inside the handle's profiling events)
+    int launch(hipStream_t s, const GemmState* h, GemmProfile* prof);        // (vsrcap.hip: gemm_dispatch(), inside prof's events when prof is given)
 };
 
 }  // namespace vsr

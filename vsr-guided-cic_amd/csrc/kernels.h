@@ -7,19 +7,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_f32.h"
+
 namespace vsr {
 
 constexpr int KMAX = 8;  // VSR_MAX_BEAM
 
-// sum of up to 8 slabs at one offset, in slab order, with every load issued before the first add (the slab count is a
+// sum of up to GEMM_MAX_SLABS slabs at one offset, in slab order, with every load issued before the first add (the slab count is a
 // run-time number: a plain loop is a chain of dependent L2 round trips)
 __device__ __forceinline__ float slab_sum(const float* __restrict__ p, int nslab, long long stride, float init = 0.f) {
-    float v[8];
+    float v[GEMM_MAX_SLABS];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? p[k * stride] : 0.f;
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? p[k * stride] : 0.f;
     float s = init;
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
         if (k < nslab) s += v[k];
     return s;
 }
@@ -27,22 +29,22 @@ __device__ __forceinline__ float slab_sum(const float* __restrict__ p, int nslab
 // slab_sum at two / four consecutive offsets (one 8- / 16-byte load per slab; p + k * stride aligned accordingly): every component is
 // slab_sum's chain of adds
 __device__ __forceinline__ float2 slab_sum2(const float* __restrict__ p, int nslab, long long stride) {
-    float2 v[8];
+    float2 v[GEMM_MAX_SLABS];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? *reinterpret_cast<const float2*>(p + k * stride) : make_float2(0.f, 0.f);
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const float2*>(p + k * stride) : make_float2(0.f, 0.f);
     float2 s = make_float2(0.f, 0.f);
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
         if (k < nslab) { s.x += v[k].x; s.y += v[k].y; }
     return s;
 }
 __device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, int nslab, long long stride) {
-    float4 v[8];
+    float4 v[GEMM_MAX_SLABS];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
         if (k < nslab) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
     return s;
 }
@@ -341,11 +343,46 @@ __global__ void k_vproj_finish(const float* __restrict__ slabs, int nsplit, long
     out[i] = s + bias;
 }
 
-__global__ void k_slab_reduce(const float* __restrict__ slabs, int nsplit, long long stride, long long n, float* __restrict__ out) {
+// 1 / (1 - p) of the p an S-SSP training forward applied, from its tape's header (layout: SSP_TAPE_HDR_INTS, ssp_kernels.h)
+__device__ __forceinline__ float ssp_keep_scale(const int* __restrict__ hdr) { return 1.0f / (1.0f - __int_as_float(hdr[1])); }
+
+// The finish of every dense product that goes through the slab scratch (products.h: the ordering models, the decoder's training pass) and
+// the plain slab sum of the decode cache, prepare() and the training x projection: out = epilogue(sum of slabs), the terms and their order
+// as stated at Prod.  ONE source; which terms exist is a compile-time choice (run_products picks the instance from the product's fields), so a
+// launch carries no load and no test for a term its product does not have:
+//   LIN    bias / act / residual may be present (each skipped when NULL / SSP_ACT_NONE); without LIN the kernel is the plain slab sum
+//   GATE   FIN_KEEP: `gate` is the site's keep bytes, compact (M N);  FIN_RELU_Y: `gate` is the taped y (leading dimension ldg)
+// scale = 1 / (1 - p): the forward passes it, the backward passes the tape's header instead.  out may be residual's buffer (accumulation:
+// each thread reads its element before it writes it), hence no __restrict__ on the two.  The operands are loaded BEFORE the slabs are
+// added: these launches are mostly a few waves bound by memory latency, and all their loads should be in flight together.  The product and
+// the sum that follows it are two roundings, spelled out so that no compiler fuses them.
+constexpr int SSP_ACT_NONE = 0, SSP_ACT_RELU = 1, SSP_ACT_TANH = 2;
+constexpr int FIN_NONE = 0, FIN_KEEP = 1, FIN_RELU_Y = 2;
+template <bool LIN, int GATE>
+__global__ void k_prod_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ bias, int act,
+                              const float* residual, long long ldr, float* out, long long ldo, const void* __restrict__ gate, long long ldg,
+                              const int* __restrict__ hdr, float scale) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float s = slab_sum(slabs + i, nsplit, stride);
-    out[i] = s;
+    if (i >= (long long)M * N) return;
+    const int m = (int)(i / N), n = (int)(i % N);
+    float b = 0.f, r = 0.f, y = 0.f;
+    uint8_t kept = 0;
+    if (LIN && bias) b = bias[n];
+    if (LIN && residual) r = residual[(long long)m * ldr + n];
+    if (GATE == FIN_KEEP) kept = static_cast<const uint8_t*>(gate)[i];
+    if (GATE == FIN_RELU_Y) y = static_cast<const float*>(gate)[(long long)m * ldg + n];
+    float s = slab_sum(slabs + i, nslab, stride);
+    if (LIN) {
+        if (bias) s = __fadd_rn(s, b);
+        if (act == SSP_ACT_RELU) s = fmaxf(s, 0.f);
+        else if (act == SSP_ACT_TANH) s = tanhf(s);
+    }
+    if (GATE != FIN_NONE) {
+        if (hdr) scale = ssp_keep_scale(hdr);
+        s = (GATE == FIN_KEEP ? kept != 0 : y > 0.f) ? __fmul_rn(s, scale) : 0.f;
+    }
+    if (LIN && residual) s = __fadd_rn(s, r);
+    out[(long long)m * ldo + n] = s;
 }
 
 // decode state at t = 0: zero h / c states (one range of n_st 4-byte words) and their two 16-bit images (n_img words each), slot
@@ -556,9 +593,9 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
         if (((H | A | D) & 3) == 0) {
             // 16-byte path: four consecutive columns per thread, every slab load of a pass issued before the first use
             for (int c = tid * 4; c < H + A; c += NT * 4) {
-                float4 v[8];
+                float4 v[GEMM_MAX_SLABS];
 #pragma unroll
-                for (int k = 0; k < 8; ++k)
+                for (int k = 0; k < GEMM_MAX_SLABS; ++k)
                     if (k < g2.nsplit) v[k] = *reinterpret_cast<const float4*>(g2.c2a + (long long)k * g2.stride_a + (long long)row * (H + A) + c);
                 float4 gp = make_float4(0, 0, 0, 0), cn = gp;
                 if (c < H) {
@@ -567,7 +604,7 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
                 }
                 float4 s = v[0];
 #pragma unroll
-                for (int k = 1; k < 8; ++k)
+                for (int k = 1; k < GEMM_MAX_SLABS; ++k)
                     if (k < g2.nsplit) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
                 if (c < H) {
                     float4 o;
@@ -583,13 +620,13 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
                 }
             }
             for (int cc = tid * 4; cc < D + A; cc += NT * 4) {
-                float4 v[8];
+                float4 v[GEMM_MAX_SLABS];
 #pragma unroll
-                for (int k = 0; k < 8; ++k)
+                for (int k = 0; k < GEMM_MAX_SLABS; ++k)
                     if (k < g2.nsplit) v[k] = *reinterpret_cast<const float4*>(g2.c2b + (long long)k * g2.stride_b + (long long)row * (D + A) + cc);
                 float4 s = v[0];
 #pragma unroll
-                for (int k = 1; k < 8; ++k)
+                for (int k = 1; k < GEMM_MAX_SLABS; ++k)
                     if (k < g2.nsplit) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
                 if (cc < D) {
                     const float4 bs = *reinterpret_cast<const float4*>(g2.b_sfc + cc);

@@ -9,7 +9,7 @@
 #include "train_batch_kernels.h"
 
 struct vsr_ssp {
-    vsr_handle cfg;                  // GEMM launch configuration only (stream-K slots, tile choice); fp32
+    GemmState cfg;                   // GEMM launch configuration only (stream-K slots, tile choice); fp32
     vsr_ssp_weights w;
     vsr_sinkhorn_weights sw;
     bool has_ssp = false, has_sh = false;
@@ -58,7 +58,7 @@ static size_t carve_ssp(int S, char* base, SspWs& w) {
     for (int l = 0; l < 3; ++l) { w.pk[l] = b.take<float>((size_t)S * SSP_LEN * H); w.pv[l] = b.take<float>((size_t)S * SSP_LEN * H); }
     w.last = b.take<float>((size_t)S * H); w.logits = b.take<float>((size_t)S * SSP_ROLES);
     w.roles32 = b.take<int>((size_t)S * SSP_LEN); w.remain = b.take<int>((size_t)S * SSP_LEN); w.tokens = b.take<int>(R); w.bad = b.take<int>(4);
-    w.scratch_floats = R * SSP_FF * 8;
+    w.scratch_floats = R * SSP_FF * GEMM_MAX_SLABS;
     w.scratch = b.take<float>(w.scratch_floats);
     return (b.off + 255) & ~size_t(255);
 }
@@ -69,89 +69,11 @@ extern "C" size_t vsr_ssp_workspace_bytes(int32_t S) {
 }
 
 // ---------------------------------------------------------------------------------------------- the dense products
-// The ONE product path of this file: inference, SinkhornNet's and S-SSP's training passes describe each product as an SspProd and hand
-// it to run_products.  out (M, N) = epilogue(sum over the k segments of A_i (M, K_i) . W_i (N, K_i)^T) on the exact fp32 kernels.
-// The epilogue (k_prod_finish), every term optional, in THIS order:
-//   + bias[n]
-//   act         SSP_ACT_RELU: max(., 0), SSP_ACT_TANH
-//   keep        (M N bytes, compact) dropout: keep ? . scale : 0 - the forward's site, or in the backward the site of the tensor whose
-//               gradient this is
-//   relu_y      backward through relu + dropout in one: the taped y = drop(relu(.)) is > 0 exactly where both let the gradient pass, and
-//               the factor there is scale (1: a ReLU without dropout)
-//   + residual  (may be out's buffer: accumulation)
-// A product has keep or relu_y, never both.  Which terms a product has selects the instance of the finish kernel (ssp_kernels.h).
-// ldo / ldy / ldr: the leading dimensions of out / relu_y / residual, 0 = N (compact).
-// in_place: where no tile of the launch is split (one slab) the GEMM writes `out` itself and no finish kernel runs.  Refused for a product
-// with an epilogue term, and meant only where the results have always been produced that way: the finish kernel's sum of ONE slab is 0.f + v,
-// which turns a -0 into +0, and the in-place write does not.
-struct SspSeg { const float* A; int lda; const float* W; int ldw; int K; };
-struct SspProd {
-    int M, N;
-    SspSeg seg[3];
-    int nseg;
-    float* out; int ldo;
-    const float* bias; int act; const uint8_t* keep; const float* relu_y; int ldy; const float* residual; int ldr;
-    bool in_place;
-};
-// what a pass gives all its products.  scale = 1 / (1 - p): the forward gives it, the backward the tape's header (hdr) that carries it.
-struct SspRun { vsr_ssp* e; hipStream_t s; float* scratch; size_t scratch_floats; const int* hdr; float scale; const char* pass; };
-static SspProd ssp_prod1(int M, int N, int K, const float* A, int lda, const float* W, int ldw, float* out, int ldo = 0) {
-    SspProd p{};
-    p.M = M; p.N = N; p.seg[0] = SspSeg{A, lda, W, ldw, K}; p.nseg = 1; p.out = out; p.ldo = ldo;
-    return p;
+// Inference, SinkhornNet's and S-SSP's training passes describe each product as a Prod and hand it to run_products (products.h), on the
+// exact fp32 kernels; their launches are not part of any GEMM profile.
+static ProdRun ssp_run(const vsr_ssp* e, hipStream_t s, float* scratch, size_t scratch_floats, const int* hdr, float scale, const char* pass) {
+    return ProdRun{&e->cfg, nullptr, s, scratch, scratch_floats, hdr, scale, pass};
 }
-// a layer of a forward pass: out = act(A W^T + bias) (+ residual), W (N, K) compact
-static SspProd lin(int M, int N, int K, const float* A, int lda, const float* W, const float* bias, float* out, int act = SSP_ACT_NONE,
-                   const float* residual = nullptr) {
-    SspProd p = ssp_prod1(M, N, K, A, lda, W, K, out);
-    p.bias = bias; p.act = act; p.residual = residual;
-    return p;
-}
-// Up to four products in ONE launch.  Problems and segments go to the GEMM in the order given (it numbers the tiles and fixes the summation
-// order, step_gemms.h); every problem gets the launch's ns slabs in the scratch, then each product its finish kernel.
-static int run_products(const SspRun& c, const SspProd* P, int n) {
-    GemmBuilder g;
-    bool in_place = true;
-    for (int i = 0; i < n; ++i) {
-        GemmProb& p = g.prob(P[i].M, P[i].N, nullptr, P[i].N);
-        for (int k = 0; k < P[i].nseg; ++k) {
-            const SspSeg& sg = P[i].seg[k];
-            if ((sg.K & 3) || (sg.lda & 3) || (sg.ldw & 3) || !aligned16(sg.A) || !aligned16(sg.W))
-                return fail("%s: operand not in whole 16-byte groups (K %d, lda %d, ldw %d)", c.pass, sg.K, sg.lda, sg.ldw);
-            GemmBuilder::seg(p, sg.A, sg.lda, nullptr, sg.W, sg.ldw, sg.K);
-        }
-        if (P[i].in_place && (P[i].bias || P[i].act != SSP_ACT_NONE || P[i].keep || P[i].relu_y || P[i].residual))
-            return fail("%s: an in-place product cannot have an epilogue", c.pass);
-        if (P[i].keep && P[i].relu_y) return fail("%s: a product has keep or relu_y, not both", c.pass);
-        in_place = in_place && P[i].in_place;
-    }
-    const int ns = g.finish(&c.e->cfg);
-    auto ld = [&](int i, int l) { return (long long)(l ? l : P[i].N); };
-    if (ns == 1 && in_place) {                    // every tile is produced by one workgroup: written in place
-        for (int i = 0; i < n; ++i) { g.a.p[i].C = P[i].out; g.a.p[i].ldc = (int)ld(i, P[i].ldo); g.a.p[i].slab_stride = 0; }
-        if (g.launch(c.s, &c.e->cfg)) return fail("%s: gemm launch failed", c.pass);
-        return 0;
-    }
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        g.a.p[i].C = c.scratch + off;
-        g.a.p[i].slab_stride = (long long)P[i].M * P[i].N;
-        off += (size_t)P[i].M * P[i].N * ns;
-    }
-    if (off > c.scratch_floats) return fail("%s: GEMM scratch too small", c.pass);
-    if (g.launch(c.s, &c.e->cfg)) return fail("%s: gemm launch failed", c.pass);
-    for (int i = 0; i < n; ++i) {
-        const SspProd& p = P[i];
-        const long long tot = (long long)p.M * p.N;
-        const bool lin = p.bias || p.act != SSP_ACT_NONE || p.residual;
-        auto finish = !p.keep && !p.relu_y ? (lin ? k_prod_finish<true, FIN_NONE> : k_prod_finish<false, FIN_NONE>)
-                                           : (p.keep ? k_prod_finish<true, FIN_KEEP> : k_prod_finish<true, FIN_RELU_Y>);
-        hipLaunchKernelGGL(finish, dim3(cdiv(tot, 256)), dim3(256), 0, c.s, g.a.p[i].C, ns, tot, p.M, p.N, p.bias, p.act, p.residual, ld(i, p.ldr), p.out,
-                           ld(i, p.ldo), p.keep ? (const void*)p.keep : (const void*)p.relu_y, ld(i, p.ldy), c.hdr, c.scale);
-    }
-    return 0;
-}
-static int run_product(const SspRun& c, const SspProd& p) { return run_products(c, &p, 1); }
 static void layernorm(hipStream_t s, const float* x, const float* w, const float* b, int rows, float* out) {
     hipLaunchKernelGGL(k_layernorm512, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, out);
 }
@@ -169,9 +91,9 @@ extern "C" int vsr_ssp_generate(vsr_ssp* e, const int64_t* verbs, const int32_t*
     hipStream_t s = (hipStream_t)stream;
     const vsr_ssp_weights& w = e->w;
     const int H = SSP_H, L = SSP_LEN;
-    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "ssp"};
+    const ProdRun run = ssp_run(e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "ssp");
     auto qkv = [&](const vsr_ssp_layer& ly, int R) {              // the three projections of the layer's input (in ws.y) in one launch
-        SspProd p[3] = {lin(R, H, H, ws.y, H, ly.Wq, ly.bq, ws.q), lin(R, H, H, ws.y, H, ly.Wk, ly.bk, ws.k), lin(R, H, H, ws.y, H, ly.Wv, ly.bv, ws.v)};
+        Prod p[3] = {lin(R, H, H, ws.y, H, ly.Wq, ly.bq, ws.q), lin(R, H, H, ws.y, H, ly.Wk, ly.bk, ws.k), lin(R, H, H, ws.y, H, ly.Wv, ly.bv, ws.v)};
         return run_products(run, p, 3);
     };
     HIPCHK(hipMemsetAsync(ws.bad, 0, 4 * sizeof(int), s));
@@ -194,7 +116,7 @@ extern "C" int vsr_ssp_generate(vsr_ssp* e, const int64_t* verbs, const int32_t*
     // keys / values of the cross attention: prior states through each decoder layer's (self-)attention K / V projections,
     // constant over the decode steps (sort_modules.py:88 re-uses self.attention for the cross attention)
     for (int l = 0; l < 3; ++l) {
-        SspProd kv[2] = {lin(R, H, H, ws.prior, H, w.dec[l].Wk, w.dec[l].bk, ws.pk[l]), lin(R, H, H, ws.prior, H, w.dec[l].Wv, w.dec[l].bv, ws.pv[l])};
+        Prod kv[2] = {lin(R, H, H, ws.prior, H, w.dec[l].Wk, w.dec[l].bk, ws.pk[l]), lin(R, H, H, ws.prior, H, w.dec[l].Wv, w.dec[l].bv, ws.pv[l])};
         if (run_products(run, kv, 2)) return 1;
     }
     LAUNCHCHK();
@@ -241,7 +163,7 @@ static size_t carve_sh_ws(int Q, int N, char* base, ShWs& w) {
     const size_t R = (size_t)Q * N;
     Bump b{base};
     carve_sh_acts(b, R, N, w.a);
-    w.scratch_floats = R * 512 * 8;
+    w.scratch_floats = R * 512 * GEMM_MAX_SLABS;
     w.scratch = b.take<float>(w.scratch_floats);
     return (b.off + 255) & ~size_t(255);
 }
@@ -252,8 +174,7 @@ extern "C" size_t vsr_sinkhorn_workspace_bytes(int32_t Q, int32_t N) {
 }
 // The five layers of SinkhornNet for Q items: seq (Q, N, 2352) -> a.th (Q, N, N).  The ONE forward of vsr_sinkhorn_assign, vsr_rank_captions
 // and vsr_sinkhorn_train_forward: with the Sinkhorn arithmetic they also share (sinkhorn_normalise), the training forward's tr has assign's bits.
-static int sinkhorn_layers(const SspRun& c, const float* seq, int Q, const ShActs& a) {
-    const vsr_sinkhorn_weights& w = c.e->sw;
+static int sinkhorn_layers(const ProdRun& c, const vsr_sinkhorn_weights& w, const float* seq, int Q, const ShActs& a) {
     const int N = w.N, R = Q * N;
     if (run_product(c, lin(R, 128, 300, seq, SH_ROW, w.W1_txt_w, w.W1_txt_b, a.t1, SSP_ACT_RELU))) return 1;
     if (run_product(c, lin(R, 512, 2048, seq + 300, SH_ROW, w.W1_vis_w, w.W1_vis_b, a.v1, SSP_ACT_RELU))) return 1;
@@ -273,7 +194,7 @@ extern "C" int vsr_sinkhorn_assign(vsr_ssp* e, const float* seq, int32_t Q, floa
     ShWs ws;
     if (carve_sh_ws(Q, w.N, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_sinkhorn_assign: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    if (sinkhorn_layers(SspRun{e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "sinkhorn forward"}, seq, Q, ws.a)) return 1;
+    if (sinkhorn_layers(ssp_run(e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "sinkhorn forward"), e->sw, seq, Q, ws.a)) return 1;
     hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Q), dim3(64), 0, s, ws.a.th, w.N, w.n_iters, w.tau, tr, assign);
     LAUNCHCHK();
     return 0;
@@ -323,7 +244,7 @@ static size_t carve_sh_train(int Q, int N, char* base, ShTrainWs& w) {
     w.dpreT = b.take<float>(N * Rp); w.f1T = b.take<float>(256 * Rp); w.df1T = b.take<float>(256 * Rp); w.catT = b.take<float>(260 * Rp);
     w.dt1T = b.take<float>(128 * Rp); w.txtT = b.take<float>(300 * Rp); w.dv2T = b.take<float>(128 * Rp); w.v1T = b.take<float>(512 * Rp);
     w.dv1T = b.take<float>(512 * Rp); w.visT = b.take<float>(2048 * Rp);
-    w.scratch_floats = std::max<size_t>((size_t)512 * 2048, R * 512) * 8;       // the forward's need (R x 512 x 8 slabs) and W1_vis's gradient in 8 slabs
+    w.scratch_floats = std::max<size_t>((size_t)512 * 2048, R * 512) * GEMM_MAX_SLABS;       // the forward's need (R x 512, every slab) and W1_vis's gradient in as many
     w.scratch = b.take<float>(w.scratch_floats);
     return (b.off + 255) & ~size_t(255);
 }
@@ -351,7 +272,7 @@ extern "C" int vsr_sinkhorn_train_forward(vsr_ssp* e, const float* seq, int32_t 
     if (carve_sh_tape(Q, N, reinterpret_cast<char*>(tape), t) > tape_bytes) return fail("vsr_sinkhorn_train_forward: tape too small");
     if (carve_sh_train(Q, N, reinterpret_cast<char*>(workspace), tw) > workspace_bytes) return fail("vsr_sinkhorn_train_forward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    if (sinkhorn_layers(SspRun{e, s, tw.scratch, tw.scratch_floats, nullptr, 1.f, "sinkhorn forward"}, seq, Q, t.a)) return 1;
+    if (sinkhorn_layers(ssp_run(e, s, tw.scratch, tw.scratch_floats, nullptr, 1.f, "sinkhorn forward"), e->sw, seq, Q, t.a)) return 1;
     hipLaunchKernelGGL(k_sinkhorn_train_fwd, dim3(Q), dim3(64), 0, s, t.a.th, N, w.n_iters, w.tau, tr, t.tr, t.div, t.hdr);
     LAUNCHCHK();
     return 0;
@@ -379,11 +300,11 @@ extern "C" int vsr_sinkhorn_train_backward(vsr_ssp* e, const float* seq, int32_t
     if (carve_sh_tape(Q, N, reinterpret_cast<char*>(const_cast<void*>(tape)), t) > tape_bytes) return fail("vsr_sinkhorn_train_backward: tape too small");
     if (carve_sh_train(Q, N, reinterpret_cast<char*>(workspace), ws) > workspace_bytes) return fail("vsr_sinkhorn_train_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "sinkhorn backward"};
+    const ProdRun run = ssp_run(e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "sinkhorn backward");
     // dst (m, n; leading dimension ldd) = A (m, k) . W (n, k)^T; relu_y: masked by the ReLU whose output it is.  The unmasked ones have
     // no epilogue and are written in place where no tile is split.
     auto product = [&](int m, int n, int k, const float* A, int lda, const float* W, int ldw, float* dst, int ldd, const float* relu_y = nullptr, int ldy = 0) {
-        SspProd p = ssp_prod1(m, n, k, A, lda, W, ldw, dst, ldd);
+        Prod p = prod1(m, n, k, A, lda, W, ldw, dst, ldd);
         p.relu_y = relu_y; p.ldy = ldy; p.in_place = !relu_y;
         return run_product(run, p);
     };
@@ -542,7 +463,7 @@ static size_t carve_ssp_train(int S, char* base, SspTrainWs& w) {
     for (auto& p : w.tE) p = b.take<float>(H * Rep);
     for (auto& p : w.wT) p = b.take<float>((size_t)SSP_FF * H);
     w.part = b.take<float>((size_t)2 * COLSUM_CHUNKS * SSP_FF);
-    w.scratch_floats = std::max<size_t>(Rd * SSP_FF, (size_t)SSP_FF * H) * 8;      // 8 slabs of the widest activation / of W1's gradient
+    w.scratch_floats = std::max<size_t>(Rd * SSP_FF, (size_t)SSP_FF * H) * GEMM_MAX_SLABS;      // every slab of the widest activation / of W1's gradient
     w.scratch = b.take<float>(w.scratch_floats);
     return (b.off + 255) & ~size_t(255);
 }
@@ -594,39 +515,39 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
     SspSites st;
     ssp_sites(S, st);
     auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
-    SspRun run{e, s, ws.scratch, ws.scratch_floats, nullptr, scale, "ssp training"};
+    const ProdRun run = ssp_run(e, s, ws.scratch, ws.scratch_floats, nullptr, scale, "ssp training");
     hipLaunchKernelGGL(k_ssp_train_prep, dim3(cdiv(Rd, 256)), dim3(256), 0, s, verbs, roles, gt, S, (int)w.n_verbs, ws.verbs32, ws.roles, ws.gt, ws.tok);
     // one layer of either stack: x (in ws.r[0]) -> x (in ws.r[0]); site0: the layer's first dropout site
     auto layer = [&](const vsr_ssp_layer& ly, SspLayerTape& lt, int R, int T, bool dec, int site0, const float* prior) -> int {
         float *x = ws.r[0], *x1 = ws.r[1];
         layernorm_train(s, x, ly.ln1_w, ly.ln1_b, R, lt.lnA);
-        SspProd qkv[3] = {lin(R, H, H, lt.lnA.y, H, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, H, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, H, ly.Wv, ly.bv, lt.v)};
+        Prod qkv[3] = {lin(R, H, H, lt.lnA.y, H, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, H, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, H, ly.Wv, ly.bv, lt.v)};
         if (run_products(run, qkv, 3)) return 1;
         hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD, lt.ctx1, lt.P1,
                            keep(site0), scale);
-        SspProd o = lin(R, H, H, lt.ctx1, H, ly.Wo, ly.bo, x1);
+        Prod o = lin(R, H, H, lt.ctx1, H, ly.Wo, ly.bo, x1);
         o.keep = keep(site0 + 1); o.residual = x;
         if (run_product(run, o)) return 1;                                                            // x1 = drop(attn) + x
         int site = site0 + 2;
         if (dec) {
             layernorm_train(s, x1, ly.ln2_w, ly.ln2_b, R, lt.lnC);
-            SspProd q2 = lin(R, H, H, lt.lnC.y, H, ly.Wq, ly.bq, lt.q2);                                // the SAME projections (sort_modules.py:87)
+            Prod q2 = lin(R, H, H, lt.lnC.y, H, ly.Wq, ly.bq, lt.q2);                                // the SAME projections (sort_modules.py:87)
             if (run_product(run, q2)) return 1;
-            SspProd kv[2] = {lin(Re, H, H, prior, H, ly.Wk, ly.bk, lt.pk), lin(Re, H, H, prior, H, ly.Wv, ly.bv, lt.pv)};
+            Prod kv[2] = {lin(Re, H, H, prior, H, ly.Wk, ly.bk, lt.pk), lin(Re, H, H, prior, H, ly.Wv, ly.bv, lt.pv)};
             if (run_products(run, kv, 2)) return 1;
             hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, T, SSP_LEN, (const int*)nullptr, 0, lt.ctx2, lt.P2,
                                keep(site), scale);
-            SspProd o2 = lin(R, H, H, lt.ctx2, H, ly.Wo, ly.bo, x);
+            Prod o2 = lin(R, H, H, lt.ctx2, H, ly.Wo, ly.bo, x);
             o2.keep = keep(site + 1); o2.residual = x1;
             if (run_product(run, o2)) return 1;                                                       // x = drop(cross) + x1
             std::swap(x, x1);                                                                         // (x1 names the feed-forward's input again)
             site += 2;
         }
         layernorm_train(s, x1, dec ? ly.ln3_w : ly.ln2_w, dec ? ly.ln3_b : ly.ln2_b, R, lt.lnF);
-        SspProd f1 = lin(R, SSP_FF, H, lt.lnF.y, H, ly.W1, ly.b1, lt.ff);
+        Prod f1 = lin(R, SSP_FF, H, lt.lnF.y, H, ly.W1, ly.b1, lt.ff);
         f1.act = SSP_ACT_RELU; f1.keep = keep(site);
         if (run_product(run, f1)) return 1;
-        SspProd f2 = lin(R, H, SSP_FF, lt.ff, SSP_FF, ly.W2, ly.b2, x);
+        Prod f2 = lin(R, H, SSP_FF, lt.ff, SSP_FF, ly.W2, ly.b2, x);
         f2.keep = keep(site + 1); f2.residual = x1;
         if (run_product(run, f2)) return 1;                                                           // x = drop(ff) + x1
         if (x != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
@@ -634,7 +555,7 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
     };
     // ---- encoder
     hipLaunchKernelGGL(k_ssp_embed_train, dim3(Re), dim3(128), 0, s, ws.roles, SSP_LEN, w.sr_embed, ws.verbs32, w.v_embed, keep(1), keep(0), scale, t.emb);
-    SspProd fc = lin(Re, H, H, t.emb, H, w.fc_w, w.fc_b, ws.r[0]);
+    Prod fc = lin(Re, H, H, t.emb, H, w.fc_w, w.fc_b, ws.r[0]);
     if (run_product(run, fc)) return 1;
     for (int l = 0; l < 3; ++l)
         if (layer(w.enc[l], t.enc[l], Re, SSP_LEN, false, 2 + 4 * l, nullptr)) return 1;
@@ -647,7 +568,7 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
         if (layer(w.dec[l], t.dec[l], Rd, SSP_TD, true, 15 + 6 * l, t.encln.y)) return 1;
     layernorm_train(s, ws.r[0], w.dec_ln_w, w.dec_ln_b, Rd, t.decln);
     // ---- loss
-    SspProd ex = lin(Rd, SSP_ROLES, H, t.decln.y, H, w.exp_w, w.exp_b, ws.logits);
+    Prod ex = lin(Rd, SSP_ROLES, H, t.decln.y, H, w.exp_w, w.exp_b, ws.logits);
     if (run_product(run, ex)) return 1;
     hipLaunchKernelGGL(k_ssp_kl_loss, dim3(cdiv(Rd, 4)), dim3(256), 0, s, ws.logits, ws.gt, one_hot, Rd, t.logp, ws.row_loss);
     hipLaunchKernelGGL(k_ssp_loss_finish, dim3(1), dim3(256), 0, s, ws.row_loss, ws.gt, one_hot, S, p_applied, masks ? 1 : 0, loss, t.hdr);
@@ -689,7 +610,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     SspSites st;
     ssp_sites(S, st);
     auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
-    SspRun run{e, s, ws.scratch, ws.scratch_floats, t.hdr, 1.f, "ssp training"};
+    const ProdRun run = ssp_run(e, s, ws.scratch, ws.scratch_floats, t.hdr, 1.f, "ssp training");
     TransBatch tb;
     auto tr_add = [&](const float* in, int ld_in, int rows, int cols, float* out, int ld_out) { tb.add(s, 0, nullptr, in, ld_in, rows, cols, out, ld_out, nullptr, 0); };
     // the gradient of x where y = drop(x) (site) and dy is given: dy itself without masks, else a masked copy in `buf`
@@ -715,8 +636,8 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     ssp_colsum(ws, s, ws.dlog, Rd, LD, ws.r[9]);                     // (28 columns; the first 26 are the bias gradient)
     HIPCHK(hipMemcpyAsync(g->exp_b, ws.r[9], SSP_ROLES * sizeof(float), hipMemcpyDeviceToDevice, s));
     {
-        SspProd pw = ssp_prod1(SSP_ROLES, H, Rdp, ws.t512[0], Rdp, ws.t512[1], Rdp, g->exp_w);
-        SspProd px = ssp_prod1(Rd, H, LD, ws.dlog, LD, ws.wT[0], LD, ws.r[2]);
+        Prod pw = prod1(SSP_ROLES, H, Rdp, ws.t512[0], Rdp, ws.t512[1], Rdp, g->exp_w);
+        Prod px = prod1(Rd, H, LD, ws.dlog, LD, ws.wT[0], LD, ws.r[2]);
         if (run_product(run, pw) || run_product(run, px)) return 1;
     }
     ln_bwd(ws.r[2], w.dec_ln_w, t.decln, nullptr, Rd, ws.r[0], g->dec_ln_w, g->dec_ln_b);
@@ -736,15 +657,15 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         tr_add(ly.W1, H, F, H, ws.wT[1], F);
         tb.flush(s);
         ssp_colsum(ws, s, dz2, R, H, gl.b2);
-        SspProd pw2 = ssp_prod1(H, F, Rp, ws.t512[0], Rp, ws.t2048[0], Rp, gl.W2);
-        SspProd pff = ssp_prod1(R, F, H, dz2, H, ws.wT[0], H, ws.dff);
+        Prod pw2 = prod1(H, F, Rp, ws.t512[0], Rp, ws.t2048[0], Rp, gl.W2);
+        Prod pff = prod1(R, F, H, dz2, H, ws.wT[0], H, ws.dff);
         pff.relu_y = lt.ff;                                                                           // d (W1 yF + b1): relu and the site's dropout in one
         if (run_product(run, pw2) || run_product(run, pff)) return 1;
         tr_add(ws.dff, F, R, F, ws.t2048[1], Rp);
         tb.flush(s);
         ssp_colsum(ws, s, ws.dff, R, F, gl.b1);
-        SspProd pw1 = ssp_prod1(F, H, Rp, ws.t2048[1], Rp, ws.t512[1], Rp, gl.W1);
-        SspProd pyf = ssp_prod1(R, H, F, ws.dff, F, ws.wT[1], F, Y);
+        Prod pw1 = prod1(F, H, Rp, ws.t2048[1], Rp, ws.t512[1], Rp, gl.W1);
+        Prod pyf = prod1(R, H, F, ws.dff, F, ws.wT[1], F, Y);
         if (run_product(run, pw1) || run_product(run, pyf)) return 1;
         ln_bwd(Y, dec ? ly.ln3_w : ly.ln2_w, lt.lnF, A, R, B, dec ? gl.ln3_w : gl.ln2_w, dec ? gl.ln3_b : gl.ln2_b);       // B = d h
         // the four attention weights, transposed once for both uses
@@ -759,7 +680,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
             tr_add(dzo2, H, R, H, ws.t512[0], Rp);
             tr_add(lt.ctx2, H, R, H, ws.t512[1], Rp);
             tb.flush(s);
-            SspProd pc = ssp_prod1(R, H, H, dzo2, H, ws.wT[0], H, Y);
+            Prod pc = prod1(R, H, H, dzo2, H, ws.wT[0], H, Y);
             if (run_product(run, pc)) return 1;
             hipLaunchKernelGGL(k_ssp_mha_bwd, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, lt.P2, keep(site0 + 2), t.hdr, Y, T, SSP_LEN, (const int*)nullptr, 0,
                                Q2, ws.dpk, ws.dpv, ws.dbk2);
@@ -768,9 +689,9 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
             tr_add(ws.dpk, H, Re, H, ws.tE[0], Rep);
             tr_add(ws.dpv, H, Re, H, ws.tE[1], Rep);
             tb.flush(s);
-            SspProd pyc = ssp_prod1(R, H, H, Q2, H, ws.wT[1], H, C);
-            SspProd pp = ssp_prod1(Re, H, H, ws.dpk, H, ws.wT[2], H, ws.dprior);
-            pp.seg[1] = SspSeg{ws.dpv, H, ws.wT[3], H, H}; pp.nseg = 2;
+            Prod pyc = prod1(R, H, H, Q2, H, ws.wT[1], H, C);
+            Prod pp = prod1(Re, H, H, ws.dpk, H, ws.wT[2], H, ws.dprior);
+            pp.seg[1] = ProdSeg{ws.dpv, H, ws.wT[3], H, H}; pp.nseg = 2;
             pp.residual = first_dec ? nullptr : ws.dprior;                                            // the three layers accumulate into d prior
             if (run_product(run, pyc) || run_product(run, pp)) return 1;
             ln_bwd(C, ly.ln2_w, lt.lnC, B, R, A, gl.ln2_w, gl.ln2_b);                                   // A = d h1
@@ -784,9 +705,9 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         tr_add(lt.ctx1, H, R, H, ws.t512[5], Rp);
         tb.flush(s);
         ssp_colsum(ws, s, dzo1, R, H, gl.bo, dzo2, R);
-        SspProd pc1 = ssp_prod1(R, H, H, dzo1, H, ws.wT[0], H, Y);
-        SspProd pwo = ssp_prod1(H, H, Rp, ws.t512[4], Rp, ws.t512[5], Rp, gl.Wo);
-        if (dec) { pwo.seg[1] = SspSeg{ws.t512[0], Rp, ws.t512[1], Rp, Rp}; pwo.nseg = 2; }
+        Prod pc1 = prod1(R, H, H, dzo1, H, ws.wT[0], H, Y);
+        Prod pwo = prod1(H, H, Rp, ws.t512[4], Rp, ws.t512[5], Rp, gl.Wo);
+        if (dec) { pwo.seg[1] = ProdSeg{ws.t512[0], Rp, ws.t512[1], Rp, Rp}; pwo.nseg = 2; }
         if (run_product(run, pc1) || run_product(run, pwo)) return 1;
         hipLaunchKernelGGL(k_ssp_mha_bwd, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, lt.P1, keep(site0), t.hdr, Y, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD,
                            C, D, E, ws.dbk1);
@@ -798,16 +719,16 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         ssp_colsum(ws, s, C, R, H, gl.bq, dec ? Q2 : nullptr, R);
         ssp_colsum(ws, s, ws.dbk1, S, H, gl.bk, dec ? ws.dbk2 : nullptr, S);                           // (k_ssp_mha_bwd: summed per sequence in fp64)
         ssp_colsum(ws, s, E, R, H, gl.bv, dec ? ws.dpv : nullptr, Re);
-        SspProd pw[3] = {ssp_prod1(H, H, Rp, ws.t512[6], Rp, ws.t512[9], Rp, gl.Wq), ssp_prod1(H, H, Rp, ws.t512[7], Rp, ws.t512[9], Rp, gl.Wk),
-                         ssp_prod1(H, H, Rp, ws.t512[8], Rp, ws.t512[9], Rp, gl.Wv)};
+        Prod pw[3] = {prod1(H, H, Rp, ws.t512[6], Rp, ws.t512[9], Rp, gl.Wq), prod1(H, H, Rp, ws.t512[7], Rp, ws.t512[9], Rp, gl.Wk),
+                         prod1(H, H, Rp, ws.t512[8], Rp, ws.t512[9], Rp, gl.Wv)};
         if (dec) {
-            pw[0].seg[1] = SspSeg{ws.t512[2], Rp, ws.t512[3], Rp, Rp}; pw[0].nseg = 2;
-            pw[1].seg[1] = SspSeg{ws.tE[0], Rep, ws.tE[2], Rep, Rep}; pw[1].nseg = 2;
-            pw[2].seg[1] = SspSeg{ws.tE[1], Rep, ws.tE[2], Rep, Rep}; pw[2].nseg = 2;
+            pw[0].seg[1] = ProdSeg{ws.t512[2], Rp, ws.t512[3], Rp, Rp}; pw[0].nseg = 2;
+            pw[1].seg[1] = ProdSeg{ws.tE[0], Rep, ws.tE[2], Rep, Rep}; pw[1].nseg = 2;
+            pw[2].seg[1] = ProdSeg{ws.tE[1], Rep, ws.tE[2], Rep, Rep}; pw[2].nseg = 2;
         }
         if (run_products(run, pw, 3)) return 1;
-        SspProd pya = ssp_prod1(R, H, H, C, H, ws.wT[1], H, Y);
-        pya.seg[1] = SspSeg{D, H, ws.wT[2], H, H}; pya.seg[2] = SspSeg{E, H, ws.wT[3], H, H}; pya.nseg = 3;
+        Prod pya = prod1(R, H, H, C, H, ws.wT[1], H, Y);
+        pya.seg[1] = ProdSeg{D, H, ws.wT[2], H, H}; pya.seg[2] = ProdSeg{E, H, ws.wT[3], H, H}; pya.nseg = 3;
         if (run_product(run, pya)) return 1;
         ln_bwd(Y, ly.ln1_w, lt.lnA, A, R, B, gl.ln1_w, gl.ln1_b);                                       // B = d x
         if (B != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
@@ -828,8 +749,8 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     tb.flush(s);
     ssp_colsum(ws, s, ws.r[0], Re, H, g->fc_b);
     {
-        SspProd pw = ssp_prod1(H, H, Rep, ws.t512[0], Rep, ws.t512[1], Rep, g->fc_w);
-        SspProd px = ssp_prod1(Re, H, H, ws.r[0], H, ws.wT[0], H, ws.r[2]);
+        Prod pw = prod1(H, H, Rep, ws.t512[0], Rep, ws.t512[1], Rep, g->fc_w);
+        Prod px = prod1(Re, H, H, ws.r[0], H, ws.wT[0], H, ws.r[2]);
         if (run_product(run, pw) || run_product(run, px)) return 1;
     }
     hipLaunchKernelGGL(k_ssp_sr_embed_bwd, dim3(SSP_ROLES, H / 64), dim3(256), 0, s, ws.roles, ws.r[2], keep(1), Re, ws.tok, d_dec, keep(14), Rd, t.hdr, g->sr_embed);
@@ -944,10 +865,10 @@ extern "C" int vsr_rank_captions(vsr_ssp* e, const int32_t* control_verb, const 
     if (vsr_ssp_generate(e, w.job_verbs, w.job_roles, S, w.pred, w.logp, w.ssp, w.ssp_bytes, stream)) return 1;
     ShWs sh;
     if (carve_sh_ws(RANK_SH_CHUNK, N_sink, w.sh, sh) > w.sh_bytes) return fail("vsr_rank_captions: Sinkhorn slot of the workspace too small");
-    SspRun run{e, s, sh.scratch, sh.scratch_floats, nullptr, 1.f, "sinkhorn forward"};
+    const ProdRun run = ssp_run(e, s, sh.scratch, sh.scratch_floats, nullptr, 1.f, "sinkhorn forward");
     for (int q = 0; q < Qpad; q += RANK_SH_CHUNK) {
         sh.a.th = w.fc + (size_t)q * N_sink * N_sink;
-        if (sinkhorn_layers(run, w.seq + (size_t)q * N_sink * SH_ROW, RANK_SH_CHUNK, sh.a)) return 1;
+        if (sinkhorn_layers(run, e->sw, w.seq + (size_t)q * N_sink * SH_ROW, RANK_SH_CHUNK, sh.a)) return 1;
     }
     hipLaunchKernelGGL(k_sinkhorn_assign, dim3(Qpad), dim3(64), 0, s, w.fc, N_sink, e->sw.n_iters, e->sw.tau, (float*)nullptr, w.assign);
     LAUNCHCHK();

@@ -76,47 +76,6 @@ __global__ __launch_bounds__(256) void k_layernorm512(const float* __restrict__ 
     layernorm512_row<false>(x, w, b, rows, out, nullptr, nullptr);
 }
 
-// 1 / (1 - p) of the p an S-SSP training forward applied, from its tape's header (layout: SSP_TAPE_HDR_INTS below)
-__device__ __forceinline__ float ssp_keep_scale(const int* __restrict__ hdr) { return 1.0f / (1.0f - __int_as_float(hdr[1])); }
-
-// The finish of every dense product of the ordering models: out = epilogue(sum of slabs), the terms and their order as stated at SspProd
-// (ssp.inc.h).  ONE source; which terms exist is a compile-time choice (run_products picks the instance from the product's fields), so a
-// launch carries no load and no test for a term its product does not have:
-//   LIN    bias / act / residual may be present (each skipped when NULL / SSP_ACT_NONE); without LIN the kernel is the plain slab sum
-//   GATE   FIN_KEEP: `gate` is the site's keep bytes, compact (M N);  FIN_RELU_Y: `gate` is the taped y (leading dimension ldg)
-// scale = 1 / (1 - p): the forward passes it, the backward passes the tape's header instead.  out may be residual's buffer (accumulation:
-// each thread reads its element before it writes it), hence no __restrict__ on the two.  The operands are loaded BEFORE the slabs are
-// added: these launches are mostly a few waves bound by memory latency, and all their loads should be in flight together.  The product and
-// the sum that follows it are two roundings, spelled out so that no compiler fuses them.
-constexpr int SSP_ACT_NONE = 0, SSP_ACT_RELU = 1, SSP_ACT_TANH = 2;
-constexpr int FIN_NONE = 0, FIN_KEEP = 1, FIN_RELU_Y = 2;
-template <bool LIN, int GATE>
-__global__ void k_prod_finish(const float* __restrict__ slabs, int nslab, long long stride, int M, int N, const float* __restrict__ bias, int act,
-                              const float* residual, long long ldr, float* out, long long ldo, const void* __restrict__ gate, long long ldg,
-                              const int* __restrict__ hdr, float scale) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)M * N) return;
-    const int m = (int)(i / N), n = (int)(i % N);
-    float b = 0.f, r = 0.f, y = 0.f;
-    uint8_t kept = 0;
-    if (LIN && bias) b = bias[n];
-    if (LIN && residual) r = residual[(long long)m * ldr + n];
-    if (GATE == FIN_KEEP) kept = static_cast<const uint8_t*>(gate)[i];
-    if (GATE == FIN_RELU_Y) y = static_cast<const float*>(gate)[(long long)m * ldg + n];
-    float s = slab_sum(slabs + i, nslab, stride);
-    if (LIN) {
-        if (bias) s = __fadd_rn(s, b);
-        if (act == SSP_ACT_RELU) s = fmaxf(s, 0.f);
-        else if (act == SSP_ACT_TANH) s = tanhf(s);
-    }
-    if (GATE != FIN_NONE) {
-        if (hdr) scale = ssp_keep_scale(hdr);
-        s = (GATE == FIN_KEEP ? kept != 0 : y > 0.f) ? __fmul_rn(s, scale) : 0.f;
-    }
-    if (LIN && residual) s = __fadd_rn(s, r);
-    out[(long long)m * ldo + n] = s;
-}
-
 // multi-head attention over short sequences: one wave per (sequence, head), lane = channel of the 64-wide head.
 //   logits[i][j] = q_i . k_j / 8, masked entries -1e3 (transformer_modules.py:36-53), softmax over ALL Tk keys, ctx = weights . v
 // mask_tok (optional): decoder self-attention, key j visible to query i iff j <= i and tok[s][j] != 0 (sort_modules.py:121-128);

@@ -180,14 +180,12 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     } else {
         t.h1s16 = t.h2s16 = t.s_t16 = t.g_t16 = t.att16 = nullptr;
     }
-    // GEMM slab scratch: 8 slabs of the largest product of the training path
+    // GEMM slab scratch: every slab of the largest product of the training path
     size_t big = std::max({4 * H * in1, V * H, 4 * H * in2, A * D, TB * H, TB * E, D * H, B * (in2 + 2 * H), H * in1, TB * V, TB * 6 * H});
-    t.scratch_floats = big * 8;
+    t.scratch_floats = big * GEMM_MAX_SLABS;
     t.scratch = b.take<float>(t.scratch_floats);
     return (b.off + 255) & ~size_t(255);
 }
-
-struct SegSpec { const float* A; int lda; const float* W; int ldw; int K; int a_cls = H2A_NONE; const uint16_t* A16 = nullptr; };
 
 // whole-pass bounds from the per-step ones (DW_step + j: max over the steps; DW_dpre1sum / DW_dpre2sum: the sums over t of dpre1 / dpre2 rows)
 // (nsum: rows one sum runs over - the T steps of a row, times the rows of an image when several share its statics)
@@ -206,68 +204,6 @@ __global__ void k_h2_dyn_fold(int* __restrict__ dyn, int T, int nsum) {
     }
 }
 
-// one problem, several K segments -> dst window (ldd), through the slab scratch
-static int gemm_to(vsr_handle* h, TrainCtx& t, hipStream_t s, int M, int N, const SegSpec* segs, int nseg, float* dst, long long ldd) {
-    GemmBuilder g;
-    GemmProb& p = g.prob(M, N, t.scratch, N);
-    for (int i = 0; i < nseg; ++i) GemmBuilder::seg(p, segs[i].A, segs[i].lda, nullptr, segs[i].W, segs[i].ldw, segs[i].K, segs[i].A16, segs[i].a_cls);
-    for (int i = 0; i < nseg; ++i) g.a_image_only = g.a_image_only || (segs[i].A16 && !h->bf16_on);
-    const int ns = g.finish(h);
-    for (int i = 0; i < nseg; ++i)
-        if (segs[i].A16 && !h->bf16_on && g.route.kernel != GemmKernel::H2A) return fail("training gemm: an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");
-    const long long stride = (long long)M * N;
-    if (ns == 1) {                          // every tile is produced by one workgroup: it writes the destination window itself
-        g.a.p[0].C = dst; g.a.p[0].ldc = (int)ldd; g.a.p[0].slab_stride = 0;
-        if (g.launch(s, h)) return fail("training gemm launch failed");
-        return 0;
-    }
-    if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small (%lld x %d)", stride, ns);
-    g.a.p[0].slab_stride = stride;
-    if (g.launch(s, h)) return fail("training gemm launch failed");
-    hipLaunchKernelGGL(k_slab_reduce_2d, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch, ns, stride, M, N, dst, ldd);
-    return 0;
-}
-static int gemm_to1(vsr_handle* h, TrainCtx& t, hipStream_t s, int M, int N, int K, const float* A, int lda, const float* W, int ldw,
-                    float* dst, long long ldd, int a_cls = H2A_NONE, bool a_is_image = false) {
-    // a_is_image: A is a transposed gradient that transpose() wrote as an fp16-pair image IN PLACE of the fp32 values (f16x2 flavour)
-    SegSpec sg{A, lda, W, ldw, K, a_cls, a_is_image ? reinterpret_cast<const uint16_t*>(A) : nullptr};
-    return gemm_to(h, t, s, M, N, &sg, 1, dst, ldd);
-}
-// Up to four INDEPENDENT products (one K segment each) in ONE launch (round 6): the weight-gradient GEMMs of a bucket.  Alone, a
-// 4000 x 1000 gradient is 128 tiles of 63 k-tiles - cut in halves to fill the chip, i.e. two slabs and a reducing launch - and a
-// 1000 x 1000 one 32 tiles cut in eight; two or three of them together are ~256 whole tiles: no slabs, no reduce, one launch.
-struct GProb { int M, N, K; const float* A; int lda; const float* W; int ldw; float* dst; long long ldd; int a_cls; bool a_img; };
-static int gemm_group(vsr_handle* h, TrainCtx& t, hipStream_t s, const GProb* P, int n) {
-    if (n <= 0) return 0;
-    GemmBuilder g;
-    for (int i = 0; i < n; ++i) {
-        GemmProb& p = g.prob(P[i].M, P[i].N, t.scratch, P[i].N);
-        GemmBuilder::seg(p, P[i].A, P[i].lda, nullptr, P[i].W, P[i].ldw, P[i].K, P[i].a_img ? reinterpret_cast<const uint16_t*>(P[i].A) : nullptr, P[i].a_cls);
-        g.a_image_only = g.a_image_only || (P[i].a_img && !h->bf16_on);
-    }
-    const int ns = g.finish(h);
-    for (int i = 0; i < n; ++i)
-        if (P[i].a_img && !h->bf16_on && g.route.kernel != GemmKernel::H2A) return fail("training gemm group: an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");
-    if (ns == 1) {                          // every tile is produced by one workgroup: written in place
-        for (int i = 0; i < n; ++i) { g.a.p[i].C = P[i].dst; g.a.p[i].ldc = (int)P[i].ldd; g.a.p[i].slab_stride = 0; }
-        if (g.launch(s, h)) return fail("training gemm group launch failed");
-        return 0;
-    }
-    size_t off[4], tot = 0;
-    for (int i = 0; i < n; ++i) {
-        g.a.p[i].nslab = gemm_tight_slabs(g.a, i);
-        off[i] = tot;
-        tot += (size_t)P[i].M * P[i].N * g.a.p[i].nslab;
-    }
-    if (tot > t.scratch_floats) return fail("training scratch too small for a gemm group (%zu floats)", tot);
-    for (int i = 0; i < n; ++i) { g.a.p[i].C = t.scratch + off[i]; g.a.p[i].slab_stride = (long long)P[i].M * P[i].N; }
-    if (g.launch(s, h)) return fail("training gemm group launch failed");
-    for (int i = 0; i < n; ++i) {
-        const long long stride = (long long)P[i].M * P[i].N;
-        hipLaunchKernelGGL(k_slab_reduce_2d, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch + off[i], g.a.p[i].nslab, stride, P[i].M, P[i].N, P[i].dst, P[i].ldd);
-    }
-    return 0;
-}
 // deterministic two-stage column sum: out[c] (and out2[c]) = sum over rows of X[r][c], through `part` (COLSUM_CHUNKS x C floats: the idle
 // slab scratch).  Shared with the ordering models' backward passes (ssp.inc.h).
 static void colsum(hipStream_t s, float* part, const float* X, long long ld, int R, int C, float* out, float* out2 = nullptr) {
@@ -450,8 +386,8 @@ static int train_xproj(vsr_handle* h, TrainCtx& t, const StepOperands& o, float*
     const long long stride = (long long)o.M * 6 * h->d.rnn_size;
     if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
     for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-    if (g.launch(s, h)) return fail("train x-projection gemm launch failed");
-    hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(stride, 256)), dim3(256), 0, s, t.scratch, ns, stride, stride, dst);
+    if (g.launch(s, h, &h->prof)) return fail("train x-projection gemm launch failed");
+    slab_sum_to(s, t.scratch, ns, o.M, 6 * h->d.rnn_size, dst);
     LAUNCHCHK();
     return 0;
 }
@@ -464,7 +400,7 @@ static int train_vocab_gemm(vsr_handle* h, TrainCtx& t, const StepOperands& o, c
     const long long stride = (long long)o.M * h->d.vocab_size;
     if ((ns_max && ns > ns_max) || (size_t)stride * ns > t.scratch_floats) { fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns); return 0; }
     g.a.p[0].slab_stride = stride;
-    if (g.launch(s, h)) { fail("train S6 gemm launch failed"); return 0; }
+    if (g.launch(s, h, &h->prof)) { fail("train S6 gemm launch failed"); return 0; }
     return ns;
 }
 // ... and the dense head over them: whole log_softmax rows -> out (o.M, V)
@@ -534,7 +470,7 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
             add_lstm1(g, d, w, o, c.scratch, L1_H2 | L1_H1);
             ns = g.finish(h);
             for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
-            if (g.launch(s, h)) return fail("train S1 gemm launch failed");
+            if (g.launch(s, h, &h->prof)) return fail("train S1 gemm launch failed");
         }
         const int nblk = d.h2_first_lstm ? 6 : 5;      // without h2 in the input the shift-gate block has no recurrent part
         with_shared_rows(K, [&](auto SH, int k) {
@@ -547,7 +483,7 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
         add_s2(g, d, w, o, c.scratch);
         const int ns = g.finish(h);
         const S2Layout l = place_s2(g, d, B, c.scratch, ns);
-        if (g.launch(s, h)) return fail("train S2 gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("train S2 gemm launch failed");
         // (Round 5: k_gate2's work inside the attention kernel's row blocks, as in decoding, with the sentinel / s_a / the shift gate stored
         // on the way for the backward pass: measured at no gain - 10.99-11.06 k against 10.85-11.10 k samples/s, profiles/r05_h_* - and not kept.)
         const long long n = (long long)B * (H + A + D + A);
@@ -563,7 +499,7 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
         float* gas = c.scratch + stride * ns;
         g.a.p[0].slab_stride = stride;
         g.a.p[1].C = gas; g.a.p[1].slab_stride = stride_g;
-        if (g.launch(s, h)) return fail("train S5 gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("train S5 gemm launch failed");
         GateLogitArgs gl{gas, ns, stride_g, q.hA, w.att_g_weight, c.zsum, nullptr, q.slot, K, c.L, B, A,
                          lg_out, lg_stride};
         gl.ga_out = q.ga;
@@ -619,7 +555,7 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         // S6 for all steps at once, sparse head: the rows in their natural (t, b) order (state slots 1 .. T: nothing to gather), then
         // k_vocab_select: the log_softmax rows stay in t.dlogits, the targets' entries go to the caller's (rows, T) tensor
         all.h2_new = t.h2s + BH; all.h2_new16 = im ? t.h2s16 + BH * 2 : nullptr;
-        const int ns = train_vocab_gemm(h, t, all, nullptr, 8, s);           // (k_vocab_select sums at most 8 slabs: slab_sum4)
+        const int ns = train_vocab_gemm(h, t, all, nullptr, GEMM_MAX_SLABS, s);           // (k_vocab_select sums at most that many slabs: slab_sum4)
         if (!ns) return 1;
         const long long stride = (long long)TB * V;
         const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;
@@ -839,7 +775,7 @@ struct GradRow {
     // (train_operands entries: K = their padded row count, N = tx's columns, exponent slot and image-in-place of A = ty's)
     int ty, r0, M, tx, col, ldd;
     int slot;                  // the dynamic slot of these rows where ty is NOT one image of one bound (-1: ty's own)
-    int launch;                // adjacent products with the same id share a gemm_group launch; ALONE: gemm_to1.  Which products share a
+    int launch;                // adjacent products with the same id share a run_products launch; ALONE: one of its own.  Which products share a
                                // launch decides tiles and slabs, i.e. the bits
     int pre;                   // code that stays code, run before the product: the sum over t and its transpose (PRE_DPRE2SUM); a memset
                                // INSTEAD of the product when no region row is valid (PRE_VA)
@@ -974,7 +910,7 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
         g.a.p[0].C = C0; g.a.p[0].slab_stride = a.st0;
         g.a.p[1].C = C1; g.a.p[1].slab_stride = a.st1;
         g.a.p[2].C = C2; g.a.p[2].slab_stride = a.st2;
-        if (g.launch(s, h)) return fail("bwd gemm 1 launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("bwd gemm 1 launch failed");
         // datt; dg_t -> shift-gate backward (dq into dpre1[:, 5H:6H], dtc); dh1 so far (= dh1_a + carry, into dh_tot) and the
         // hh part of the new dh2 carry (the LSTM1-input part is added by the next k_bwd_head from GEMM 3's slabs)
         a.C0 = C0; a.C1 = C1; a.C2 = C2; a.M = B; a.H = H; a.D = D;
@@ -1014,7 +950,7 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
         float *Ca = t.scratch, *Cb = Ca + st * ns;
         g.a.p[0].C = Ca; g.a.p[0].slab_stride = st;
         g.a.p[1].C = Cb; g.a.p[1].slab_stride = st;
-        if (g.launch(s, h)) return fail("bwd gemm 2 launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("bwd gemm 2 launch failed");
         hipLaunchKernelGGL(k_bwd_tail, dim3(cdiv((long long)BH, 256)), dim3(256), 0, s, Ca, Cb, ns, st, t.dh_tot, t.dtc, t.dc1_c[cb], q.g1, q.c1n,
                            tt > 0 ? q.c1o : (float*)nullptr, B, H, q.dpre1, t.dc1_c[cb ^ 1], p.ptr(y + DY_dpre1));
     }
@@ -1026,7 +962,7 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
         p.ns3 = g.finish(h);
         g.a.p[0].C = t.scratch; g.a.p[0].slab_stride = st3;
         if (d.h2_first_lstm) { g.a.p[1].C = t.scratch + st3 * p.ns3; g.a.p[1].slab_stride = st3; }
-        if (g.launch(s, h)) return fail("bwd gemm 3 launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("bwd gemm 3 launch failed");
     }
     LAUNCHCHK();
     return 0;
@@ -1111,7 +1047,14 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     // ---- phase 0: dlogits (t,b) and the vocabulary part of dh2 for every step
     if (t.sparse) hipLaunchKernelGGL(k_dlogits_sel, dim3(TB), dim3(256), 0, s, grad_logp_words, t.tgt32, B, T, V, Vp, t.dlogits, p.ptr(DW_dlogits));
     else hipLaunchKernelGGL(k_dlogits_tb, dim3(TB), dim3(256), 0, s, t.logp_w, grad_logp_words, B, T, V, Vp, t.dlogits, p.ptr(DW_dlogits));
-    if (gemm_to1(h, t, s, TB, H, Vp, t.dlogits, Vp, t.wT_out, Vp, t.dh2_voc, H, p.slot(DW_dlogits))) return 1;
+    // the dense products outside the time loop (products.h): written in place where no tile is split, else summed out of the slab scratch
+    const ProdRun run{h, &h->prof, s, t.scratch, t.scratch_floats, nullptr, 1.f, who};
+    auto in_place = [](Prod q) { q.in_place = true; return q; };
+    {
+        Prod q = in_place(prod1(TB, H, Vp, t.dlogits, Vp, t.wT_out, Vp, t.dh2_voc, H));
+        q.seg[0].a_cls = p.slot(DW_dlogits);
+        if (run_product(run, q)) return 1;
+    }
     LAUNCHCHK();
 
     // ---- phase A: reverse time (the cell-carry buffers alternate)
@@ -1155,8 +1098,9 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     auto product = [&](const GradRow& r) {              // (the operands by entry: K = their padded rows)
         const TOperand &Y = ops[r.ty], &X = ops[r.tx];
         const int Kp = (int)Y.ld_out;
-        return GProb{r.M, X.C, Kp, t.*Y.buf + (size_t)r.r0 * Kp, Kp, t.*X.buf, (int)X.ld_out, G[r.g] + r.col, r.ldd,
-                     p.slot(a_img[r.ty] || r.slot < 0 ? Y.slot : r.slot), a_img[r.ty]};
+        Prod q = in_place(prod1(r.M, X.C, Kp, t.*Y.buf + (size_t)r.r0 * Kp, Kp, t.*X.buf, (int)X.ld_out, G[r.g] + r.col, r.ldd));
+        q.seg[0].a_cls = p.slot(a_img[r.ty] || r.slot < 0 ? Y.slot : r.slot); q.seg[0].a_img = a_img[r.ty];
+        return q;
     };
     int bucket = 0;
     for (size_t i = 0; i < rows.size();) {
@@ -1174,18 +1118,17 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
                 sum_over_t(s, t.dpre2, T, K, B, 4 * H, t.dpre2sum);
                 tr(TY_dpre2sum, false, -1, nullptr);
             }
-            const GProb P = product(r);
-            if (gemm_to1(h, t, s, P.M, P.N, P.K, P.A, P.lda, P.W, P.ldw, P.dst, P.ldd, P.a_cls, P.a_img)) return 1;
+            if (run_product(run, product(r))) return 1;
             ++i;
         } else if (r.kind == GradRow::PROD) {           // the run of products that share this launch
-            GProb P[4];
+            Prod P[GEMM_MAX_PROB];
             int n = 0;
             for (; i < rows.size() && rows[i].kind == GradRow::PROD && rows[i].launch == r.launch && rows[i].bucket == r.bucket; ++i) {
                 if (!rows[i].on) continue;
-                if (n == 4) return fail("%s: more than four products in one launch of the gradient table", who);
+                if (n == GEMM_MAX_PROB) return fail("%s: more than %d products in one launch of the gradient table", who, GEMM_MAX_PROB);
                 P[n++] = product(rows[i]);
             }
-            if (gemm_group(h, t, s, P, n)) return 1;
+            if (n && run_products(run, P, n)) return 1;
         } else if (r.kind == GradRow::COLSUM) {         // (through the idle slab scratch, like colsum())
             const bool shared = i > 0 && rows[i - 1].kind == GradRow::COLSUM && rows[i - 1].src == r.src && rows[i - 1].bucket == r.bucket;
             if (!shared) hipLaunchKernelGGL(k_colsum, dim3(cdiv(r.C, 64), COLSUM_CHUNKS), dim3(256), 0, s, t.*r.src, (long long)r.ld, TB, r.C, t.scratch);
@@ -1193,10 +1136,12 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
             ++i;
         } else {   // EMBED: dx = dpre1 . [W_ih1 ; W_is ; W_ig][:, x columns], summed onto the rows that were looked up (ordered, no atomics)
             const int xoff = (d.h2_first_lstm ? H : 0) + D, sP1 = p.slot(DW_step + DY_dpre1), sQ = p.slot(DW_step + DY_dq);
-            SegSpec sg[3] = {{t.dpre1, 6 * H, t.wT_ih1 + (size_t)xoff * 4 * H, 4 * H, 4 * H, sP1},
-                             {t.dpre1 + 4 * H, 6 * H, t.wT_is + (size_t)xoff * H, H, H, sP1},
-                             {t.dpre1 + 5 * H, 6 * H, t.wT_ig + (size_t)xoff * H, H, H, sQ}};
-            if (gemm_to(h, t, s, TB, E, sg, 3, t.dx_all, E)) return 1;
+            Prod q = in_place(prod1(TB, E, 4 * H, t.dpre1, 6 * H, t.wT_ih1 + (size_t)xoff * 4 * H, 4 * H, t.dx_all, E));
+            q.seg[0].a_cls = sP1;
+            q.seg[1] = ProdSeg{t.dpre1 + 4 * H, 6 * H, t.wT_is + (size_t)xoff * H, H, H, sP1};
+            q.seg[2] = ProdSeg{t.dpre1 + 5 * H, 6 * H, t.wT_ig + (size_t)xoff * H, H, H, sQ};
+            q.nseg = 3;
+            if (run_product(run, q)) return 1;
             HIPCHK(hipMemsetAsync(G[r.g], 0, (size_t)V * E * sizeof(float), s));
             hipLaunchKernelGGL(k_embed_grad_rows, dim3(TB), dim3(256), 0, s, t.dx_all, t.word32, TB, E, G[r.g]);
             ++i;

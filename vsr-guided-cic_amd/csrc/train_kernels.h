@@ -149,16 +149,6 @@ __global__ __launch_bounds__(256) void k_transpose_multi(const TransMulti m, con
     transpose_tile<false, IMG>(m.in[i], m.ld_in[i], nullptr, m.R[i], m.C[i], m.out[i], m.ld_out[i], m.out16[i], exps, m.slot[i], nullptr, local % tc, local / tc);
 }
 
-// dst (rows, w) window with leading dimension ldd  =  sum of nslab compact (rows, w) slabs
-__global__ void k_slab_reduce_2d(const float* __restrict__ slabs, int nslab, long long stride, int rows, int w,
-                                 float* __restrict__ dst, long long ldd) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)rows * w) return;
-    const int r = (int)(i / w), c = (int)(i % w);
-    float s = slab_sum(slabs + i, nslab, stride);
-    dst[(long long)r * ldd + c] = s;
-}
-
 // column sums: out[c] = sum_r X[r][c]   (bias gradients).  Two deterministic stages: grid (C/64, NCH) blocks each sum
 // a chunk of rows into part[chunk][c], then k_colsum_finish adds the NCH partials in order.
 constexpr int COLSUM_CHUNKS = 32;
@@ -742,14 +732,14 @@ __global__ void k_train_indices(const int64_t* __restrict__ word_in, const int64
 // - the rows of t.dlogits, (t, b) order, stride Vp = up8(V), idle during the forward - and hands out logp_sel (rows, T) only;
 // vsr_train_backward_selected turns the rows into dlogits in place.  No (B, T, V) tensor exists on either side.
 
-// sum of up to 8 slabs + bias, four columns at once: every slab's load is issued before the first add (as slab_sum)
+// sum of up to GEMM_MAX_SLABS slabs + bias, four columns at once: every slab's load is issued before the first add (as slab_sum)
 __device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, int nslab, long long stride, const float* __restrict__ bias) {
-    float4 v[8];
+    float4 v[GEMM_MAX_SLABS];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 s = *reinterpret_cast<const float4*>(bias);
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
         if (k < nslab) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
     return s;
 }

@@ -119,15 +119,9 @@ struct vsr_handle : GemmState {         // (gemm_route.h: the GEMM flavours swit
     int adam_blocks = 0;         // grid budget of vsr_adam_step: the workgroups the device holds at once (set at its first call)
     int split_pre1 = 1;          // the h1 part of the next step's LSTM1 sums in the S5 launch, the h2 part with the vocabulary (run_step; VSR_SPLIT_PRE1=0: all of it with the vocabulary, as in rounds 2-5)
     Ctx c;
-    // measurement
-    bool profiling = false;
     hipEvent_t ev_count = nullptr;   // prepare(): the row count has reached the host
     int* host_back = nullptr;        // pinned landing place of that read-back (2 ints)
-    std::vector<hipEvent_t> ev;      // pool, pairs (start, stop)
-    size_t ev_used = 0;
-    double prof_flops = 0, prof_bytes = 0;
-    int prof_every = 1;              // time every prof_every-th GEMM launch (1 = all of them)
-    long long prof_seen = 0;         // GEMM launches since vsr_profile_begin*
+    GemmProfile prof;                // measurement (vsr_profile_*): every GEMM launch of the decoder is handed it
 };
 
 // ---------------------------------------------------------------------------------------------- workspace
@@ -184,7 +178,7 @@ static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
     c.att = b.take<float>(M * D);
     c.zsum = b.take<float>(M);
     c.lg = b.take<float>(M * 2);
-    c.ga_slabs = b.take<float>(M * A * 8);
+    c.ga_slabs = b.take<float>(M * A * GEMM_MAX_SLABS);
     c.top_v = b.take<float>(M * KMAX);
     c.top_i = b.take<int>(M * KMAX);
     c.hist_parent = b.take<int>(T * M);
@@ -196,12 +190,12 @@ static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
     c.forced_w32 = b.take<int>(T * M);
     c.forced_g32 = b.take<int>(T * M);
     c.tmp_i64 = b.take<int64_t>(T * M);
-    // split-K slab scratch: the widest stage, 8 slabs
+    // split-K slab scratch: the widest stage, GEMM_MAX_SLABS slabs
     size_t widest = std::max({6 * H, (H + A) + (D + A), 4 * H + A, V});
     size_t stage = std::max(M * widest, B * 6 * H);
-    c.scratch_floats = std::max(stage * 8, std::max(rows, prows) * A * 8);   // att_va slabs of prepare(): over the bank rows when indexed
+    c.scratch_floats = std::max(stage, std::max(rows, prows) * A) * GEMM_MAX_SLABS;   // att_va slabs of prepare(): over the bank rows when indexed
     c.scratch = b.take<float>(c.scratch_floats);
-    c.pre1 = b.take<float>(M * 6 * H * 8);
+    c.pre1 = b.take<float>(M * 6 * H * GEMM_MAX_SLABS);
     b.off = (b.off + 15) & ~size_t(15);
     for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j) c.st16[i][j] = b.take<uint16_t>(2 * ((M * H + 7) & ~size_t(7)));      // (bf16: 2 bytes per element; fp16 pairs: 4)
@@ -212,24 +206,30 @@ static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
 }
 
 // ------------------------------------------- GEMM launch (routing and planning: GemmBuilder::finish, gemm_route.h; the kernel switch: gemm_dispatch.h)
-int vsr::GemmBuilder::launch(hipStream_t s, vsr_handle* h) {
+int vsr::GemmBuilder::launch(hipStream_t s, const GemmState* h, GemmProfile* p) {
     if (stale_h2) return fail("f16x2 flavour: a GEMM launch names a transposed operand of the training pass that only exists as an fp16-pair image but cannot take an f16x2 kernel (gemm mode / tile override changed since vsr_train_forward, or K / leading dimensions not multiples of 8)");
     if (stale_w) return fail("bf16 mode: a GEMM launch names a transposed operand that only exists as a bf16 image but cannot take the bf16 kernel (K / leading dimensions must be multiples of 8)");
     if (!h->gk.xcd_groups) a.xcd_chunk = 0;              // VSR_XCD_GROUPS=0: ceil(G / 8) workgroups per XCD whatever the m-groups (A/B)
-    const bool prof = h->profiling && (h->prof_seen++ % h->prof_every) == 0 && h->ev_used + 2 <= h->ev.size();
-    if (prof) (void)hipEventRecord(h->ev[h->ev_used], s);
+    const bool prof = p && p->on && (p->seen++ % p->every) == 0 && p->ev_used + 2 <= p->ev.size();
+    if (prof) (void)hipEventRecord(p->ev[p->ev_used], s);
     gemm_dispatch(route, a, s);
     if (prof) {
-        (void)hipEventRecord(h->ev[h->ev_used + 1], s);
-        h->ev_used += 2;
-        h->prof_flops += gemm_flops(a);
-        h->prof_bytes += gemm_bytes(a, route.kernel == GemmKernel::BF16W ? 2 : 4);      // (quirk kept: the all-DMA bf16 kernel, B16A, is accounted with 4-byte weights)
+        (void)hipEventRecord(p->ev[p->ev_used + 1], s);
+        p->ev_used += 2;
+        p->flops += gemm_flops(a);
+        p->bytes += gemm_bytes(a, route.kernel == GemmKernel::BF16W ? 2 : 4);      // (quirk kept: the all-DMA bf16 kernel, B16A, is accounted with 4-byte weights)
     }
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 constexpr int VOCAB_LDS_MAX = 12288;    // 48 KB of dynamic LDS for the combined row
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// dst (M, N), compact = the sum of ns compact (M, N) slabs: the finish kernel without an epilogue term
+static void slab_sum_to(hipStream_t s, const float* slabs, int ns, int M, int N, float* dst) {
+    const long long tot = (long long)M * N;
+    hipLaunchKernelGGL((k_prod_finish<false, FIN_NONE>), dim3(cdiv(tot, 256)), dim3(256), 0, s, slabs, ns, tot, M, N, nullptr, SSP_ACT_NONE, nullptr, 0LL, dst,
+                       (long long)N, nullptr, 0LL, nullptr, 1.f);
+}
 
 // ---------------------------------------------------------------------------------------------- API: lifetime
 extern "C" int vsr_abi_version(void) { return VSR_ABI_VERSION; }
@@ -264,7 +264,7 @@ extern "C" int vsr_create(const vsr_dims* dims, vsr_handle** out) {
 
 extern "C" void vsr_destroy(vsr_handle* h) {
     if (!h) return;
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
     if (h->ev_count) (void)hipEventDestroy(h->ev_count);
     if (h->host_back) (void)hipHostFree(h->host_back);
     free_train_ctx(h->tc);
@@ -276,40 +276,42 @@ extern "C" void vsr_destroy(vsr_handle* h) {
 extern "C" int vsr_profile_begin_sampled(vsr_handle* h, int32_t every);
 extern "C" int vsr_profile_begin(vsr_handle* h) { return vsr_profile_begin_sampled(h, 1); }
 
-extern "C" int64_t vsr_profile_seen(const vsr_handle* h) { return h ? (int64_t)h->prof_seen : 0; }
-extern "C" double vsr_profile_bytes(const vsr_handle* h) { return h ? h->prof_bytes : 0.0; }
+extern "C" int64_t vsr_profile_seen(const vsr_handle* h) { return h ? (int64_t)h->prof.seen : 0; }
+extern "C" double vsr_profile_bytes(const vsr_handle* h) { return h ? h->prof.bytes : 0.0; }
 
 extern "C" int vsr_profile_begin_sampled(vsr_handle* h, int32_t every) {
     if (!h) return fail("vsr_profile_begin: null handle");
     if (every < 1) return fail("vsr_profile_begin_sampled: every must be >= 1");
-    h->prof_every = every;
-    h->prof_seen = 0;
+    GemmProfile& p = h->prof;
+    p.every = every;
+    p.seen = 0;
     const size_t want = 2 * 4096;
-    while (h->ev.size() < want) {
+    while (p.ev.size() < want) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
-        h->ev.push_back(e);
+        p.ev.push_back(e);
     }
-    h->ev_used = 0;
-    h->prof_flops = 0;
-    h->prof_bytes = 0;
-    h->profiling = true;
+    p.ev_used = 0;
+    p.flops = 0;
+    p.bytes = 0;
+    p.on = true;
     return 0;
 }
 
 extern "C" int vsr_profile_end(vsr_handle* h, void* stream, double* gemm_ms, int64_t* gemm_launches, double* gemm_flops) {
-    if (!h || !h->profiling) return fail("vsr_profile_end: profiling not active");
+    if (!h || !h->prof.on) return fail("vsr_profile_end: profiling not active");
+    GemmProfile& p = h->prof;
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     double ms = 0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
+    for (size_t i = 0; i + 1 < p.ev_used; i += 2) {
         float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
+        HIPCHK(hipEventElapsedTime(&t, p.ev[i], p.ev[i + 1]));
         ms += t;
     }
     if (gemm_ms) *gemm_ms = ms;
-    if (gemm_launches) *gemm_launches = (int64_t)(h->ev_used / 2);
-    if (gemm_flops) *gemm_flops = h->prof_flops;
-    h->profiling = false;
+    if (gemm_launches) *gemm_launches = (int64_t)(p.ev_used / 2);
+    if (gemm_flops) *gemm_flops = p.flops;
+    p.on = false;
     return 0;
 }
 
@@ -349,7 +351,7 @@ static const int XPROJ_CHUNK = 512;
 extern "C" size_t vsr_decode_cache_floats(const vsr_handle* h) {
     if (!h) return 0;
     const size_t V = h->d.vocab_size, H = h->d.rnn_size;
-    return V * 6 * H + (size_t)XPROJ_CHUNK * 6 * H * 8 + 64;
+    return V * 6 * H + (size_t)XPROJ_CHUNK * 6 * H * GEMM_MAX_SLABS + 64;
 }
 extern "C" int vsr_build_decode_cache(vsr_handle* h, float* buf, size_t n_floats, void* stream) {
     if (!h || !h->bound) return fail("vsr_build_decode_cache: weights not bound");
@@ -373,8 +375,8 @@ extern "C" int vsr_build_decode_cache(vsr_handle* h, float* buf, size_t n_floats
         const int ns = g.finish(h);
         const long long stride = (long long)m * 6 * H;
         for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-        if (g.launch(s, h)) return fail("decode cache gemm launch failed");
-        hipLaunchKernelGGL(k_slab_reduce, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, s, slabs, ns, stride, stride, buf + (size_t)v0 * 6 * H);
+        if (g.launch(s, h, &h->prof)) return fail("decode cache gemm launch failed");
+        slab_sum_to(s, slabs, ns, m, 6 * H, buf + (size_t)v0 * 6 * H);
     }
     LAUNCHCHK();
     h->xproj = buf;
@@ -773,7 +775,7 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
         const int ns = g.finish(h);
         const long long stride = (long long)B * 6 * H;
         for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-        if (g.launch(s, h)) return fail("vproj gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("vproj gemm launch failed");
         const long long n = (long long)B * 6 * H;
         hipLaunchKernelGGL(k_vproj_finish, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, ns, stride, B, H,
                            w.lstm1_bias_ih, w.lstm1_bias_hh, w.W1_is_bias, w.W1_hs_bias, w.W1_ig_bias, w.W1_hg_bias, c.vproj);
@@ -787,8 +789,8 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
         const int ns = g.finish(h);
         const long long stride = (long long)B * 4 * H;
         g.a.p[0].slab_stride = stride;
-        if (g.launch(s, h)) return fail("vproj2 gemm launch failed");
-        hipLaunchKernelGGL(k_slab_reduce, dim3(cdiv(stride, 256)), dim3(256), 0, s, c.scratch, ns, stride, stride, c.vproj2);
+        if (g.launch(s, h, &h->prof)) return fail("vproj2 gemm launch failed");
+        slab_sum_to(s, c.scratch, ns, B, 4 * H, c.vproj2);
         LAUNCHCHK();
     }
     c.bounded = bound > 0;
@@ -813,7 +815,7 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
         if ((size_t)stride * ns > c.scratch_floats)
             return fail("%s: att_va slabs (%lld x %d floats) exceed the workspace scratch (%zu)", who, stride, ns, c.scratch_floats);
         g.a.p[0].slab_stride = stride;
-        if (g.launch(s, h)) return fail("att_va gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("att_va gemm launch failed");
         hipLaunchKernelGGL(k_slab_reduce_scatter, dim3(cdiv(stride, 4 * 256)), dim3(256), 0, s, c.scratch, ns, stride, c.nvalid, A, c.vlist, c.P,
                            bound > 0 ? c.nvalid_dev : (const int*)nullptr);
         LAUNCHCHK();
@@ -974,7 +976,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
         if (g.a.nprob > 0) {
             ns = g.finish(h);
             for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride1;
-            if (g.launch(s, h)) return fail("S1 gemm launch failed");
+            if (g.launch(s, h, &h->prof)) return fail("S1 gemm launch failed");
         }
         hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns, stride1, c.vproj, io.rpi,
                            io.parent, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, io.word_prev, nblk, 0, h1n16, s_t16, isc);
@@ -985,7 +987,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
         add_s2(g, d, w, o, c.scratch);
         const int ns = g.finish(h);
         const S2Layout l = place_s2(g, d, M, c.scratch, ns);
-        if (g.launch(s, h)) return fail("S2 gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("S2 gemm launch failed");
         // k_gate2's work (g_t, hA, s_a, sentinel from the S2 slabs) is done by the attention kernel's row blocks themselves
         const Gate2Args g2{c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias, H, c.g_t, c.hA, g_t16, isc};
         launch_attend(h, s, g2, M, io.rpi, io.slot, io.fixed_slot, c.hA, c.sa, c.sent, c.att, io.alpha_out, att16, att_exp);
@@ -1016,7 +1018,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
         for (int i = 1; i < g6.a.nprob; ++i) ns_pre1 = std::max(ns_pre1, gemm_tight_slabs(g6.a, i));
     };
     plan56(io.s1_for_next && h->split_pre1 && d.h2_first_lstm);
-    if (ns_h1 > 0 && ns_h1 + ns_pre1 > 8) plan56(false);
+    if (ns_h1 > 0 && ns_h1 + ns_pre1 > GEMM_MAX_SLABS) plan56(false);
     // ---- S5
     GateLogitArgs gate_args;
     {
@@ -1030,7 +1032,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
         c.pre1_skip5 = ns_h1;
         const int ns_lstm2 = g.a.p[0].nslab;
         if ((size_t)stride * ns5 > c.scratch_floats) return fail("S5: slabs exceed the workspace scratch");
-        if (g.launch(s, h)) return fail("S5 gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("S5 gemm launch failed");
         hipLaunchKernelGGL(k_lstm2, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns_lstm2, stride, w.lstm2_bias_ih,
                            w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, io.rpi, io.parent, c2o, M, H, h2n, c2n, h2n16, isc);
         // the gate logits (z_g, log_softmax([z_g, zsum]), step :185-188) are nobody's input before the selection: the
@@ -1048,11 +1050,11 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
             g.a.p[i].C += c.pre1_skip5 * stride1; g.a.p[i].slab_stride = stride1; g.a.p[i].nslab = ns_pre1;
         }
         c.pre1_ns = (g.a.nprob > 1 ? ns_pre1 : ns6) + c.pre1_skip5; c.pre1_nblk = nblk6; c.pre1_stride = stride1;
-        if (c.pre1_ns > 8) return fail("S6: the LSTM1 sums of the next step would need %d slabs (8 fit)", c.pre1_ns);
+        if (c.pre1_ns > GEMM_MAX_SLABS) return fail("S6: the LSTM1 sums of the next step would need %d slabs (%d fit)", c.pre1_ns, GEMM_MAX_SLABS);
         // the vocabulary tiles (K = H) are cut into fewer pieces than the LSTM1 tiles (K = 2 H) they share the launch with: k_vocab
         // adds only the slabs they wrote (60 -> 40 MB of logits per beam-5 step)
         const int ns_vocab = g.a.p[0].nslab = gemm_tight_slabs(g.a, 0);
-        if (g.launch(s, h)) return fail("S6 gemm launch failed");
+        if (g.launch(s, h, &h->prof)) return fail("S6 gemm launch failed");
         launch_vocab(h, s, io, c.scratch, ns_vocab, stride, gate_args);
     }
     c.st16_ok[io.cur ^ 1] = sh;               // the new state's bf16 images exist iff this step wrote them
@@ -1276,6 +1278,7 @@ extern "C" int vsr_step(vsr_handle* h, int32_t t, int32_t rows_per_image, const 
 }
 
 // ---------------------------------------------------------------------------------------------- training path
+#include "products.h"
 #include "train.inc.h"
 #include "cider.inc.h"
 #include "ssp.inc.h"
