@@ -1,7 +1,8 @@
 """The grouped GEMM kernels on their own, outside the decoder: tools/gemm_bench `fuzz` launches random ragged grouped problems
 (1-3 problems of 1-3 k segments, row gathers, K tails, odd leading dimensions and offsets of the output window, 8-256 workgroup
-slots, stream-K ranges and k-aligned pieces) and compares the slab sums with an fp64 host reference; columns outside the output
-window must stay untouched.  Variants: the fp32 64x64 / 128x64 / 128x128 kernels, the rows-16 kernel, and the two 16-wave kernels
+slots, stream-K ranges and k-aligned pieces) and compares the slab sums with an fp64 host reference; C starts as a finite sentinel,
+so an element left unwritten (a missed zero-fill of an unused slab) fails the sum, and columns outside the output window and slabs
+beyond a problem's own must stay untouched.  Variants: the fp32 64x64 / 128x64 / 128x128 kernels, the rows-16 kernel, and the two 16-wave kernels
 with hand-written asynchronous loads (bf16 with fp32 A and - 1665 - with bf16 images of A: tolerance of bf16 operands; f32x3 in both
 tile widths, 128 x 256 and - "3300 21" - 128 x 128, and the weight-streaming f32x3 kernel of gemm_x3s.h - "3400 1" -: fp32 tolerance;
 the f16x2 kernels of gemm_h2.h on fp16-pair weight images with measured scale exponents - "5200 1" / "5200 21" the 16-wave tiles,

@@ -1,7 +1,7 @@
 """csrc/products.h, the planning half of the dense-product path (plan_products), on the CPU: tools/products_host.hip is built into a temp
 dir and asked to plan launches on a GemmState of 256 CUs, in the exact flavour (x3_on = false, the ordering models') and in f32x3.  What is
 held: what is refused, when a launch is written in place, and how the slabs of the others are placed in the scratch.  The slab counts are
-those of the planners (gemm_f32.h) at the commit that introduced this path."""
+those of the planners (gemm_grouped.h) at the commit that introduced this path."""
 import importlib.util
 import os
 import subprocess

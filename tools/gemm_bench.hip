@@ -285,6 +285,10 @@ __global__ __launch_bounds__(512) void feed_kernel(const float* __restrict__ A, 
 
 // ---- fuzz: random ragged grouped launches (1-3 problems, 1-3 k segments each, row gathers, K tails, odd leading dimensions of C,
 // both work decompositions) of the variant under test against an fp64 host reference.  `tools/gemm_bench fuzz <tm> <tn> [cases] [seed]`
+// Every C allocation starts as this finite sentinel: a window element the launch leaves unwritten (a missed zero-fill of an unused slab
+// included) is then off by ~7e7 in the slab sum, and anything written outside the window or the problem's slabs is seen as well.
+static const float fuzz_sentinel = -7.0e7f;
+static const unsigned fuzz_sentinel_bits = [] { unsigned u; memcpy(&u, &fuzz_sentinel, 4); return u; }();
 static int fuzz(int tm, int tn, int cases, unsigned seed) {
     set_variant_globals(tm);
     const bool wide = g_bf16 || is_x3(tm) || is_h2(tm);            // the 16-wave kernels and the f16x2 images: K multiples of 8
@@ -308,7 +312,7 @@ static int fuzz(int tm, int tn, int cases, unsigned seed) {
             h.ldc = h.N + h.coff + (rnd(0, 1) ? 4 * rnd(0, 4) : rnd(0, 7));
             if (rnd(0, 2)) { h.ldc = (h.ldc + 3) & ~3; h.coff &= ~3; }
             CK(hipMalloc(&h.C, (size_t)8 * h.M * h.ldc * sizeof(float) + 64)); to_free.push_back(h.C);
-            CK(hipMemset(h.C, 0, (size_t)8 * h.M * h.ldc * sizeof(float) + 64));
+            CK(hipMemsetD32((hipDeviceptr_t)h.C, (int)fuzz_sentinel_bits, (size_t)8 * h.M * h.ldc + 16));      // (not zero: an element the launch leaves unwritten must show)
             GemmProb& gp = b.prob(h.M, h.N, h.C + h.coff, h.ldc);
             const int nseg = rnd(1, 3);
             double amp2k = 0;
@@ -345,9 +349,10 @@ static int fuzz(int tm, int tn, int cases, unsigned seed) {
         b.launch(0);
         CK(hipDeviceSynchronize());
         double worst = 0, scale = 0;
+        unsigned long long hash = 14695981039346656037ull;      // FNV-1a over the bytes of every problem's nslab slab windows, in slab / row order
         for (int p = 0; p < nprob; ++p) {
             Host& h = H[p];
-            std::vector<float> hC((size_t)ns * h.M * h.ldc);
+            std::vector<float> hC((size_t)GEMM_MAX_SLABS * h.M * h.ldc);
             CK(hipMemcpy(hC.data(), h.C, hC.size() * 4, hipMemcpyDeviceToHost));
             int ktot = 0; for (int k : h.K) ktot += k;
             for (int i = 0; i < h.M; ++i)
@@ -364,18 +369,25 @@ static int fuzz(int tm, int tn, int cases, unsigned seed) {
                     worst = fmax(worst, fabs(got - ref));
                 }
             scale = fmax(scale, sqrt(g_h2 ? h.amp2k : (double)ktot) * 0.083);      // |a| |w| ~ U(-0.5, 0.5) (x the segment's amplitude): products ~ 1/12 rms
-            // the columns of the C window outside [coff, coff + N) must stay untouched (zero)
+            // the columns of the C window outside [coff, coff + N) must stay untouched (the sentinel), and so must every slab the problem
+            // does not own (q >= its nslab: its consumers never add them, the launch must not write them), window included
             for (int i = 0; i < h.M; ++i)
                 for (int j = 0; j < h.ldc; ++j)
-                    if (j < h.coff || j >= h.coff + h.N)
-                        for (int q = 0; q < ns; ++q)
-                            if (hC[(size_t)q * h.M * h.ldc + (size_t)i * h.ldc + j] != 0.f) { worst = 1e9; }
+                    for (int q = 0; q < GEMM_MAX_SLABS; ++q)
+                        if (j < h.coff || j >= h.coff + h.N || q >= b.a.p[p].nslab)
+                            if (hC[(size_t)q * h.M * h.ldc + (size_t)i * h.ldc + j] != fuzz_sentinel) { worst = 1e9; }
+            for (int q = 0; q < b.a.p[p].nslab; ++q)
+                for (int i = 0; i < h.M; ++i) {
+                    const unsigned char* row = reinterpret_cast<const unsigned char*>(hC.data() + (size_t)q * h.M * h.ldc + (size_t)i * h.ldc + h.coff);
+                    for (size_t k = 0; k < (size_t)h.N * sizeof(float); ++k) { hash ^= row[k]; hash *= 1099511628211ull; }
+                }
         }
         const double tol = (g_bf16 ? 2e-2 : 2e-5) * fmax(1.0, scale);
         const bool ok = worst < tol;
         bad += !ok;
         printf("fuzz %3d: %d problems (M %d N %d ...), slots %d, %s, G %d nslab %d: max |err| %.3g (tol %.3g) %s\n", cs, nprob, H[0].M, H[0].N, slots,
                b.a.aligned ? "k-aligned" : "stream-K", b.a.G, ns, worst, tol, ok ? "OK" : "FAIL");
+        printf("fuzz %3d: slab hash %016llx\n", cs, hash);
         for (void* q : to_free) CK(hipFree(q));
         for (Twin& t : g_twins) { if (t.b) CK(hipFree(t.b)); if (t.h2) CK(hipFree(t.h2)); }
         g_twins.clear();

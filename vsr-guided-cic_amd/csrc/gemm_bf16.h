@@ -102,32 +102,8 @@ void gemm_nt_bf16w_kernel(const GemmArgs args) {
     const int r = lane & 31, hh = lane >> 5;
 
     // ------------------------------------------------------------------ tile bookkeeping (both kinds: the epilogue is shared)
-    int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;
-    bool c_last = false;
-    auto decode = [&](int it) __attribute__((always_inline)) {
-        if (args.aligned) {                                // one piece of one tile: nothing to search
-            c_prob = rg.prob; c_tile = rg.tile; c_piece = rg.piece;
-            c_left = it1 - it;
-            c_last = rg.piece == rg.split - 1;
-            return it - (args.p[rg.prob].it_begin + rg.tile * args.p[rg.prob].ktiles);
-        }
-        int p = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < args.nprob && it >= args.p[i].it_begin) p = i;
-        const GemmProb& P = args.p[p];
-        const int local = it - P.it_begin;
-        c_prob = p;
-        c_tile = local / P.ktiles;
-        const int kt = local - c_tile * P.ktiles;
-        const int tile_base = it - kt;
-        const int g_first = (int)((((long long)tile_base + 1) * G - 1) / args.total_iters);
-        c_piece = g - g_first;
-        const int rem = P.ktiles - kt;
-        c_left = rem < it1 - it ? rem : it1 - it;
-        c_last = (c_left == rem);
-        return kt;
-    };
+    GemmPiece c = {};
+    auto decode = [&](int it) __attribute__((always_inline)) { return gemm_piece_at(args, rg, g, it, it1, c); };
 
     // Epilogue of one tile piece.  Accumulator element e of subtile (ti, tj) is row (e & 3) + 8 (e >> 2) + 4 hh, column r.  Bands
     // of 32 tile rows are staged in a k buffer by the four multiplier waves that own them and leave as 16-byte row stores issued
@@ -136,10 +112,12 @@ void gemm_nt_bf16w_kernel(const GemmArgs args) {
     static_assert(32 * ST_LD * 4 <= BUF * 2, "staging band must fit one k buffer");
     f32x16 acc[TM][TN];
     auto flush = [&](auto MULT, float* stage) __attribute__((always_inline)) {
-        const GemmProb& P = args.p[c_prob];
-        const int m0 = (c_tile % P.tiles_m) * BM, n0 = (c_tile / P.tiles_m) * BN;
-        float* C = P.C + (long long)c_piece * P.slab_stride;
-        const int extra = c_last ? P.nslab - 1 - c_piece : 0;     // unused slabs of a finished tile: zeros
+        const GemmProb& P = args.p[c.prob];
+        // (this kernel keeps its own copy of gemm_out_of / gemm_store4 (gemm_grouped.h): through the shared functions hipcc gives the
+        // <true, 1> instance 84 VGPRs instead of 78 - a lower occupancy figure, 5 instead of 6 waves per SIMD)
+        const int m0 = (c.tile % P.tiles_m) * BM, n0 = (c.tile / P.tiles_m) * BN;
+        float* C = P.C + (long long)c.piece * P.slab_stride;
+        const int extra = c.last ? P.nslab - 1 - c.piece : 0;     // unused slabs of a finished tile: zeros
         const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
         constexpr int TPR = BN / 4;                        // 64 threads per staged row
         constexpr int RPP = B16_THREADS / TPR;             // 16 / 32 rows per store pass
@@ -192,7 +170,7 @@ void gemm_nt_bf16w_kernel(const GemmArgs args) {
     int cur = 0, it = it0;
     auto end_of_ktile = [&](auto MULT) __attribute__((always_inline)) {
         ++it;
-        const bool piece_done = --c_left == 0;
+        const bool piece_done = --c.left == 0;
         __syncthreads();
         if (piece_done) {
             flush(MULT, reinterpret_cast<float*>(sA(cur)));
@@ -332,7 +310,7 @@ void gemm_nt_bf16w_kernel(const GemmArgs args) {
         using S1 = std::integral_constant<int, 1>;
         // k-tile j:  [wait for tile j+1 (issued one k-tile ago; tile j+2 may stay in flight)] [tile j+1 -> bf16 -> the other buffer]
         //            [issue tile j+3 into the set just emptied] [barrier]
-        open_tile(c_prob, c_tile, kt0);
+        open_tile(c.prob, c.tile, kt0);
         issue(S0{});                                       // tile 0
         landed_set(S0{}, false);
         store_tile(S0{}, 0);

@@ -24,111 +24,9 @@
 // Workgroup ranges are dealt XCD-contiguously (blocks b and b+8 share an XCD), so the m-tiles of one weight
 // n-tile run on one XCD back to back and the weight tile is fetched from HBM once.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "gemm_grouped.h"
 
 namespace vsr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// The limits of one grouped launch.  The planners cut no tile into more than GEMM_MAX_SLABS pieces; every consumer of slabs (slab_sum*,
-// k_attend's fused sums) holds that many loads in flight, and every slab workspace is sized by it.
-constexpr int GEMM_MAX_SLABS = 8;
-constexpr int GEMM_MAX_PROB = 4;     // problems per launch
-constexpr int GEMM_MAX_SEG = 3;      // K segments per problem
-
-struct GemmSeg {
-    const float* A;      // (rows, lda) activations
-    const int* a_idx;    // optional row gather: row m reads A + a_idx[m] * lda
-    const float* W;      // (N, ldw) weight window start (already offset to the segment's first column)
-    int lda;
-    int ldw;
-    int K;               // multiple of 4
-    int exp_idx;         // f16x2 kernels only (gemm_h2.h): slots of GemmArgs::exps with the power-of-two scale exponents of W's image (low 16 bits) and of A's bound (high 16 bits)
-    const uint16_t* A16; // bf16 kernel only, optional: a bf16 image of A (same rows, same lda) written by A's producer
-};
-
-struct GemmProb {
-    GemmSeg seg[GEMM_MAX_SEG];
-    float* C;            // (nslab, M, ldc)
-    long long slab_stride;
-    int nseg;
-    int M;
-    int N;
-    int ldc;
-    int tiles_m;
-    int tiles_n;
-    int ktiles;          // 32-wide k-tiles over all segments
-    int it_begin;        // first global iteration of this problem
-    int g_begin;         // aligned plan only: first workgroup of this problem ...
-    int split;           // ... and the number of equal k pieces every one of its tiles is cut into
-    int nslab;           // slabs THIS problem's tiles write (<= GemmArgs::nslab): its consumers add exactly these
-};
-
-struct GemmArgs {
-    GemmProb p[GEMM_MAX_PROB];
-    int nprob;
-    int total_iters;
-    int G;               // workgroups with a non-empty range (1 <= G <= total_iters); grid = 8 * ceil(G / 8)
-    int nslab;           // slabs per tile (S)
-    int aligned;         // 0: stream-K ranges (gemm_plan); 1: one k-aligned piece of one tile per workgroup (gemm_plan_aligned)
-    const int* exps;     // f16x2 kernels only: device table of scale exponents (GemmSeg::w_exp / a_exp index it)
-    int xcd_chunk;       // 0: ceil(G / 8) workgroups per XCD.  > 0 (aligned plan, gemm_plan_aligned): the workgroups are dealt in whole GROUPS of
-    int xcd_unit;        // xcd_unit (= tiles_m) consecutive numbers, xcd_lo groups per XCD and one more on the first xcd_extra XCDs;
-    int xcd_lo, xcd_extra;   // xcd_chunk = the largest per-XCD count = xcd_unit (xcd_lo + (xcd_extra > 0))
-};
-
-// Workgroup number of this block.  Blocks are dispatched round-robin over the 8 XCDs (block b runs on XCD b & 7); XCD x takes the
-// CONTIGUOUS workgroup numbers [x chunk, (x + 1) chunk): neighbouring tiles share their operand windows in that XCD's L2.
-// Returns G (= "no work") for the padding blocks of the grid.
-__device__ __forceinline__ int gemm_wg_of_block(const GemmArgs& a) {
-    const int i = blockIdx.x >> 3, x = blockIdx.x & 7;
-    if (a.xcd_chunk == 0) {
-        const int ch = (a.G + 7) >> 3;
-        return x * ch + i;                     // (>= G for the padding blocks)
-    }
-    const int mine = a.xcd_unit * (a.xcd_lo + (x < a.xcd_extra ? 1 : 0));
-    const int first = a.xcd_unit * (x * a.xcd_lo + (x < a.xcd_extra ? x : a.xcd_extra));
-    return i < mine ? first + i : a.G;
-}
-inline int gemm_grid(const GemmArgs& a) { return 8 * (a.xcd_chunk ? a.xcd_chunk : (a.G + 7) / 8); }
-
-// tile index -> tile origin: m fastest (the m-tiles of a weight n-tile are neighbours)
-__device__ __forceinline__ void gemm_tile_origin(const GemmProb& P, int tile, int BM, int BN, int& m0, int& n0) {
-    m0 = (tile % P.tiles_m) * BM; n0 = (tile / P.tiles_m) * BN;
-}
-
-constexpr int GEMM_BK = 32;
-constexpr int GEMM_LDS = GEMM_BK + 4;
-
-__device__ __host__ inline int gemm_range_begin(int g, int total, int G) { return (int)(((long long)g * total) / G); }
-
-// the k-tile range [it0, it1) of workgroup g (both plans) and, for the aligned plan, its problem / tile / piece
-struct GemmRange { int it0, it1, prob, tile, piece, split; };
-__device__ __forceinline__ GemmRange gemm_range(const GemmArgs& args, int g) {
-    GemmRange r;
-    if (!args.aligned) {
-        r.it0 = gemm_range_begin(g, args.total_iters, args.G);
-        r.it1 = gemm_range_begin(g + 1, args.total_iters, args.G);
-        r.prob = r.tile = r.piece = r.split = 0;
-        return r;
-    }
-    int p = 0;
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (i < args.nprob && g >= args.p[i].g_begin) p = i;
-    const GemmProb& P = args.p[p];
-    const int local = g - P.g_begin, tiles = P.tiles_m * P.tiles_n;
-    r.prob = p;
-    r.piece = local / tiles;
-    r.tile = local - r.piece * tiles;
-    r.split = P.split;
-    const int base = P.it_begin + r.tile * P.ktiles;
-    r.it0 = base + (int)(((long long)r.piece * P.ktiles) / P.split);
-    r.it1 = base + (int)(((long long)(r.piece + 1) * P.ktiles) / P.split);
-    return r;
-}
-
 
 // TM x TN 32x32 MFMA tiles per wave, WM x WN waves per workgroup; workgroup tile = (32 TM WM) x (32 TN WN)
 // Occupancy is LDS-bound (160 KB / (2 (BM + BN) 36 4 B) workgroups per CU); telling the register allocator so
@@ -241,27 +139,7 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
     };
 
     // ------------------------------------------------------------------ compute-side tile bookkeeping
-    int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;   // iterations left before this tile's piece is flushed
-    bool c_last = false;                                   // this piece completes the tile
-    auto decode = [&](int it) __attribute__((always_inline)) {                            // global iteration -> tile, piece, #iterations here
-        int p = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < args.nprob && it >= args.p[i].it_begin) p = i;
-        const GemmProb& P = args.p[p];
-        const int local = it - P.it_begin;
-        c_prob = p;
-        c_tile = local / P.ktiles;
-        const int kt = local - c_tile * P.ktiles;
-        const int tile_base = it - kt;
-        // first workgroup whose range contains the tile's first iteration
-        const int g_first = (int)((((long long)tile_base + 1) * G - 1) / args.total_iters);
-        c_piece = g - g_first;
-        const int rem = P.ktiles - kt;
-        c_left = rem < it1 - it ? rem : it1 - it;
-        c_last = (c_left == rem);
-        return kt;
-    };
+    GemmPiece c = {};                                      // (stream-K ranges only: the exact kernels are never given an aligned plan)
 
     // Epilogue of one tile piece.  The accumulator (C/D layout: col = lane & 31, row = (e & 3) + 8 (e >> 2) +
     // 4 (lane >> 5)) is transposed through the LDS buffer the k loop has just finished with, so that the tile
@@ -269,16 +147,12 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
     // address arithmetic; unused slabs of a finished tile get zeros the same way.
     constexpr int ST_LD = BN + 4;
     auto flush = [&](const f32x16 (&acc)[TM][TN], float* stage) __attribute__((always_inline)) {
-        const GemmProb& P = args.p[c_prob];
-        int m0, n0;
-        gemm_tile_origin(P, c_tile, BM, BN, m0, n0);
-        float* C = P.C + (long long)c_piece * P.slab_stride;
-        const int extra = c_last ? P.nslab - 1 - c_piece : 0;     // unused slabs of a finished tile: zeros
-        const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
+        const GemmProb& P = args.p[c.prob];
+        const GemmOut out = gemm_out_of(P, c, BM, BN);
         constexpr int TPR = BN / 4;                        // threads per staged row
         constexpr int RPP = NT / TPR;                      // rows per store pass
         const int c4 = (tid % TPR) * 4;
-        const int n = n0 + c4;
+        const int n = out.n0 + c4;
 #pragma unroll
         for (int band = 0; band < BM / 64; ++band) {       // 64 tile rows per pass through the staging buffer
 #pragma unroll
@@ -296,22 +170,11 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
 #pragma unroll
             for (int i = 0; i < 64 / RPP; ++i) {
                 const int sr = tid / TPR + RPP * i;        // staged row 0..63
-                const int m = m0 + band * 64 + sr;
+                const int m = out.m0 + band * 64 + sr;
                 if (m < P.M && n < P.N) {
                     const float4 v = *reinterpret_cast<const float4*>(stage + sr * ST_LD + c4);
-                    float* dst = C + (long long)m * P.ldc + n;
-                    if (vec_ok && n + 3 < P.N) {
-                        *reinterpret_cast<float4*>(dst) = v;
-                        for (int x = 1; x <= extra; ++x)
-                            *reinterpret_cast<float4*>(dst + (long long)x * P.slab_stride) = make_float4(0.f, 0.f, 0.f, 0.f);
-                    } else {
-                        const float vv[4] = {v.x, v.y, v.z, v.w};
-                        for (int q = 0; q < 4; ++q)
-                            if (n + q < P.N) {
-                                dst[q] = vv[q];
-                                for (int x = 1; x <= extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
-                            }
-                    }
+                    float* dst = out.C + (long long)m * P.ldc + n;
+                    gemm_store4(dst, v, n, P.N, out);
                 }
             }
             __syncthreads();                               // the next pass / store_tile() overwrites `stage`
@@ -319,8 +182,8 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
     };
 
     {
-        const int kt = decode(it0);
-        open_tile(c_prob, c_tile, kt);
+        const int kt = gemm_piece_streamk(args, g, it0, it1, c);
+        open_tile(c.prob, c.tile, kt);
     }
     load_next();
     store_tile(0);
@@ -337,7 +200,7 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-        const int n_it = c_left;
+        const int n_it = c.left;
         for (int j_it = 0; j_it < n_it; ++j_it, ++it) {
             const bool more = it + 1 < it1;
             if (more) load_next();                         // global -> registers, in flight during the MFMAs
@@ -367,7 +230,7 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
             }
         }
         flush(acc, sA(cur ^ 1));
-        if (it < it1) decode(it);
+        if (it < it1) gemm_piece_streamk(args, g, it, it1, c);
     }
 }
 
@@ -393,7 +256,8 @@ void gemm_nt_f32_kernel(const GemmArgs args) {
 //   The global loads of the next k-tile are issued BETWEEN the MFMA groups (two loads, 14 MFMAs, ...): issued in one
 //   burst in front of them, a wave spends ~2 300 cycles queueing on the CU's address path before its first MFMA
 //   (measured: 6 000 cycles per k-step against 3 584 of MFMA with one wave per SIMD).
-// Stream-K decomposition, slab outputs, cursor and epilogue staging are those of gemm_nt_f32_kernel.
+// Stream-K decomposition and slab outputs are those of gemm_nt_f32_kernel; tile bookkeeping and row store are the shared pieces of
+// gemm_grouped.h, the load cursor and the epilogue staging are written out here.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int r16_band_tiles(int TM, int BN) {          // 16-row tiles per epilogue pass: the staging rows must fit one k buffer
@@ -500,41 +364,19 @@ void gemm_nt_f32_r16_kernel(const GemmArgs args) {
     };
 
     // ------------------------------------------------------------------ compute-side tile bookkeeping
-    int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;
-    bool c_last = false;
-    auto decode = [&](int it) __attribute__((always_inline)) {
-        int p = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < args.nprob && it >= args.p[i].it_begin) p = i;
-        const GemmProb& P = args.p[p];
-        const int local = it - P.it_begin;
-        c_prob = p;
-        c_tile = local / P.ktiles;
-        const int kt = local - c_tile * P.ktiles;
-        const int tile_base = it - kt;
-        const int g_first = (int)((((long long)tile_base + 1) * G - 1) / args.total_iters);
-        c_piece = g - g_first;
-        const int rem = P.ktiles - kt;
-        c_left = rem < it1 - it ? rem : it1 - it;
-        c_last = (c_left == rem);
-        return kt;
-    };
+    GemmPiece c = {};
 
     // Epilogue: accumulator element e of tile (ti, tj) is C[16 ti + 4 q + e][16 TN wn + 16 tj + r].  TB 16-row tiles per
     // pass go through the idle k buffer: the k-half-1 waves put their sums there, the k-half-0 waves add their own on top
     // (half 0 + half 1, always in that order), then the rows leave as 16-byte stores (512-byte runs per row).
     constexpr int TB = r16_band_tiles(TM, BN);
     auto flush = [&](const f32x4 (&acc)[TM][TN], float* stage) __attribute__((always_inline)) {
-        const GemmProb& P = args.p[c_prob];
-        const int m0 = (c_tile % P.tiles_m) * BM, n0 = (c_tile / P.tiles_m) * BN;
-        float* C = P.C + (long long)c_piece * P.slab_stride;
-        const int extra = c_last ? P.nslab - 1 - c_piece : 0;
-        const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
+        const GemmProb& P = args.p[c.prob];
+        const GemmOut out = gemm_out_of(P, c, BM, BN);
         constexpr int TPR = BN / 4;                        // threads per staged row
         constexpr int RPP = NT / TPR;                      // rows per store pass
         const int c4 = (tid % TPR) * 4;
-        const int n = n0 + c4;
+        const int n = out.n0 + c4;
 #pragma unroll
         for (int b0 = 0; b0 < TM; b0 += TB) {
             if (wk == 1) {
@@ -563,22 +405,11 @@ void gemm_nt_f32_r16_kernel(const GemmArgs args) {
 #pragma unroll
             for (int i = 0; i < (BAND + RPP - 1) / RPP; ++i) {
                 const int sr = tid / TPR + RPP * i;
-                const int m = m0 + 16 * b0 + sr;
+                const int m = out.m0 + 16 * b0 + sr;
                 if (sr < BAND && 16 * b0 + sr < BM && m < P.M && n < P.N) {
                     const float4 v = *reinterpret_cast<const float4*>(stage + sr * BN + c4);
-                    float* dst = C + (long long)m * P.ldc + n;
-                    if (vec_ok && n + 3 < P.N) {
-                        *reinterpret_cast<float4*>(dst) = v;
-                        for (int x = 1; x <= extra; ++x)
-                            *reinterpret_cast<float4*>(dst + (long long)x * P.slab_stride) = make_float4(0.f, 0.f, 0.f, 0.f);
-                    } else {
-                        const float vv[4] = {v.x, v.y, v.z, v.w};
-                        for (int qq = 0; qq < 4; ++qq)
-                            if (n + qq < P.N) {
-                                dst[qq] = vv[qq];
-                                for (int x = 1; x <= extra; ++x) dst[(long long)x * P.slab_stride + qq] = 0.f;
-                            }
-                    }
+                    float* dst = out.C + (long long)m * P.ldc + n;
+                    gemm_store4(dst, v, n, P.N, out);
                 }
             }
             __syncthreads();
@@ -586,8 +417,8 @@ void gemm_nt_f32_r16_kernel(const GemmArgs args) {
     };
 
     {
-        const int kt = decode(it0);
-        open_tile(c_prob, c_tile, kt);
+        const int kt = gemm_piece_streamk(args, g, it0, it1, c);
+        open_tile(c.prob, c.tile, kt);
     }
     advance();
 #pragma unroll
@@ -606,7 +437,7 @@ void gemm_nt_f32_r16_kernel(const GemmArgs args) {
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
-        const int n_it = c_left;
+        const int n_it = c.left;
         for (int j_it = 0; j_it < n_it; ++j_it, ++it) {
             const bool more = it + 1 < it1;
             if (more) advance();
@@ -659,133 +490,8 @@ void gemm_nt_f32_r16_kernel(const GemmArgs args) {
             }
         }
         flush(acc, sA(cur ^ 1));
-        if (it < it1) decode(it);
+        if (it < it1) gemm_piece_streamk(args, g, it, it1, c);
     }
-}
-
-// Host side: fill tiles / iteration offsets, pick the number of workgroups and the slab count.
-//   slots      resident workgroups the launch should fill (CUs x 4 for this 36.9 KB-LDS kernel)
-//   min_iters  smallest range worth a workgroup (prologue + flush amortisation)
-// Returns nslab; the caller then sets every problem's C / slab_stride (slabs are nslab deep).
-inline int gemm_plan(GemmArgs& a, int slots, int min_iters = 8, int BM = 64, int BN = 64, int BK = GEMM_BK) {
-    int total = 0, kt_max = 1;
-    for (int i = 0; i < a.nprob; ++i) {
-        GemmProb& p = a.p[i];
-        p.tiles_m = (p.M + BM - 1) / BM;
-        p.tiles_n = (p.N + BN - 1) / BN;
-        p.ktiles = 0;
-        for (int s = 0; s < p.nseg; ++s) p.ktiles += (p.seg[s].K + BK - 1) / BK;
-        p.it_begin = total;
-        total += p.tiles_m * p.tiles_n * p.ktiles;
-        if (p.ktiles > kt_max) kt_max = p.ktiles;
-    }
-    a.total_iters = total;
-    int G = total / min_iters;
-    if (G > slots) G = slots;
-    const int L_min = (kt_max + GEMM_MAX_SLABS - 2) / (GEMM_MAX_SLABS - 1);            // keep pieces per tile <= GEMM_MAX_SLABS
-    if (G > total / L_min) G = total / L_min;
-    if (G < 1) G = 1;
-    a.G = G;
-    const int L = total / G;                       // shortest range
-    a.nslab = G == 1 ? 1 : (kt_max + L - 1) / L + 1;
-    if (a.nslab > GEMM_MAX_SLABS) a.nslab = GEMM_MAX_SLABS;
-    for (int i = 0; i < a.nprob; ++i) a.p[i].nslab = a.nslab;      // (gemm_tight_slabs: fewer for a short-K problem of a merged launch)
-    a.aligned = 0;
-    a.xcd_chunk = 0;
-    return a.nslab;
-}
-
-// K-ALIGNED plan (the 128 x 256 kernels of gemm_bf16.h / gemm_f32x3.h): every tile of problem p is cut into split_p equal k
-// pieces and every workgroup takes exactly ONE piece of ONE tile; workgroups are numbered piece-major, tiles m-fastest, so the
-// 32 workgroups of an XCD (contiguous numbers) are neighbouring tiles AT THE SAME k: they walk the same weight / activation
-// k-windows at the same time and share them in L2, where the stream-K ranges (k offsets shifted from tile to tile) send almost
-// every tile load to the Infinity Cache.  The slab count is exact (max split) and a tile writes exactly
-// split_p slabs.  Chooses the smallest critical path T = max_p ceil(ktiles_p / split_p) with sum_p tiles_p split_p <= slots,
-// pieces of at least min_iters k-tiles, split <= GEMM_MAX_SLABS.  Returns 0 (and leaves the plan untouched) when the tiles alone exceed the
-// slots: the caller then uses gemm_plan.
-inline int gemm_plan_aligned(GemmArgs& a, int slots, int min_iters, int BM, int BN, int BK) {
-    int tiles[GEMM_MAX_PROB], kt[GEMM_MAX_PROB], kt_max = 1, sum_tiles = 0;
-    for (int i = 0; i < a.nprob; ++i) {
-        const GemmProb& p = a.p[i];
-        tiles[i] = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-        kt[i] = 0;
-        for (int s = 0; s < p.nseg; ++s) kt[i] += (p.seg[s].K + BK - 1) / BK;
-        if (kt[i] > kt_max) kt_max = kt[i];
-        sum_tiles += tiles[i];
-    }
-    if (sum_tiles > slots || sum_tiles == 0) return 0;
-    int best_T = kt_max;
-    for (int T = kt_max; T >= 1; --T) {
-        int wgs = 0;
-        bool ok = true;
-        for (int i = 0; i < a.nprob && ok; ++i) {
-            const int s = (kt[i] + T - 1) / T;
-            ok = s <= GEMM_MAX_SLABS && (s == 1 || kt[i] / s >= min_iters);
-            wgs += tiles[i] * s;
-        }
-        if (!ok || wgs > slots) break;
-        best_T = T;
-    }
-    int total = 0, g = 0, nslab = 1;
-    for (int i = 0; i < a.nprob; ++i) {
-        GemmProb& p = a.p[i];
-        p.tiles_m = (p.M + BM - 1) / BM;
-        p.tiles_n = (p.N + BN - 1) / BN;
-        p.ktiles = kt[i];
-        p.it_begin = total;
-        total += tiles[i] * kt[i];
-        p.split = (kt[i] + best_T - 1) / best_T;
-        p.g_begin = g;
-        g += tiles[i] * p.split;
-        if (p.split > nslab) nslab = p.split;
-    }
-    a.total_iters = total;
-    a.G = g;
-    a.nslab = nslab;
-    for (int i = 0; i < a.nprob; ++i) a.p[i].nslab = nslab;       // every problem writes / zero-fills the launch's slab count (gemm_tight_slabs: its own split)
-    a.aligned = 1;
-    // XCD dealing in whole m-groups (round 6): workgroups are numbered m-fastest, so tiles_m consecutive numbers are the m-tiles of ONE
-    // weight n-tile at ONE k window.  With ceil(G / 8) numbers per XCD a group straddles two XCDs whenever that is not a multiple of
-    // tiles_m (G = 200, tiles_m = 4: 25 per XCD, every fourth group split) and its weight window is fetched by two L2s.  Deal whole
-    // groups instead - when every problem has the same tiles_m and the larger chunk still fits the XCD's share of the slots.
-    a.xcd_chunk = 0;
-    int u = a.p[0].tiles_m;
-    for (int i = 1; i < a.nprob; ++i) if (a.p[i].tiles_m != u) u = 1;
-    if (u > 1 && g % u == 0) {
-        const int groups = g / u, lo = groups / 8, extra = groups % 8, ch = u * (lo + (extra ? 1 : 0));
-        if (ch <= (slots + 7) / 8) { a.xcd_chunk = ch; a.xcd_unit = u; a.xcd_lo = lo; a.xcd_extra = extra; }
-    }
-    return nslab;
-}
-
-// Slabs problem i of a planned launch really needs: a tile of k k-tiles meets at most ceil(k / L) + 1 stream-K ranges of at least L
-// iterations (k-aligned plan: exactly its split).  A caller whose consumer reads problem i on its own may lower GemmProb::nslab to
-// this (the kernel then writes / zero-fills that many slabs for the problem, the consumer adds that many): the vocabulary GEMM that
-// shares a launch with the LSTM1 sums of the next step, att_ga next to LSTM2.
-inline int gemm_tight_slabs(const GemmArgs& a, int i) {
-    if (a.aligned) return a.p[i].split;
-    if (a.G <= 1) return 1;
-    const int L = a.total_iters / a.G;
-    const int ns = (a.p[i].ktiles + L - 1) / L + 1;
-    return ns < a.nslab ? ns : a.nslab;
-}
-
-inline double gemm_flops(const GemmArgs& a) {
-    double f = 0;
-    for (int i = 0; i < a.nprob; ++i)
-        for (int s = 0; s < a.p[i].nseg; ++s) f += 2.0 * a.p[i].M * a.p[i].N * a.p[i].seg[s].K;
-    return f;
-}
-
-// ALGORITHMIC bytes of a launch: every operand element and every output element once (w_bytes = bytes per weight element:
-// 4, or 2 when the W operands are bf16 copies); gathered A rows count once per output row.
-inline double gemm_bytes(const GemmArgs& a, int w_bytes) {
-    double b = 0;
-    for (int i = 0; i < a.nprob; ++i) {
-        b += 4.0 * a.p[i].M * a.p[i].N;
-        for (int s = 0; s < a.p[i].nseg; ++s) b += 4.0 * a.p[i].M * a.p[i].seg[s].K + (double)w_bytes * a.p[i].N * a.p[i].seg[s].K;
-    }
-    return b;
 }
 
 }  // namespace vsr

@@ -19,7 +19,8 @@
 // 5 vector instructions per MFMA on the split), and the streaming kernel puts them from global memory straight into the matrix
 // core.  Only A (activations: a third of the wide tile's rows, a few rows of the streaming kernel's) is split in the kernel.
 //
-// Two kernels, both with the work decompositions of gemm_f32.h (stream-K ranges / k-aligned pieces, slab outputs):
+// Two kernels, both with the work decompositions of gemm_grouped.h (stream-K ranges / k-aligned pieces, slab outputs; the wide kernel's
+// tile bookkeeping, row store and k-cursors are the shared pieces there):
 //   gemm_nt_h2_kernel<TM, TN, NW>  16 waves (8 multiply, 8 move), 128 x 256 / 128 x 128 x 32 tiles, W by LDS-DMA into a ring of NW stages
 //   gemm_nt_h2s_kernel<MT, NS>  4 waves, <= 128 rows: W global -> register -> MFMA B operand, A staged through LDS: gemm_x3s.h's
 #pragma once
@@ -297,32 +298,8 @@ void gemm_nt_h2_kernel(const GemmArgs args) {
     for (int i = 0; i < 4; ++i) pS |= (unsigned)((i < args.nprob ? h2_prob_exp(args, args.p[i]) : 0) & 0xff) << (8 * i);
     auto exp_of_prob = [&](int p) __attribute__((always_inline)) { return (int)(pS << (24 - 8 * p)) >> 24; };
 
-    int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;
-    bool c_last = false;
-    auto decode = [&](int it) __attribute__((always_inline)) {
-        if (args.aligned) {
-            c_prob = rg.prob; c_tile = rg.tile; c_piece = rg.piece;
-            c_left = it1 - it;
-            c_last = rg.piece == rg.split - 1;
-            return it - (args.p[rg.prob].it_begin + rg.tile * args.p[rg.prob].ktiles);
-        }
-        int p = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < args.nprob && it >= args.p[i].it_begin) p = i;
-        const GemmProb& P = args.p[p];
-        const int local = it - P.it_begin;
-        c_prob = p;
-        c_tile = local / P.ktiles;
-        const int kt = local - c_tile * P.ktiles;
-        const int tile_base = it - kt;
-        const int g_first = (int)((((long long)tile_base + 1) * G - 1) / args.total_iters);
-        c_piece = g - g_first;
-        const int rem = P.ktiles - kt;
-        c_left = rem < it1 - it ? rem : it1 - it;
-        c_last = (c_left == rem);
-        return kt;
-    };
+    GemmPiece c = {};
+    auto decode = [&](int it) __attribute__((always_inline)) { return gemm_piece_at(args, rg, g, it, it1, c); };
 
     // Epilogue of one tile piece, staged band by band in the W stage the multipliers have just finished with (32 rows x BN floats = one
     // stage exactly).  Every request in flight is waited for first: the stage may be the target of nothing then, and stores share vmcnt.
@@ -330,22 +307,19 @@ void gemm_nt_h2_kernel(const GemmArgs args) {
     static_assert(32 * ST_LD * 4 <= WSTAGE * 2, "staging band must fit one W stage");
     f32x16 acc[TM][TN];
     auto flush = [&](auto MULT, float* stage) __attribute__((always_inline)) {
-        const GemmProb& P = args.p[c_prob];
-        const float unscale = h2_pow2(-exp_of_prob(c_prob));
-        const int m0 = (c_tile % P.tiles_m) * BM, n0 = (c_tile / P.tiles_m) * BN;
-        float* C = P.C + (long long)c_piece * P.slab_stride;
-        const int extra = c_last ? P.nslab - 1 - c_piece : 0;
-        const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
+        const GemmProb& P = args.p[c.prob];
+        const float unscale = h2_pow2(-exp_of_prob(c.prob));
+        const GemmOut out = gemm_out_of(P, c, BM, BN);
         constexpr int TPR = BN / 4;
         constexpr int RPP = H2_THREADS / TPR;
         const int c4 = (tid % TPR) * 4;
-        const int n = n0 + c4;
+        const int n = out.n0 + c4;
         const int wm = wave / WN, wn = wave % WN;
         wait_loads<0>();
         __syncthreads();                                   // ... for every wave's requests: nothing lands in `stage` from here on
 #pragma unroll
         for (int band = 0; band < BM / 32; ++band) {
-            if (m0 + band * 32 >= P.M) break;
+            if (out.m0 + band * 32 >= P.M) break;
             if constexpr (decltype(MULT)::value) {
 #pragma unroll
                 for (int ti = 0; ti < TM; ++ti)
@@ -361,20 +335,22 @@ void gemm_nt_h2_kernel(const GemmArgs args) {
 #pragma unroll
             for (int i = 0; i < (32 + RPP - 1) / RPP; ++i) {
                 const int sr = tid / TPR + RPP * i;
-                const int m = m0 + band * 32 + sr;
+                const int m = out.m0 + band * 32 + sr;
                 if (sr < 32 && m < P.M && n < P.N) {
                     const float4 v = *reinterpret_cast<const float4*>(stage + sr * ST_LD + c4);
-                    float* dst = C + (long long)m * P.ldc + n;
-                    if (vec_ok && n + 3 < P.N) {
+                    float* dst = out.C + (long long)m * P.ldc + n;
+                    // (gemm_store4's text, kept here: through the shared function hipcc gives the <2, 1, 3> instance 74 VGPRs instead of
+                    // 72 - a lower occupancy figure, 6 instead of 7 waves per SIMD)
+                    if (out.vec_ok && n + 3 < P.N) {
                         *reinterpret_cast<float4*>(dst) = v;
-                        for (int x = 1; x <= extra; ++x)
+                        for (int x = 1; x <= out.extra; ++x)
                             *reinterpret_cast<float4*>(dst + (long long)x * P.slab_stride) = make_float4(0.f, 0.f, 0.f, 0.f);
                     } else {
                         const float vv[4] = {v.x, v.y, v.z, v.w};
                         for (int q = 0; q < 4; ++q)
                             if (n + q < P.N) {
                                 dst[q] = vv[q];
-                                for (int x = 1; x <= extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
+                                for (int x = 1; x <= out.extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
                             }
                     }
                 }
@@ -389,7 +365,7 @@ void gemm_nt_h2_kernel(const GemmArgs args) {
     int j = 0, it = it0, ws = 0;                           // ws = j % NW
     auto end_of_ktile = [&](auto MULT) __attribute__((always_inline)) {
         ++it;
-        const bool piece_done = --c_left == 0;
+        const bool piece_done = --c.left == 0;
         __syncthreads();
         if (piece_done) {
             flush(MULT, reinterpret_cast<float*>(sW + ws * WSTAGE));
@@ -416,28 +392,7 @@ void gemm_nt_h2_kernel(const GemmArgs args) {
                               + (unsigned)__builtin_amdgcn_readfirstlane(mw) * 1024u;
         // TWO cursors walk the k-tiles of the range: W runs NW - 1 k-tiles ahead, A two.  (Scalars only; the pointers a role derives
         // from its cursor are recomputed when the cursor enters a segment.)
-        struct Cursor {
-            int prob, tile, tile_left, seg, seg_left, k, K;
-            bool fresh;
-            __device__ __forceinline__ void open(const GemmArgs& a, int prob_, int tile_, int kt) {
-                prob = prob_; tile = tile_;
-                const GemmProb& P = a.p[prob_];
-                tile_left = P.ktiles - kt;
-                int sg = 0;
-                while (sg < P.nseg - 1 && kt >= (P.seg[sg].K + H2_BK - 1) / H2_BK) { kt -= (P.seg[sg].K + H2_BK - 1) / H2_BK; ++sg; }
-                seg = sg; K = P.seg[sg].K; k = kt * H2_BK; seg_left = (K + H2_BK - 1) / H2_BK - kt; fresh = true;
-            }
-            __device__ __forceinline__ void settle(const GemmArgs& a) {      // stand on a k-tile: cross segment / tile / problem boundaries
-                if (tile_left == 0) {
-                    if (tile + 1 < a.p[prob].tiles_m * a.p[prob].tiles_n) open(a, prob, tile + 1, 0);
-                    else open(a, prob + 1, 0, 0);
-                } else if (seg_left == 0) {
-                    ++seg; K = a.p[prob].seg[seg].K; k = 0; seg_left = (K + H2_BK - 1) / H2_BK; fresh = true;
-                }
-            }
-            __device__ __forceinline__ void next() { k += H2_BK; --seg_left; --tile_left; }
-        };
-        Cursor cw, ca;
+        GemmKCursor<BK> cw, ca;
         const float* pa[LA];
         const float* pbW[LB];
         float a_sc = 1.f;
@@ -510,7 +465,7 @@ void gemm_nt_h2_kernel(const GemmArgs args) {
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
         // prologue: W(0 .. NW - 2), A(0), A(1); A(0) -> buffer 0
-        cw.open(args, c_prob, c_tile, kt0);
+        cw.open(args, c.prob, c.tile, kt0);
         ca = cw;
         {
             int st = 0;

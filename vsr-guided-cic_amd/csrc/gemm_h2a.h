@@ -44,32 +44,8 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
     const int r = lane & (MF - 1);                        // the lane's operand row in an MF-row block
 
     int cur_s = 0;                                         // multipliers: exponent of the products accumulated so far (2^cur_s units)
-    int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;
-    bool c_last = false;
-    auto decode = [&](int it) __attribute__((always_inline)) {
-        if (args.aligned) {
-            c_prob = rg.prob; c_tile = rg.tile; c_piece = rg.piece;
-            c_left = it1 - it;
-            c_last = rg.piece == rg.split - 1;
-            return it - (args.p[rg.prob].it_begin + rg.tile * args.p[rg.prob].ktiles);
-        }
-        int p = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < args.nprob && it >= args.p[i].it_begin) p = i;
-        const GemmProb& P = args.p[p];
-        const int local = it - P.it_begin;
-        c_prob = p;
-        c_tile = local / P.ktiles;
-        const int kt = local - c_tile * P.ktiles;
-        const int tile_base = it - kt;
-        const int g_first = (int)((((long long)tile_base + 1) * G - 1) / args.total_iters);
-        c_piece = g - g_first;
-        const int rem = P.ktiles - kt;
-        c_left = rem < it1 - it ? rem : it1 - it;
-        c_last = (c_left == rem);
-        return kt;
-    };
+    GemmPiece c = {};
+    auto decode = [&](int it) __attribute__((always_inline)) { return gemm_piece_at(args, rg, g, it, it1, c); };
 
     // Epilogue of one tile piece, staged band by band in the W stage the multipliers have just finished with (32 rows x BN floats = one
     // stage exactly).  Every request in flight is waited for first: the stage may be the target of nothing then, and stores share vmcnt.
@@ -77,12 +53,11 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
     static_assert(32 * ST_LD * 4 <= WSTAGE * 2, "staging band must fit one W stage");
     acc_t acc[AM][AN];
     auto flush = [&](auto MULT, float* stage, bool range_done) __attribute__((always_inline)) {
-        const GemmProb& P = args.p[c_prob];
+        const GemmProb& P = args.p[c.prob];
         const float unscale = h2_pow2(-cur_s);
-        const int m0 = (c_tile % P.tiles_m) * BM, n0 = (c_tile / P.tiles_m) * BN;
-        float* C = P.C + (long long)c_piece * P.slab_stride;
-        const int extra = c_last ? P.nslab - 1 - c_piece : 0;
-        const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
+        const GemmOut out = gemm_out_of(P, c, BM, BN);
+        // (the two row stores below are gemm_store4's text (gemm_grouped.h), kept in this kernel: through the shared function the beam-5
+        // benchmark measured 0.3 - 0.7 % under the parent's range in two calls of alternating runs - profiles/r25_a_*)
         // (the flush's indices start from an opaque copy of the thread id: computed here, they are not hoisted into the k loop's live
         // range - at 4 waves per SIMD the 16 x 16 loop has no register to spare for them)
         int ft = tid;
@@ -97,7 +72,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
         constexpr int TPR = BN / 4;
         constexpr int RPP = H2_THREADS / TPR;
         const int c4 = (ft % TPR) * 4;
-        const int n = n0 + c4;
+        const int n = out.n0 + c4;
         const int wm = wave / WN, wn = wave % WN;
         wait_loads<0>();
         __syncthreads();                                   // ... for every wave's requests: nothing lands in `stage` from here on
@@ -121,20 +96,20 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
 #pragma unroll
             for (int i = 0; i < BM / RPP; ++i) {
                 const int sr = ft / TPR + RPP * i;
-                const int m = m0 + sr;
+                const int m = out.m0 + sr;
                 if (m < P.M && n < P.N) {
                     const float4 v = *reinterpret_cast<const float4*>(all + sr * ST_LD + (c4 ^ swz(sr)));
-                    float* dst = C + (long long)m * P.ldc + n;
-                    if (vec_ok && n + 3 < P.N) {
+                    float* dst = out.C + (long long)m * P.ldc + n;
+                    if (out.vec_ok && n + 3 < P.N) {              // (gemm_store4's text: see the note at the head of this flush)
                         *reinterpret_cast<float4*>(dst) = v;
-                        for (int x = 1; x <= extra; ++x)
+                        for (int x = 1; x <= out.extra; ++x)
                             *reinterpret_cast<float4*>(dst + (long long)x * P.slab_stride) = make_float4(0.f, 0.f, 0.f, 0.f);
                     } else {
                         const float vv[4] = {v.x, v.y, v.z, v.w};
                         for (int q = 0; q < 4; ++q)
                             if (n + q < P.N) {
                                 dst[q] = vv[q];
-                                for (int x = 1; x <= extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
+                                for (int x = 1; x <= out.extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
                             }
                     }
                 }
@@ -145,7 +120,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
         }
 #pragma unroll
         for (int band = 0; band < BM / 32; ++band) {
-            if (m0 + band * 32 >= P.M) break;
+            if (out.m0 + band * 32 >= P.M) break;
             if constexpr (decltype(MULT)::value) {
 #pragma unroll
                 for (int ti = 0; ti < AM; ++ti)                   // (16 x 16: a band is two blocks)
@@ -161,20 +136,20 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
 #pragma unroll
             for (int i = 0; i < (32 + RPP - 1) / RPP; ++i) {
                 const int sr = ft / TPR + RPP * i;
-                const int m = m0 + band * 32 + sr;
+                const int m = out.m0 + band * 32 + sr;
                 if (sr < 32 && m < P.M && n < P.N) {
                     const float4 v = *reinterpret_cast<const float4*>(stage + sr * ST_LD + (c4 ^ swz(sr)));
-                    float* dst = C + (long long)m * P.ldc + n;
-                    if (vec_ok && n + 3 < P.N) {
+                    float* dst = out.C + (long long)m * P.ldc + n;
+                    if (out.vec_ok && n + 3 < P.N) {              // (gemm_store4's text: see the note at the head of this flush)
                         *reinterpret_cast<float4*>(dst) = v;
-                        for (int x = 1; x <= extra; ++x)
+                        for (int x = 1; x <= out.extra; ++x)
                             *reinterpret_cast<float4*>(dst + (long long)x * P.slab_stride) = make_float4(0.f, 0.f, 0.f, 0.f);
                     } else {
                         const float vv[4] = {v.x, v.y, v.z, v.w};
                         for (int q = 0; q < 4; ++q)
                             if (n + q < P.N) {
                                 dst[q] = vv[q];
-                                for (int x = 1; x <= extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
+                                for (int x = 1; x <= out.extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
                             }
                     }
                 }
@@ -189,7 +164,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
     int j = 0, it = it0, ws = 0;                           // ws = j % NW
     auto end_of_ktile = [&](auto MULT) __attribute__((always_inline)) {
         ++it;
-        const bool piece_done = --c_left == 0;
+        const bool piece_done = --c.left == 0;
         __syncthreads();
         if (piece_done) {
             flush(MULT, reinterpret_cast<float*>(sW + ws * STG), it >= it1);
@@ -213,28 +188,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
         const int wboff = (wc & 3) * 8 + (wc >> 2) * 4;    // its offset in the row's k-tile, in floats (32 bytes per group, the lo half 16 bytes in)
         const unsigned lds_0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)(__attribute__((address_space(3))) void*)sW)
                              + (unsigned)__builtin_amdgcn_readfirstlane(mw) * 1024u;
-        struct Cursor {
-            int prob, tile, tile_left, seg, seg_left, k, K;
-            bool fresh;
-            __device__ __forceinline__ void open(const GemmArgs& a, int prob_, int tile_, int kt) {
-                prob = prob_; tile = tile_;
-                const GemmProb& P = a.p[prob_];
-                tile_left = P.ktiles - kt;
-                int sg = 0;
-                while (sg < P.nseg - 1 && kt >= (P.seg[sg].K + H2_BK - 1) / H2_BK) { kt -= (P.seg[sg].K + H2_BK - 1) / H2_BK; ++sg; }
-                seg = sg; K = P.seg[sg].K; k = kt * H2_BK; seg_left = (K + H2_BK - 1) / H2_BK - kt; fresh = true;
-            }
-            __device__ __forceinline__ void settle(const GemmArgs& a) {
-                if (tile_left == 0) {
-                    if (tile + 1 < a.p[prob].tiles_m * a.p[prob].tiles_n) open(a, prob, tile + 1, 0);
-                    else open(a, prob + 1, 0, 0);
-                } else if (seg_left == 0) {
-                    ++seg; K = a.p[prob].seg[seg].K; k = 0; seg_left = (K + H2_BK - 1) / H2_BK; fresh = true;
-                }
-            }
-            __device__ __forceinline__ void next() { k += H2_BK; --seg_left; --tile_left; }
-        };
-        Cursor cw;
+        GemmKCursor<BK> cw;
         const float* pa[LA];
         const float* pbW[LB];
         int seg_exp = 0;
@@ -272,7 +226,7 @@ void gemm_nt_h2a_kernel(const GemmArgs args) {
             cw.next();
         };
         // prologue: k-tiles 0 .. NW - 2
-        cw.open(args, c_prob, c_tile, kt0);
+        cw.open(args, c.prob, c.tile, kt0);
         {
             int st = 0;
             for (int n = 0; n < NW - 1 && it0 + n < it1; ++n) { issue(st); ++st; }

@@ -70,32 +70,8 @@ void gemm_nt_x3_kernel(const GemmArgs args) {
     const bool mover = wave >= 8;
     const int r = lane & 31, hh = lane >> 5;
 
-    int c_prob = 0, c_tile = 0, c_left = 0, c_piece = 0;
-    bool c_last = false;
-    auto decode = [&](int it) __attribute__((always_inline)) {
-        if (args.aligned) {                                // one piece of one tile: nothing to search
-            c_prob = rg.prob; c_tile = rg.tile; c_piece = rg.piece;
-            c_left = it1 - it;
-            c_last = rg.piece == rg.split - 1;
-            return it - (args.p[rg.prob].it_begin + rg.tile * args.p[rg.prob].ktiles);
-        }
-        int p = 0;
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < args.nprob && it >= args.p[i].it_begin) p = i;
-        const GemmProb& P = args.p[p];
-        const int local = it - P.it_begin;
-        c_prob = p;
-        c_tile = local / P.ktiles;
-        const int kt = local - c_tile * P.ktiles;
-        const int tile_base = it - kt;
-        const int g_first = (int)((((long long)tile_base + 1) * G - 1) / args.total_iters);
-        c_piece = g - g_first;
-        const int rem = P.ktiles - kt;
-        c_left = rem < it1 - it ? rem : it1 - it;
-        c_last = (c_left == rem);
-        return kt;
-    };
+    GemmPiece c = {};
+    auto decode = [&](int it) __attribute__((always_inline)) { return gemm_piece_at(args, rg, g, it, it1, c); };
 
     // Epilogue of one tile piece: bands of 32 tile rows are staged in a k buffer by the multiplier waves that own them and leave
     // as 16-byte row stores issued by all 1024 threads; unused slabs of a finished tile get zeros the same way.
@@ -103,20 +79,17 @@ void gemm_nt_x3_kernel(const GemmArgs args) {
     static_assert(32 * ST_LD * 4 <= BUF * 2, "staging band must fit one k buffer");
     f32x16 acc[TM][TN];
     auto flush = [&](auto MULT, float* stage) __attribute__((always_inline)) {
-        const GemmProb& P = args.p[c_prob];
-        const int m0 = (c_tile % P.tiles_m) * BM, n0 = (c_tile / P.tiles_m) * BN;
-        float* C = P.C + (long long)c_piece * P.slab_stride;
-        const int extra = c_last ? P.nslab - 1 - c_piece : 0;
-        const bool vec_ok = ((P.ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(P.C) & 15) == 0) && ((P.slab_stride & 3) == 0);
+        const GemmProb& P = args.p[c.prob];
+        const GemmOut out = gemm_out_of(P, c, BM, BN);
         constexpr int TPR = BN / 4;                        // threads per staged row
         constexpr int RPP = X3_THREADS / TPR;              // rows per store pass (16 / 32 / 64)
         const int c4 = (tid % TPR) * 4;
-        const int n = n0 + c4;
+        const int n = out.n0 + c4;
         const int wm = wave / WN, wn = wave % WN;          // (multipliers)
         wait_loads<0>();                                   // stores share vmcnt with the asynchronous loads: start from an empty queue
 #pragma unroll
         for (int band = 0; band < BM / 32; ++band) {
-            if (m0 + band * 32 >= P.M) break;              // rows past the problem (a short m-tile): nothing to stage or store
+            if (out.m0 + band * 32 >= P.M) break;              // rows past the problem (a short m-tile): nothing to stage or store
             if constexpr (decltype(MULT)::value) {
 #pragma unroll
                 for (int ti = 0; ti < TM; ++ti)
@@ -132,22 +105,11 @@ void gemm_nt_x3_kernel(const GemmArgs args) {
 #pragma unroll
             for (int i = 0; i < (32 + RPP - 1) / RPP; ++i) {
                 const int sr = tid / TPR + RPP * i;
-                const int m = m0 + band * 32 + sr;
+                const int m = out.m0 + band * 32 + sr;
                 if (sr < 32 && m < P.M && n < P.N) {
                     const float4 v = *reinterpret_cast<const float4*>(stage + sr * ST_LD + c4);
-                    float* dst = C + (long long)m * P.ldc + n;
-                    if (vec_ok && n + 3 < P.N) {
-                        *reinterpret_cast<float4*>(dst) = v;
-                        for (int x = 1; x <= extra; ++x)
-                            *reinterpret_cast<float4*>(dst + (long long)x * P.slab_stride) = make_float4(0.f, 0.f, 0.f, 0.f);
-                    } else {
-                        const float vv[4] = {v.x, v.y, v.z, v.w};
-                        for (int q = 0; q < 4; ++q)
-                            if (n + q < P.N) {
-                                dst[q] = vv[q];
-                                for (int x = 1; x <= extra; ++x) dst[(long long)x * P.slab_stride + q] = 0.f;
-                            }
-                    }
+                    float* dst = out.C + (long long)m * P.ldc + n;
+                    gemm_store4(dst, v, n, P.N, out);
                 }
             }
             __syncthreads();
@@ -159,7 +121,7 @@ void gemm_nt_x3_kernel(const GemmArgs args) {
     int cur = 0, it = it0;
     auto end_of_ktile = [&](auto MULT) __attribute__((always_inline)) {
         ++it;
-        const bool piece_done = --c_left == 0;
+        const bool piece_done = --c.left == 0;
         __syncthreads();
         if (piece_done) {
             flush(MULT, reinterpret_cast<float*>(smem + cur * BUF));
@@ -270,7 +232,7 @@ void gemm_nt_x3_kernel(const GemmArgs args) {
         using S1 = std::integral_constant<int, 1>;
         // k-tile j:  [wait for tile j+1 (issued one k-tile ago; tile j+2 may stay in flight)] [tile j+1 -> three planes of the other
         //            buffer] [issue tile j+3 into the set just emptied] [barrier]
-        open_tile(c_prob, c_tile, kt0);
+        open_tile(c.prob, c.tile, kt0);
         issue(S0{});                                       // tile 0
         landed_set(S0{}, false);
         store_tile(S0{}, 0);
