@@ -106,7 +106,8 @@ int vsr_set_verb_table(vsr_handle* h, const int32_t* row_ptr, const int32_t* voc
  * (step :147-152, :181): weight-only work, so it is hoisted out of the call.  The buffer is caller-owned and must
  * outlive its use.  Dropped by vsr_build_decode_cache(h, NULL, ...) (no launch) and by every flavour transition and every refresh
  * (vsr_bind_weights has the rules): build it last, in the final flavour.  A write to the weights that no such call follows (the fp32
- * flavours have no refresh) leaves it stale: drop or rebuild it (the training calls never use it). */
+ * flavours have no refresh) leaves it stale: drop or rebuild it (the training calls never use it).  A buffer that is not 8-byte
+ * aligned costs vsr_beam one extra launch per step (the selection is then not fused into the LSTM1 kernel); the results are the same. */
 size_t vsr_decode_cache_floats(const vsr_handle* h);
 int vsr_build_decode_cache(vsr_handle* h, float* buffer, size_t n_floats, void* stream);
 

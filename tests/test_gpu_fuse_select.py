@@ -1,4 +1,4 @@
-"""The selection of step t made INSIDE the LSTM1 kernel of step t + 1 (csrc/kernels.h: k_select_lstm1 for beam search, k_select_simple_lstm1
+"""The selection of step t made INSIDE the LSTM1 kernel of step t + 1 (csrc/kernels.h: k_select_lstm1_x2 for beam search, k_select_simple_lstm1
 for greedy / sampling / replay; round 5) against the separate launches it replaces (VSR_FUSE_SELECT=0).  Same expressions in the same order:
 ids, returned log-probs and beam scores must agree BIT FOR BIT, at M = 500 / 100 (wide and narrow GEMM tiles), 13 images (streaming
 kernel), every beam width, verb forcing, and the both-streams-EOS freeze branch.

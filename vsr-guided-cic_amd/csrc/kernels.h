@@ -13,39 +13,29 @@ namespace vsr {
 
 constexpr int KMAX = 8;  // VSR_MAX_BEAM
 
-// sum of up to GEMM_MAX_SLABS slabs at one offset, in slab order, with every load issued before the first add (the slab count is a
-// run-time number: a plain loop is a chain of dependent L2 round trips)
-__device__ __forceinline__ float slab_sum(const float* __restrict__ p, int nslab, long long stride, float init = 0.f) {
-    float v[GEMM_MAX_SLABS];
-#pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? p[k * stride] : 0.f;
-    float s = init;
-#pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
-        if (k < nslab) s += v[k];
-    return s;
-}
+// a += b, component by component
+__device__ __forceinline__ void vadd(float& a, float b) { a += b; }
+__device__ __forceinline__ void vadd(float2& a, float2 b) { a.x += b.x; a.y += b.y; }
+__device__ __forceinline__ void vadd(float4& a, float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+// zero of each width, through make_floatN (with `V{}` for it hipcc turns every add of an absent slab into a select:
+// k_select_lstm1_x2<5> 156 v_cndmask instead of 144, 2 v_pk_add_f32 instead of 14, 17.2 against 15.9 us per launch, profiles/r26_a_*)
+template <class V> __device__ __forceinline__ V vzero();
+template <> __device__ __forceinline__ float vzero<float>() { return 0.f; }
+template <> __device__ __forceinline__ float2 vzero<float2>() { return make_float2(0.f, 0.f); }
+template <> __device__ __forceinline__ float4 vzero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// slab_sum at two / four consecutive offsets (one 8- / 16-byte load per slab; p + k * stride aligned accordingly): every component is
-// slab_sum's chain of adds
-__device__ __forceinline__ float2 slab_sum2(const float* __restrict__ p, int nslab, long long stride) {
-    float2 v[GEMM_MAX_SLABS];
+// init + the sum of up to GEMM_MAX_SLABS slabs at one offset, in slab order, with every load issued before the first add (the slab count
+// is a run-time number: a plain loop is a chain of dependent L2 round trips).  V = float, or float2 / float4: that many consecutive
+// offsets (one 8- / 16-byte load per slab; p + k * stride aligned accordingly), every component the same chain of adds.
+template <class V = float>
+__device__ __forceinline__ V slab_sum(const float* __restrict__ p, int nslab, long long stride, V init = vzero<V>()) {
+    V v[GEMM_MAX_SLABS];
 #pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const float2*>(p + k * stride) : make_float2(0.f, 0.f);
-    float2 s = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
-        if (k < nslab) { s.x += v[k].x; s.y += v[k].y; }
-    return s;
-}
-__device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, int nslab, long long stride) {
-    float4 v[GEMM_MAX_SLABS];
-#pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const V*>(p + k * stride) : vzero<V>();
+    V s = init;
 #pragma unroll
     for (int k = 0; k < GEMM_MAX_SLABS; ++k)
-        if (k < nslab) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
+        if (k < nslab) vadd(s, v[k]);
     return s;
 }
 
@@ -322,7 +312,7 @@ __global__ void k_slab_reduce_scatter(const float* __restrict__ slabs, int nslab
     if (rows_dev && *rows_dev < rows) rows = *rows_dev;
     if (i >= (long long)rows * A) return;
     const int m = (int)(i / A), a = (int)(i % A);
-    const float4 s = slab_sum4(slabs + i, nslab, stride);
+    const float4 s = slab_sum<float4>(slabs + i, nslab, stride);
     *reinterpret_cast<float4*>(P + (long long)vlist[m] * A + a) = s;
 }
 
@@ -440,31 +430,57 @@ __global__ void k_i32_to_i64(const int* src, int64_t* dst, int n) {
 // pre: (nsplit, M, 6H) raw GEMM sums of [h2 | x | h1_old]; vproj: (B, 6H) hoisted vbar part + biases.
 // xproj (optional): (V, 6H) cached projection of every embedding row (decode cache), gathered by word[row];
 // nblk: number of leading gate blocks (of 6) that the GEMM produced (the rest only has hoisted terms).
-// the cell itself: q = [i, f, g, o, s-gate, g-gate image part] pre-activations of one (row, unit)
-__device__ __forceinline__ void lstm1_cell(const float (&q)[6], float c_old, float& c, float& h1v, float& stv) {
-    c = sigmoidf_(q[1]) * c_old + sigmoidf_(q[0]) * tanhf(q[2]);
+// the cell itself: q = [i, f, g, o, s-gate, g-gate image part] pre-activations of one (row, unit).  Returns the five activations: the
+// training forward saves them, the decode kernels drop them.
+struct Lstm1Act { float i, f, g, o, s; };
+__device__ __forceinline__ Lstm1Act lstm1_cell(const float (&q)[6], float c_old, float& c, float& h1v, float& stv) {
+    const Lstm1Act a = {sigmoidf_(q[0]), sigmoidf_(q[1]), tanhf(q[2]), sigmoidf_(q[3]), sigmoidf_(q[4])};
+    c = a.f * c_old + a.i * a.g;
     const float tc = tanhf(c);
-    h1v = sigmoidf_(q[3]) * tc;
-    stv = sigmoidf_(q[4]) * tc;
+    h1v = a.o * tc;
+    stv = a.s * tc;
+    return a;
 }
-__device__ __forceinline__ void lstm1_point(const float (&q)[6], float c_old, long long i, float* __restrict__ h1n, float* __restrict__ c1n,
-                                            float* __restrict__ s_t, float* __restrict__ gpre, uint16_t* __restrict__ h1n16,
-                                            uint16_t* __restrict__ s_t16, float isc) {
+// the raw sums of the six gate blocks of one (row, unit) - V = float2: of two adjacent units - at p = pre + the row's base + the unit:
+// blocks [0, nblk) are the ones the GEMM produced, and block 5 does not have the skip5 leading slabs
+template <class V = float>
+__device__ __forceinline__ void lstm1_sums(const float* __restrict__ p, int H, int nsplit, long long stride, int nblk, int skip5, V (&q)[6]) {
+#pragma unroll
+    for (int g = 0; g < 6; ++g) {
+        const int sk = g == 5 ? skip5 : 0;
+        q[g] = g < nblk ? slab_sum<V>(p + (long long)g * H + sk * stride, nsplit - sk, stride) : vzero<V>();
+    }
+}
+// ... and its stores for element i = (row, unit)
+__device__ __forceinline__ Lstm1Act lstm1_point(const float (&q)[6], float c_old, long long i, float* __restrict__ h1n, float* __restrict__ c1n,
+                                                float* __restrict__ s_t, float* __restrict__ gpre, uint16_t* __restrict__ h1n16,
+                                                uint16_t* __restrict__ s_t16, float isc) {
     float c, h1v, stv;
-    lstm1_cell(q, c_old, c, h1v, stv);
+    const Lstm1Act a = lstm1_cell(q, c_old, c, h1v, stv);
     h1n[i] = h1v;
     c1n[i] = c;
     s_t[i] = stv;
     gpre[i] = q[5];
     if (h1n16) { img_store(h1n16, i, h1v, isc); img_store(s_t16, i, stv, isc); }
+    return a;
 }
 // ... of the two units i (even), i + 1 of a row: the same cell twice, 8-byte stores (all bases 8-byte aligned, the images 4-byte)
 __device__ __forceinline__ void lstm1_point2(const float (&qa)[6], const float (&qb)[6], float2 c_old, long long i, float* __restrict__ h1n,
                                              float* __restrict__ c1n, float* __restrict__ s_t, float* __restrict__ gpre,
                                              uint16_t* __restrict__ h1n16, uint16_t* __restrict__ s_t16, float isc) {
+    // (lstm1_cell's formulas in this kernel's own text, and lstm1_sums' loop in the kernel: through the two shared functions every instance
+    // of k_select_lstm1_x2 takes 46 - 47 VGPRs instead of 44 - 47 still with the cell alone shared, 46 with the loop alone - and bench.py
+    // beam 5 ran under the range of the commit before in six runs of six, profiles/r26_a_step_pointwise_shared.md.  As written here the
+    // kernel compiles to that commit's instructions.)
+    auto cell = [](const float (&q)[6], float c_old, float& c, float& h1v, float& stv) {
+        c = sigmoidf_(q[1]) * c_old + sigmoidf_(q[0]) * tanhf(q[2]);
+        const float tc = tanhf(c);
+        h1v = sigmoidf_(q[3]) * tc;
+        stv = sigmoidf_(q[4]) * tc;
+    };
     float ca, ha, sa, cb, hb, sb;
-    lstm1_cell(qa, c_old.x, ca, ha, sa);
-    lstm1_cell(qb, c_old.y, cb, hb, sb);
+    cell(qa, c_old.x, ca, ha, sa);
+    cell(qb, c_old.y, cb, hb, sb);
     *reinterpret_cast<float2*>(h1n + i) = make_float2(ha, hb);
     *reinterpret_cast<float2*>(c1n + i) = make_float2(ca, cb);
     *reinterpret_cast<float2*>(s_t + i) = make_float2(sa, sb);
@@ -488,18 +504,28 @@ __global__ void k_lstm1(const float* __restrict__ pre, int nsplit, long long str
     const float* vp = vproj + (long long)(row / rpi) * 6 * H + j;
     const float* xp = xproj ? xproj + (long long)word[row] * 6 * H + j : nullptr;
     float q[6];
+    lstm1_sums(pre + base, H, nsplit, stride, nblk, skip5, q);
 #pragma unroll
     for (int g = 0; g < 6; ++g) {
-        const int sk = g == 5 ? skip5 : 0;
-        float s = g < nblk ? slab_sum(pre + base + (long long)g * H + sk * stride, nsplit - sk, stride) : 0.f;
+        float s = q[g];
         if (xp) s += xp[(long long)g * H];
         q[g] = s + vp[(long long)g * H];
     }
     lstm1_point(q, c1_old[(long long)prow * H + j], i, h1n, c1n, s_t, gpre, h1n16, s_t16, isc);
 }
 
+// the shift-gate vector g_t = sigmoid(gpre + W1_hg h1_new) * tanh(c1_new), s = the slab sum of W1_hg h1_new     (step :155, :181-182)
+// gg: the sigmoid alone (the training forward saves it)
+__device__ __forceinline__ float shift_gate(float gpre, float s, float c1n, float& gg) {
+    gg = sigmoidf_(gpre + s);
+    return gg * tanhf(c1n);
+}
+__device__ __forceinline__ float shift_gate(float gpre, float s, float c1n) {
+    float gg;
+    return shift_gate(gpre, s, c1n, gg);
+}
+
 // reduce the slabs of h1 -> [W1_hg | att_ha] and s_t -> [s_fc | att_sa]; finish the shift-gate vector
-// g_t = sigmoid(gpre + W1_hg h1_new) * tanh(c1_new)                                     (step :155, :181-182)
 __global__ void k_gate2(const float* __restrict__ c2a, const float* __restrict__ c2b, int nsplit, long long stride_a,
                         long long stride_b, const float* __restrict__ gpre, const float* __restrict__ c1n,
                         const float* __restrict__ b_sfc, int M, int H, int A, int D, float* __restrict__ g_t,
@@ -514,8 +540,8 @@ __global__ void k_gate2(const float* __restrict__ c2a, const float* __restrict__
         float s = slab_sum(c2a + (long long)row * (H + A) + c, nsplit, stride_a);
         if (c < H) {
             const long long o = (long long)row * H + c;
-            const float gg = sigmoidf_(gpre[o] + s);
-            const float gv = gg * tanhf(c1n[o]);
+            float gg;
+            const float gv = shift_gate(gpre[o], s, c1n[o], gg);
             g_t[o] = gv;
             if (g_t16) img_store(g_t16, o, gv, isc);
             if (gates6) gates6[(long long)row * 6 * H + 5LL * H + c] = gg;
@@ -589,71 +615,35 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
         // Slab sums of the S2 GEMM for this row.  FOUR columns per thread and pass with every slab load (and the g_t operands)
         // issued before the first use: one column per loop iteration made each iteration's loads wait for the previous
         // iteration's global store (8 dependent L2 round trips per row: 10 of the kernel's 34 us).
+        // H, A and D are multiples of 4 (vsr_create) and the slabs, states and outputs are 16-byte aligned (workspace carve): a thread's
+        // four columns are one side of every H / D boundary and every access is one 16-byte one.
+        // The sums start from zero, as k_gate2's do (they used to start from slab 0: the same value unless a slab holds -0.0f).
         const int H = g2.H;
-        if (((H | A | D) & 3) == 0) {
-            // 16-byte path: four consecutive columns per thread, every slab load of a pass issued before the first use
-            for (int c = tid * 4; c < H + A; c += NT * 4) {
-                float4 v[GEMM_MAX_SLABS];
-#pragma unroll
-                for (int k = 0; k < GEMM_MAX_SLABS; ++k)
-                    if (k < g2.nsplit) v[k] = *reinterpret_cast<const float4*>(g2.c2a + (long long)k * g2.stride_a + (long long)row * (H + A) + c);
-                float4 gp = make_float4(0, 0, 0, 0), cn = gp;
-                if (c < H) {
-                    gp = *reinterpret_cast<const float4*>(g2.gpre + (long long)row * H + c);
-                    cn = *reinterpret_cast<const float4*>(g2.c1n + (long long)row * H + c);
-                }
-                float4 s = v[0];
-#pragma unroll
-                for (int k = 1; k < GEMM_MAX_SLABS; ++k)
-                    if (k < g2.nsplit) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
-                if (c < H) {
-                    float4 o;
-                    o.x = sigmoidf_(gp.x + s.x) * tanhf(cn.x); o.y = sigmoidf_(gp.y + s.y) * tanhf(cn.y);
-                    o.z = sigmoidf_(gp.z + s.z) * tanhf(cn.z); o.w = sigmoidf_(gp.w + s.w) * tanhf(cn.w);
-                    if (first) {
-                        *reinterpret_cast<float4*>(g2.g_t + (long long)row * H + c) = o;
-                        if (g2.g_t16) img_store4(g2.g_t16, (long long)row * H + c, o, g2.isc);
-                    }
-                } else {
-                    *reinterpret_cast<float4*>(hA_s + (c - H)) = s;
-                    if (first) *reinterpret_cast<float4*>(g2.hA_out + (long long)row * A + (c - H)) = s;
-                }
+        for (int c = tid * 4; c < H + A; c += NT * 4) {
+            float4 gp = make_float4(0, 0, 0, 0), cn = gp;
+            if (c < H) {
+                gp = *reinterpret_cast<const float4*>(g2.gpre + (long long)row * H + c);
+                cn = *reinterpret_cast<const float4*>(g2.c1n + (long long)row * H + c);
             }
-            for (int cc = tid * 4; cc < D + A; cc += NT * 4) {
-                float4 v[GEMM_MAX_SLABS];
-#pragma unroll
-                for (int k = 0; k < GEMM_MAX_SLABS; ++k)
-                    if (k < g2.nsplit) v[k] = *reinterpret_cast<const float4*>(g2.c2b + (long long)k * g2.stride_b + (long long)row * (D + A) + cc);
-                float4 s = v[0];
-#pragma unroll
-                for (int k = 1; k < GEMM_MAX_SLABS; ++k)
-                    if (k < g2.nsplit) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
-                if (cc < D) {
-                    const float4 bs = *reinterpret_cast<const float4*>(g2.b_sfc + cc);
-                    s.x += bs.x; s.y += bs.y; s.z += bs.z; s.w += bs.w;
-                    *reinterpret_cast<float4*>(sent_s + cc) = s;
-                } else {
-                    *reinterpret_cast<float4*>(sa_s + (cc - D)) = s;
+            const float4 s = slab_sum<float4>(g2.c2a + (long long)row * (H + A) + c, g2.nsplit, g2.stride_a);
+            if (c < H) {
+                const float4 o = make_float4(shift_gate(gp.x, s.x, cn.x), shift_gate(gp.y, s.y, cn.y), shift_gate(gp.z, s.z, cn.z), shift_gate(gp.w, s.w, cn.w));
+                if (first) {
+                    *reinterpret_cast<float4*>(g2.g_t + (long long)row * H + c) = o;
+                    if (g2.g_t16) img_store4(g2.g_t16, (long long)row * H + c, o, g2.isc);
                 }
+            } else {
+                *reinterpret_cast<float4*>(hA_s + (c - H)) = s;
+                if (first) *reinterpret_cast<float4*>(g2.hA_out + (long long)row * A + (c - H)) = s;
             }
-        } else {
-            for (int c = tid; c < H + A; c += NT) {
-                const float s = slab_sum(g2.c2a + (long long)row * (H + A) + c, g2.nsplit, g2.stride_a);
-                if (c < H) {
-                    const float gv = sigmoidf_(g2.gpre[(long long)row * H + c] + s) * tanhf(g2.c1n[(long long)row * H + c]);
-                    if (first) {
-                        g2.g_t[(long long)row * H + c] = gv;
-                        if (g2.g_t16) img_store(g2.g_t16, (long long)row * H + c, gv, g2.isc);
-                    }
-                } else {
-                    hA_s[c - H] = s;
-                    if (first) g2.hA_out[(long long)row * A + (c - H)] = s;
-                }
-            }
-            for (int cc = tid; cc < D + A; cc += NT) {
-                const float s = slab_sum(g2.c2b + (long long)row * (D + A) + cc, g2.nsplit, g2.stride_b);
-                if (cc < D) sent_s[cc] = s + g2.b_sfc[cc];
-                else sa_s[cc - D] = s;
+        }
+        for (int cc = tid * 4; cc < D + A; cc += NT * 4) {
+            float4 s = slab_sum<float4>(g2.c2b + (long long)row * (D + A) + cc, g2.nsplit, g2.stride_b);
+            if (cc < D) {
+                vadd(s, *reinterpret_cast<const float4*>(g2.b_sfc + cc));
+                *reinterpret_cast<float4*>(sent_s + cc) = s;
+            } else {
+                *reinterpret_cast<float4*>(sa_s + (cc - D)) = s;
             }
         }
     } else {
@@ -787,6 +777,25 @@ __global__ __launch_bounds__(NT) void k_attend(const Gate2Args g2, const float* 
 }
 
 // LSTM2 pointwise                                                                     (step :176-177)
+// pre-activations [i, f, g, o] of unit j of a row: slab sum + b_ih + b_hh, then + the hoisted image part where there is one.
+// p = pre + the row's base + j;  vp2 = vproj2 + the image's base + j, or null
+__device__ __forceinline__ void lstm2_pre(const float* __restrict__ p, int nsplit, long long stride, const float* __restrict__ b_ih,
+                                          const float* __restrict__ b_hh, const float* __restrict__ vp2, int H, int j, float (&q)[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        float s = slab_sum(p + (long long)g * H, nsplit, stride);
+        s += b_ih[g * H + j] + b_hh[g * H + j];
+        if (vp2) s += vp2[(long long)g * H];
+        q[g] = s;
+    }
+}
+// the cell; gates (optional): the four activations go to gates[0], [H], [2H], [3H] (the training forward saves them)
+__device__ __forceinline__ void lstm2_cell(const float (&q)[4], float c_old, float& c, float& h2v, float* __restrict__ gates = nullptr, int H = 0) {
+    const float ig = sigmoidf_(q[0]), fg = sigmoidf_(q[1]), gg = tanhf(q[2]), og = sigmoidf_(q[3]);
+    c = fg * c_old + ig * gg;
+    h2v = og * tanhf(c);
+    if (gates) { gates[0] = ig; gates[H] = fg; gates[2LL * H] = gg; gates[3LL * H] = og; }
+}
 __global__ void k_lstm2(const float* __restrict__ pre, int nsplit, long long stride, const float* __restrict__ b_ih,
                         const float* __restrict__ b_hh, const float* __restrict__ vproj2, int rpi,
                         const int* __restrict__ parent, const float* __restrict__ c2_old, int M, int H,
@@ -795,18 +804,11 @@ __global__ void k_lstm2(const float* __restrict__ pre, int nsplit, long long str
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)M * H) return;
     const int row = (int)(i / H), j = (int)(i % H);
-    const long long base = (long long)row * 4 * H + j;
     float q[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        float s = slab_sum(pre + base + (long long)g * H, nsplit, stride);
-        s += b_ih[g * H + j] + b_hh[g * H + j];
-        if (vproj2) s += vproj2[(long long)(row / rpi) * 4 * H + g * H + j];
-        q[g] = s;
-    }
+    lstm2_pre(pre + (long long)row * 4 * H + j, nsplit, stride, b_ih, b_hh, vproj2 ? vproj2 + (long long)(row / rpi) * 4 * H + j : nullptr, H, j, q);
     const int prow = parent ? parent[row] : row;
-    const float c = sigmoidf_(q[1]) * c2_old[(long long)prow * H + j] + sigmoidf_(q[0]) * tanhf(q[2]);
-    const float h2v = sigmoidf_(q[3]) * tanhf(c);
+    float c, h2v;
+    lstm2_cell(q, c2_old[(long long)prow * H + j], c, h2v);
     h2n[i] = h2v;
     c2n[i] = c;
     if (h2n16) img_store(h2n16, i, h2v, isc);
@@ -1270,11 +1272,7 @@ __global__ void k_select_simple_lstm1(const SelSimpleArgs sel, const float* __re
     const float* vp = vproj + (long long)(row / rpi) * 6 * H + j;
     // the slab sums do not depend on the selection: their loads are in flight while it is made
     float q[6];
-#pragma unroll
-    for (int g = 0; g < 6; ++g) {
-        const int sk = g == 5 ? skip5 : 0;
-        q[g] = g < nblk ? slab_sum(pre + base + (long long)g * H + sk * stride, nsplit - sk, stride) : 0.f;
-    }
+    lstm1_sums(pre + base, H, nsplit, stride, nblk, skip5, q);
     const int w = select_simple_row(sel, row, j == 0);
     const float* xp = xproj + (long long)w * 6 * H + j;
 #pragma unroll
@@ -1391,63 +1389,19 @@ __device__ __forceinline__ void select_beam_wave(const SelBeamArgs& a, int b, in
 template <int K>
 __global__ __launch_bounds__(64) void k_select_beam(const SelBeamArgs a) { select_beam_wave<K>(a, blockIdx.x, threadIdx.x, true, nullptr); }
 
-// k_select_beam of step t - 1 inside k_lstm1 of step t (round 5).  One workgroup per (image, slice of SL_UB = 64 hidden units) of
+// k_select_beam of step t - 1 inside k_lstm1 of step t (round 5).  One workgroup per (image, slice of 2 SL_UB = 128 hidden units) of
 // (beam + 1) waves: the last wave makes the image's selection (every slice's workgroup makes it - it is one wave's work - slice 0 stores
 // it) WHILE wave p < cb adds the LSTM1 / gate slabs of the image's PARENT row p for the slice's units (the sums do not depend on the
 // selection; a child row reads its parent's) into LDS; then wave q is CHILD row q: its parent's sums from LDS, its word's cached
-// embedding projection, the image's hoisted terms - the expressions and their order are k_lstm1's (slab_sum, + xproj, + vproj,
-// lstm1_point), and every (row, unit) element is one thread's work as there.  (A first version gave a thread all five rows of a unit:
+// embedding projection, the image's hoisted terms - the expressions and their order are k_lstm1's (lstm1_sums, + xproj, + vproj,
+// lstm1_cell; this kernel keeps its own text of both, lstm1_point2 says why), and every (row, unit) element is computed once as there.  (A first version gave a thread all five rows of a unit:
 // five dependent rounds of loads instead of one - slower than the two launches it replaced, profiles/r05_f_*.)
+// A lane carries TWO adjacent hidden units: 8-byte loads and stores.  With one unit per lane (slices of 64: a kernel this one replaced)
+// 100 images x beam 5 x H = 1000 were 1 600 workgroups of 6 waves, of which 256 CUs x 5 hold 1 280: the last 320 ran the whole dependent
+// chain (loads, selection, barrier, gather, cell, stores) a second time on a fifth of the chip.  These are 800 and resident at once.
+// Needs an even H (vsr_create: H % 4 == 0) and 8-byte aligned bases (4-byte for the images): the workspace is carved at 256 bytes, and
+// vsr_beam does not fuse the selection over a decode cache that is not (vsr_build_decode_cache: xproj_al8).
 constexpr int SL_UB = 64;
-template <int K>
-__global__ __launch_bounds__((K + 1) * 64) void k_select_lstm1(const SelBeamArgs sel, const float* __restrict__ pre, int nsplit, long long stride,
-                                                               const float* __restrict__ vproj, const float* __restrict__ c1_old, int H, int nslice,
-                                                               float* __restrict__ h1n, float* __restrict__ c1n, float* __restrict__ s_t,
-                                                               float* __restrict__ gpre, const float* __restrict__ xproj, int nblk,
-                                                               uint16_t* __restrict__ h1n16, uint16_t* __restrict__ s_t16, float isc, int skip5) {
-    __shared__ float sums[K * 7 * SL_UB];                  // per parent: six gate sums and its old cell state
-    __shared__ int sel_s[2 * KMAX];
-    const int b = blockIdx.x / nslice, slice = blockIdx.x % nslice;
-    const int wave = threadIdx.x >> 6, u = threadIdx.x & 63, cb = sel.cb;
-    const int j = slice * SL_UB + u;
-    float vp[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (wave == K) {
-        select_beam_wave<K>(sel, b, u, slice == 0, sel_s);
-    } else if (j < H) {
-        // everything that does not depend on the selection is requested before the barrier: the parents' sums and cell states (into LDS:
-        // a child reads its parent's), the image's hoisted terms (the same for every row of the image)
-#pragma unroll
-        for (int g = 0; g < 6; ++g) vp[g] = vproj[(long long)b * 6 * H + (long long)g * H + j];
-        if (wave < cb) {
-            const long long base = (long long)(b * cb + wave) * 6 * H + j;
-            const float co = c1_old[(long long)(b * cb + wave) * H + j];
-#pragma unroll
-            for (int g = 0; g < 6; ++g) {
-                const int sk = g == 5 ? skip5 : 0;
-                sums[(wave * 7 + g) * SL_UB + u] = g < nblk ? slab_sum(pre + base + (long long)g * H + sk * stride, nsplit - sk, stride) : 0.f;
-            }
-            sums[(wave * 7 + 6) * SL_UB + u] = co;
-        }
-    }
-    __syncthreads();
-    if (wave == K || j >= H) return;
-    const int pl = sel_s[wave], w = sel_s[KMAX + wave];
-    const int row = b * K + wave;
-    const float* xp = xproj + (long long)w * 6 * H + j;
-    float q[6];
-#pragma unroll
-    for (int g = 0; g < 6; ++g) {
-        float s = sums[(pl * 7 + g) * SL_UB + u];
-        s += xp[(long long)g * H];
-        q[g] = s + vp[g];
-    }
-    lstm1_point(q, sums[(pl * 7 + 6) * SL_UB + u], (long long)row * H + j, h1n, c1n, s_t, gpre, h1n16, s_t16, isc);
-}
-// The same kernel with TWO adjacent hidden units per lane, i.e. a slice of 128 units per workgroup: 8-byte loads and stores, half the
-// workgroups.  At 100 images x beam 5 x H = 1000 the one-unit launch is 1 600 workgroups of 6 waves, of which 256 CUs x 5 hold 1 280: the
-// last 320 ran the whole dependent chain (loads, selection, barrier, gather, cell, stores) a second time on a fifth of the chip.  These
-// are 800 and resident at once.  Every (row, unit) element is still the expressions above in their order - a lane just carries two of
-// them.  Needs an even H and 8-byte aligned bases (4-byte for the images): run_step chooses, the one-unit kernel takes the rest.
 template <int K>
 __global__ __launch_bounds__((K + 1) * 64) void k_select_lstm1_x2(const SelBeamArgs sel, const float* __restrict__ pre, int nsplit, long long stride,
                                                                   const float* __restrict__ vproj, const float* __restrict__ c1_old, int H, int nslice,
@@ -1465,15 +1419,18 @@ __global__ __launch_bounds__((K + 1) * 64) void k_select_lstm1_x2(const SelBeamA
     if (wave == K) {
         select_beam_wave<K>(sel, b, u, slice == 0, sel_s);
     } else if (j < H) {
+        // everything that does not depend on the selection is requested before the barrier: the parents' sums and cell states (into LDS:
+        // a child reads its parent's), the image's hoisted terms (the same for every row of the image)
 #pragma unroll
         for (int g = 0; g < 6; ++g) vp[g] = *reinterpret_cast<const float2*>(vproj + (long long)b * 6 * H + (long long)g * H + j);
         if (wave < cb) {
-            const long long base = (long long)(b * cb + wave) * 6 * H + j;
             const float2 co = *reinterpret_cast<const float2*>(c1_old + (long long)(b * cb + wave) * H + j);
+            // (lstm1_sums' loop in this kernel's own text, each sum straight into LDS: see lstm1_point2)
+            const long long base = (long long)(b * cb + wave) * 6 * H + j;
 #pragma unroll
             for (int g = 0; g < 6; ++g) {
                 const int sk = g == 5 ? skip5 : 0;
-                sums[(wave * 7 + g) * SL_UB + u] = g < nblk ? slab_sum2(pre + base + (long long)g * H + sk * stride, nsplit - sk, stride) : make_float2(0.f, 0.f);
+                sums[(wave * 7 + g) * SL_UB + u] = g < nblk ? slab_sum<float2>(pre + base + (long long)g * H + sk * stride, nsplit - sk, stride) : make_float2(0.f, 0.f);
             }
             sums[(wave * 7 + 6) * SL_UB + u] = co;
         }

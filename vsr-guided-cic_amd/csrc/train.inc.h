@@ -555,7 +555,7 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         // S6 for all steps at once, sparse head: the rows in their natural (t, b) order (state slots 1 .. T: nothing to gather), then
         // k_vocab_select: the log_softmax rows stay in t.dlogits, the targets' entries go to the caller's (rows, T) tensor
         all.h2_new = t.h2s + BH; all.h2_new16 = im ? t.h2s16 + BH * 2 : nullptr;
-        const int ns = train_vocab_gemm(h, t, all, nullptr, GEMM_MAX_SLABS, s);           // (k_vocab_select sums at most that many slabs: slab_sum4)
+        const int ns = train_vocab_gemm(h, t, all, nullptr, GEMM_MAX_SLABS, s);           // (k_vocab_select sums at most that many slabs: slab_sum)
         if (!ns) return 1;
         const long long stride = (long long)TB * V;
         const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;

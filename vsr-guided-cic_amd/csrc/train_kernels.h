@@ -280,21 +280,11 @@ __global__ void k_lstm1_train(const float* __restrict__ pre, int nsplit, long lo
     const long long base = (long long)row * 6 * H + j;
     const long long vbase = SHARED ? (long long)(row / rpi) * 6 * H + j : base;
     float q[6];
+    lstm1_sums(pre + base, H, nsplit, stride, nblk, 0, q);
 #pragma unroll
-    for (int g = 0; g < 6; ++g) {
-        const float s = g < nblk ? slab_sum(pre + base + (long long)g * H, nsplit, stride) : 0.f;
-        q[g] = s + xproj[base + (long long)g * H] + vproj[vbase + (long long)g * H];
-    }
-    const float ig = sigmoidf_(q[0]), fg = sigmoidf_(q[1]), gg = tanhf(q[2]), og = sigmoidf_(q[3]), sg = sigmoidf_(q[4]);
-    const float c = fg * c1_old[i] + ig * gg;
-    const float tc = tanhf(c);
-    const float h1v = og * tc, stv = sg * tc;
-    h1n[i] = h1v;
-    c1n[i] = c;
-    s_t[i] = stv;
-    gpre[i] = q[5];
-    if (h1n16) { img_store(h1n16, i, h1v, isc); img_store(s_t16, i, stv, isc); }
-    gates[base] = ig; gates[base + H] = fg; gates[base + 2LL * H] = gg; gates[base + 3LL * H] = og; gates[base + 4LL * H] = sg;
+    for (int g = 0; g < 6; ++g) q[g] = q[g] + xproj[base + (long long)g * H] + vproj[vbase + (long long)g * H];
+    const Lstm1Act a = lstm1_point(q, c1_old[i], i, h1n, c1n, s_t, gpre, h1n16, s_t16, isc);
+    gates[base] = a.i; gates[base + H] = a.f; gates[base + 2LL * H] = a.g; gates[base + 3LL * H] = a.o; gates[base + 4LL * H] = a.s;
 }
 
 // after the S5 GEMM, one launch: blocks [0, gblocks = M) finish att_ga(g_t) from its slabs (saved for the backward pass) and
@@ -316,19 +306,11 @@ __global__ __launch_bounds__(256) void k_fwd_tail(const GateLogitArgs gl, int gb
     const int row = (int)(i / H), j = (int)(i % H);
     const long long base = (long long)row * 4 * H + j;
     float q[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        float s = slab_sum(pre + base + (long long)g * H, nsplit, stride);
-        s += b_ih[g * H + j] + b_hh[g * H + j];
-        if (vproj2) s += vproj2[(SHARED ? (long long)(row / rpi) * 4 * H + j : base) + (long long)g * H];
-        q[g] = s;
-    }
-    const float ig = sigmoidf_(q[0]), fg = sigmoidf_(q[1]), gg = tanhf(q[2]), og = sigmoidf_(q[3]);
-    const float c = fg * c2_old[i] + ig * gg;
-    const float h2v = og * tanhf(c);
+    lstm2_pre(pre + base, nsplit, stride, b_ih, b_hh, vproj2 ? vproj2 + (SHARED ? (long long)(row / rpi) * 4 * H + j : base) : nullptr, H, j, q);
+    float c, h2v;
+    lstm2_cell(q, c2_old[i], c, h2v, gates + base, H);
     h2n[i] = h2v;
     c2n[i] = c;
-    gates[base] = ig; gates[base + H] = fg; gates[base + 2LL * H] = gg; gates[base + 3LL * H] = og;
     if (h2n16) img_store(h2n16, i, h2v, isc);
 }
 
@@ -573,7 +555,29 @@ __global__ __launch_bounds__(256) void k_dP_rows_sum(const float* __restrict__ p
 // ---------------------------------------------------------------------------------------------- fused step kernels
 // One backward step used to be 11 pointwise launches of ~5 us around its 3 GEMMs; the three kernels below do the same
 // arithmetic in the same order (bit-identical results) in 3 launches + k_dalpha + k_attend_bwd.
-//
+
+// LSTM cell backward of one (row, unit), both cells (formulas at the head of this section).  g: the saved activations [i f g o] at
+// g[0], [H], [2H], [3H];  d: the pre-activation gradients, same layout;  dtc: the whole gradient reaching tanh(c) (dhv * o, plus
+// LSTM1's s_t / g_t paths: the caller forms it).  Returns tanh(c), dc_prev and max |d0..3|.
+struct LstmCellBwd { float tc, dc_prev, mx; };
+__device__ __forceinline__ LstmCellBwd lstm_cell_bwd(const float* __restrict__ g, int H, float c, float c_prev, float dhv, float dtc, float dc_next,
+                                                     float* __restrict__ d) {
+    const float ig = g[0], fg = g[H], gg = g[2LL * H], og = g[3LL * H];
+    const float tc = tanhf(c);
+    const float dc = dc_next + dtc * (1.f - tc * tc);
+    const float d0 = dc * gg * ig * (1.f - ig), d1 = dc * c_prev * fg * (1.f - fg);
+    // (g^2 is rounded on its own: in both kernels the compiler used to pack it with dc * i into one v_pk_mul_f32, which kept it out of an
+    // fma with the 1 -; left to itself it fuses the two here, and the gradients moved in the last bit against the commit before)
+    float gg2;
+    {
+#pragma clang fp contract(off)
+        gg2 = gg * gg;
+    }
+    const float d2 = dc * ig * (1.f - gg2), d3 = dhv * tc * og * (1.f - og);
+    d[0] = d0; d[H] = d1; d[2LL * H] = d2; d[3LL * H] = d3;
+    return {tc, dc * fg, fmaxf(fmaxf(fabsf(d0), fabsf(d1)), fmaxf(fabsf(d2), fabsf(d3)))};
+}
+
 // k_bwd_head: (a) blocks [0, gblocks): gate log-softmax backward, one wave per row (the former k_gatelogit_bwd);
 //             (b) the remaining blocks, one thread per (row, j): finish the carries of the LATER step's GEMM 3 straight from its
 //                 slabs (dh1 carry -> dh1_c; LSTM1-input part of the dh2 carry added to the hh part in dh2_c), add the
@@ -624,16 +628,10 @@ __global__ __launch_bounds__(256) void k_bwd_head(const BwdHeadArgs q) {
         }
         const float dhv = q.dh2_voc[i] + carry + 0.f;
         const float* g = q.gates2 + (long long)row * 4 * H + j;
-        const float ig = g[0], fg = g[H], gg = g[2LL * H], og = g[3LL * H];
-        const float tc = tanhf(q.c2[i]);
-        const float dtc = dhv * og;
-        const float dc = q.dc_next[i] + dtc * (1.f - tc * tc);
-        float* d = q.dpre2 + (long long)row * 4 * H + j;
-        const float d0 = dc * gg * ig * (1.f - ig), d1 = dc * (q.c2_prev ? q.c2_prev[i] : 0.f) * fg * (1.f - fg);
-        const float d2 = dc * ig * (1.f - gg * gg), d3 = dhv * tc * og * (1.f - og);
-        d[0] = d0; d[H] = d1; d[2LL * H] = d2; d[3LL * H] = d3;
-        q.dc_prev[i] = dc * fg;
-        mx = fmaxf(fmaxf(fabsf(d0), fabsf(d1)), fmaxf(fabsf(d2), fabsf(d3)));
+        const LstmCellBwd r = lstm_cell_bwd(g, H, q.c2[i], q.c2_prev ? q.c2_prev[i] : 0.f, dhv, dhv * g[3LL * H], q.dc_next[i],
+                                            q.dpre2 + (long long)row * 4 * H + j);
+        q.dc_prev[i] = r.dc_prev;
+        mx = r.mx;
     }
     if (q.bm_dpre2) block_absmax_to(mx, q.bm_dpre2);
 }
@@ -691,20 +689,16 @@ __global__ __launch_bounds__(256) void k_bwd_tail(const float* __restrict__ Ca, 
         const float dhv = slab_sum(Ca + i, nslab, st, dh_tot[i]);
         const float ds = slab_sum(Cb + i, nslab, st);
         const float* g = gates1 + (long long)row * 6 * H + j;
-        const float ig = g[0], fg = g[H], gg = g[2LL * H], og = g[3LL * H], sg = g[4LL * H];
-        const float tc = tanhf(c1[i]);
+        const float sg = g[4LL * H];
         float* d = dpre1 + (long long)row * 6 * H + j;
-        const float d4 = ds * tc * sg * (1.f - sg);
-        d[4LL * H] = d4;
         const float extra = dtc_in[i] + ds * sg;
-        float dtc = dhv * og;
+        float dtc = dhv * g[3LL * H];
         dtc += extra;
-        const float dc = dc_next[i] + dtc * (1.f - tc * tc);
-        const float d0 = dc * gg * ig * (1.f - ig), d1 = dc * (c1_prev ? c1_prev[i] : 0.f) * fg * (1.f - fg);
-        const float d2 = dc * ig * (1.f - gg * gg), d3 = dhv * tc * og * (1.f - og);
-        d[0] = d0; d[H] = d1; d[2LL * H] = d2; d[3LL * H] = d3;
-        dc_prev[i] = dc * fg;
-        mx = fmaxf(fmaxf(fmaxf(fabsf(d0), fabsf(d1)), fmaxf(fabsf(d2), fabsf(d3))), fabsf(d4));
+        const LstmCellBwd r = lstm_cell_bwd(g, H, c1[i], c1_prev ? c1_prev[i] : 0.f, dhv, dtc, dc_next[i], d);
+        const float d4 = ds * r.tc * sg * (1.f - sg);
+        d[4LL * H] = d4;
+        dc_prev[i] = r.dc_prev;
+        mx = fmaxf(r.mx, fabsf(d4));
     }
     if (bm_dpre1) block_absmax_to(mx, bm_dpre1);      // (rows [0, 5H) of dpre1; the gate block [5H, 6H) is k_bwd_mid's dq)
 }
@@ -732,18 +726,6 @@ __global__ void k_train_indices(const int64_t* __restrict__ word_in, const int64
 // - the rows of t.dlogits, (t, b) order, stride Vp = up8(V), idle during the forward - and hands out logp_sel (rows, T) only;
 // vsr_train_backward_selected turns the rows into dlogits in place.  No (B, T, V) tensor exists on either side.
 
-// sum of up to GEMM_MAX_SLABS slabs + bias, four columns at once: every slab's load is issued before the first add (as slab_sum)
-__device__ __forceinline__ float4 slab_sum4(const float* __restrict__ p, int nslab, long long stride, const float* __restrict__ bias) {
-    float4 v[GEMM_MAX_SLABS];
-#pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k) v[k] = k < nslab ? *reinterpret_cast<const float4*>(p + k * stride) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 s = *reinterpret_cast<const float4*>(bias);
-#pragma unroll
-    for (int k = 0; k < GEMM_MAX_SLABS; ++k)
-        if (k < nslab) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
-    return s;
-}
-
 // Forward: one workgroup per (t, b) row of the S6 slabs (natural row order: no gather).  x = bias + slabs (<= 8), staged in LDS when the
 // launch passes V floats of dynamic LDS (lds_row) and re-summed from the slabs by the later passes otherwise; lse = max + log sum exp;
 // x - lse -> columns [0, V) of the row of `rows`; logp_sel[b T + t] = the target's entry.  targets (rows, T) int64: a word id, or -1 = not
@@ -768,14 +750,15 @@ __global__ __launch_bounds__(NT) void k_vocab_select(const float* __restrict__ l
         tg = -1;
     }
     const int tgt = (int)tg;
-    auto x1 = [&](int v) { return slab_sum(src + v, nsplit, stride, bias[v]); };
+    auto x1 = [&](int v) { return slab_sum(src + v, nsplit, stride, bias[v]); };       // bias + slabs of one column / of four
+    auto x4 = [&](int v0) { return slab_sum(src + v0, nsplit, stride, *reinterpret_cast<const float4*>(bias + v0)); };
 
     // ---- pass 1: the combined row (-> LDS) and its maximum
     float mx = -INFINITY;
     if (vec) {
 #pragma unroll 2
         for (int v0 = tid * 4; v0 < V; v0 += 4 * NT) {
-            const float4 a = slab_sum4(src + v0, nsplit, stride, bias + v0);
+            const float4 a = x4(v0);
             if (use_lds) *reinterpret_cast<float4*>(lrow + v0) = a;
             mx = fmaxf(fmaxf(mx, fmaxf(a.x, a.y)), fmaxf(a.z, a.w));
         }
@@ -798,7 +781,7 @@ __global__ __launch_bounds__(NT) void k_vocab_select(const float* __restrict__ l
     if (vec) {
 #pragma unroll 2
         for (int v0 = tid * 4; v0 < V; v0 += 4 * NT) {
-            const float4 a = use_lds ? *reinterpret_cast<const float4*>(lrow + v0) : slab_sum4(src + v0, nsplit, stride, bias + v0);
+            const float4 a = use_lds ? *reinterpret_cast<const float4*>(lrow + v0) : x4(v0);
             se += expf(a.x - mx); se += expf(a.y - mx); se += expf(a.z - mx); se += expf(a.w - mx);
         }
     } else {
@@ -816,7 +799,7 @@ __global__ __launch_bounds__(NT) void k_vocab_select(const float* __restrict__ l
     if (vec) {
 #pragma unroll 2
         for (int v0 = tid * 4; v0 < V; v0 += 4 * NT) {
-            float4 a = use_lds ? *reinterpret_cast<const float4*>(lrow + v0) : slab_sum4(src + v0, nsplit, stride, bias + v0);
+            float4 a = use_lds ? *reinterpret_cast<const float4*>(lrow + v0) : x4(v0);
             a.x -= lse; a.y -= lse; a.z -= lse; a.w -= lse;
             *reinterpret_cast<float4*>(dst + v0) = a;
             const int e = tgt - v0;

@@ -104,8 +104,8 @@ struct vsr_handle : GemmState {         // (gemm_route.h: the GEMM flavours swit
     long long gen_counter = 0;        // generations of the training forwards: strictly increasing per handle
     const char* ws_lo = nullptr;      // the workspace the current vsr_prepare*() carved (h->c points into it)
     size_t ws_bytes = 0;
-    // the selection of step t inside the LSTM1 kernel of step t + 1 (kernels.h: k_select_lstm1, k_select_simple_lstm1); VSR_FUSE_SELECT=0: a launch of its own
-    int fuse_select = 3;              // bit 0: greedy / sampling / replay (k_select_simple_lstm1), bit 1: beam search (k_select_lstm1)
+    // the selection of step t inside the LSTM1 kernel of step t + 1 (kernels.h: k_select_lstm1_x2, k_select_simple_lstm1); VSR_FUSE_SELECT=0: a launch of its own
+    int fuse_select = 3;              // bit 0: greedy / sampling / replay (k_select_simple_lstm1), bit 1: beam search (k_select_lstm1_x2)
     int bf16_a16 = 1;            // bf16 mode: the decode step's producers write bf16 images of the GEMM A operands (VSR_BF16_A16=0: off)
     vsr_dims d;
     vsr_weights w;
@@ -114,6 +114,7 @@ struct vsr_handle : GemmState {         // (gemm_route.h: the GEMM flavours swit
     const int* vt_ids = nullptr;
     int n_verbs = 0;
     const float* xproj = nullptr;     // decode cache: (V, 6H) projection of the embedding table, valid for the bound weights
+    bool xproj_al8 = false;           // ... at an 8-byte aligned address: what k_select_lstm1_x2 needs (everything else it touches is the workspace's)
     long long rows_bound = 0;    // vsr_set_valid_rows_bound: > 0 = the caller's upper bound on the non-padding region rows; vsr_prepare*() then never waits for the host
     int attend_parts = 2, attend_limit = 256;        // workgroups per row of k_attend in launches of <= attend_limit / parts rows (VSR_ATTEND_PARTS, VSR_ATTEND_LIMIT)
     int adam_blocks = 0;         // grid budget of vsr_adam_step: the workgroups the device holds at once (set at its first call)
@@ -319,8 +320,13 @@ extern "C" int vsr_profile_end(vsr_handle* h, void* stream, double* gemm_ms, int
 // VOID_REFRESH: copies / images rebuilt in the same flavour: cache and statics are of older weights; the saved forwards stay (a training
 // step refreshes, then differentiates).  VOID_FLAVOUR: flavour or weight pointers changed: a saved forward is not differentiated in another.
 enum VoidLevel { VOID_REFRESH, VOID_FLAVOUR };
+// the decode cache pointer and what vsr_beam asks of it (k_select_lstm1_x2 reads it 8 bytes at a time; nothing else it touches can be misaligned)
+static void set_xproj(vsr_handle* h, const float* buf) {
+    h->xproj = buf;
+    h->xproj_al8 = buf && (reinterpret_cast<uintptr_t>(buf) & 7) == 0;
+}
 static void void_derived(vsr_handle* h, VoidLevel level) {
-    h->xproj = nullptr;
+    set_xproj(h, nullptr);
     h->prepared = false;              // vsr_prepare*() again (check_ready says so)
     if (level == VOID_FLAVOUR) { invalidate_train_ctx(h->tc); drop_saved_forwards(h->saved); }
 }
@@ -355,7 +361,7 @@ extern "C" size_t vsr_decode_cache_floats(const vsr_handle* h) {
 }
 extern "C" int vsr_build_decode_cache(vsr_handle* h, float* buf, size_t n_floats, void* stream) {
     if (!h || !h->bound) return fail("vsr_build_decode_cache: weights not bound");
-    if (!buf) { h->xproj = nullptr; return 0; }
+    if (!buf) { set_xproj(h, nullptr); return 0; }
     if (n_floats < vsr_decode_cache_floats(h)) return fail("vsr_build_decode_cache: buffer too small");
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;
@@ -379,7 +385,7 @@ extern "C" int vsr_build_decode_cache(vsr_handle* h, float* buf, size_t n_floats
         slab_sum_to(s, slabs, ns, m, 6 * H, buf + (size_t)v0 * 6 * H);
     }
     LAUNCHCHK();
-    h->xproj = buf;
+    set_xproj(h, buf);
     return 0;
 }
 
@@ -629,7 +635,7 @@ extern "C" int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr
     // what a refresh voids (vsr_bind_weights has the rules); with no flavour product the fp32 kernels read the weights live: only the
     // decode cache is of the old weights
     if (h->h2_on || h->bf16_on) void_derived(h, VOID_REFRESH);
-    else h->xproj = nullptr;
+    else set_xproj(h, nullptr);
     return 0;
 }
 
@@ -873,7 +879,7 @@ struct StepIO {
     float* lg_out = nullptr; long long lg_stride = 2;
     float* alpha_out = nullptr;
     bool s1_from_prev = false;   // this step's LSTM1 sums are already in c.pre1 (computed over the parent rows)
-    // the selection of the PREVIOUS step, still to be made: it rides in this step's LSTM1 kernel (k_select_lstm1 / k_select_simple_lstm1;
+    // the selection of the PREVIOUS step, still to be made: it rides in this step's LSTM1 kernel (k_select_lstm1_x2 / k_select_simple_lstm1;
     // only with s1_from_prev).  sel_images: images of the beam selection (its parents are sel_beam->cb rows per image).
     const SelBeamArgs* sel_beam = nullptr;
     const SelSimpleArgs* sel_simple = nullptr;
@@ -948,18 +954,12 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     // ---- S1
     if (io.s1_from_prev && io.sel_beam) {
         const SelBeamArgs& sb = *io.sel_beam;
-        // two units per lane (8-byte accesses) wherever H is even and every base is 8-byte aligned (the images: 4-byte).  vsr_create
-        // admits only H % 4 == 0 and the workspace is carved at 256 bytes: what is left for the one-unit kernel is a caller's decode
-        // cache buffer (vsr_build_decode_cache) at an address that is only 4-byte aligned
-        uintptr_t al = 0, al16 = reinterpret_cast<uintptr_t>(h1n16) | reinterpret_cast<uintptr_t>(s_t16);
-        for (const void* p : {(const void*)c.pre1, (const void*)c.vproj, (const void*)c1o, (const void*)h1n, (const void*)c1n, (const void*)c.s_t,
-                              (const void*)c.gpre, (const void*)h->xproj})
-            al |= reinterpret_cast<uintptr_t>(p);
-        const bool x2 = H % 2 == 0 && (al & 7) == 0 && (al16 & 3) == 0;
-        const int nslice = cdiv(H, x2 ? 2 * SL_UB : SL_UB);
+        // two units per lane, 8-byte accesses: H % 4 == 0 (vsr_create), the workspace is 16-byte aligned and carved at 256 bytes, and
+        // vsr_beam leaves a selection pending only over a decode cache at an 8-byte aligned address (xproj_al8)
+        const int nslice = cdiv(H, 2 * SL_UB);
         with_const_1to8(sb.beam, [&](auto KK) {
             constexpr int K = decltype(KK)::value;
-            hipLaunchKernelGGL(x2 ? k_select_lstm1_x2<K> : k_select_lstm1<K>, dim3(sb.B * nslice), dim3((K + 1) * 64), 0, s, sb, c.pre1, c.pre1_ns, c.pre1_stride,
+            hipLaunchKernelGGL(k_select_lstm1_x2<K>, dim3(sb.B * nslice), dim3((K + 1) * 64), 0, s, sb, c.pre1, c.pre1_ns, c.pre1_stride,
                                c.vproj, c1o, H, nslice, h1n, c1n, c.s_t, c.gpre, h->xproj, c.pre1_nblk, h1n16, s_t16, isc, c.pre1_skip5);
         });
     } else if (io.s1_from_prev && io.sel_simple) {
@@ -1177,8 +1177,9 @@ extern "C" int vsr_beam(vsr_handle* h, int32_t beam, int32_t out_size, int64_t e
     const int B = c.B, T = h->d.seq_len;
     const int K = beam;
     if (zero_state(h, B, s)) return 1;
-    // The beam selection of step t rides in the LSTM1 kernel of step t + 1 (k_select_lstm1) wherever that kernel starts from cached sums
-    // (decode cache); the last step's, and every step's with VSR_FUSE_SELECT=0, is a launch of its own (k_select_beam).
+    // The beam selection of step t rides in the LSTM1 kernel of step t + 1 (k_select_lstm1_x2) wherever that kernel starts from cached sums
+    // (decode cache); the last step's, and every step's with VSR_FUSE_SELECT=0 or over a decode cache that is not 8-byte aligned, is a
+    // launch of its own (k_select_beam, then k_lstm1: the same values).
     SelBeamArgs pending{};
     bool have_pending = false;
     for (int t = 0; t < T; ++t) {
@@ -1196,7 +1197,7 @@ extern "C" int vsr_beam(vsr_handle* h, int32_t beam, int32_t out_size, int64_t e
         const SelBeamArgs sa{t, cb, beam, c.L, eos_word, eos_gate, c.top_v, c.top_i, c.lg, c.slot[cur], c.word[cur], c.gate[cur], c.seq[cur],
                              c.seq[cur ^ 1], c.mask[cur], c.mask[cur ^ 1], c.word[cur ^ 1], c.gate[cur ^ 1], c.slot[cur ^ 1], c.parent,
                              c.hist_parent, c.hist_word, c.hist_gate, c.hist_lpw, c.hist_lpg, B};
-        have_pending = (h->fuse_select & 2) && t + 1 < T && h->xproj != nullptr;       // (the next step is then s1_from_prev)
+        have_pending = (h->fuse_select & 2) && t + 1 < T && h->xproj_al8;       // (the next step is then s1_from_prev)
         if (have_pending) pending = sa;
         else with_const_1to8(K, [&](auto KK) { hipLaunchKernelGGL((k_select_beam<decltype(KK)::value>), dim3(B), dim3(64), 0, s, sa); });
         LAUNCHCHK();
