@@ -1,7 +1,7 @@
 """More than one live forward per model (round-5 review, Missing #3).  The reference runs under eager autograd, where two forwards
 followed by (l1 + l2).backward(), micro-batch accumulation, or a decode call between a forward and its backward just work
 (/root/reference/models/CaptioningModel.py:22-36).  Rounds 1-5 kept ONE saved forward per handle and raised at the second backward; now
-every live forward holds its own pair of workspaces (vsrcap/engine.py: _Slot; include/vsrcap.h: vsr_train_select)."""
+every live forward holds its own pair of workspaces (vsrcap/forwards.py: Slot; include/vsrcap.h: vsr_train_select)."""
 import numpy as np
 import pytest
 import torch
@@ -94,7 +94,7 @@ def test_micro_batches_reuse_one_pair_of_buffers():
         l = vo.xe_loss(out, gate, c, g)[0]
         l.backward()
         keep.append((out, gate, l))                 # the graphs stay referenced, as in a loop that logs its losses later
-    assert len(m._engine(torch.device(DEV))._slots) == 1
+    assert len(m._engine(torch.device(DEV)).forwards.slots) == 1
     _check(m, want)
 
 
@@ -147,3 +147,29 @@ def test_second_backward_after_a_later_forward_raises():
     with pytest.raises(RuntimeError, match="saved activations are gone"):
         l1.backward()
     vo.xe_loss(out2, gate2, c2, g2)[0].backward()
+
+
+def test_second_backward_after_a_later_larger_forward_raises():
+    """the same with a later forward that does NOT fit the first one's buffers: both workspaces are replaced, the first forward's went back
+    to the allocator, and the library (which drops saved forwards by address overlap) may still hold its entry - the host side knows that
+    no buffers hold that forward any more and raises before any library call (vsrcap/forwards.py)"""
+    cfg, w, b1, _ = _setup()
+    meta, _ = load_golden("g1_xe_small")
+    b2 = helpers.train_inputs(dict(cfg, B=2 * cfg["B"]), meta["seed"] + 17)
+    _, want = _oracle_sum_grads(cfg, w, [b1, b2])
+    m = helpers.build_model(cfg, w, DEV).train()
+    m.zero_grad()
+    d1, s1, c1, g1 = _dev(b1)
+    d2, s2, c2, g2 = _dev(b2)
+    out1, gate1 = m((d1,), (c1, s1))
+    l1 = vo.xe_loss(out1, gate1, c1, g1)[0]
+    l1.backward(retain_graph=True)
+    eng = m._engine(torch.device(DEV))
+    ws1 = eng.workspace()
+    out2, gate2 = m((d2,), (c2, s2))                 # grows the differentiated forward's buffers
+    assert eng.workspace() is not ws1 and len(eng.forwards.slots) == 1
+    with pytest.raises(RuntimeError, match="saved activations are gone"):
+        l1.backward()
+    assert eng.live_forwards() == 1                  # the second forward is still owed its backward
+    vo.xe_loss(out2, gate2, c2, g2)[0].backward()
+    _check(m, want)                                  # (l1's first backward has accumulated already)

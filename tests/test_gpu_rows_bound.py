@@ -110,7 +110,7 @@ def test_a_bound_that_is_too_small_zeroes_the_unprojected_rows_and_is_counted():
     with torch.no_grad():
         m.set_valid_rows_bound(exact - 40)
         a = m.test(det, ctrl)
-        eng._ws.fill_(0x7f)                       # poison the workspace (NaN-ish floats) and decode again
+        eng.workspace().fill_(0x7f)                       # poison the workspace (NaN-ish floats) and decode again
         m.invalidate_cache()
         b = m.test(det, ctrl)
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])

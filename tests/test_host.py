@@ -121,11 +121,11 @@ def test_weights_generation_moves_with_everything_that_can_move_the_weights():
 
 
 def test_live_forward_slots_bookkeeping():
-    """vsrcap.engine._Slot: a slot is 'live' while its forward's token is alive and the forward has not been differentiated"""
+    """vsrcap.forwards.Slot: a slot is 'live' while its forward's token is alive and the forward has not been differentiated"""
     import gc
-    from vsrcap.engine import _Slot, ForwardToken
+    from vsrcap.forwards import Slot, ForwardToken
     import weakref
-    s = _Slot()
+    s = Slot()
     assert not s.live()
     tok = ForwardToken(7)
     s.token, s.generation, s.differentiated = weakref.ref(tok), 7, False

@@ -1,6 +1,9 @@
 """Thin host-side driver of the C ABI: owns one vsr_handle, borrows torch storage for weights / tensors /
 workspace and enqueues everything on torch's current HIP stream.  PyTorch is plumbing here (device memory,
 streams); all arithmetic happens in libvsrcap.so.
+What has to be remembered between calls has two owners, and this engine is the backend of both (allocation, ctypes, device, stream):
+vsrcap/derived.py for the state derived from the weights, vsrcap/forwards.py for the live training forwards, the buffer pairs they
+are saved in and the key of the prepared statics.
 """
 import contextlib
 import ctypes as C
@@ -12,6 +15,7 @@ import torch
 
 from . import _lib
 from .derived import Derived
+from .forwards import MAX_LIVE_FORWARDS, Forwards        # (the limit: importable from here as before)
 
 
 def _on_device(fn):
@@ -58,33 +62,6 @@ def _grown(buf, n, dtype, device):
     return buf
 
 
-class ForwardToken:
-    """Lives in the autograd node of one training forward (train._DecoderFn): while it is alive and its forward has not been
-    differentiated, the buffers that forward was saved in are not handed to anyone else."""
-    __slots__ = ("generation", "__weakref__")
-
-    def __init__(self, generation):
-        self.generation = generation
-
-
-class _Slot:
-    """One pair of caller buffers of the C ABI - the vsr_prepare*() workspace and the training workspace - plus the inputs they borrow.
-    A saved training forward lives in exactly one slot (include/vsrcap.h, vsr_train_select)."""
-    __slots__ = ("ws", "tws", "keep", "token", "generation", "differentiated")
-
-    def __init__(self):
-        self.ws = self.tws = self.keep = self.token = None
-        self.generation = 0
-        self.differentiated = True
-
-    def live(self):
-        """holds a forward somebody can still ask the gradient of for the FIRST time"""
-        return self.token is not None and self.token() is not None and not self.differentiated
-
-
-MAX_LIVE_FORWARDS = 8
-
-
 class Engine:
     def __init__(self, dims, device=None):
         """dims: dict with the vsr_dims fields; device: the torch cuda device this handle lives on (one handle per device)."""
@@ -102,36 +79,16 @@ class Engine:
         self._derived = Derived()        # the state derived from the weights (vsrcap/derived.py); this engine is its backend
         self._wbuf = {"bf16": None, "h2": None, "cache": None}      # ... the buffers its products live in
         self._wdev = None                # ... and the device of the weights last handed to sync_weights()
-        self._slots = [_Slot()]          # buffer pairs; more than one only while several training forwards are alive
-        self._slot = self._slots[0]
-        self._prep_key = None
+        self.forwards = Forwards()       # the live training forwards and their buffer pairs (vsrcap/forwards.py); its backend too
         self._verb_dev = None
         self.grad_sink = None       # list of 28 tensors (WEIGHT_FIELDS order): backward writes there and autograd gets no tensors
 
-    # the current slot's buffers under their old names
-    _ws = property(lambda self: self._slot.ws, lambda self, v: setattr(self._slot, "ws", v))
-    _tws = property(lambda self: self._slot.tws, lambda self, v: setattr(self._slot, "tws", v))
-    _keep = property(lambda self: self._slot.keep, lambda self, v: setattr(self._slot, "keep", v))
-
-    def _claim_slot(self):
-        """Called before a vsr_prepare*() that will overwrite the current slot's workspace (_prepare_in_slot: the prepare key is already
-        void): if a live forward is saved there, move to a free slot (one whose forward is gone or already differentiated), or open
-        a new one.  The reference has no such limit at all (eager autograd); MAX_LIVE_FORWARDS pairs of buffers is where this build stops."""
-        if not self._slot.live():
-            return
-        for sl in self._slots:
-            if not sl.live():
-                self._slot = sl
-                return
-        if len(self._slots) >= MAX_LIVE_FORWARDS:
-            raise RuntimeError("%d training forwards of this model are alive and not yet differentiated: each holds its own workspaces "
-                               "(~GBs at batch 100). Call backward() on some of them (or drop their outputs) before the next forward."
-                               % len(self._slots))
-        self._slot = _Slot()
-        self._slots.append(self._slot)
-
     def live_forwards(self):
-        return sum(1 for sl in self._slots if sl.live())
+        return self.forwards.live_count()
+
+    def workspace(self):
+        """the vsr_prepare*() workspace the handle's statics are in"""
+        return self.forwards.current.ws
 
     def __del__(self):
         try:
@@ -155,7 +112,7 @@ class Engine:
         dims8 = all(getattr(self.dims, k) % 8 == 0 for k in ("det_feat_size", "input_encoding_size", "rnn_size", "att_size"))
         self._wdev = t.device
         if self._derived.sync((tuple(ptrs), weights_version, compute_dtype, dims8, training), self):
-            self._prep_key = None
+            self.forwards.void_key()
 
     def invalidate(self):
         """Forget the cached prepare() and everything derived from the weights.  prepare() keys its cache on (data_ptr,
@@ -184,7 +141,7 @@ class Engine:
             self._derived.invalidate(self)       # launches may have gone out: nothing derived is known to be current
             raise
         self._derived.stepped(ptrs, weights_version)
-        self._prep_key = None
+        self.forwards.void_key()
 
     # the backend of vsrcap/derived.py, one method per library call (include/vsrcap.h says what each of them voids in the handle)
     def bind(self, ptrs):
@@ -257,23 +214,21 @@ class Engine:
         return B
 
     def _prepare_in_slot(self, key, for_training, rows_bound, keep, size, size_args, call, args):
-        """The tail prepare() and prepare_indexed() share: served from the cache when the key matches; else the library call into the
-        workspace of a slot that holds no live forward.  keep: the inputs, borrowed by the library until the next prepare."""
+        """The tail prepare() and prepare_indexed() share: served from the cache, or the library call into the workspace of the slot
+        Forwards.begin_prepare names (one that holds no live forward).  keep: the inputs, borrowed by the library until the next prepare."""
         if keep[0].size(2) != self.dims.det_feat_size:
             raise RuntimeError("feature size %d != det_feat_size %d" % (keep[0].size(2), self.dims.det_feat_size))
-        if key == self._prep_key and not (for_training and self._slot.live()):
+        slot = self.forwards.begin_prepare(key, for_training)       # from here on a call that raises leaves no key behind
+        if slot is None:
             return
-        self._prep_key = None                # from here on the handle's statics are in flux: a call that raises leaves no key behind
-        self._claim_slot()
         _lib.check(self.lib.vsr_set_valid_rows_bound(self.h, int(rows_bound or 0)))
         need = size(self.h, *size_args)
         if need == 0:
             raise RuntimeError("%s rejected the shapes" % size.__name__)
         dev = keep[0].device
-        self._ws = _grown(self._ws, need, torch.uint8, dev)
-        _lib.check(call(self.h, *args, _ptr(self._ws), self._ws.numel(), self._stream(dev)))
-        self._keep = keep
-        self._prep_key = key
+        slot.ws = _grown(slot.ws, need, torch.uint8, dev)
+        _lib.check(call(self.h, *args, _ptr(slot.ws), slot.ws.numel(), self._stream(dev)))
+        self.forwards.prepared(key, keep)
 
     @_on_device
     def prepare_indexed(self, det, bank, slot_idx, row_img, beam, weights_version=None, rows_bound=None, for_training=False):
@@ -349,21 +304,18 @@ class Engine:
                 self.lib.vsr_train_workspace_bytes_rows(self.h, n_img, K, T))
         if need == 0:
             raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
-        self._tws = _grown(self._tws, need, torch.uint8, device)
+        slot = self.forwards.filing_slot("training forward")
+        slot.tws = _grown(slot.tws, need, torch.uint8, device)
         out = torch.empty((B, T) if targets is not None else (B, T, self.dims.vocab_size), dtype=torch.float32, device=device)
         gate = torch.empty(B, T, 2, dtype=torch.float32, device=device)
-        if self._slot.live():
-            raise RuntimeError("internal: training forward into a slot that holds a live forward (prepare(for_training=True) first)")
-        tail = (T, _ptr(out), _ptr(gate), _ptr(self._tws), self._tws.numel(), self._stream(device))
+        tail = (T, _ptr(out), _ptr(gate), _ptr(slot.tws), slot.tws.numel(), self._stream(device))
         if targets is not None:
             _lib.check(self.lib.vsr_train_forward_selected(self.h, K, _ptr(word_in), _ptr(slots), _ptr(targets), *tail))
         elif K == 1:
             _lib.check(self.lib.vsr_train_forward(self.h, _ptr(word_in), _ptr(slots), *tail))
         else:
             _lib.check(self.lib.vsr_train_forward_rows(self.h, K, _ptr(word_in), _ptr(slots), *tail))
-        self._slot.generation = self.train_generation()
-        self._slot.token = None
-        self._slot.differentiated = True      # (until train.py attaches the autograd node's token: note_forward)
+        self.forwards.filed(self.train_generation())      # (not live until train.py attaches the autograd node's token: note_forward)
         self.raise_on_bad_ids(device, who)
         return out, gate
 
@@ -377,11 +329,7 @@ class Engine:
 
     def note_forward(self):
         """the autograd node of the forward just taken: returns the token that keeps its buffers reserved"""
-        import weakref
-        tok = ForwardToken(self._slot.generation)
-        self._slot.token = weakref.ref(tok)
-        self._slot.differentiated = False
-        return tok
+        return self.forwards.note_forward()
 
     def train_generation(self):
         """identity of the forward pass saved in the handle (0 = none): see vsr_train_generation in include/vsrcap.h"""
@@ -395,8 +343,7 @@ class Engine:
         the gradients to instead of fresh allocations.
         selected: the forward was train_forward_selected and grad_out is the (rows, T) gradient of its log-probs (train_backward_selected)."""
         if generation is not None:
-            self._make_current(device, generation, "backward of a forward pass")
-            self._slot.differentiated = True
+            self._make_current(device, generation, "backward of a forward pass", differentiate=True)
         grad_out = _f32(grad_out, "grad of word log-probs")
         grad_gate = _f32(grad_gate, "grad of gate log-probs")
         if into is not None:
@@ -416,21 +363,12 @@ class Engine:
         consumes the forward's saved log-prob rows in place: a second backward of the same forward raises."""
         return self.train_backward(device, grad_sel, grad_gate, shapes, generation, into, selected=True)
 
-    def _make_current(self, device, generation, who):
+    def _make_current(self, device, generation, who, differentiate=False):
         """several forwards may be alive (each in its own slot): make this one the handle's current forward again"""
-        if self.lib.vsr_train_select(self.h, int(generation), self._stream(device)) != 0:
-            raise RuntimeError(
-                "%s whose saved activations are gone (%s). A forward stays differentiable until its "
-                "buffers are reused: that happens once it HAS been differentiated (a second backward needs a new forward - "
-                "retain_graph=True is not supported across a later forward), when more than %d forwards are alive, or when "
-                "the compute dtype / the parameters' storage changed in between."
-                % (who, self.lib.vsr_last_error().decode(), MAX_LIVE_FORWARDS))
-        if self._slot.generation != generation:
-            for sl in self._slots:
-                if sl.generation == generation:
-                    self._slot = sl
-                    self._prep_key = None           # the handle's hoisted state is this slot's now
-                    break
+        def select(g):
+            if self.lib.vsr_train_select(self.h, int(g), self._stream(device)) != 0:
+                return self.lib.vsr_last_error().decode()
+        self.forwards.make_current(generation, who, select, differentiate)
 
     # ------------------------------------------------------------------ tape: a training forward taken one step per call (vsrcap/steptape.py)
     @_on_device
@@ -440,12 +378,11 @@ class Engine:
         need = self.lib.vsr_train_workspace_bytes(self.h, B, int(max_steps))
         if need == 0:
             raise RuntimeError("vsr_train_workspace_bytes rejected the shapes (prepare() first, same batch)")
-        if self._slot.live():
-            raise RuntimeError("internal: tape into a slot that holds a live forward (prepare(for_training=True) first)")
-        self._tws = _grown(self._tws, need, torch.uint8, device)
-        _lib.check(self.lib.vsr_train_tape_begin(self.h, int(max_steps), _ptr(self._tws), self._tws.numel(), self._stream(device)))
-        self._slot.generation = self.train_generation()
-        return self._slot.generation, self.note_forward()
+        slot = self.forwards.filing_slot("tape")
+        slot.tws = _grown(slot.tws, need, torch.uint8, device)
+        _lib.check(self.lib.vsr_train_tape_begin(self.h, int(max_steps), _ptr(slot.tws), slot.tws.numel(), self._stream(device)))
+        self.forwards.filed(self.train_generation())
+        return slot.generation, self.note_forward()
 
     @_on_device
     def tape_step(self, device, generation, B, word, slot):
