@@ -227,6 +227,20 @@ int vsr_sample(vsr_handle* h, uint64_t seed, const int64_t* forced_words, const 
  * call on K-times repeated images would use.  vsr_sample is the rows_per_image = 1 case. */
 int vsr_sample_rows(vsr_handle* h, int32_t rows_per_image, uint64_t seed, const int64_t* forced_words, const int64_t* forced_gates,
                     int64_t* words, int64_t* gates, float* lp_words, float* lp_gates, void* stream);
+/* vsr_sample_rows with the greedy decode of every image - the self-critical baseline of SCST (coco_scripts/train.py:129) - in the same
+ * launches.  rows_per_image = K samples per image, K >= 1 and K + 1 <= the beam vsr_prepare*() was called with: the decoder runs
+ * M = B (K + 1) rows, K + 1 adjacent rows per image that share its statics.
+ *   rows:    decoder row b (K + 1) is the baseline of image b, row b (K + 1) + 1 + j its sample j.
+ *   baseline rows take the arg-max word (the key is the logit itself, the lowest index wins a tie) and the gate (l1 > l0) ? 1 : 0, as
+ *            vsr_greedy does; they draw no noise and write base_words / base_gates (B,T) int64 row b.  Their log-probs are not returned.
+ *   sample rows behave as in vsr_sample_rows(K): sample j of image b writes row b K + j of words / gates / lp_words / lp_gates
+ *            (B K,T), reads its forced ids at that row of forced_words / forced_gates (B K,T), and its Philox key is
+ *            (seed, b K + j, t) - in terms of its decoder row r, r - r / (K + 1) - 1: the noise of the call without baseline rows.
+ * Nothing of (B (K + 1),T) is staged: every row is written to its destination.  Fails on K < 1, K + 1 > the prepared beam, a null
+ * output, or one forced pointer without the other. */
+int vsr_sample_rows_baseline(vsr_handle* h, int32_t rows_per_image, uint64_t seed, const int64_t* forced_words,
+                             const int64_t* forced_gates, int64_t* words, int64_t* gates, float* lp_words, float* lp_gates,
+                             int64_t* base_words, int64_t* base_gates, void* stream);
 /* CaptioningModel.beam_search / beam_search_v (:116-294): joint (word x gate) beam search.
  * words/gates (B,out_size,T) int64; lp_* (B,out_size,T) fp32 (the reference's per-slot log-probs, quirk 2
  * of SURVEY.md 8a); scores (B,out_size) fp32 final sequence log-probs, may be NULL. */
@@ -267,7 +281,9 @@ int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const int64_t* slot
                       float* logp_gates, void* train_workspace, size_t train_workspace_bytes, void* stream);
 int vsr_train_backward(vsr_handle* h, const float* grad_logp_words, const float* grad_logp_gates, const vsr_weights* grads,
                        void* stream);
-/* The same with rows_per_image = K decoder rows per image (the replay of vsr_sample_rows' samples): vsr_prepare*(beam >= K), M = B K
+/* The same with rows_per_image = K decoder rows per image (the replay of vsr_sample_rows' samples, or of vsr_sample_rows_baseline's - the
+ * K sample rows only, under its beam of K + 1; K = 1 included, which vsr_train_forward itself refuses under a beam above 1):
+ * vsr_prepare*(beam >= K), M = B K
  * rows in the order of repeat_interleave(K, 0); word_in / slots (M,T), logp_words (M,T,V), logp_gates (M,T,2).  Statics are shared:
  * att_va runs once per image, and the backward pass adds the K rows' contributions to everything that is per image - dP of an
  * (image, slot), the gradient of the hoisted v-bar projections - in ascending row order (no float atomics: runs repeat bit for bit).

@@ -879,6 +879,9 @@ struct TopEntry { float v; int i; };
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 enum VocabMode { VM_TOPK = 0, VM_SAMPLE = 1, VM_FORCED = 2, VM_FULL = 3 };
+// Decoder rows of a sampling call with a greedy baseline row per image (gs = K + 1 rows per image: the baseline, then the K samples):
+// the index sample j of image b has in the K samples per image call, b K + j, from its decoder row b gs + 1 + j
+__device__ __forceinline__ int sample_row(int row, int gs) { return row - row / gs - 1; }
 
 // Per row: logits = sum of slabs + bias; log-sum-exp; then by mode
 //   VM_TOPK   K best (log-prob, id) pairs (K = 1: greedy arg-max)          (CaptioningModel.py:47, :152)
@@ -886,6 +889,9 @@ enum VocabMode { VM_TOPK = 0, VM_SAMPLE = 1, VM_FORCED = 2, VM_FULL = 3 };
 //   VM_FORCED log-prob of a given id (sampling replay)
 //   VM_FULL   the whole log_softmax row is written to full_out             (step :178, forward :34)
 // Verb-forced rows (step_v :268-293) emit one word with log-prob 0 and -1e6 elsewhere.
+// gs > 0 (VM_SAMPLE / VM_FORCED launches of vsr_sample_rows_baseline, rpi = gs): rows with row % gs == 0 are greedy baseline rows - their
+// mode is VM_TOPK (K = 1: the arg-max of the logits, no noise drawn); the others are sample sample_row(row, gs) of a gs - 1 samples per
+// image call: that index keys their noise and reads their forced id.  The mode is uniform per workgroup (one row per block).
 template <int K, int NT>
 __global__ __launch_bounds__(NT) void k_vocab(const float* __restrict__ logits, int nsplit, long long stride,
                                                const float* __restrict__ bias, int M, int V, int mode,
@@ -895,7 +901,7 @@ __global__ __launch_bounds__(NT) void k_vocab(const float* __restrict__ logits, 
                                                const float* __restrict__ verbs, const int* __restrict__ slot, int rpi,
                                                int L, int gt, const int* __restrict__ vt_ptr,
                                                const int* __restrict__ vt_ids, int n_verbs, int lds_row,
-                                               const GateLogitArgs gate, int* __restrict__ bad) {
+                                               const GateLogitArgs gate, int* __restrict__ bad, int gs) {
     constexpr int NW = NT / 64;
     __shared__ float sv[NT * K];
     __shared__ int si[NT * K];
@@ -905,6 +911,10 @@ __global__ __launch_bounds__(NT) void k_vocab(const float* __restrict__ logits, 
     extern __shared__ float lrow[];          // V floats when the launch passes dynamic LDS: the combined row is
     const bool use_lds = lds_row != 0;       // summed from the slabs ONCE and the later passes read it from LDS
     const int row = blockIdx.x;
+    int srow = row;                          // the row's index among the samples: noise key, forced id
+    if (gs > 0) {
+        if (row % gs == 0) mode = VM_TOPK; else srow = sample_row(row, gs);
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* src = logits + (long long)row * V;
     const int V4 = (V + 3) & ~3;
@@ -964,7 +974,7 @@ __global__ __launch_bounds__(NT) void k_vocab(const float* __restrict__ logits, 
                 top_i[(long long)row * K + tid] = id;
             }
         } else if (tid == 0) {
-            int id = (mode == VM_FORCED) ? forced[row] : pick;   // Categorical over {0, -1e6...} is a point mass
+            int id = (mode == VM_FORCED) ? forced[srow] : pick;   // Categorical over {0, -1e6...} is a point mass
             top_v[row] = (id == pick) ? 0.f : -1e6f;
             top_i[row] = id;
         }
@@ -1015,7 +1025,7 @@ __global__ __launch_bounds__(NT) void k_vocab(const float* __restrict__ logits, 
             const int v0 = vb + 4 * NT * u;
             if (v0 >= V4) break;
             uint32_t rnd[4] = {0, 0, 0, 0};
-            if (mode == VM_SAMPLE) Philox::gen(seed, (uint32_t)(v0 >> 2), (uint32_t)row, t, 0u, rnd);
+            if (mode == VM_SAMPLE) Philox::gen(seed, (uint32_t)(v0 >> 2), (uint32_t)srow, t, 0u, rnd);
             if (use_lds && vec) *reinterpret_cast<float4*>(lrow + v0) = make_float4(xs_all[u][0], xs_all[u][1], xs_all[u][2], xs_all[u][3]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -1132,7 +1142,7 @@ __global__ __launch_bounds__(NT) void k_vocab(const float* __restrict__ logits, 
     }
     if (mode == VM_FORCED) {
         if (tid == 0) {
-            const int id = forced[row];
+            const int id = forced[srow];
             top_v[row] = getx(id) - lse;
             top_i[row] = id;
         }
@@ -1226,16 +1236,25 @@ struct SelSimpleArgs {
     int mode; const float* top_v; const int* top_i; const float* lg; const int* forced_gate; uint64_t seed; uint32_t t;
     const int* slot; int L, M, T;
     int* word_next; int* gate_next; int* slot_next; int64_t* words; int64_t* gates; float* lp_w; float* lp_g;
+    // gs > 0 (k_vocab has the row rule): M = images x gs decoder rows; the baseline row of image b writes base_words / base_gates
+    // (images, T) row b and no log-probs, a sample row writes row sample_row(row, gs) of words / gates / lp_w / lp_g (images x (gs - 1), T)
+    int gs; int64_t* base_words; int64_t* base_gates;
 };
 // one row's selection; `write`: this thread stores the row's outputs.  Returns the word.
 __device__ __forceinline__ int select_simple_row(const SelSimpleArgs& a, int row, bool write) {
     const float l0 = a.lg[row * 2], l1 = a.lg[row * 2 + 1];
+    int mode = a.mode, srow = row;
+    bool base = false;
+    if (a.gs > 0) {
+        base = row % a.gs == 0;
+        if (base) mode = VM_TOPK; else srow = sample_row(row, a.gs);
+    }
     int g;
-    if (a.mode == VM_TOPK) g = (l1 > l0) ? 1 : 0;                       // torch.max: first maximum on ties
-    else if (a.mode == VM_FORCED) g = a.forced_gate[row];
+    if (mode == VM_TOPK) g = (l1 > l0) ? 1 : 0;                         // torch.max: first maximum on ties
+    else if (mode == VM_FORCED) g = a.forced_gate[srow];
     else {
         uint32_t rnd[4];
-        Philox::gen(a.seed, 0xFFFFFFFFu, (uint32_t)row, a.t, 1u, rnd);
+        Philox::gen(a.seed, 0xFFFFFFFFu, (uint32_t)srow, a.t, 1u, rnd);
         g = (Philox::u01(rnd[0]) < expf(l0)) ? 0 : 1;
     }
     const int w = a.top_i[row];
@@ -1244,10 +1263,15 @@ __device__ __forceinline__ int select_simple_row(const SelSimpleArgs& a, int row
         a.gate_next[row] = g;
         int k = a.slot[row] + g;
         a.slot_next[row] = k < 0 ? 0 : (k > a.L - 1 ? a.L - 1 : k);
-        a.words[(long long)row * a.T + a.t] = w;
-        a.gates[(long long)row * a.T + a.t] = g;
-        if (a.lp_w) a.lp_w[(long long)row * a.T + a.t] = a.top_v[row];
-        if (a.lp_g) a.lp_g[(long long)row * a.T + a.t] = g ? l1 : l0;
+        if (base) {
+            a.base_words[(long long)(row / a.gs) * a.T + a.t] = w;
+            a.base_gates[(long long)(row / a.gs) * a.T + a.t] = g;
+        } else {
+            a.words[(long long)srow * a.T + a.t] = w;
+            a.gates[(long long)srow * a.T + a.t] = g;
+            if (a.lp_w) a.lp_w[(long long)srow * a.T + a.t] = a.top_v[row];
+            if (a.lp_g) a.lp_g[(long long)srow * a.T + a.t] = g ? l1 : l0;
+        }
     }
     return w;
 }

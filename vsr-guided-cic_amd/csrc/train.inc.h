@@ -516,12 +516,15 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
 // per image - the hoisted projections, P, the region rows, masks and index lists - is read through row / K, as the beams of the decode
 // path do; K = 1 launches the kernels of the one-row-per-image path (the <false> instantiations).
 // targets != null: the sparse head (vsr_train_forward_selected) - logp_words is then the (rows, T) tensor of the targets' log-probs
+// rows_call: one of the rows_per_image entry points, which take any K up to the prepared beam - K = 1 under a larger beam too (the replay
+// of one sample per image drawn next to its greedy baseline row, vsr_sample_rows_baseline); vsr_train_forward itself asks for beam = 1
 static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, const int64_t* slots, int32_t T, float* logp_words,
-                              float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream, const int64_t* targets = nullptr) {
+                              float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream, const int64_t* targets = nullptr,
+                              bool rows_call = false) {
     if (check_ready(h, targets ? "vsr_train_forward_selected" : "vsr_train_forward")) return 1;
     if (!word_in || !logp_words || !logp_gates || !train_ws) return fail("%s: null tensor", targets ? "vsr_train_forward_selected" : "vsr_train_forward");
     Ctx& c = h->c;
-    if (K == 1 && c.beam != 1 && c.Mmax != c.B) return fail("vsr_train_forward: prepare() must be called with beam = 1");
+    if (K == 1 && !rows_call && c.beam != 1 && c.Mmax != c.B) return fail("vsr_train_forward: prepare() must be called with beam = 1");
     if (K < 1 || K > c.beam) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, the prepared beam %d] (the workspace of vsr_prepare*() is sized by the beam)", K, c.beam);
     // index-list regions (vsr_prepare_indexed) train too, with one decoder row per image (the XE / SCST batches of train.py: every
     // sample brings its own detections): the backward pass sums dP over the entries of a row that name the same bank row
@@ -581,7 +584,7 @@ extern "C" int vsr_train_forward(vsr_handle* h, const int64_t* word_in, const in
 extern "C" int vsr_train_forward_rows(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots, int32_t T,
                                       float* logp_words, float* logp_gates, void* train_ws, size_t train_ws_bytes, void* stream) {
     if (rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return fail("vsr_train_forward_rows: rows_per_image %d not in [1, %d]", rows_per_image, VSR_MAX_BEAM);
-    return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_words, logp_gates, train_ws, train_ws_bytes, stream);
+    return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_words, logp_gates, train_ws, train_ws_bytes, stream, nullptr, true);
 }
 // The sparse head: targets (rows, T) int64 (a word id, or -1 = not selected) -> logp_sel (rows, T); the gate head stays dense
 extern "C" int vsr_train_forward_selected(vsr_handle* h, int32_t rows_per_image, const int64_t* word_in, const int64_t* slots,
@@ -589,7 +592,7 @@ extern "C" int vsr_train_forward_selected(vsr_handle* h, int32_t rows_per_image,
                                           size_t train_ws_bytes, void* stream) {
     if (rows_per_image < 1 || rows_per_image > VSR_MAX_BEAM) return fail("vsr_train_forward_selected: rows_per_image %d not in [1, %d]", rows_per_image, VSR_MAX_BEAM);
     if (!targets) return fail("vsr_train_forward_selected: null targets (the dense head is vsr_train_forward / vsr_train_forward_rows)");
-    return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_sel, logp_gates, train_ws, train_ws_bytes, stream, targets);
+    return train_forward_impl(h, rows_per_image, word_in, slots, T, logp_sel, logp_gates, train_ws, train_ws_bytes, stream, targets, true);
 }
 
 // ---------------------------------------------------------------------------------------------- tape: the forward, one step per call

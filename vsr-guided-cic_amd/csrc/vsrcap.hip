@@ -872,6 +872,7 @@ struct StepIO {
     const int* slot = nullptr;         // (M) int32 or null -> fixed_slot
     int fixed_slot = 0;
     int vmode = VM_TOPK, K = 1;
+    int gs = 0;                        // > 0: greedy baseline rows in a sampling launch (kernels.h, k_vocab): rows with row % gs == 0
     float* full_out = nullptr; long long full_stride = 0;
     const int* forced = nullptr;
     uint64_t seed = 0;
@@ -919,7 +920,7 @@ static void launch_vocab(vsr_handle* h, hipStream_t s, const StepIO& io, const f
         auto go = [&](auto NT) {
             hipLaunchKernelGGL((k_vocab<decltype(KK)::value, decltype(NT)::value>), dim3(io.M), dim3(decltype(NT)::value), vsm, s, logits, ns, stride, h->w.out_fc_bias,
                                io.M, V, io.vmode, c.top_v, c.top_i, io.full_out, io.full_stride, io.forced, io.seed, (uint32_t)io.t, io.verbs, io.slot, io.rpi, c.L,
-                               io.gt, h->vt_ptr, h->vt_ids, h->n_verbs, lds_row, gate, c.nvalid_dev + 2);
+                               io.gt, h->vt_ptr, h->vt_ids, h->n_verbs, lds_row, gate, c.nvalid_dev + 2, io.gs);
         };
         if (V >= 4096) go(std::integral_constant<int, 512>{}); else go(std::integral_constant<int, 256>{});
     });
@@ -1102,16 +1103,20 @@ extern "C" int vsr_bad_ids(vsr_handle* h, int32_t* count, void* stream) {
 // ---------------------------------------------------------------------------------------------- greedy / sampling
 // rpi rows per image (vsr_sample_rows: several independent samples of every image): the rows of an image are adjacent and read its
 // statics as beams do (row / rpi) - nothing is copied; there are no parent pointers, every row is its own history
+// gs = rpi > 1 (vsr_sample_rows_baseline): the first row of every image is its greedy baseline -> base_w / base_g (images, T); the other
+// rpi - 1 are its samples: the caller's forced ids and outputs are the (images x (rpi - 1), T) tensors of the call without baseline rows
 static int decode_simple(vsr_handle* h, int vmode, uint64_t seed, const int64_t* forced_w, const int64_t* forced_g,
-                         const float* verbs, int gt, int64_t* words, int64_t* gates, float* lp_w, float* lp_g, hipStream_t s, int rpi = 1) {
+                         const float* verbs, int gt, int64_t* words, int64_t* gates, float* lp_w, float* lp_g, hipStream_t s, int rpi = 1,
+                         int gs = 0, int64_t* base_w = nullptr, int64_t* base_g = nullptr) {
     Ctx& c = h->c;
     const int B = c.B * rpi, T = h->d.seq_len;          // (B: decoder rows)
+    const int Bf = gs > 0 ? c.B * (gs - 1) : B;         // rows of the forced ids
     if (verbs && vmode != VM_TOPK) return fail("verb forcing is only defined for greedy / beam decoding");
     if (zero_state(h, B, s)) return 1;
     if (vmode == VM_FORCED) {
         for (int t = 0; t < T; ++t) {
-            hipLaunchKernelGGL(k_i64_to_i32, dim3(cdiv(B, 256)), dim3(256), 0, s, forced_w + t, (long long)T, c.forced_w32 + (size_t)t * B, B, h->d.vocab_size, c.nvalid_dev + 2);
-            hipLaunchKernelGGL(k_i64_to_i32, dim3(cdiv(B, 256)), dim3(256), 0, s, forced_g + t, (long long)T, c.forced_g32 + (size_t)t * B, B, 2, c.nvalid_dev + 2);
+            hipLaunchKernelGGL(k_i64_to_i32, dim3(cdiv(Bf, 256)), dim3(256), 0, s, forced_w + t, (long long)T, c.forced_w32 + (size_t)t * Bf, Bf, h->d.vocab_size, c.nvalid_dev + 2);
+            hipLaunchKernelGGL(k_i64_to_i32, dim3(cdiv(Bf, 256)), dim3(256), 0, s, forced_g + t, (long long)T, c.forced_g32 + (size_t)t * Bf, Bf, 2, c.nvalid_dev + 2);
         }
     }
     // The selection of step t is per row and tiny: where the next step's LSTM1 kernel starts from cached sums (decode cache) it makes the
@@ -1124,14 +1129,15 @@ static int decode_simple(vsr_handle* h, int vmode, uint64_t seed, const int64_t*
         io.t = t; io.M = B; io.rpi = rpi; io.cur = cur;
         io.word_prev = c.word[cur]; io.slot = c.slot[cur];
         io.sel_simple = have_pending ? &pending : nullptr;
-        io.vmode = vmode;
-        io.forced = (vmode == VM_FORCED) ? c.forced_w32 + (size_t)t * B : nullptr;
+        io.vmode = vmode; io.gs = gs;
+        io.forced = (vmode == VM_FORCED) ? c.forced_w32 + (size_t)t * Bf : nullptr;
         io.seed = seed; io.verbs = verbs; io.gt = gt; io.lg_out = c.lg;
         io.s1_from_prev = t > 0 && h->xproj != nullptr;
         io.s1_for_next = t + 1 < T && h->xproj != nullptr;
         if (run_step(h, io, s)) return 1;
-        const SelSimpleArgs sa{vmode, c.top_v, c.top_i, c.lg, (vmode == VM_FORCED) ? c.forced_g32 + (size_t)t * B : nullptr, seed, (uint32_t)t,
-                               c.slot[cur], c.L, B, T, c.word[cur ^ 1], c.gate[cur ^ 1], c.slot[cur ^ 1], words, gates, lp_w, lp_g};
+        const SelSimpleArgs sa{vmode, c.top_v, c.top_i, c.lg, (vmode == VM_FORCED) ? c.forced_g32 + (size_t)t * Bf : nullptr, seed, (uint32_t)t,
+                               c.slot[cur], c.L, B, T, c.word[cur ^ 1], c.gate[cur ^ 1], c.slot[cur ^ 1], words, gates, lp_w, lp_g,
+                               gs, base_w, base_g};
         have_pending = (h->fuse_select & 1) && t + 1 < T && h->xproj != nullptr;       // (the next step is then s1_from_prev)
         if (have_pending) pending = sa;
         else hipLaunchKernelGGL(k_select_simple, dim3(cdiv(B, 256)), dim3(256), 0, s, sa);
@@ -1163,6 +1169,20 @@ extern "C" int vsr_sample_rows(vsr_handle* h, int32_t rows_per_image, uint64_t s
     if ((forced_words == nullptr) != (forced_gates == nullptr)) return fail("vsr_sample_rows: forced_words and forced_gates go together");
     return decode_simple(h, forced_words ? VM_FORCED : VM_SAMPLE, seed, forced_words, forced_gates, nullptr, 0, words, gates,
                          lp_words, lp_gates, (hipStream_t)stream, rows_per_image);
+}
+
+extern "C" int vsr_sample_rows_baseline(vsr_handle* h, int32_t rows_per_image, uint64_t seed, const int64_t* forced_words,
+                                        const int64_t* forced_gates, int64_t* words, int64_t* gates, float* lp_words, float* lp_gates,
+                                        int64_t* base_words, int64_t* base_gates, void* stream) {
+    if (check_ready(h, "vsr_sample_rows_baseline")) return 1;
+    const int K = rows_per_image;
+    if (K < 1) return fail("vsr_sample_rows_baseline: rows_per_image %d < 1", K);
+    if (K + 1 > h->c.beam)
+        return fail("vsr_sample_rows_baseline: %d samples + the baseline row per image exceed the prepared beam %d", K, h->c.beam);
+    if (!words || !gates || !lp_words || !lp_gates || !base_words || !base_gates) return fail("vsr_sample_rows_baseline: null output");
+    if ((forced_words == nullptr) != (forced_gates == nullptr)) return fail("vsr_sample_rows_baseline: forced_words and forced_gates go together");
+    return decode_simple(h, forced_words ? VM_FORCED : VM_SAMPLE, seed, forced_words, forced_gates, nullptr, 0, words, gates,
+                         lp_words, lp_gates, (hipStream_t)stream, K + 1, K + 1, base_words, base_gates);
 }
 
 // ---------------------------------------------------------------------------------------------- beam search

@@ -336,21 +336,28 @@ class ControllableCaptioningModel(CaptioningModel):
         lp_sel, gate = self.forward_selected((detections,), (captions, ctrl_det_seqs), targets)
         return xe_loss_from_selected(lp_sel, gate, targets, ctrl_det_gts, gate_weight)
 
-    def _run_sample(self, statics, seed=None, forced=None, samples_per_image=1, sparse_head=False):
+    def _run_sample(self, statics, seed=None, forced=None, samples_per_image=1, sparse_head=False, greedy_baseline=False):
         """samples_per_image = K (extension; the reference draws one sample per image and its SCST caller repeats every image): K
         samples of every image in ONE call, rows b * K + j = sample j of image b (the order of repeat_interleave(K, 0)).  The image's
         statics - region rows, att_va(regions), the pooled descriptor's projections - exist once, forward and backward.
-        sparse_head (extension): the graph of the returned log-probs goes through the sparse vocabulary head (forward_selected's)."""
+        sparse_head (extension): the graph of the returned log-probs goes through the sparse vocabulary head (forward_selected's).
+        greedy_baseline (extension): the greedy decode of every image - SCST's self-critical baseline, test() of the same weights - runs
+        as one more decoder row per image in the same call -> (outs, log_probs, (base_words, base_gates)), the baseline (B, T) int64;
+        outs / log_probs / forced are the (B * K, T) tensors of the call without it.  The baseline rows draw no noise and are not
+        replayed: they have no log-probs and no gradient."""
         K = int(samples_per_image)
         if not 1 <= K <= _lib.MAX_BEAM:
             raise ValueError("samples_per_image must be in [1, %d] (the rows of an image share the beam workspace), got %r"
                              % (_lib.MAX_BEAM, samples_per_image))
+        if greedy_baseline and K > _lib.MAX_BEAM - 1:
+            raise ValueError("samples_per_image must be in [1, %d] with greedy_baseline=True (the baseline row and the samples of an image "
+                             "share the beam workspace of %d rows), got %r" % (_lib.MAX_BEAM - 1, _lib.MAX_BEAM, samples_per_image))
         det, ctrl = statics[0], statics[1]
         with_grad = self._builds_graph()
         eng = self._engine(det.device, weights_may_have_moved=with_grad)
         if with_grad and isinstance(ctrl, IndexedRegions) and ctrl.row_img is not None:
             raise RuntimeError("sample_rl with gradients on IndexedRegions needs one decoder row per image (row_img=None)")
-        B = self._prepare(eng, det, ctrl, K, for_training=with_grad)
+        B = self._prepare(eng, det, ctrl, K + 1 if greedy_baseline else K, for_training=with_grad)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             # data-parallel ranks that called torch.manual_seed(s) with the same s would otherwise draw IDENTICAL Gumbel /
@@ -358,11 +365,16 @@ class ControllableCaptioningModel(CaptioningModel):
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
                 seed ^= (dist.get_rank() + 1) << 48
-        outs, lps = eng.sample(B, det.device, seed, forced, K)
+        base = None
+        if greedy_baseline:
+            outs, lps, base = eng.sample(B, det.device, seed, forced, K, greedy_baseline=True)
+        else:
+            outs, lps = eng.sample(B, det.device, seed, forced, K)
         if with_grad:
+            # (the replay runs over the K sample rows of every image only: the prepared beam of K + 1 admits rows_per_image = K)
             from vsrcap.train import sample_logprobs_with_grad
             lps = sample_logprobs_with_grad(self, eng, det, ctrl, outs, lps, K, sparse_head=bool(sparse_head))
-        return outs, lps
+        return (outs, lps, base) if greedy_baseline else (outs, lps)
 
     def _run_beam(self, statics, eos_idxs, beam_size, out_size, with_verbs, gt):
         det, ctrl = statics[0], statics[1]

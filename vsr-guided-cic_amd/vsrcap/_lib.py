@@ -106,6 +106,7 @@ SIGNATURES = {
     "vsr_greedy": (I32, [P, P, I32, P, P, P]),
     "vsr_sample": (I32, [P, U64, P, P, P, P, P, P, P]),
     "vsr_sample_rows": (I32, [P, I32, U64, P, P, P, P, P, P, P]),
+    "vsr_sample_rows_baseline": (I32, [P, I32, U64, P, P, P, P, P, P, P, P, P]),
     "vsr_beam": (I32, [P, I32, I32, I64, I64, P, I32, P, P, P, P, P, P]),
     "vsr_xe_forward": (I32, [P, P, I32, P, P, P]),
     "vsr_train_workspace_bytes": (SZ, [P, I32, I32]),

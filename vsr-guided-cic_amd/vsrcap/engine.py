@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .baseline_rows import output_rows
 from .derived import Derived
 from .forwards import MAX_LIVE_FORWARDS, Forwards        # (the limit: importable from here as before)
 
@@ -81,6 +82,7 @@ class Engine:
         self._wdev = None                # ... and the device of the weights last handed to sync_weights()
         self.forwards = Forwards()       # the live training forwards and their buffer pairs (vsrcap/forwards.py); its backend too
         self._verb_dev = None
+        self._beam = 1                   # the beam of the last prepare*() (one sample per image next to its baseline row replays under beam 2)
         self.grad_sink = None       # list of 28 tensors (WEIGHT_FIELDS order): backward writes there and autograd gets no tensors
 
     def live_forwards(self):
@@ -218,6 +220,7 @@ class Engine:
         Forwards.begin_prepare names (one that holds no live forward).  keep: the inputs, borrowed by the library until the next prepare."""
         if keep[0].size(2) != self.dims.det_feat_size:
             raise RuntimeError("feature size %d != det_feat_size %d" % (keep[0].size(2), self.dims.det_feat_size))
+        self._beam = size_args[-1]       # (the beam of the statics the next call reads, served from the cache or not)
         slot = self.forwards.begin_prepare(key, for_training)       # from here on a call that raises leaves no key behind
         if slot is None:
             return
@@ -311,7 +314,7 @@ class Engine:
         tail = (T, _ptr(out), _ptr(gate), _ptr(slot.tws), slot.tws.numel(), self._stream(device))
         if targets is not None:
             _lib.check(self.lib.vsr_train_forward_selected(self.h, K, _ptr(word_in), _ptr(slots), _ptr(targets), *tail))
-        elif K == 1:
+        elif K == 1 and self._beam == 1:
             _lib.check(self.lib.vsr_train_forward(self.h, _ptr(word_in), _ptr(slots), *tail))
         else:
             _lib.check(self.lib.vsr_train_forward_rows(self.h, K, _ptr(word_in), _ptr(slots), *tail))
@@ -455,10 +458,16 @@ class Engine:
         return words, gates
 
     @_on_device
-    def sample(self, B, device, seed, forced=None, rows_per_image=1):
-        """rows_per_image = K > 1: K samples of every image in one call, outputs (B * K, T), row b * K + j = sample j of image b"""
+    def sample(self, B, device, seed, forced=None, rows_per_image=1, greedy_baseline=False):
+        """rows_per_image = K > 1: K samples of every image in one call, outputs (B * K, T), row b * K + j = sample j of image b.
+        greedy_baseline: the greedy decode of every image rides in the same launches as one more row per image (vsr_sample_rows_baseline;
+        prepare() with beam >= K + 1) -> (words, gates), (lpw, lpg), (base_words, base_gates), the baseline (B, T) int64; the sample
+        tensors and `forced` are those of the call without it (vsrcap/baseline_rows.py has the layout)."""
         K = int(rows_per_image)
+        n_img = B
         B = B * K
+        if greedy_baseline:
+            B, n_base = output_rows(n_img, K)
         T = self.dims.seq_len
         words = torch.empty(B, T, dtype=torch.int64, device=device)
         gates = torch.empty(B, T, dtype=torch.int64, device=device)
@@ -470,7 +479,12 @@ class Engine:
             fg = forced[1].to(device=device, dtype=torch.int64).contiguous()
             if tuple(fw.shape) != (B, T) or tuple(fg.shape) != (B, T):
                 raise RuntimeError("forced samples must be two (%d, %d) tensors, got %s and %s" % (B, T, tuple(fw.shape), tuple(fg.shape)))
-        if K == 1:
+        if greedy_baseline:
+            bw = torch.empty(n_base, T, dtype=torch.int64, device=device)
+            bg = torch.empty(n_base, T, dtype=torch.int64, device=device)
+            _lib.check(self.lib.vsr_sample_rows_baseline(self.h, K, C.c_uint64(seed), _ptr(fw), _ptr(fg), _ptr(words), _ptr(gates),
+                                                         _ptr(lpw), _ptr(lpg), _ptr(bw), _ptr(bg), self._stream(device)))
+        elif K == 1:
             _lib.check(self.lib.vsr_sample(self.h, C.c_uint64(seed), _ptr(fw), _ptr(fg), _ptr(words), _ptr(gates), _ptr(lpw),
                                            _ptr(lpg), self._stream(device)))
         else:
@@ -478,6 +492,8 @@ class Engine:
                                                 _ptr(lpg), self._stream(device)))
         if forced is not None:
             self.raise_on_bad_ids(device, "sample (forced ids)")
+        if greedy_baseline:
+            return (words, gates), (lpw, lpg), (bw, bg)
         return (words, gates), (lpw, lpg)
 
     @_on_device

@@ -288,16 +288,24 @@ class DataParallelStep:
         stats = torch.stack([loss.detach(), loss_cap.detach(), loss_gate.detach()]).double()
         return self._sum(stats)                              # global loss, loss_cap, loss_gate
 
-    def scst_step(self, det, ctrl, reward_fn, samples_per_image=1):
+    def scst_step(self, det, ctrl, reward_fn, samples_per_image=1, greedy_baseline=False):
         """reward_fn(words (b,T)) -> (reward (b,), baseline (b,)) tensors (vsrcap.reward.CiderD on the device, or the caller's).
         samples_per_image = K > 1: sample_fn(det, ctrl, samples_per_image=K) draws K samples of each of the b images in one call
         (model.sample_rl: statics shared); reward_fn then sees (b * K, T) words, row i * K + j = sample j of image i, and the global
-        count is the number of samples."""
+        count is the number of samples.
+        greedy_baseline: sample_fn(det, ctrl, samples_per_image=K, greedy_baseline=True) also returns the greedy decode of the b images
+        (model.sample_rl: one more decoder row per image in the same call); reward_fn(words (b * K, T), base_words (b, T)) ->
+        (reward (b * K,), reward_base (b,)), and the baseline of sample i * K + j is reward_base[i]."""
         kw = {"sparse_head": True} if self.sparse_head else {}
-        if samples_per_image != 1:
+        if samples_per_image != 1 or greedy_baseline:
             kw["samples_per_image"] = samples_per_image
-        (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl, **kw)
-        reward, baseline = reward_fn(words)
+        if greedy_baseline:
+            (words, gates), (lp_w, lp_g), (base_words, _) = self.sample_fn(det, ctrl, greedy_baseline=True, **kw)
+            reward, baseline = reward_fn(words, base_words)
+            baseline = baseline.repeat_interleave(int(samples_per_image))
+        else:
+            (words, gates), (lp_w, lp_g) = self.sample_fn(det, ctrl, **kw)
+            reward, baseline = reward_fn(words)
         n = torch.tensor([float(words.shape[0])], dtype=torch.float64, device=lp_w.device)
         self._sum(n)
         per = -(lp_w.mean(-1) + lp_g.mean(-1)) * (reward - baseline).to(lp_w.dtype)
