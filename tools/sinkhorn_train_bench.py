@@ -6,7 +6,7 @@
       host side of autograd - the call pattern of coco_scripts/train_sinkhorn.py:189-215
   (c) oracle/ssp_oracle.py's SinkhornOracle under torch autograd on the same GPU, all Q items in one batch
 
-    python tools/sinkhorn_train_bench.py [--q 256] [--steps 20] [--warmup 5] [--out profiles/NAME.json]
+    python tools/sinkhorn_train_bench.py [--q 256] [--steps 20] [--warmup 5] [--variants abc] [--out profiles/NAME.json]
 
 Each figure is the median over --steps steps of a device-synchronised wall time (torch.cuda.synchronize() on both sides of the step),
 after --warmup untimed steps - the same two settings for all three variants; the inputs stay on the device.  Prints one JSON line."""
@@ -50,6 +50,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--variants", default="abc", help="which of the three to run (the device path alone: --variants a)")
     a = ap.parse_args()
     from models import SinkhornNet
     N, Q, scale = 10, a.q, 1.0 / 16
@@ -73,7 +74,8 @@ def main():
         loss = m.loc_loss(x, tr_locs, gt_locs, scale)
         loss.backward()
         opt.step()
-    res["a_one_call_ms"], res["a_min_ms"] = timed(step_a, a.steps, a.warmup)
+    if "a" in a.variants:
+        res["a_one_call_ms"], res["a_min_ms"] = timed(step_a, a.steps, a.warmup)
 
     m, opt = fresh()
 
@@ -86,7 +88,8 @@ def main():
         loss = loss * scale
         loss.backward()
         opt.step()
-    res["b_per_item_ms"], res["b_min_ms"] = timed(step_b, a.steps, a.warmup)
+    if "b" in a.variants:
+        res["b_per_item_ms"], res["b_min_ms"] = timed(step_b, a.steps, a.warmup)
 
     o = so.SinkhornOracle({k: torch.from_numpy(v).to(DEV) for k, v in w.items()})
     for k in o.p:
@@ -100,7 +103,8 @@ def main():
         loss = ((resort - gt_locs) ** 2).mean(1).sum() * scale
         loss.backward()
         opt_c.step()
-    res["c_torch_autograd_ms"], res["c_min_ms"] = timed(step_c, a.steps, a.warmup)
+    if "c" in a.variants:
+        res["c_torch_autograd_ms"], res["c_min_ms"] = timed(step_c, a.steps, a.warmup)
 
     res.update(Q=Q, N=N, n_iters=20, steps=a.steps, warmup=a.warmup, device=torch.cuda.get_device_name(0),
                compute_units=torch.cuda.get_device_properties(0).multi_processor_count, torch=torch.__version__)

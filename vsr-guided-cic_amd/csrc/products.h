@@ -46,11 +46,11 @@ inline Prod prod1(int M, int N, int K, const float* A, int lda, const float* W, 
     p.M = M; p.N = N; p.seg[0] = ProdSeg{A, lda, W, ldw, K}; p.nseg = 1; p.out = out; p.ldo = ldo;
     return p;
 }
-// a layer of a forward pass: out = act(A W^T + bias) (+ residual), W (N, K) compact
+// a layer of a forward pass: out = drop(act(A W^T + bias)) (+ residual), W (N, K) compact; keep: the dropout site's bytes, null = none
 inline Prod lin(int M, int N, int K, const float* A, int lda, const float* W, const float* bias, float* out, int act = SSP_ACT_NONE,
-                const float* residual = nullptr) {
+                const float* residual = nullptr, const uint8_t* keep = nullptr) {
     Prod p = prod1(M, N, K, A, lda, W, K, out);
-    p.bias = bias; p.act = act; p.residual = residual;
+    p.bias = bias; p.act = act; p.residual = residual; p.keep = keep;
     return p;
 }
 // the instance of k_prod_finish a product takes: k_prod_finish<lin, gate>

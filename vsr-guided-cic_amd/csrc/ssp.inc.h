@@ -4,6 +4,9 @@
 // through one call each, and the results (role orders, assignments) stay on the device: vsr_rank_captions (at the end of this
 // file, kernels in rank_kernels.h) turns them into the (N, L) rank tensor vsr_reorder_slots consumes without a read-back.
 // vsrcap/evalbatch.py: rank_captions is the same flow with the integer bookkeeping on the host.
+// Each model has ONE forward on the host: ssp_layer is the transformer layer of vsr_ssp_generate (encoder and every decode step) and of
+// vsr_ssp_train_forward, sinkhorn_layers the five layers of assign, rank and the Sinkhorn training forward.  What training differentiates
+// is what inference runs by construction, not by copies kept alike.
 #include "ssp_kernels.h"
 #include "rank_kernels.h"
 #include "train_batch_kernels.h"
@@ -46,7 +49,7 @@ extern "C" int vsr_ssp_bind(vsr_ssp* e, const vsr_ssp_weights* w, const vsr_sink
 
 struct SspWs {
     float *x, *y, *q, *k, *v, *ctx, *x1, *ff, *prior, *pk[3], *pv[3], *last, *logits, *scratch;
-    int *roles32, *remain, *tokens, *bad;
+    int *roles32, *remain, *tokens;
     size_t scratch_floats;
 };
 static size_t carve_ssp(int S, char* base, SspWs& w) {
@@ -57,7 +60,7 @@ static size_t carve_ssp(int S, char* base, SspWs& w) {
     w.prior = b.take<float>((size_t)S * SSP_LEN * H);
     for (int l = 0; l < 3; ++l) { w.pk[l] = b.take<float>((size_t)S * SSP_LEN * H); w.pv[l] = b.take<float>((size_t)S * SSP_LEN * H); }
     w.last = b.take<float>((size_t)S * H); w.logits = b.take<float>((size_t)S * SSP_ROLES);
-    w.roles32 = b.take<int>((size_t)S * SSP_LEN); w.remain = b.take<int>((size_t)S * SSP_LEN); w.tokens = b.take<int>(R); w.bad = b.take<int>(4);
+    w.roles32 = b.take<int>((size_t)S * SSP_LEN); w.remain = b.take<int>((size_t)S * SSP_LEN); w.tokens = b.take<int>(R);
     w.scratch_floats = R * SSP_FF * GEMM_MAX_SLABS;
     w.scratch = b.take<float>(w.scratch_floats);
     return (b.off + 255) & ~size_t(255);
@@ -74,8 +77,67 @@ extern "C" size_t vsr_ssp_workspace_bytes(int32_t S) {
 static ProdRun ssp_run(const vsr_ssp* e, hipStream_t s, float* scratch, size_t scratch_floats, const int* hdr, float scale, const char* pass) {
     return ProdRun{&e->cfg, nullptr, s, scratch, scratch_floats, hdr, scale, pass};
 }
-static void layernorm(hipStream_t s, const float* x, const float* w, const float* b, int rows, float* out) {
-    hipLaunchKernelGGL(k_layernorm512, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, out);
+
+// ---------------------------------------------------------------------------------------------- the S-SSP layer
+// Where a layer's intermediates land: the training tape's entries, or a view of the inference workspace (ssp_ws_view) whose xhat / rstd / P
+// are null - which selects the plain kernels: inference writes no tape data.
+struct SspLnTape { float *y, *xhat, *rstd; };
+// lnA / lnC / lnF: the LayerNorm in front of the self attention / cross attention (decoder only) / feed-forward.  pk set: a decoder layer
+struct SspLayerTape { SspLnTape lnA, lnC, lnF; float *q, *k, *v, *P1, *ctx1, *q2, *pk, *pv, *P2, *ctx2, *ff; };
+static SspLayerTape ssp_ws_view(const SspWs& ws, int dec_layer /* -1: an encoder layer */) {
+    SspLayerTape v{};
+    v.lnA.y = v.lnC.y = v.lnF.y = ws.y;
+    v.q = v.q2 = ws.q; v.k = ws.k; v.v = ws.v; v.ctx1 = v.ctx2 = ws.ctx; v.ff = ws.ff;
+    if (dec_layer >= 0) { v.pk = ws.pk[dec_layer]; v.pv = ws.pv[dec_layer]; }
+    return v;
+}
+static void layernorm(hipStream_t s, const float* x, const float* w, const float* b, int rows, const SspLnTape& t) {
+    if (t.xhat) hipLaunchKernelGGL(k_layernorm512_train, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, t.y, t.xhat, t.rstd);
+    else hipLaunchKernelGGL(k_layernorm512, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, t.y);
+}
+// ctx (S, Tq, 512) = multi-head attention of q (S, Tq) on k / v (S, Tk).  P set: the softmax weights are taped and the site's keep bytes applied
+static void ssp_mha(const ProdRun& run, const float* q, const float* k, const float* v, int S, int Tq, int Tk, const int* mask_tok, int ld_tok, float* ctx, float* P,
+                    const uint8_t* keep) {
+    if (P) hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, run.s, q, k, v, Tq, Tk, mask_tok, ld_tok, ctx, P, keep, run.scale);
+    else hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, run.s, q, k, v, Tq, Tk, mask_tok, ld_tok, ctx);
+}
+// keys / values of a decoder layer's cross attention: the prior (Re rows) through the layer's (self-)attention K / V projections
+// (sort_modules.py:88 re-uses self.attention for the cross attention), one launch
+static int ssp_cross_kv(const ProdRun& run, const vsr_ssp_layer& ly, const float* prior, int Re, float* pk, float* pv) {
+    Prod kv[2] = {lin(Re, SSP_H, SSP_H, prior, SSP_H, ly.Wk, ly.bk, pk), lin(Re, SSP_H, SSP_H, prior, SSP_H, ly.Wv, ly.bv, pv)};
+    return run_products(run, kv, 2);
+}
+// One pre-LN layer of either stack for S sequences of T positions: THE layer of generate (encoder, every decode step) and of the training forward.
+// The input is in x and so is the output on return; x1 is the other row buffer (the two are exchanged when the result falls into it).
+//   mask_tok  the decoder's self-attention mask tokens (leading dimension ld_tok), or null
+//   prior     decoder: the encoder's output, projected to lt.pk / lt.pv here, after the q2 product; null: the caller has filled them
+//   keep      the keep bytes of the layer's dropout sites in order (4 encoder, 6 decoder), each null without dropout; run.scale = 1 / (1 - p)
+static const uint8_t* const SSP_NO_DROPOUT[6] = {};
+static int ssp_layer(const ProdRun& run, const vsr_ssp_layer& ly, const SspLayerTape& lt, int S, int T, const int* mask_tok, int ld_tok, const float* prior,
+                     const uint8_t* const* keep, float*& x, float*& x1) {
+    const int H = SSP_H, R = S * T;
+    const bool dec = lt.pk != nullptr;
+    // ---- self attention: x1 = drop(Wo ctx1 + bo) + x, ctx1 = mha(q, k, v = W yA + b), yA = LN(x); the three projections in one launch
+    layernorm(run.s, x, ly.ln1_w, ly.ln1_b, R, lt.lnA);
+    Prod qkv[3] = {lin(R, H, H, lt.lnA.y, H, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, H, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, H, ly.Wv, ly.bv, lt.v)};
+    if (run_products(run, qkv, 3)) return 1;
+    ssp_mha(run, lt.q, lt.k, lt.v, S, T, T, mask_tok, ld_tok, lt.ctx1, lt.P1, keep[0]);
+    if (run_product(run, lin(R, H, H, lt.ctx1, H, ly.Wo, ly.bo, x1, SSP_ACT_NONE, x, keep[1]))) return 1;
+    keep += 2;
+    if (dec) {
+        // ---- cross attention: x = drop(Wo ctx2 + bo) + x1, ctx2 = mha(q2 = Wq yC + bq, pk, pv), yC = LN(x1): the SAME projections (sort_modules.py:87)
+        layernorm(run.s, x1, ly.ln2_w, ly.ln2_b, R, lt.lnC);
+        if (run_product(run, lin(R, H, H, lt.lnC.y, H, ly.Wq, ly.bq, lt.q2))) return 1;
+        if (prior && ssp_cross_kv(run, ly, prior, S * SSP_LEN, lt.pk, lt.pv)) return 1;
+        ssp_mha(run, lt.q2, lt.pk, lt.pv, S, T, SSP_LEN, nullptr, 0, lt.ctx2, lt.P2, keep[0]);
+        if (run_product(run, lin(R, H, H, lt.ctx2, H, ly.Wo, ly.bo, x, SSP_ACT_NONE, x1, keep[1]))) return 1;
+        std::swap(x, x1);                                                                             // (x1 names the feed-forward's input again)
+        keep += 2;
+    }
+    // ---- feed-forward: x = drop(W2 ff + b2) + x1, ff = drop(relu(W1 yF + b1)), yF = LN(x1)
+    layernorm(run.s, x1, dec ? ly.ln3_w : ly.ln2_w, dec ? ly.ln3_b : ly.ln2_b, R, lt.lnF);
+    if (run_product(run, lin(R, SSP_FF, H, lt.lnF.y, H, ly.W1, ly.b1, lt.ff, SSP_ACT_RELU, nullptr, keep[0]))) return 1;
+    return run_product(run, lin(R, H, SSP_FF, lt.ff, SSP_FF, ly.W2, ly.b2, x, SSP_ACT_NONE, x1, keep[1]));
 }
 
 // S_SSP.generate(mode='not-normal') (sort_model.py:105-183) for S sequences at once.
@@ -92,57 +154,26 @@ extern "C" int vsr_ssp_generate(vsr_ssp* e, const int64_t* verbs, const int32_t*
     const vsr_ssp_weights& w = e->w;
     const int H = SSP_H, L = SSP_LEN;
     const ProdRun run = ssp_run(e, s, ws.scratch, ws.scratch_floats, nullptr, 1.f, "ssp");
-    auto qkv = [&](const vsr_ssp_layer& ly, int R) {              // the three projections of the layer's input (in ws.y) in one launch
-        Prod p[3] = {lin(R, H, H, ws.y, H, ly.Wq, ly.bq, ws.q), lin(R, H, H, ws.y, H, ly.Wk, ly.bk, ws.k), lin(R, H, H, ws.y, H, ly.Wv, ly.bv, ws.v)};
-        return run_products(run, p, 3);
-    };
-    HIPCHK(hipMemsetAsync(ws.bad, 0, 4 * sizeof(int), s));
-    hipLaunchKernelGGL(k_ssp_init, dim3(cdiv(S * (L + 1), 256)), dim3(256), 0, s, roles, S, ws.remain, ws.tokens, pred, logp, ws.bad);
+    hipLaunchKernelGGL(k_ssp_init, dim3(cdiv(S * (L + 1), 256)), dim3(256), 0, s, roles, S, ws.remain, ws.tokens, pred, logp);
     // ---- encoder (sort_modules.py:50-62): embeddings -> fc_feat -> 3 pre-LN layers -> LN
     int R = S * L;
-    hipLaunchKernelGGL(k_ssp_embed, dim3(R), dim3(128), 0, s, roles, L, L, w.sr_embed, verbs, w.v_embed, w.n_verbs, S, ws.y, ws.bad);
+    hipLaunchKernelGGL(k_ssp_embed, dim3(R), dim3(128), 0, s, roles, L, L, w.sr_embed, verbs, w.v_embed, w.n_verbs, S, ws.y);
     if (run_product(run, lin(R, H, H, ws.y, H, w.fc_w, w.fc_b, ws.x))) return 1;
-    for (int l = 0; l < 3; ++l) {
-        const vsr_ssp_layer& ly = w.enc[l];
-        layernorm(s, ws.x, ly.ln1_w, ly.ln1_b, R, ws.y);
-        if (qkv(ly, R)) return 1;
-        hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, s, ws.q, ws.k, ws.v, L, L, (const int*)nullptr, 0, ws.ctx);
-        if (run_product(run, lin(R, H, H, ws.ctx, H, ly.Wo, ly.bo, ws.x1, SSP_ACT_NONE, ws.x))) return 1;
-        layernorm(s, ws.x1, ly.ln2_w, ly.ln2_b, R, ws.y);
-        if (run_product(run, lin(R, SSP_FF, H, ws.y, H, ly.W1, ly.b1, ws.ff, SSP_ACT_RELU))) return 1;
-        if (run_product(run, lin(R, H, SSP_FF, ws.ff, SSP_FF, ly.W2, ly.b2, ws.x, SSP_ACT_NONE, ws.x1))) return 1;
-    }
-    layernorm(s, ws.x, w.enc_ln_w, w.enc_ln_b, R, ws.prior);
-    // keys / values of the cross attention: prior states through each decoder layer's (self-)attention K / V projections,
-    // constant over the decode steps (sort_modules.py:88 re-uses self.attention for the cross attention)
-    for (int l = 0; l < 3; ++l) {
-        Prod kv[2] = {lin(R, H, H, ws.prior, H, w.dec[l].Wk, w.dec[l].bk, ws.pk[l]), lin(R, H, H, ws.prior, H, w.dec[l].Wv, w.dec[l].bv, ws.pv[l])};
-        if (run_products(run, kv, 2)) return 1;
-    }
+    for (int l = 0; l < 3; ++l)
+        if (ssp_layer(run, w.enc[l], ssp_ws_view(ws, -1), S, L, nullptr, 0, nullptr, SSP_NO_DROPOUT, ws.x, ws.x1)) return 1;
+    layernorm(s, ws.x, w.enc_ln_w, w.enc_ln_b, R, SspLnTape{ws.prior, nullptr, nullptr});
+    // the cross attention's keys / values are constant over the decode steps: projected once, here
+    for (int l = 0; l < 3; ++l)
+        if (ssp_cross_kv(run, w.dec[l], ws.prior, R, ws.pk[l], ws.pv[l])) return 1;
     LAUNCHCHK();
     // ---- decoder: step t re-runs the stack on [bos, picks 0..t-1] as the reference does (:154-160) and picks among the remaining roles
     for (int t = 0; t < L; ++t) {
         const int T = t + 1;
-        R = S * T;
-        hipLaunchKernelGGL(k_ssp_embed, dim3(R), dim3(128), 0, s, ws.tokens, L + 1, T, w.sr_embed, (const int64_t*)nullptr, (const float*)nullptr, 0, S,
-                           ws.x, ws.bad);
-        for (int l = 0; l < 3; ++l) {
-            const vsr_ssp_layer& ly = w.dec[l];
-            layernorm(s, ws.x, ly.ln1_w, ly.ln1_b, R, ws.y);
-            if (qkv(ly, R)) return 1;
-            hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, s, ws.q, ws.k, ws.v, T, T, ws.tokens, L + 1, ws.ctx);
-            if (run_product(run, lin(R, H, H, ws.ctx, H, ly.Wo, ly.bo, ws.x1, SSP_ACT_NONE, ws.x))) return 1;            // h1 = attn + x
-            layernorm(s, ws.x1, ly.ln2_w, ly.ln2_b, R, ws.y);
-            if (run_product(run, lin(R, H, H, ws.y, H, ly.Wq, ly.bq, ws.q))) return 1;
-            hipLaunchKernelGGL(k_ssp_mha, dim3(S, SSP_HEADS), dim3(64), 0, s, ws.q, ws.pk[l], ws.pv[l], T, L, (const int*)nullptr, 0, ws.ctx);
-            if (run_product(run, lin(R, H, H, ws.ctx, H, ly.Wo, ly.bo, ws.x, SSP_ACT_NONE, ws.x1))) return 1;            // h2 = cross + h1   (in ws.x)
-            layernorm(s, ws.x, ly.ln3_w, ly.ln3_b, R, ws.y);
-            if (run_product(run, lin(R, SSP_FF, H, ws.y, H, ly.W1, ly.b1, ws.ff, SSP_ACT_RELU))) return 1;
-            if (run_product(run, lin(R, H, SSP_FF, ws.ff, SSP_FF, ly.W2, ly.b2, ws.x1, SSP_ACT_NONE, ws.x))) return 1;    // h3 = ff + h2      (in ws.x1)
-            std::swap(ws.x, ws.x1);
-        }
+        hipLaunchKernelGGL(k_ssp_embed, dim3(S * T), dim3(128), 0, s, ws.tokens, L + 1, T, w.sr_embed, (const int64_t*)nullptr, (const float*)nullptr, 0, S, ws.x);
+        for (int l = 0; l < 3; ++l)
+            if (ssp_layer(run, w.dec[l], ssp_ws_view(ws, l), S, T, ws.tokens, L + 1, nullptr, SSP_NO_DROPOUT, ws.x, ws.x1)) return 1;
         hipLaunchKernelGGL(k_ssp_last, dim3(S), dim3(128), 0, s, ws.x, T, ws.last);
-        layernorm(s, ws.last, w.dec_ln_w, w.dec_ln_b, S, ws.y);
+        layernorm(s, ws.last, w.dec_ln_w, w.dec_ln_b, S, SspLnTape{ws.y, nullptr, nullptr});
         if (run_product(run, lin(S, SSP_ROLES, H, ws.y, H, w.exp_w, w.exp_b, ws.logits))) return 1;
         hipLaunchKernelGGL(k_ssp_select, dim3(S), dim3(64), 0, s, ws.logits, roles, ws.remain, t, S, ws.tokens, pred, logp);
         LAUNCHCHK();
@@ -402,9 +433,6 @@ extern "C" int vsr_ssp_dropout_masks(uint64_t seed, float p, int32_t S, uint8_t*
     return 0;
 }
 
-struct SspLnTape { float *y, *xhat, *rstd; };
-// lnA / lnC / lnF: the LayerNorm in front of the self attention / cross attention (decoder only) / feed-forward
-struct SspLayerTape { SspLnTape lnA, lnC, lnF; float *q, *k, *v, *P1, *ctx1, *q2, *pk, *pv, *P2, *ctx2, *ff; };
 struct SspTape { int* hdr; float* emb; SspLayerTape enc[3], dec[3]; SspLnTape encln, decln; float* logp; };
 static size_t carve_ssp_tape(int S, char* base, SspTape& t) {
     const size_t Re = (size_t)S * SSP_LEN, Rd = (size_t)S * SSP_TD, H = SSP_H;
@@ -487,10 +515,6 @@ extern "C" size_t vsr_ssp_train_workspace_bytes(int32_t S) {
     return carve_ssp_train(S, nullptr, w);
 }
 
-static void layernorm_train(hipStream_t s, const float* x, const float* w, const float* b, int rows, const SspLnTape& t) {
-    hipLaunchKernelGGL(k_layernorm512_train, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, rows, t.y, t.xhat, t.rstd);
-}
-
 static int ssp_train_args(const char* who, vsr_ssp* e, const void* verbs, const void* roles, const void* gt, int32_t S, const void* tape, const void* ws) {
     if (!e || !e->has_ssp) return fail("%s: S-SSP weights not bound", who);
     if (!verbs || !roles || !gt || !tape || !ws || S <= 0 || S > SSP_TRAIN_MAX_S) return fail("%s: bad arguments (1 <= S <= %d)", who, SSP_TRAIN_MAX_S);
@@ -517,56 +541,26 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
     auto keep = [&](int site) -> const uint8_t* { return masks ? masks + st.off[site] : nullptr; };
     const ProdRun run = ssp_run(e, s, ws.scratch, ws.scratch_floats, nullptr, scale, "ssp training");
     hipLaunchKernelGGL(k_ssp_train_prep, dim3(cdiv(Rd, 256)), dim3(256), 0, s, verbs, roles, gt, S, (int)w.n_verbs, ws.verbs32, ws.roles, ws.gt, ws.tok);
-    // one layer of either stack: x (in ws.r[0]) -> x (in ws.r[0]); site0: the layer's first dropout site
-    auto layer = [&](const vsr_ssp_layer& ly, SspLayerTape& lt, int R, int T, bool dec, int site0, const float* prior) -> int {
-        float *x = ws.r[0], *x1 = ws.r[1];
-        layernorm_train(s, x, ly.ln1_w, ly.ln1_b, R, lt.lnA);
-        Prod qkv[3] = {lin(R, H, H, lt.lnA.y, H, ly.Wq, ly.bq, lt.q), lin(R, H, H, lt.lnA.y, H, ly.Wk, ly.bk, lt.k), lin(R, H, H, lt.lnA.y, H, ly.Wv, ly.bv, lt.v)};
-        if (run_products(run, qkv, 3)) return 1;
-        hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q, lt.k, lt.v, T, T, dec ? ws.tok : (const int*)nullptr, SSP_TD, lt.ctx1, lt.P1,
-                           keep(site0), scale);
-        Prod o = lin(R, H, H, lt.ctx1, H, ly.Wo, ly.bo, x1);
-        o.keep = keep(site0 + 1); o.residual = x;
-        if (run_product(run, o)) return 1;                                                            // x1 = drop(attn) + x
-        int site = site0 + 2;
-        if (dec) {
-            layernorm_train(s, x1, ly.ln2_w, ly.ln2_b, R, lt.lnC);
-            Prod q2 = lin(R, H, H, lt.lnC.y, H, ly.Wq, ly.bq, lt.q2);                                // the SAME projections (sort_modules.py:87)
-            if (run_product(run, q2)) return 1;
-            Prod kv[2] = {lin(Re, H, H, prior, H, ly.Wk, ly.bk, lt.pk), lin(Re, H, H, prior, H, ly.Wv, ly.bv, lt.pv)};
-            if (run_products(run, kv, 2)) return 1;
-            hipLaunchKernelGGL(k_ssp_mha_train, dim3(S, SSP_HEADS), dim3(64), 0, s, lt.q2, lt.pk, lt.pv, T, SSP_LEN, (const int*)nullptr, 0, lt.ctx2, lt.P2,
-                               keep(site), scale);
-            Prod o2 = lin(R, H, H, lt.ctx2, H, ly.Wo, ly.bo, x);
-            o2.keep = keep(site + 1); o2.residual = x1;
-            if (run_product(run, o2)) return 1;                                                       // x = drop(cross) + x1
-            std::swap(x, x1);                                                                         // (x1 names the feed-forward's input again)
-            site += 2;
-        }
-        layernorm_train(s, x1, dec ? ly.ln3_w : ly.ln2_w, dec ? ly.ln3_b : ly.ln2_b, R, lt.lnF);
-        Prod f1 = lin(R, SSP_FF, H, lt.lnF.y, H, ly.W1, ly.b1, lt.ff);
-        f1.act = SSP_ACT_RELU; f1.keep = keep(site);
-        if (run_product(run, f1)) return 1;
-        Prod f2 = lin(R, H, SSP_FF, lt.ff, SSP_FF, ly.W2, ly.b2, x);
-        f2.keep = keep(site + 1); f2.residual = x1;
-        if (run_product(run, f2)) return 1;                                                           // x = drop(ff) + x1
-        if (x != ws.r[0]) std::swap(ws.r[0], ws.r[1]);
-        return 0;
+    // a layer's dropout sites are consecutive from site0, in the order ssp_layer takes them
+    auto layer = [&](const vsr_ssp_layer& ly, const SspLayerTape& lt, int T, const int* mask_tok, int site0, const float* prior) {
+        const uint8_t* k[6] = {};
+        for (int i = 0; i < (lt.pk ? 6 : 4); ++i) k[i] = keep(site0 + i);
+        return ssp_layer(run, ly, lt, S, T, mask_tok, SSP_TD, prior, k, ws.r[0], ws.r[1]);
     };
     // ---- encoder
     hipLaunchKernelGGL(k_ssp_embed_train, dim3(Re), dim3(128), 0, s, ws.roles, SSP_LEN, w.sr_embed, ws.verbs32, w.v_embed, keep(1), keep(0), scale, t.emb);
     Prod fc = lin(Re, H, H, t.emb, H, w.fc_w, w.fc_b, ws.r[0]);
     if (run_product(run, fc)) return 1;
     for (int l = 0; l < 3; ++l)
-        if (layer(w.enc[l], t.enc[l], Re, SSP_LEN, false, 2 + 4 * l, nullptr)) return 1;
-    layernorm_train(s, ws.r[0], w.enc_ln_w, w.enc_ln_b, Re, t.encln);
+        if (layer(w.enc[l], t.enc[l], SSP_LEN, nullptr, 2 + 4 * l, nullptr)) return 1;
+    layernorm(s, ws.r[0], w.enc_ln_w, w.enc_ln_b, Re, t.encln);
     LAUNCHCHK();
     // ---- decoder
     hipLaunchKernelGGL(k_ssp_embed_train, dim3(Rd), dim3(128), 0, s, ws.tok, SSP_TD, w.sr_embed, (const int*)nullptr, (const float*)nullptr, keep(14),
                        (const uint8_t*)nullptr, scale, ws.r[0]);
     for (int l = 0; l < 3; ++l)
-        if (layer(w.dec[l], t.dec[l], Rd, SSP_TD, true, 15 + 6 * l, t.encln.y)) return 1;
-    layernorm_train(s, ws.r[0], w.dec_ln_w, w.dec_ln_b, Rd, t.decln);
+        if (layer(w.dec[l], t.dec[l], SSP_TD, ws.tok, 15 + 6 * l, t.encln.y)) return 1;
+    layernorm(s, ws.r[0], w.dec_ln_w, w.dec_ln_b, Rd, t.decln);
     // ---- loss
     Prod ex = lin(Rd, SSP_ROLES, H, t.decln.y, H, w.exp_w, w.exp_b, ws.logits);
     if (run_product(run, ex)) return 1;
@@ -574,13 +568,6 @@ extern "C" int vsr_ssp_train_forward(vsr_ssp* e, const int64_t* verbs, const int
     hipLaunchKernelGGL(k_ssp_loss_finish, dim3(1), dim3(256), 0, s, ws.row_loss, ws.gt, one_hot, S, p_applied, masks ? 1 : 0, loss, t.hdr);
     LAUNCHCHK();
     return 0;
-}
-
-// out[c] = column sums of X (R, C) (+ those of X2 (R2, C)), in the fixed order of k_colsum and k_ssp_colsum_finish
-static void ssp_colsum(SspTrainWs& ws, hipStream_t s, const float* X, int R, int C, float* out, const float* X2 = nullptr, int R2 = 0) {
-    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, (long long)C, R, C, ws.part);
-    if (X2) hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X2, (long long)C, R2, C, ws.part + (size_t)COLSUM_CHUNKS * C);
-    hipLaunchKernelGGL(k_ssp_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, ws.part, (X2 ? 2 : 1) * COLSUM_CHUNKS, C, out);
 }
 
 extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const int32_t* roles, const int32_t* gt, int32_t S, const uint8_t* masks, const void* tape,
@@ -619,10 +606,12 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         hipLaunchKernelGGL(k_ssp_drop_bwd, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, dy, keep(site), t.hdr, n, buf);
         return buf;
     };
+    // out = the column sums of X (R, C) (+ those of X2 (R2, C)): the second use of a shared bias
+    auto bias_sum = [&](const float* X, int R, int C, float* out, const float* X2 = nullptr, int R2 = 0) { colsum(s, ws.part, X, C, R, C, out, nullptr, X2, R2); };
     auto ln_bwd = [&](const float* dy, const float* gamma, const SspLnTape& lt, const float* add, int R, float* dx, float* dgamma, float* dbeta) {
         hipLaunchKernelGGL(k_layernorm512_bwd, dim3(cdiv(R, 4)), dim3(256), 0, s, dy, gamma, lt.xhat, lt.rstd, add, R, dx, ws.r[9]);
-        ssp_colsum(ws, s, ws.r[9], R, H, dgamma);
-        ssp_colsum(ws, s, dy, R, H, dbeta);
+        bias_sum(ws.r[9], R, H, dgamma);
+        bias_sum(dy, R, H, dbeta);
     };
     hipLaunchKernelGGL(k_ssp_train_prep, dim3(cdiv(Rd, 256)), dim3(256), 0, s, verbs, roles, gt, S, (int)w.n_verbs, ws.verbs32, ws.roles, ws.gt, ws.tok);
 
@@ -633,7 +622,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     tr_add(w.exp_w, H, SSP_ROLES, H, ws.wT[0], LD);
     tr_add(t.encln.y, H, Re, H, ws.tE[2], Rep);                      // prior^T: the k operand of the three layers' cross-attention d W_k, d W_v
     tb.flush(s);
-    ssp_colsum(ws, s, ws.dlog, Rd, LD, ws.r[9]);                     // (28 columns; the first 26 are the bias gradient)
+    bias_sum(ws.dlog, Rd, LD, ws.r[9]);                     // (28 columns; the first 26 are the bias gradient)
     HIPCHK(hipMemcpyAsync(g->exp_b, ws.r[9], SSP_ROLES * sizeof(float), hipMemcpyDeviceToDevice, s));
     {
         Prod pw = prod1(SSP_ROLES, H, Rdp, ws.t512[0], Rdp, ws.t512[1], Rdp, g->exp_w);
@@ -656,14 +645,14 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         tr_add(ly.W2, F, H, F, ws.wT[0], H);
         tr_add(ly.W1, H, F, H, ws.wT[1], F);
         tb.flush(s);
-        ssp_colsum(ws, s, dz2, R, H, gl.b2);
+        bias_sum(dz2, R, H, gl.b2);
         Prod pw2 = prod1(H, F, Rp, ws.t512[0], Rp, ws.t2048[0], Rp, gl.W2);
         Prod pff = prod1(R, F, H, dz2, H, ws.wT[0], H, ws.dff);
         pff.relu_y = lt.ff;                                                                           // d (W1 yF + b1): relu and the site's dropout in one
         if (run_product(run, pw2) || run_product(run, pff)) return 1;
         tr_add(ws.dff, F, R, F, ws.t2048[1], Rp);
         tb.flush(s);
-        ssp_colsum(ws, s, ws.dff, R, F, gl.b1);
+        bias_sum(ws.dff, R, F, gl.b1);
         Prod pw1 = prod1(F, H, Rp, ws.t2048[1], Rp, ws.t512[1], Rp, gl.W1);
         Prod pyf = prod1(R, H, F, ws.dff, F, ws.wT[1], F, Y);
         if (run_product(run, pw1) || run_product(run, pyf)) return 1;
@@ -704,7 +693,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         tr_add(dzo1, H, R, H, ws.t512[4], Rp);
         tr_add(lt.ctx1, H, R, H, ws.t512[5], Rp);
         tb.flush(s);
-        ssp_colsum(ws, s, dzo1, R, H, gl.bo, dzo2, R);
+        bias_sum(dzo1, R, H, gl.bo, dzo2, R);
         Prod pc1 = prod1(R, H, H, dzo1, H, ws.wT[0], H, Y);
         Prod pwo = prod1(H, H, Rp, ws.t512[4], Rp, ws.t512[5], Rp, gl.Wo);
         if (dec) { pwo.seg[1] = ProdSeg{ws.t512[0], Rp, ws.t512[1], Rp, Rp}; pwo.nseg = 2; }
@@ -716,9 +705,9 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
         tr_add(E, H, R, H, ws.t512[8], Rp);
         tr_add(lt.lnA.y, H, R, H, ws.t512[9], Rp);
         tb.flush(s);
-        ssp_colsum(ws, s, C, R, H, gl.bq, dec ? Q2 : nullptr, R);
-        ssp_colsum(ws, s, ws.dbk1, S, H, gl.bk, dec ? ws.dbk2 : nullptr, S);                           // (k_ssp_mha_bwd: summed per sequence in fp64)
-        ssp_colsum(ws, s, E, R, H, gl.bv, dec ? ws.dpv : nullptr, Re);
+        bias_sum(C, R, H, gl.bq, dec ? Q2 : nullptr, R);
+        bias_sum(ws.dbk1, S, H, gl.bk, dec ? ws.dbk2 : nullptr, S);                           // (k_ssp_mha_bwd: summed per sequence in fp64)
+        bias_sum(E, R, H, gl.bv, dec ? ws.dpv : nullptr, Re);
         Prod pw[3] = {prod1(H, H, Rp, ws.t512[6], Rp, ws.t512[9], Rp, gl.Wq), prod1(H, H, Rp, ws.t512[7], Rp, ws.t512[9], Rp, gl.Wk),
                          prod1(H, H, Rp, ws.t512[8], Rp, ws.t512[9], Rp, gl.Wv)};
         if (dec) {
@@ -747,7 +736,7 @@ extern "C" int vsr_ssp_train_backward(vsr_ssp* e, const int64_t* verbs, const in
     tr_add(t.emb, H, Re, H, ws.t512[1], Rep);
     tr_add(w.fc_w, H, H, H, ws.wT[0], H);
     tb.flush(s);
-    ssp_colsum(ws, s, ws.r[0], Re, H, g->fc_b);
+    bias_sum(ws.r[0], Re, H, g->fc_b);
     {
         Prod pw = prod1(H, H, Rep, ws.t512[0], Rep, ws.t512[1], Rep, g->fc_w);
         Prod px = prod1(Re, H, H, ws.r[0], H, ws.wT[0], H, ws.r[2]);

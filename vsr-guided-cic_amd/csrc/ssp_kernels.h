@@ -19,17 +19,17 @@ constexpr int SSP_H = 512, SSP_HEADS = 8, SSP_HD = 64, SSP_FF = 2048, SSP_LEN = 
 // sort_modules.py:52: v_embed(verb) + sr_embed(roles); sort_modules.py:125: embed_layer(tokens))
 __global__ __launch_bounds__(128) void k_ssp_embed(const int* __restrict__ tok, int ld_tok, int len, const float* __restrict__ table,
                                                    const int64_t* __restrict__ verbs, const float* __restrict__ vtable, int n_verbs,
-                                                   int S, float* __restrict__ out, int* __restrict__ bad) {
+                                                   int S, float* __restrict__ out) {
     const int row = blockIdx.x;                       // s * len + j
     const int s = row / len, j = row - s * len;
     int t = tok[s * ld_tok + j];
-    if (t < 0 || t >= SSP_ROLES) { if (threadIdx.x == 0) atomicAdd(bad, 1); t = 0; }
+    if (t < 0 || t >= SSP_ROLES) t = 0;
     const float sc = 22.627416997969522f;             // sqrt(512)
     const float4 a = *reinterpret_cast<const float4*>(table + (long long)t * SSP_H + threadIdx.x * 4);
     float4 o = make_float4(a.x * sc, a.y * sc, a.z * sc, a.w * sc);
     if (verbs) {
         long long v = verbs[s] % 10000;                // sort_model.py:108
-        if (v < 0 || v >= n_verbs) { if (threadIdx.x == 0) atomicAdd(bad, 1); v = 0; }
+        if (v < 0 || v >= n_verbs) v = 0;
         const float4 b = *reinterpret_cast<const float4*>(vtable + v * SSP_H + threadIdx.x * 4);
         o = make_float4(b.x * sc + a.x * sc, b.y * sc + a.y * sc, b.z * sc + a.z * sc, b.w * sc + a.w * sc);
     }
@@ -160,15 +160,14 @@ __global__ __launch_bounds__(64) void k_ssp_select(const float* __restrict__ log
     }
 }
 
-// A role id outside [0, SSP_ROLES) is not "remaining" (k_ssp_select indexes the 26 logits with it) and is counted in `bad`;
-// the reference raises IndexError in its embedding for such an id (sort_model.py:108), the host wrapper does the same.
+// A role id outside [0, SSP_ROLES) is not "remaining" (k_ssp_select indexes the 26 logits with it); the reference raises IndexError in
+// its embedding for such an id (sort_model.py:108), the host wrapper does the same before the call.
 __global__ void k_ssp_init(const int* __restrict__ roles, int S, int* __restrict__ remain, int* __restrict__ tokens, int* __restrict__ pred,
-                           float* __restrict__ logp, int* __restrict__ bad) {
+                           float* __restrict__ logp) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < S * SSP_LEN) {
         const int r = roles[i];
         const bool ok = r >= 0 && r < SSP_ROLES;
-        if (!ok) atomicAdd(bad, 1);
         remain[i] = ok && r != 0;
         pred[i] = 0;
         logp[i] = 0.f;
@@ -556,15 +555,6 @@ __global__ void k_ssp_drop_bwd(const float* __restrict__ in, const uint8_t* __re
     if (i >= n) return;
     const float4 f = ssp_keep4(keep, i, ssp_keep_scale(hdr)), v = *reinterpret_cast<const float4*>(in + i);
     *reinterpret_cast<float4*>(out + i) = make_float4(v.x * f.x, v.y * f.y, v.z * f.z, v.w * f.w);
-}
-
-// out[c] = the sum of `chunks` partial rows of k_colsum tables laid one after the other (two uses of one bias: two tables), in order
-__global__ void k_ssp_colsum_finish(const float* __restrict__ part, int chunks, int C, float* __restrict__ out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    float s = 0.f;
-    for (int k = 0; k < chunks; ++k) s += part[(long long)k * C + c];
-    out[c] = s;
 }
 
 // The label-smoothed KL term of one row (compute_loss, sort_model.py:66-78; LabelSmoothingKLDivLoss), one wave per row (lane = class):

@@ -12,7 +12,8 @@
 //            dW[n][k] = sum_rows dY^T[n][row] * X^T[k][row]   (both operands transposed once per call)
 // so every matrix product of the backward pass runs on the same stream-K fp32-MFMA kernel as the forward pass.
 // Stated once: the transposed operands (train_operands), a step's slices of the saved arrays (train_step_slices), the step's grouped
-// GEMMs (step_gemms.h), the 28 gradients with their producers and buckets (train_grad_table).
+// GEMMs (step_gemms.h), the 28 gradients with their producers and buckets (train_grad_table), the ordered column sum of every bias
+// gradient here and in the ordering models (colsum_partials / colsum_finish / colsum, one finishing kernel).
 
 constexpr int VSR_GRAD_BUCKETS = 5;
 // f16x2 backward: the "dynamic" slots of the exponent table (from H2_DYN0), where the producers of the gradient operands fold max |x|.
@@ -204,11 +205,21 @@ __global__ void k_h2_dyn_fold(int* __restrict__ dyn, int T, int nsum) {
     }
 }
 
-// deterministic two-stage column sum: out[c] (and out2[c]) = sum over rows of X[r][c], through `part` (COLSUM_CHUNKS x C floats: the idle
-// slab scratch).  Shared with the ordering models' backward passes (ssp.inc.h).
-static void colsum(hipStream_t s, float* part, const float* X, long long ld, int R, int C, float* out, float* out2 = nullptr) {
-    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, ld, R, C, part);
-    hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(C, 256)), dim3(256), 0, s, part, C, 0, C, out, out2);
+// THE deterministic two-stage column sum (bias gradients) of the decoder's and the ordering models' (ssp.inc.h) backward passes.
+// colsum_partials: table[chunk][c] = the sum of that chunk of X's rows (R rows, C columns, leading dimension ld); COLSUM_CHUNKS x C floats.
+// colsum_finish: out[c] (and out2[c]) = the ordered sum of the partials of columns [c0, c0 + n) of a table of C columns; two: of TWO tables, one
+// after the other in memory and in the sum.  Several finishes may share a table (the gradient table's column windows of dpre1).
+static void colsum_partials(hipStream_t s, const float* X, long long ld, int R, int C, float* table) {
+    hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), COLSUM_CHUNKS), dim3(256), 0, s, X, ld, R, C, table);
+}
+static void colsum_finish(hipStream_t s, const float* table, int C, int c0, int n, float* out, float* out2 = nullptr, bool two = false) {
+    hipLaunchKernelGGL(two ? k_colsum_finish<2> : k_colsum_finish<1>, dim3(cdiv(n, 256)), dim3(256), 0, s, table, C, c0, n, out, out2);
+}
+// the pair for a whole matrix, through `part` (the idle slab scratch, or S-SSP's own two tables); X2 (R2, C; compact): the second use of one bias
+static void colsum(hipStream_t s, float* part, const float* X, long long ld, int R, int C, float* out, float* out2 = nullptr, const float* X2 = nullptr, int R2 = 0) {
+    colsum_partials(s, X, ld, R, C, part);
+    if (X2) colsum_partials(s, X2, C, R2, C, part + (size_t)COLSUM_CHUNKS * C);
+    colsum_finish(s, part, C, 0, C, out, out2, X2 != nullptr);
 }
 // up to ZERO_MT buffers zeroed by one launch (sizes in bytes, multiples of 16; pointers 16-byte aligned)
 struct ZeroList {
@@ -1132,10 +1143,10 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
                 P[n++] = product(rows[i]);
             }
             if (n && run_products(run, P, n)) return 1;
-        } else if (r.kind == GradRow::COLSUM) {         // (through the idle slab scratch, like colsum())
+        } else if (r.kind == GradRow::COLSUM) {         // (through the idle slab scratch)
             const bool shared = i > 0 && rows[i - 1].kind == GradRow::COLSUM && rows[i - 1].src == r.src && rows[i - 1].bucket == r.bucket;
-            if (!shared) hipLaunchKernelGGL(k_colsum, dim3(cdiv(r.C, 64), COLSUM_CHUNKS), dim3(256), 0, s, t.*r.src, (long long)r.ld, TB, r.C, t.scratch);
-            hipLaunchKernelGGL(k_colsum_finish, dim3(cdiv(r.n, 256)), dim3(256), 0, s, t.scratch, r.C, r.c0, r.n, G[r.g], r.g2 >= 0 ? G[r.g2] : (float*)nullptr);
+            if (!shared) colsum_partials(s, t.*r.src, r.ld, TB, r.C, t.scratch);
+            colsum_finish(s, t.scratch, r.C, r.c0, r.n, G[r.g], r.g2 >= 0 ? G[r.g2] : nullptr);
             ++i;
         } else {   // EMBED: dx = dpre1 . [W_ih1 ; W_is ; W_ig][:, x columns], summed onto the rows that were looked up (ordered, no atomics)
             const int xoff = (d.h2_first_lstm ? H : 0) + D, sP1 = p.slot(DW_step + DY_dpre1), sQ = p.slot(DW_step + DY_dq);

@@ -166,12 +166,16 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ X, lon
         part[(long long)blockIdx.y * C + c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 // columns [c0, c0 + C) of a partial table with Cs columns per chunk; out2 (optional): a second copy (the two bias vectors of an LSTM cell /
-// a gate pair receive the same gradient: lstm_cell_N.bias_ih / bias_hh, W1_is.bias / W1_hs.bias, W1_ig.bias / W1_hg.bias)
-__global__ void k_colsum_finish(const float* __restrict__ part, int Cs, int c0, int C, float* __restrict__ out, float* __restrict__ out2 = nullptr) {
+// a gate pair receive the same gradient: lstm_cell_N.bias_ih / bias_hh, W1_is.bias / W1_hs.bias, W1_ig.bias / W1_hg.bias).
+// TABLES = 2: a bias with two uses (S-SSP's decoder re-uses its attention projections) has two tables laid one after the other; table 0's
+// partials are added first, then table 1's, in one chain.
+template <int TABLES>
+__global__ void k_colsum_finish(const float* __restrict__ part, int Cs, int c0, int C, float* __restrict__ out, float* __restrict__ out2) {
+    static_assert(TABLES == 1 || TABLES == 2, "one table, or the two uses of a shared bias");
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     float s = 0.f;
-    for (int k = 0; k < COLSUM_CHUNKS; ++k) s += part[(long long)k * Cs + c0 + c];
+    for (int k = 0; k < TABLES * COLSUM_CHUNKS; ++k) s += part[(long long)k * Cs + c0 + c];
     out[c] = s;
     if (out2) out2[c] = s;
 }
