@@ -19,6 +19,10 @@ OUT = os.path.join(HERE, "vsrcap", "libvsrcap.so")
 TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "gemm_bench.hip")
 TOOL_DEPS = [TOOL_SRC] + GEMM_HEADERS
 TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "gemm_bench")
+# standalone check of the selection kernels (k_vocab, k_select_beam, k_backtrack) against a host reference; run by tests/test_gpu_select_kernels.py
+SEL_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "select_check.hip")
+SEL_TOOL_DEPS = [SEL_TOOL_SRC, os.path.join(HERE, "csrc", "kernels.h")] + GEMM_HEADERS
+SEL_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "select_check")
 # the caption-ranking logic (csrc/rank_logic.h) on the CPU: plain C++, host compiler; driven by tests/test_rank_logic.py
 RANK_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "rank_logic_host.cpp")
 RANK_TOOL_DEPS = [RANK_TOOL_SRC, os.path.join(HERE, "csrc", "rank_logic.h")]
@@ -69,11 +73,13 @@ def build(force=False, verbose=False):
 
 
 def build_tool(force=False):
-    if not force and os.path.exists(TOOL_OUT) and all(not os.path.exists(d) or os.path.getmtime(d) <= os.path.getmtime(TOOL_OUT) for d in TOOL_DEPS):
-        return TOOL_OUT
+    """tools/gemm_bench and tools/select_check (the GPU tests that run them skip when they are absent)"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-o", TOOL_OUT + ".tmp", TOOL_SRC], check=True)
-    os.replace(TOOL_OUT + ".tmp", TOOL_OUT)
+    for src, deps, out in ((TOOL_SRC, TOOL_DEPS, TOOL_OUT), (SEL_TOOL_SRC, SEL_TOOL_DEPS, SEL_TOOL_OUT)):
+        if not force and os.path.exists(out) and all(not os.path.exists(d) or os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+            continue
+        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-o", out + ".tmp", src], check=True)
+        os.replace(out + ".tmp", out)
     return TOOL_OUT
 
 

@@ -883,6 +883,18 @@ enum VocabMode { VM_TOPK = 0, VM_SAMPLE = 1, VM_FORCED = 2, VM_FULL = 3 };
 // the index sample j of image b has in the K samples per image call, b K + j, from its decoder row b gs + 1 + j
 __device__ __forceinline__ int sample_row(int row, int gs) { return row - row / gs - 1; }
 
+// k_vocab's launch, decided in one place (launch_vocab of the library and tools/select_check call it): 512 threads per row from V = 4096
+// up, 256 below; rows of up to VOCAB_LDS_MAX logits are summed from the slabs once into dynamic LDS, longer ones are re-read from global
+constexpr int VOCAB_LDS_MAX = 12288;    // 48 KB of dynamic LDS for the combined row
+struct VocabLaunch { int nt; int lds_row; size_t lds_bytes; };
+inline VocabLaunch vocab_launch_rule(int V) {
+    VocabLaunch r;
+    r.nt = V >= 4096 ? 512 : 256;
+    r.lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;
+    r.lds_bytes = r.lds_row ? (size_t)V * sizeof(float) : 0;
+    return r;
+}
+
 // Per row: logits = sum of slabs + bias; log-sum-exp; then by mode
 //   VM_TOPK   K best (log-prob, id) pairs (K = 1: greedy arg-max)          (CaptioningModel.py:47, :152)
 //   VM_SAMPLE Gumbel-max draw from Categorical(logits) + its log-prob      (:66-70)

@@ -223,7 +223,6 @@ int vsr::GemmBuilder::launch(hipStream_t s, const GemmState* h, GemmProfile* p) 
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-constexpr int VOCAB_LDS_MAX = 12288;    // 48 KB of dynamic LDS for the combined row
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 // dst (M, N), compact = the sum of ns compact (M, N) slabs: the finish kernel without an epilogue term
 static void slab_sum_to(hipStream_t s, const float* slabs, int ns, int M, int N, float* dst) {
@@ -914,15 +913,14 @@ static void launch_attend(vsr_handle* h, hipStream_t s, const Gate2Args& g2, int
 static void launch_vocab(vsr_handle* h, hipStream_t s, const StepIO& io, const float* logits, int ns, long long stride, const GateLogitArgs& gate) {
     const Ctx& c = h->c;
     const int V = h->d.vocab_size;
-    const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;          // combined logits row staged in LDS (<= 96 KB)
-    const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
+    const VocabLaunch vl = vocab_launch_rule(V);             // threads per row, combined logits row staged in LDS or not (kernels.h)
     with_const_1to8(io.K, [&](auto KK) {
         auto go = [&](auto NT) {
-            hipLaunchKernelGGL((k_vocab<decltype(KK)::value, decltype(NT)::value>), dim3(io.M), dim3(decltype(NT)::value), vsm, s, logits, ns, stride, h->w.out_fc_bias,
-                               io.M, V, io.vmode, c.top_v, c.top_i, io.full_out, io.full_stride, io.forced, io.seed, (uint32_t)io.t, io.verbs, io.slot, io.rpi, c.L,
-                               io.gt, h->vt_ptr, h->vt_ids, h->n_verbs, lds_row, gate, c.nvalid_dev + 2, io.gs);
+            hipLaunchKernelGGL((k_vocab<decltype(KK)::value, decltype(NT)::value>), dim3(io.M), dim3(decltype(NT)::value), vl.lds_bytes, s, logits, ns, stride,
+                               h->w.out_fc_bias, io.M, V, io.vmode, c.top_v, c.top_i, io.full_out, io.full_stride, io.forced, io.seed, (uint32_t)io.t, io.verbs,
+                               io.slot, io.rpi, c.L, io.gt, h->vt_ptr, h->vt_ids, h->n_verbs, vl.lds_row, gate, c.nvalid_dev + 2, io.gs);
         };
-        if (V >= 4096) go(std::integral_constant<int, 512>{}); else go(std::integral_constant<int, 256>{});
+        if (vl.nt == 512) go(std::integral_constant<int, 512>{}); else go(std::integral_constant<int, 256>{});
     });
 }
 
