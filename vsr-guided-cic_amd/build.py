@@ -37,6 +37,12 @@ PROD_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "products_host.hip"
 PROD_TOOL_DEPS = [PROD_TOOL_SRC, os.path.join(HERE, "csrc", "products.h"), os.path.join(HERE, "csrc", "kernels.h")] + GEMM_HEADERS
 PROD_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "products_host")
 
+# slab placement of the step launches (csrc/step_gemms.h) on the CPU, likewise with hipcc; driven by tests/test_step_slabs_logic.py
+SLAB_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "step_slabs_host.hip")
+SLAB_TOOL_DEPS = [SLAB_TOOL_SRC, os.path.join(HERE, "csrc", "step_gemms.h"), os.path.join(HERE, "csrc", "kernels.h"),
+                  os.path.join(os.path.dirname(HERE), "include", "vsrcap.h")] + GEMM_HEADERS
+SLAB_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "step_slabs_host")
+
 
 STAMP = OUT + ".flags"      # the extra hipcc flags the library on disk was built with
 
@@ -113,6 +119,16 @@ def build_products_tool(out=PROD_TOOL_OUT, force=False):
     return out
 
 
+def build_step_slabs_tool(out=SLAB_TOOL_OUT, force=False):
+    """tools/step_slabs_host with hipcc at -O1, as tools/products_host"""
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in SLAB_TOOL_DEPS):
+        return out
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, "-O1", "--offload-arch=gfx950", "-std=c++17", "-o", out + ".tmp", SLAB_TOOL_SRC], check=True)
+    os.replace(out + ".tmp", out)
+    return out
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))
     if "--tool" in sys.argv:
@@ -120,3 +136,4 @@ if __name__ == "__main__":
         print(build_rank_tool(force="--force" in sys.argv))
         print(build_train_batch_tool(force="--force" in sys.argv))
         print(build_products_tool(force="--force" in sys.argv))
+        print(build_step_slabs_tool(force="--force" in sys.argv))

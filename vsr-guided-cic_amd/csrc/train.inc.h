@@ -184,8 +184,12 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     } else {
         t.h1s16 = t.h2s16 = t.s_t16 = t.g_t16 = t.att16 = nullptr;
     }
-    // GEMM slab scratch: every slab of the largest product of the training path
-    size_t big = std::max({4 * H * in1, V * H, 4 * H * in2, A * D, TB * H, TB * E, D * H, B * (in2 + 2 * H), H * in1, TB * V, TB * 6 * H});
+    // GEMM slab scratch: every slab of the largest product of the training path (products.h), and of the step launches placed in it, by
+    // their layouts (step_gemms.h): the x projection and the vocabulary projection over T B rows.  The backward step's GEMM 1 stays at
+    // B (in2 + 2H): its layout (bwd1_slabs) takes B (3H + D), which that equals, or with img_second_lstm exceeds by B D (kept: no size
+    // changes); GEMM 2 and 3 take B 2H, less than GEMM 1.
+    size_t big = std::max({4 * H * in1, V * H, 4 * H * in2, A * D, TB * H, TB * E, D * H, B * (in2 + 2 * H), H * in1, TB * slab_row_floats(vocab_slabs(d)),
+                           TB * slab_row_floats(lstm1_slabs(d))});
     t.scratch_floats = big * GEMM_MAX_SLABS;
     t.scratch = b.take<float>(t.scratch_floats);
     return (b.off + 255) & ~size_t(255);
@@ -394,37 +398,31 @@ static int train_file(vsr_handle* h, TrainCtx& t, hipStream_t s) {
 }
 // The x part of the LSTM1 / gate pre-activations of o.M rows does not depend on the recurrence: one GEMM -> dst (o.M, 6H)
 static int train_xproj(vsr_handle* h, TrainCtx& t, const StepOperands& o, float* dst, hipStream_t s) {
-    GemmBuilder g;
-    add_lstm1(g, h->d, h->w, o, t.scratch, L1_X);
-    const int ns = g.finish(h);
-    const long long stride = (long long)o.M * 6 * h->d.rnn_size;
-    if ((size_t)stride * ns > t.scratch_floats) return fail("training scratch too small for the x projection (%lld x %d)", stride, ns);
-    for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-    if (g.launch(s, h, &h->prof)) return fail("train x-projection gemm launch failed");
-    slab_sum_to(s, t.scratch, ns, o.M, 6 * h->d.rnn_size, dst);
+    if (xproj_rows(h, o, SlabArea{t.scratch, t.scratch_floats}, dst, s, "train x-projection")) return 1;
     LAUNCHCHK();
     return 0;
 }
-// S6 of o.M rows (gathered through `rows` when given): logits = h2 . out_fc^T as slabs of stride o.M V in t.scratch.  Returns their
-// number (at most ns_max when that is given), 0 after a failure; the caller's head kernel (launch_vocab, k_vocab_select) sums them
-static int train_vocab_gemm(vsr_handle* h, TrainCtx& t, const StepOperands& o, const int* rows, int ns_max, hipStream_t s) {
+// S6 of o.M rows (gathered through `rows` when given): logits = h2 . out_fc^T as slabs in t.scratch -> v (at most ns_max of them when that
+// is given); the caller's head kernel (launch_vocab, k_vocab_select) sums them
+static int train_vocab_gemm(vsr_handle* h, TrainCtx& t, const StepOperands& o, const int* rows, int ns_max, SlabView& v, hipStream_t s) {
     GemmBuilder g;
-    add_vocab(g, h->d, h->w, o, t.scratch, rows);
+    add_vocab(g, h->d, h->w, o, rows);
     const int ns = g.finish(h);
-    const long long stride = (long long)o.M * h->d.vocab_size;
-    if ((ns_max && ns > ns_max) || (size_t)stride * ns > t.scratch_floats) { fail("training scratch too small for the vocabulary projection (%lld x %d)", stride, ns); return 0; }
-    g.a.p[0].slab_stride = stride;
-    if (g.launch(s, h, &h->prof)) { fail("train S6 gemm launch failed"); return 0; }
-    return ns;
+    if (ns_max && ns > ns_max) return fail("train S6: the vocabulary projection's %d slabs are more than its head kernel sums (%d)", ns, ns_max);
+    SlabPlan pl;
+    if (place(g, o.M, vocab_slabs(h->d), {SlabArea{t.scratch, t.scratch_floats}}, pl, "train S6")) return 1;
+    if (g.launch(s, h, &h->prof)) return fail("train S6 gemm launch failed");
+    v = pl.v[0];
+    return 0;
 }
 // ... and the dense head over them: whole log_softmax rows -> out (o.M, V)
 static int train_vocab_full(vsr_handle* h, TrainCtx& t, const StepOperands& o, const int* rows, float* out, hipStream_t s) {
-    const int ns = train_vocab_gemm(h, t, o, rows, 0, s);
-    if (!ns) return 1;
+    SlabView v;
+    if (train_vocab_gemm(h, t, o, rows, 0, v, s)) return 1;
     const GateLogitArgs no_gate{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 0, 0, nullptr, 0};
     StepIO io;                                         // (K = 1, no gate logits)
     io.M = o.M; io.vmode = VM_FULL; io.full_out = out; io.full_stride = h->d.vocab_size;
-    launch_vocab(h, s, io, t.scratch, ns, (long long)o.M * h->d.vocab_size, no_gate);
+    launch_vocab(h, s, io, v.base, v.n, v.stride, no_gate);
     LAUNCHCHK();
     return 0;
 }
@@ -476,50 +474,47 @@ static int train_forward_step(vsr_handle* h, TrainCtx& t, int K, int tt, bool im
     o.M = B;
     o.h1_old = q.h1o; o.h2_old = q.h2o; o.h1_new = q.h1n; o.h2_new = q.h2n; o.s_t = q.s_t; o.g_t = q.g_t; o.att = q.att;
     o.h1_old16 = q.h1o16; o.h2_old16 = q.h2o16; o.h1_new16 = q.h1n16; o.h2_new16 = q.h2n16; o.s_t16 = q.s_t16; o.g_t16 = q.g_t16; o.att16 = q.att16;
-    {   // S1: the recurrent parts only (h2, h1 of the previous step); nothing to multiply at step 0
-        int ns = 0;
-        const long long stride = (long long)B * 6 * H;
-        if (tt > 0) {
-            GemmBuilder g;
-            add_lstm1(g, d, w, o, c.scratch, L1_H2 | L1_H1);
-            ns = g.finish(h);
-            for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride;
-            if (g.launch(s, h, &h->prof)) return fail("train S1 gemm launch failed");
-        }
+    const SlabArea scratch{c.scratch, c.scratch_floats};   // (the step's launches go through the decode workspace's scratch)
+    SlabPlan pl;
+    {   // S1: the recurrent parts only (h2, h1 of the previous step); nothing to multiply at step 0: no launch, a view without slabs
+        GemmBuilder g;
+        if (tt > 0) { add_lstm1(g, d, w, o, L1_H2 | L1_H1); g.finish(h); }
+        if (place(g, B, lstm1_slabs(d, g.a.nprob), {scratch}, pl, "train S1")) return 1;
+        if (tt > 0 && g.launch(s, h, &h->prof)) return fail("train S1 gemm launch failed");
         const int nblk = d.h2_first_lstm ? 6 : 5;      // without h2 in the input the shift-gate block has no recurrent part
+        const SlabView& v = pl.v[0];
         with_shared_rows(K, [&](auto SH, int k) {
-            hipLaunchKernelGGL(k_lstm1_train<decltype(SH)::value>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, c.scratch, ns, stride, c.vproj,
+            hipLaunchKernelGGL(k_lstm1_train<decltype(SH)::value>, dim3(cdiv((long long)B * H, 256)), dim3(256), 0, s, v.base, v.n, v.stride, c.vproj,
                                q.xproj, q.c1o, B, H, q.h1n, q.c1n, q.s_t, c.gpre, q.g1, nblk, q.h1n16, q.s_t16, isc, k);
         });
     }
     {   // S2
         GemmBuilder g;
-        add_s2(g, d, w, o, c.scratch);
-        const int ns = g.finish(h);
-        const S2Layout l = place_s2(g, d, B, c.scratch, ns);
+        add_s2(g, d, w, o);
+        g.finish(h);
+        if (place(g, B, s2_slabs(d), {scratch}, pl, "train S2")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("train S2 gemm launch failed");
         // (Round 5: k_gate2's work inside the attention kernel's row blocks, as in decoding, with the sentinel / s_a / the shift gate stored
         // on the way for the backward pass: measured at no gain - 10.99-11.06 k against 10.85-11.10 k samples/s, profiles/r05_h_* - and not kept.)
         const long long n = (long long)B * (H + A + D + A);
-        hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, q.c1n, w.s_fc_bias,
+        const SlabView &va = pl.v[0], &vb = pl.v[1];
+        hipLaunchKernelGGL(k_gate2, dim3(cdiv(n, 256)), dim3(256), 0, s, va.base, vb.base, va.n, va.stride, vb.stride, c.gpre, q.c1n, w.s_fc_bias,
                            B, H, A, D, q.g_t, q.hA, q.sent, q.sa, q.g1, q.g_t16, isc);
     }
     launch_attend(h, s, Gate2Args{}, B, K, q.slot, 0, q.hA, q.sa, q.sent, q.att, q.alpha, q.att16, att_exp);
     {   // S5
         GemmBuilder g;
-        add_s5(g, d, w, o, c.scratch, tt > 0);
-        const int ns = g.finish(h);
-        const long long stride = (long long)B * 4 * H, stride_g = (long long)B * A;
-        float* gas = c.scratch + stride * ns;
-        g.a.p[0].slab_stride = stride;
-        g.a.p[1].C = gas; g.a.p[1].slab_stride = stride_g;
+        add_s5(g, d, w, o, tt > 0);
+        g.finish(h);
+        if (place(g, B, s5_slabs(d), {scratch}, pl, "train S5")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("train S5 gemm launch failed");
-        GateLogitArgs gl{gas, ns, stride_g, q.hA, w.att_g_weight, c.zsum, nullptr, q.slot, K, c.L, B, A,
+        const SlabView &v = pl.v[0], &vg = pl.v[1];
+        GateLogitArgs gl{vg.base, vg.n, vg.stride, q.hA, w.att_g_weight, c.zsum, nullptr, q.slot, K, c.L, B, A,
                          lg_out, lg_stride};
         gl.ga_out = q.ga;
         const int gblocks = B;
         with_shared_rows(K, [&](auto SH, int k) {
-            hipLaunchKernelGGL(k_fwd_tail<decltype(SH)::value>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, c.scratch, ns, stride,
+            hipLaunchKernelGGL(k_fwd_tail<decltype(SH)::value>, dim3(gblocks + cdiv((long long)B * H, 256)), dim3(256), 0, s, gl, gblocks, v.base, v.n, v.stride,
                                w.lstm2_bias_ih, w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, q.c2o, B, H, q.h2n, q.c2n, q.g2, q.h2n16, isc, k);
         });
     }
@@ -575,15 +570,14 @@ static int train_forward_impl(vsr_handle* h, int K, const int64_t* word_in, cons
         // S6 for all steps at once, sparse head: the rows in their natural (t, b) order (state slots 1 .. T: nothing to gather), then
         // k_vocab_select: the log_softmax rows stay in t.dlogits, the targets' entries go to the caller's (rows, T) tensor
         all.h2_new = t.h2s + BH; all.h2_new16 = im ? t.h2s16 + BH * 2 : nullptr;
-        const int ns = train_vocab_gemm(h, t, all, nullptr, GEMM_MAX_SLABS, s);           // (k_vocab_select sums at most that many slabs: slab_sum)
-        if (!ns) return 1;
-        const long long stride = (long long)TB * V;
+        SlabView v;
+        if (train_vocab_gemm(h, t, all, nullptr, GEMM_MAX_SLABS, v, s)) return 1;        // (k_vocab_select sums at most that many slabs: slab_sum)
         const int lds_row = V <= VOCAB_LDS_MAX ? 1 : 0;
         const size_t vsm = lds_row ? (size_t)V * sizeof(float) : 0;
         const int Vp = (int)up4(V);
         auto select = [&](auto NT, auto ST) {              // the instance: threads per row, with / without the row statistics
             constexpr int nt = decltype(NT)::value;
-            hipLaunchKernelGGL((k_vocab_select<nt, decltype(ST)::value>), dim3(TB), dim3(nt), vsm, s, t.scratch, ns, stride, w.out_fc_bias, B, T, V, Vp,
+            hipLaunchKernelGGL((k_vocab_select<nt, decltype(ST)::value>), dim3(TB), dim3(nt), vsm, s, v.base, v.n, v.stride, w.out_fc_bias, B, T, V, Vp,
                                lds_row, targets, t.dlogits, logp_words, t.tgt32, c.nvalid_dev + 2, logp_mean, entropy);
         };
         using N512 = std::integral_constant<int, 512>; using N256 = std::integral_constant<int, 256>;
@@ -899,10 +893,20 @@ struct BwdPass {
     const float* dlg = nullptr;    // the gradient of the gate log-probs (B, T, 2)
     int* dyn = nullptr;            // the dynamic slots of the exponent table when the pass runs on the f16x2 kernels, else null
     int cb = 0;                    // which of the two cell-carry buffers holds the carries of step tt + 1
-    int ns3 = 0;                   // slabs of the later step's GEMM 3 waiting in t.scratch (consumed by k_bwd_head)
+    SlabView dh1_3{}, dh2_3{};     // slabs of the later step's GEMM 3 waiting in t.scratch (consumed by k_bwd_head; bwd_gemm3)
     int slot(int i) const { return dyn ? H2_DYN0 + i : (int)H2A_NONE; }
     int* ptr(int i) const { return dyn ? dyn + i : nullptr; }
 };
+// GEMM 3 of a step (o = null: none - step 0, and before the first step) and where its slabs wait in t.scratch for the NEXT step's k_bwd_head
+static int bwd_gemm3(vsr_handle* h, TrainCtx& t, const BwdStepOperands* o, BwdPass& p, hipStream_t s) {
+    GemmBuilder g;
+    if (o) { add_bwd3(g, h->d, *o); g.finish(h); }
+    SlabPlan pl;
+    if (place(g, t.B, bwd3_slabs(h->d, g.a.nprob), {SlabArea{t.scratch, t.scratch_floats}}, pl, "bwd gemm 3")) return 1;
+    p.dh1_3 = pl.v[0]; p.dh2_3 = pl.v[1];
+    if (o && g.launch(s, h, &h->prof)) return fail("bwd gemm 3 launch failed");
+    return 0;
+}
 // Step tt of the reverse-time loop: k_bwd_head, GEMM 1, k_bwd_mid, k_dalpha, k_attend_bwd, GEMM 2, k_bwd_tail, GEMM 3 (data gradients
 // only; the GEMMs' problem lists are step_gemms.h's).  Mirrors train_forward_step.
 static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, hipStream_t s) {
@@ -911,7 +915,8 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
     const vsr_weights& w = h->w;
     const int B = t.B, T = t.T, K = t.rpi, Bi = B / K, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, R1 = c.R + 1, cb = p.cb;
     const size_t BH = (size_t)B * H;
-    const long long st3 = (long long)B * H;
+    const SlabArea scratch{t.scratch, t.scratch_floats};
+    SlabPlan pl;
     const StepSlices q = train_step_slices(h, t, tt);
     const int y = tt * DYN_PER_STEP;                   // the step's block of dynamic slots
     BwdStepOperands o;
@@ -926,7 +931,7 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
         a.lg = t.logp_g + (size_t)tt * 2; a.dlg = p.dlg + (size_t)tt * 2; a.lg_stride = (long long)T * 2;
         a.ga = q.ga; a.hA = q.hA; a.w_g = w.att_g_weight; a.A = A;
         a.dga = q.dga; a.dhA = q.dhA; a.dzsum = t.dzsum; a.dwg_rows = q.dwg; a.gblocks = B;
-        a.s_h1 = t.scratch; a.s_h2 = d.h2_first_lstm ? t.scratch + st3 * p.ns3 : nullptr; a.nslab3 = p.ns3; a.stride3 = st3;
+        a.s_h1 = p.dh1_3.base; a.s_h2 = d.h2_first_lstm ? p.dh2_3.base : nullptr; a.nslab3 = p.dh1_3.n; a.stride3 = p.dh1_3.stride;
         a.dh1_c = t.dh1_c; a.dh2_c = t.dh2_c; a.dh2_voc = q.dh2_voc;
         a.dc_next = t.dc2_c[cb]; a.gates2 = q.g2; a.c2 = q.c2n; a.c2_prev = tt > 0 ? q.c2o : nullptr;
         a.M = B; a.H = H; a.dpre2 = q.dpre2; a.dc_prev = t.dc2_c[cb ^ 1];
@@ -936,17 +941,14 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
     {   // grouped GEMM 1: dpre2 -> [dh1_a | datt (| dvbar)] , dh2 carry (hh part);  dga -> dg_t
         GemmBuilder g;
         add_bwd1(g, d, o);
-        const int ns1 = g.finish(h);
-        BwdMidArgs a;
-        a.nslab = ns1; a.st0 = (long long)B * (H + D); a.st1 = (long long)B * H; a.st2 = (long long)B * H;
-        float *C0 = t.scratch, *C1 = C0 + a.st0 * ns1, *C2 = C1 + a.st1 * ns1;
-        g.a.p[0].C = C0; g.a.p[0].slab_stride = a.st0;
-        g.a.p[1].C = C1; g.a.p[1].slab_stride = a.st1;
-        g.a.p[2].C = C2; g.a.p[2].slab_stride = a.st2;
+        g.finish(h);
+        if (place(g, B, bwd1_slabs(d), {scratch}, pl, "bwd gemm 1")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("bwd gemm 1 launch failed");
+        BwdMidArgs a;
+        a.nslab = pl.v[0].n; a.st0 = pl.v[0].stride; a.st1 = pl.v[1].stride; a.st2 = pl.v[2].stride;
         // datt; dg_t -> shift-gate backward (dq into dpre1[:, 5H:6H], dtc); dh1 so far (= dh1_a + carry, into dh_tot) and the
         // hh part of the new dh2 carry (the LSTM1-input part is added by the next k_bwd_head from GEMM 3's slabs)
-        a.C0 = C0; a.C1 = C1; a.C2 = C2; a.M = B; a.H = H; a.D = D;
+        a.C0 = pl.v[0].base; a.C1 = pl.v[1].base; a.C2 = pl.v[2].base; a.M = B; a.H = H; a.D = D;
         a.datt = t.datt; a.dh1_c = t.dh1_c; a.dh_tot = t.dh_tot; a.dh2_c = t.dh2_c;
         a.gates1 = q.g1; a.c1 = q.c1n; a.dq = q.dpre1 + 5 * H; a.dtc = t.dtc; a.bm_dq = p.ptr(y + DY_dq);
         const int wmax = D > H ? D : H;
@@ -978,25 +980,14 @@ static int train_backward_step(vsr_handle* h, TrainCtx& t, int tt, BwdPass& p, h
     {   // grouped GEMM 2: [dq | dhA] -> dh1_b ; [dsent | dsa] -> ds_t;  then the sentinel gate and LSTM1 pointwise backward
         GemmBuilder g;
         add_bwd2(g, d, o);
-        const int ns = g.finish(h);
-        const long long st = (long long)B * H;
-        float *Ca = t.scratch, *Cb = Ca + st * ns;
-        g.a.p[0].C = Ca; g.a.p[0].slab_stride = st;
-        g.a.p[1].C = Cb; g.a.p[1].slab_stride = st;
+        g.finish(h);
+        if (place(g, B, bwd2_slabs(d), {scratch}, pl, "bwd gemm 2")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("bwd gemm 2 launch failed");
-        hipLaunchKernelGGL(k_bwd_tail, dim3(cdiv((long long)BH, 256)), dim3(256), 0, s, Ca, Cb, ns, st, t.dh_tot, t.dtc, t.dc1_c[cb], q.g1, q.c1n,
+        hipLaunchKernelGGL(k_bwd_tail, dim3(cdiv((long long)BH, 256)), dim3(256), 0, s, pl.v[0].base, pl.v[1].base, pl.v[0].n, pl.v[0].stride, t.dh_tot, t.dtc, t.dc1_c[cb], q.g1, q.c1n,
                            tt > 0 ? q.c1o : (float*)nullptr, B, H, q.dpre1, t.dc1_c[cb ^ 1], p.ptr(y + DY_dpre1));
     }
     // grouped GEMM 3: dpre1 -> dh1 carry, dh2 carry (LSTM1 input part); its slabs stay in t.scratch for the next k_bwd_head
-    p.ns3 = 0;
-    if (tt > 0) {
-        GemmBuilder g;
-        add_bwd3(g, d, o);
-        p.ns3 = g.finish(h);
-        g.a.p[0].C = t.scratch; g.a.p[0].slab_stride = st3;
-        if (d.h2_first_lstm) { g.a.p[1].C = t.scratch + st3 * p.ns3; g.a.p[1].slab_stride = st3; }
-        if (g.launch(s, h, &h->prof)) return fail("bwd gemm 3 launch failed");
-    }
+    if (bwd_gemm3(h, t, tt > 0 ? &o : nullptr, p, s)) return 1;
     LAUNCHCHK();
     return 0;
 }
@@ -1049,6 +1040,7 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     p.dlg = grad_logp_gates;
     p.dyn = h2b ? h->h2_exps + H2_DYN0 : nullptr;
     if (h2b) HIPCHK(hipMemsetAsync(p.dyn, 0, H2_NDYN * sizeof(int), s));
+    if (bwd_gemm3(h, t, nullptr, p, s)) return 1;          // (nothing waits for the first step's k_bwd_head)
     const int NV = c.nvalid, NVp = (int)up4((size_t)NV);     // non-padding region rows: the only ones att_va saw
     // under a caller's row bound (vsr_set_valid_rows_bound) NV is the BOUND and the list's tail [n, NV) repeats its first entry: the two
     // gathers below read those rows as zeros (k_transpose_t's rlimit = the device-side count), so att_va's gradient sums over n rows

@@ -68,6 +68,7 @@ struct Ctx {
     int *slot[2], *word[2], *gate[2], *parent;
     float *s_t, *gpre, *g_t, *hA, *sa, *sent, *att, *zsum, *lg, *top_v;
     float* ga_slabs;             // att_ga(g_t) partial sums: kept apart from `scratch`, the vocabulary GEMM overwrites that first
+    size_t ga_floats = 0, pre1_floats = 0;       // capacities of ga_slabs and pre1, as scratch_floats is scratch's
     int* top_i;
     float *seq[2], *mask[2];
     int *hist_parent, *hist_word, *hist_gate;
@@ -140,7 +141,7 @@ struct Bump {
 
 static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
     const vsr_dims& d = h->d;
-    const size_t B = c.B, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, V = d.vocab_size, T = d.seq_len;
+    const size_t B = c.B, H = d.rnn_size, A = d.att_size, D = d.det_feat_size, T = d.seq_len;
     const size_t M = c.Mmax, rows = B * c.L * c.R;
     const size_t prows = c.Rb > 0 ? (size_t)c.n_img * c.Rb : rows;      // rows the hoisted att_va projection covers
     Bump b{base};
@@ -179,7 +180,10 @@ static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
     c.att = b.take<float>(M * D);
     c.zsum = b.take<float>(M);
     c.lg = b.take<float>(M * 2);
-    c.ga_slabs = b.take<float>(M * A * GEMM_MAX_SLABS);
+    // The slab areas are sized by the layouts the launches are placed with (step_gemms.h): every group at GEMM_MAX_SLABS slabs.
+    const SlabLayout l5 = s5_decode_slabs(d);      // decode S5: LSTM2 in scratch, att_ga in ga_slabs, the next step's LSTM1 sums in pre1
+    c.ga_floats = slab_floats(l5, M, 1);
+    c.ga_slabs = b.take<float>(c.ga_floats);
     c.top_v = b.take<float>(M * KMAX);
     c.top_i = b.take<int>(M * KMAX);
     c.hist_parent = b.take<int>(T * M);
@@ -191,12 +195,14 @@ static size_t carve(const vsr_handle* h, Ctx& c, char* base) {
     c.forced_w32 = b.take<int>(T * M);
     c.forced_g32 = b.take<int>(T * M);
     c.tmp_i64 = b.take<int64_t>(T * M);
-    // split-K slab scratch: the widest stage, GEMM_MAX_SLABS slabs
-    size_t widest = std::max({6 * H, (H + A) + (D + A), 4 * H + A, V});
-    size_t stage = std::max(M * widest, B * 6 * H);
-    c.scratch_floats = std::max(stage, std::max(rows, prows) * A) * GEMM_MAX_SLABS;   // att_va slabs of prepare(): over the bank rows when indexed
+    // split-K slab scratch: the widest stage of a step (S1, S2, S5 as training packs it - decoding's takes less -, S6), the hoisted vbar
+    // projections over the B images (the LSTM2 one is narrower) and att_va over the rows prepare() may project (the bank rows when indexed)
+    size_t widest = std::max({slab_row_floats(lstm1_slabs(d)), slab_row_floats(s2_slabs(d)), slab_row_floats(s5_slabs(d)), slab_row_floats(vocab_slabs(d))});
+    size_t stage = std::max(M * widest, B * slab_row_floats(lstm1_slabs(d)));
+    c.scratch_floats = std::max(stage, std::max(rows, prows) * slab_row_floats(att_va_slabs(d))) * GEMM_MAX_SLABS;
     c.scratch = b.take<float>(c.scratch_floats);
-    c.pre1 = b.take<float>(M * 6 * H * GEMM_MAX_SLABS);
+    c.pre1_floats = slab_floats(l5, M, 2);
+    c.pre1 = b.take<float>(c.pre1_floats);
     b.off = (b.off + 15) & ~size_t(15);
     for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j) c.st16[i][j] = b.take<uint16_t>(2 * ((M * H + 7) & ~size_t(7)));      // (bf16: 2 bytes per element; fp16 pairs: 4)
@@ -229,6 +235,23 @@ static void slab_sum_to(hipStream_t s, const float* slabs, int ns, int M, int N,
     const long long tot = (long long)M * N;
     hipLaunchKernelGGL((k_prod_finish<false, FIN_NONE>), dim3(cdiv(tot, 256)), dim3(256), 0, s, slabs, ns, tot, M, N, nullptr, SSP_ACT_NONE, nullptr, 0LL, dst,
                        (long long)N, nullptr, 0LL, nullptr, 1.f);
+}
+// Places the slab groups of a planned launch of M-row problems (step_gemms.h: place_slabs) in `areas` (the layout's area 0, 1, ..); the
+// groups' views in pl.v are what the consumer kernels are given.  A group that does not fit its area fails under the launch's name.
+static int place(GemmBuilder& g, int M, const SlabLayout& l, std::initializer_list<SlabArea> areas, SlabPlan& pl, const char* launch) {
+    return place_slabs(g.a, M, l, areas.begin(), (int)areas.size(), pl) ? fail("%s: %s", launch, pl.err) : 0;
+}
+// The x part of the LSTM1 / gate pre-activations of o.M rows does not depend on the recurrence: one GEMM through the slabs of `scratch`
+// -> dst (o.M, 6H).  The decode cache's chunks of vocabulary rows and the training forwards' input rows.
+static int xproj_rows(vsr_handle* h, const StepOperands& o, SlabArea scratch, float* dst, hipStream_t s, const char* who) {
+    GemmBuilder g;
+    add_lstm1(g, h->d, h->w, o, L1_X);
+    g.finish(h);
+    SlabPlan pl;
+    if (place(g, o.M, lstm1_slabs(h->d), {scratch}, pl, who)) return 1;
+    if (g.launch(s, h, &h->prof)) return fail("%s gemm launch failed", who);
+    slab_sum_to(s, pl.v[0].base, pl.v[0].n, o.M, 6 * h->d.rnn_size, dst);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- API: lifetime
@@ -356,32 +379,20 @@ static const int XPROJ_CHUNK = 512;
 extern "C" size_t vsr_decode_cache_floats(const vsr_handle* h) {
     if (!h) return 0;
     const size_t V = h->d.vocab_size, H = h->d.rnn_size;
-    return V * 6 * H + (size_t)XPROJ_CHUNK * 6 * H * GEMM_MAX_SLABS + 64;
+    return V * 6 * H + slab_floats(lstm1_slabs(h->d), XPROJ_CHUNK) + 64;      // the cache, then a chunk's slabs
 }
 extern "C" int vsr_build_decode_cache(vsr_handle* h, float* buf, size_t n_floats, void* stream) {
     if (!h || !h->bound) return fail("vsr_build_decode_cache: weights not bound");
     if (!buf) { set_xproj(h, nullptr); return 0; }
     if (n_floats < vsr_decode_cache_floats(h)) return fail("vsr_build_decode_cache: buffer too small");
     hipStream_t s = (hipStream_t)stream;
-    const vsr_dims& d = h->d;
-    const vsr_weights& w = h->w;
-    const int V = d.vocab_size, H = d.rnn_size, E = d.input_encoding_size, D = d.det_feat_size;
-    const int in1 = (d.h2_first_lstm ? H : 0) + D + E, xoff = (d.h2_first_lstm ? H : 0) + D;
-    float* slabs = buf + (size_t)V * 6 * H;
+    const int V = h->d.vocab_size, H = h->d.rnn_size, E = h->d.input_encoding_size;
+    const SlabArea slabs{buf + (size_t)V * 6 * H, slab_floats(lstm1_slabs(h->d), XPROJ_CHUNK)};
     for (int v0 = 0; v0 < V; v0 += XPROJ_CHUNK) {
-        const int m = std::min(XPROJ_CHUNK, V - v0);
-        GemmBuilder g;
-        const float* Wih[3] = {w.lstm1_weight_ih, w.W1_is_weight, w.W1_ig_weight};
-        const int Nn[3] = {4 * H, H, H}, off[3] = {0, 4 * H, 5 * H};
-        for (int i = 0; i < 3; ++i) {
-            GemmProb& p = g.prob(m, Nn[i], slabs + off[i], 6 * H);
-            GemmBuilder::seg(p, w.embed_weight + (size_t)v0 * E, E, nullptr, Wih[i] + xoff, in1, E, nullptr, H2A_EMBED);
-        }
-        const int ns = g.finish(h);
-        const long long stride = (long long)m * 6 * H;
-        for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
-        if (g.launch(s, h, &h->prof)) return fail("decode cache gemm launch failed");
-        slab_sum_to(s, slabs, ns, m, 6 * H, buf + (size_t)v0 * 6 * H);
+        StepOperands o;                       // the chunk's rows of the embedding table, ungathered
+        o.M = std::min(XPROJ_CHUNK, V - v0);
+        o.x = h->w.embed_weight + (size_t)v0 * E;
+        if (xproj_rows(h, o, slabs, buf + (size_t)v0 * 6 * H, s, "decode cache")) return 1;
     }
     LAUNCHCHK();
     set_xproj(h, buf);
@@ -695,7 +706,7 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     hipStream_t s = (hipStream_t)stream;
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
-    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size;
+    const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size;
     Ctx& c = h->c;
     c.B = B; c.R0 = R0; c.L = L; c.R = R; c.beam = beam; c.Mmax = B * beam;
     c.n_img = indexed ? n_img : 0; c.Rb = indexed ? Rb : 0;
@@ -767,35 +778,26 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     LAUNCHCHK();
 
     // hoisted vbar projections: columns [voff, voff + D) of the LSTM1 / gate input weights
-    const int in1 = (d.h2_first_lstm ? H : 0) + D + E;
-    const int voff = d.h2_first_lstm ? H : 0;
+    const SlabArea scratch{c.scratch, c.scratch_floats};
+    SlabPlan pl;
     {
         GemmBuilder g;
-        GemmProb& p0 = g.prob(B, 4 * H, c.scratch, 6 * H);
-        GemmBuilder::seg(p0, c.vbar, D, nullptr, w.lstm1_weight_ih + voff, in1, D, nullptr, H2A_DET);
-        GemmProb& p1 = g.prob(B, H, c.scratch + 4 * H, 6 * H);
-        GemmBuilder::seg(p1, c.vbar, D, nullptr, w.W1_is_weight + voff, in1, D, nullptr, H2A_DET);
-        GemmProb& p2 = g.prob(B, H, c.scratch + 5 * H, 6 * H);
-        GemmBuilder::seg(p2, c.vbar, D, nullptr, w.W1_ig_weight + voff, in1, D, nullptr, H2A_DET);
-        const int ns = g.finish(h);
-        const long long stride = (long long)B * 6 * H;
-        for (int i = 0; i < 3; ++i) g.a.p[i].slab_stride = stride;
+        add_vproj(g, d, w, c.vbar, B);
+        g.finish(h);
+        if (place(g, B, lstm1_slabs(d), {scratch}, pl, "vproj")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("vproj gemm launch failed");
-        const long long n = (long long)B * 6 * H;
-        hipLaunchKernelGGL(k_vproj_finish, dim3(cdiv(n, 256)), dim3(256), 0, s, c.scratch, ns, stride, B, H,
+        const SlabView& v = pl.v[0];
+        hipLaunchKernelGGL(k_vproj_finish, dim3(cdiv(v.stride, 256)), dim3(256), 0, s, v.base, v.n, v.stride, B, H,
                            w.lstm1_bias_ih, w.lstm1_bias_hh, w.W1_is_bias, w.W1_hs_bias, w.W1_ig_bias, w.W1_hg_bias, c.vproj);
         LAUNCHCHK();
     }
     if (d.img_second_lstm) {
-        const int in2 = H + 2 * D;
         GemmBuilder g;
-        GemmProb& p0 = g.prob(B, 4 * H, c.scratch, 4 * H);
-        GemmBuilder::seg(p0, c.vbar, D, nullptr, w.lstm2_weight_ih + H + D, in2, D, nullptr, H2A_DET);
-        const int ns = g.finish(h);
-        const long long stride = (long long)B * 4 * H;
-        g.a.p[0].slab_stride = stride;
+        add_vproj2(g, d, w, c.vbar, B);
+        g.finish(h);
+        if (place(g, B, vproj2_slabs(d), {scratch}, pl, "vproj2")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("vproj2 gemm launch failed");
-        slab_sum_to(s, c.scratch, ns, B, 4 * H, c.vproj2);
+        slab_sum_to(s, pl.v[0].base, pl.v[0].n, B, 4 * H, c.vproj2);
         LAUNCHCHK();
     }
     c.bounded = bound > 0;
@@ -812,16 +814,12 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     }
     if (c.nvalid > 0) {
         GemmBuilder g;
-        g.keep_fp32 = true;
-        GemmProb& p0 = g.prob(c.nvalid, A, c.scratch, A);
-        GemmBuilder::seg(p0, regions, D, c.vlist, w.att_va_weight, D, D, nullptr, H2A_REGION);
-        const int ns = g.finish(h);
-        const long long stride = (long long)c.nvalid * A;
-        if ((size_t)stride * ns > c.scratch_floats)
-            return fail("%s: att_va slabs (%lld x %d floats) exceed the workspace scratch (%zu)", who, stride, ns, c.scratch_floats);
-        g.a.p[0].slab_stride = stride;
+        add_att_va(g, d, w, regions, c.vlist, c.nvalid);
+        g.finish(h);
+        if (place_slabs(g.a, c.nvalid, att_va_slabs(d), &scratch, 1, pl)) return fail("%s: att_va slabs over %d rows: %s", who, c.nvalid, pl.err);
         if (g.launch(s, h, &h->prof)) return fail("att_va gemm launch failed");
-        hipLaunchKernelGGL(k_slab_reduce_scatter, dim3(cdiv(stride, 4 * 256)), dim3(256), 0, s, c.scratch, ns, stride, c.nvalid, A, c.vlist, c.P,
+        const SlabView& v = pl.v[0];
+        hipLaunchKernelGGL(k_slab_reduce_scatter, dim3(cdiv(v.stride, 4 * 256)), dim3(256), 0, s, v.base, v.n, v.stride, c.nvalid, A, c.vlist, c.P,
                            bound > 0 ? c.nvalid_dev : (const int*)nullptr);
         LAUNCHCHK();
     }
@@ -928,7 +926,7 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     const vsr_dims& d = h->d;
     const vsr_weights& w = h->w;
     Ctx& c = h->c;
-    const int H = d.rnn_size, A = d.att_size, V = d.vocab_size;
+    const int H = d.rnn_size, A = d.att_size;
     const int M = io.M;
     float* const* so = c.st[io.cur];          // old state
     float* const* sn = c.st[io.cur ^ 1];      // new state
@@ -948,7 +946,8 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     o.h1_old = so[0]; o.h2_old = so[2]; o.h1_new = h1n; o.h2_new = h2n; o.s_t = c.s_t; o.g_t = c.g_t; o.att = c.att;
     o.h1_old16 = sh_old ? c.st16[io.cur][0] : nullptr; o.h2_old16 = sh_old ? c.st16[io.cur][1] : nullptr;
     o.h1_new16 = h1n16; o.h2_new16 = h2n16; o.s_t16 = s_t16; o.g_t16 = g_t16; o.att16 = att16;
-    const long long stride1 = (long long)M * 6 * H;      // a slab of the LSTM1 / gate sums
+    const SlabArea scratch{c.scratch, c.scratch_floats}, ga{c.ga_slabs, c.ga_floats}, pre1{c.pre1, c.pre1_floats};
+    SlabPlan pl;                              // the slab groups of the launch in hand (step_gemms.h)
 
     // ---- S1
     if (io.s1_from_prev && io.sel_beam) {
@@ -969,26 +968,26 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
                            io.parent, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, io.word_prev, c.pre1_nblk, 1, h1n16, s_t16, isc, c.pre1_skip5);
     } else {
         // the state parts from step 1 on; the embedding part unless it comes from the decode cache
+        // (nothing to multiply at step 0 over a decode cache: no launch, and a view without slabs)
         GemmBuilder g;
-        const int nblk = add_lstm1(g, d, w, o, c.scratch, (io.t > 0 ? L1_H2 | L1_H1 : 0) | (h->xproj ? 0 : L1_X));
-        int ns = 0;
-        if (g.a.nprob > 0) {
-            ns = g.finish(h);
-            for (int i = 0; i < g.a.nprob; ++i) g.a.p[i].slab_stride = stride1;
-            if (g.launch(s, h, &h->prof)) return fail("S1 gemm launch failed");
-        }
-        hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns, stride1, c.vproj, io.rpi,
+        const int nblk = add_lstm1(g, d, w, o, (io.t > 0 ? L1_H2 | L1_H1 : 0) | (h->xproj ? 0 : L1_X));
+        if (g.a.nprob > 0) g.finish(h);
+        if (place(g, M, lstm1_slabs(d, g.a.nprob), {scratch}, pl, "S1")) return 1;
+        if (g.a.nprob > 0 && g.launch(s, h, &h->prof)) return fail("S1 gemm launch failed");
+        const SlabView& v = pl.v[0];
+        hipLaunchKernelGGL(k_lstm1, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, v.base, v.n, v.stride, c.vproj, io.rpi,
                            io.parent, c1o, M, H, h1n, c1n, c.s_t, c.gpre, h->xproj, io.word_prev, nblk, 0, h1n16, s_t16, isc);
     }
     // ---- S2
     {
         GemmBuilder g;
-        add_s2(g, d, w, o, c.scratch);
-        const int ns = g.finish(h);
-        const S2Layout l = place_s2(g, d, M, c.scratch, ns);
+        add_s2(g, d, w, o);
+        g.finish(h);
+        if (place(g, M, s2_slabs(d), {scratch}, pl, "S2")) return 1;
         if (g.launch(s, h, &h->prof)) return fail("S2 gemm launch failed");
         // k_gate2's work (g_t, hA, s_a, sentinel from the S2 slabs) is done by the attention kernel's row blocks themselves
-        const Gate2Args g2{c.scratch, l.c2b, ns, l.stride_a, l.stride_b, c.gpre, c1n, w.s_fc_bias, H, c.g_t, c.hA, g_t16, isc};
+        const SlabView &va = pl.v[0], &vb = pl.v[1];
+        const Gate2Args g2{va.base, vb.base, va.n, va.stride, vb.stride, c.gpre, c1n, w.s_fc_bias, H, c.g_t, c.hA, g_t16, isc};
         launch_attend(h, s, g2, M, io.rpi, io.slot, io.fixed_slot, c.hA, c.sa, c.sent, c.att, io.alpha_out, att16, att_exp);
     }
     // ---- S5 and S6 are planned together, before either is launched.
@@ -998,63 +997,40 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     // Round 6 (split_pre1): the h1 part of those sums (h1_new . [W_hh1 ; W1_hs]) rides in S5 instead: S5's k-aligned plan left 56 of 256 CUs
     // idle (64 LSTM2 tiles x 3 pieces + 8 att_ga tiles), and without these K = H tiles the vocabulary launch is UNIFORM (every tile K = H:
     // one k-aligned piece per tile, no slabs at all).  Measured on the beam-5 shapes (tools/gemm_bench GEMM_REPACK=1, profiles/r06_e_*):
-    // 148-153 -> 133 us for the two launches.  Both parts land in the 8 slabs of pre1 - S5's in the leading ns_h1, S6's behind them: when
-    // the two plans would not fit (the exact-fp32 flavour cuts its 64 x 64 tiles into up to 8 stream-K pieces) both launches are planned
-    // again in the round-5 composition.
-    GemmBuilder g5, g6;
-    int ns5 = 0, ns6 = 0, ns_h1 = 0, ns_pre1 = 1, nblk6 = 0;
-    auto plan56 = [&](bool split) {
-        g5 = GemmBuilder(); g6 = GemmBuilder();
-        add_s5(g5, d, w, o, c.scratch, io.t > 0);
-        if (split) add_lstm1(g5, d, w, o, c.pre1, L1_NEXT | L1_H1);
-        add_vocab(g6, d, w, o, c.scratch);
-        nblk6 = io.s1_for_next ? add_lstm1(g6, d, w, o, c.pre1, L1_NEXT | L1_H2 | (split ? 0 : L1_H1)) : 0;
-        ns5 = g5.finish(h); ns6 = g6.finish(h);
-        // the LSTM1 / gate problems write (and k_lstm1 adds) only the slabs THEIR tiles can meet - all of a launch's get the largest of
-        // their counts, k_lstm1 takes one count for its six gate blocks
-        ns_h1 = 0; ns_pre1 = 1;
-        for (int i = 2; i < g5.a.nprob; ++i) ns_h1 = std::max(ns_h1, gemm_tight_slabs(g5.a, i));
-        for (int i = 1; i < g6.a.nprob; ++i) ns_pre1 = std::max(ns_pre1, gemm_tight_slabs(g6.a, i));
-    };
-    plan56(io.s1_for_next && h->split_pre1 && d.h2_first_lstm);
-    if (ns_h1 > 0 && ns_h1 + ns_pre1 > GEMM_MAX_SLABS) plan56(false);
+    // 148-153 -> 133 us for the two launches.  The composition, its slab counts and the re-plan when the two parts would not fit pre1's
+    // 8 slabs: plan_s56 (step_gemms.h).
+    Step56 p56;
+    plan_s56(h, d, w, o, io.t > 0, io.s1_for_next, io.s1_for_next && h->split_pre1 && d.h2_first_lstm, p56);
     // ---- S5
     GateLogitArgs gate_args;
+    SlabView h1_part;                         // the h1 part of the next step's LSTM1 sums in pre1 (no slabs without the split)
     {
-        GemmBuilder& g = g5;
-        const long long stride = (long long)M * 4 * H, stride_g = (long long)M * A;
-        g.a.p[0].slab_stride = stride;
-        g.a.p[0].nslab = gemm_tight_slabs(g.a, 0);
-        g.a.p[1].C = c.ga_slabs; g.a.p[1].slab_stride = stride_g;
-        g.a.p[1].nslab = gemm_tight_slabs(g.a, 1);
-        for (int i = 2; i < g.a.nprob; ++i) { g.a.p[i].slab_stride = stride1; g.a.p[i].nslab = ns_h1; }
-        c.pre1_skip5 = ns_h1;
-        const int ns_lstm2 = g.a.p[0].nslab;
-        if ((size_t)stride * ns5 > c.scratch_floats) return fail("S5: slabs exceed the workspace scratch");
+        GemmBuilder& g = p56.g5;
+        if (place(g, M, s5_decode_slabs(d, g.a.nprob, p56.ns_h1), {scratch, ga, pre1}, pl, "S5")) return 1;
+        const SlabView &v = pl.v[0], &vg = pl.v[1];
+        h1_part = pl.v[2];
+        c.pre1_skip5 = h1_part.n;
         if (g.launch(s, h, &h->prof)) return fail("S5 gemm launch failed");
-        hipLaunchKernelGGL(k_lstm2, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, c.scratch, ns_lstm2, stride, w.lstm2_bias_ih,
+        hipLaunchKernelGGL(k_lstm2, dim3(cdiv((long long)M * H, 256)), dim3(256), 0, s, v.base, v.n, v.stride, w.lstm2_bias_ih,
                            w.lstm2_bias_hh, d.img_second_lstm ? c.vproj2 : nullptr, io.rpi, io.parent, c2o, M, H, h2n, c2n, h2n16, isc);
         // the gate logits (z_g, log_softmax([z_g, zsum]), step :185-188) are nobody's input before the selection: the
         // vocabulary kernel's row blocks compute them on the side instead of a launch of their own
         // (att_ga has a quarter of LSTM2's K: fewer stream-K pieces per tile, fewer slabs for the gate logits to add)
-        gate_args = GateLogitArgs{c.ga_slabs, g.a.p[1].nslab, stride_g, c.hA, w.att_g_weight, c.zsum, io.verbs, io.slot, io.rpi, c.L, M, A,
+        gate_args = GateLogitArgs{vg.base, vg.n, vg.stride, c.hA, w.att_g_weight, c.zsum, io.verbs, io.slot, io.rpi, c.L, M, A,
                                   io.lg_out, io.lg_stride};
     }
     // ---- S6
     {
-        GemmBuilder& g = g6;
-        const long long stride = (long long)M * V;
-        g.a.p[0].slab_stride = stride;
-        for (int i = 1; i < g.a.nprob; ++i) {             // (behind the slabs the S5 launch above wrote the h1 part into)
-            g.a.p[i].C += c.pre1_skip5 * stride1; g.a.p[i].slab_stride = stride1; g.a.p[i].nslab = ns_pre1;
-        }
-        c.pre1_ns = (g.a.nprob > 1 ? ns_pre1 : ns6) + c.pre1_skip5; c.pre1_nblk = nblk6; c.pre1_stride = stride1;
+        GemmBuilder& g = p56.g6;
+        c.pre1_ns = (g.a.nprob > 1 ? p56.ns_pre1 : g.a.nslab) + c.pre1_skip5; c.pre1_nblk = p56.nblk6;
         if (c.pre1_ns > GEMM_MAX_SLABS) return fail("S6: the LSTM1 sums of the next step would need %d slabs (%d fit)", c.pre1_ns, GEMM_MAX_SLABS);
         // the vocabulary tiles (K = H) are cut into fewer pieces than the LSTM1 tiles (K = 2 H) they share the launch with: k_vocab
-        // adds only the slabs they wrote (60 -> 40 MB of logits per beam-5 step)
-        const int ns_vocab = g.a.p[0].nslab = gemm_tight_slabs(g.a, 0);
+        // adds only the slabs they wrote (60 -> 40 MB of logits per beam-5 step); the LSTM1 sums go behind the slabs the S5 launch
+        // above wrote the h1 part into
+        if (place(g, M, s6_slabs(d, g.a.nprob, p56.ns_pre1), {scratch, area_behind(pre1, h1_part)}, pl, "S6")) return 1;
+        c.pre1_stride = pl.v[1].stride;
         if (g.launch(s, h, &h->prof)) return fail("S6 gemm launch failed");
-        launch_vocab(h, s, io, c.scratch, ns_vocab, stride, gate_args);
+        launch_vocab(h, s, io, pl.v[0].base, pl.v[0].n, pl.v[0].stride, gate_args);
     }
     c.st16_ok[io.cur ^ 1] = sh;               // the new state's bf16 images exist iff this step wrote them
     LAUNCHCHK();
