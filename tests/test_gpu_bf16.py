@@ -190,3 +190,32 @@ def test_bf16_producer_written_a_images_change_nothing(monkeypatch):
         res.append((w.cpu(), g.cpu(), bw.cpu(), bg.cpu(), lw.cpu(), lg.cpu()))
     for a, b in zip(*res):
         assert torch.equal(a, b)
+
+
+def test_bf16_select_back_accumulates_the_same_bits():
+    """bf16 mode with two live forwards: backward of the second, then of the FIRST - vsr_train_select makes the first forward current again
+    and registers the bf16 twins of its workspace's transposed operands anew (the live-forward tests run in the other three flavours only).
+    Held against a fresh model that takes forward / backward of batch 1, then of batch 2: every forward's kernels, inputs and summation
+    order are the same, fp32 addition of the two contributions commutes and the library's runs are reproducible, so the accumulated .grad
+    of all 28 parameters is equal bit for bit."""
+    from test_gpu_live_forwards import _setup, _dev
+    cfg, w, b1, b2 = _setup()                            # g1_xe_small: B 4, T 12, H 64, D 512, A 32, V 50 - all multiples of 8
+    grads = []
+    for interleaved in (True, False):
+        m = helpers.build_model(cfg, w, DEV).train()
+        m.set_compute_dtype("bf16")
+        m.zero_grad()
+        (d1, s1, c1, g1), (d2, s2, c2, g2) = _dev(b1), _dev(b2)
+        if interleaved:
+            out1, gate1 = m((d1,), (c1, s1))
+            out2, gate2 = m((d2,), (c2, s2))
+            vo.xe_loss(out2, gate2, c2, g2)[0].backward()
+            vo.xe_loss(out1, gate1, c1, g1)[0].backward()      # forces the select back to the first forward
+        else:
+            for d, s, c, g in ((d1, s1, c1, g1), (d2, s2, c2, g2)):
+                out, gate = m((d,), (c, s))
+                vo.xe_loss(out, gate, c, g)[0].backward()
+        grads.append({k: p.grad.detach().cpu().clone() for k, p in m.named_parameters()})
+    assert len(grads[0]) == 28 and any(float(v.abs().max()) > 0 for v in grads[0].values())
+    for k in grads[0]:
+        assert torch.equal(grads[0][k], grads[1][k]), (k, (grads[0][k] - grads[1][k]).abs().max().item())

@@ -42,7 +42,10 @@ SLAB_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "step_slabs_host.hi
 SLAB_TOOL_DEPS = [SLAB_TOOL_SRC, os.path.join(HERE, "csrc", "step_gemms.h"), os.path.join(HERE, "csrc", "kernels.h"),
                   os.path.join(os.path.dirname(HERE), "include", "vsrcap.h")] + GEMM_HEADERS
 SLAB_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "step_slabs_host")
-
+# the flavour rule and the registry of operand images (csrc/gemm_route.h) on the CPU, likewise with hipcc; driven by tests/test_route_logic.py
+ROUTE_TOOL_SRC = os.path.join(os.path.dirname(HERE), "tools", "route_host.hip")
+ROUTE_TOOL_DEPS = [ROUTE_TOOL_SRC] + GEMM_HEADERS
+ROUTE_TOOL_OUT = os.path.join(os.path.dirname(HERE), "tools", "route_host")
 
 STAMP = OUT + ".flags"      # the extra hipcc flags the library on disk was built with
 
@@ -66,8 +69,7 @@ def needs_build():
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-o", OUT + ".tmp", SRC]
+    cmd = [_hipcc(), "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-o", OUT + ".tmp", SRC]
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
     cmd[1:1] = _flags().split()              # experiments only (e.g. -save-temps); recorded in the stamp so that a later plain run rebuilds
@@ -78,62 +80,65 @@ def build(force=False, verbose=False):
     return OUT
 
 
+def _hipcc():
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def _cxx():
+    return os.environ.get("CXX", "c++")
+
+
+def build_host_tool(src, deps, out, compiler, flags, force=False, missing_ok=False):
+    """One stand-alone tool: `compiler flags -o out src`, unless `out` is newer than every one of `deps`.  A dependency that does not
+    exist raises, except for the two GPU tools (missing_ok: as they always were)"""
+    if not force and os.path.exists(out) and all((missing_ok and not os.path.exists(d)) or os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+        return out
+    subprocess.run([compiler, *flags, "-o", out + ".tmp", src], check=True)
+    os.replace(out + ".tmp", out)
+    return out
+
+
+GPU_TOOL_FLAGS = ("-O3", "--offload-arch=gfx950", "-std=c++17")
+# hipcc at -O1: the kernels these tools pull in are never launched; they run on a machine without a GPU
+CPU_HIP_TOOL_FLAGS = ("-O1", "--offload-arch=gfx950", "-std=c++17")
+CXX_TOOL_FLAGS = ("-O2", "-std=c++17", "-Wall", "-Wextra")
+
+
 def build_tool(force=False):
     """tools/gemm_bench and tools/select_check (the GPU tests that run them skip when they are absent)"""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     for src, deps, out in ((TOOL_SRC, TOOL_DEPS, TOOL_OUT), (SEL_TOOL_SRC, SEL_TOOL_DEPS, SEL_TOOL_OUT)):
-        if not force and os.path.exists(out) and all(not os.path.exists(d) or os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
-            continue
-        subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-o", out + ".tmp", src], check=True)
-        os.replace(out + ".tmp", out)
+        build_host_tool(src, deps, out, _hipcc(), GPU_TOOL_FLAGS, force, missing_ok=True)
     return TOOL_OUT
 
 
 def build_rank_tool(out=RANK_TOOL_OUT, force=False, extra_flags=()):
     """tools/rank_logic_host with the host compiler ($CXX, default c++); extra_flags e.g. ("-fsanitize=address,undefined", "-g")"""
-    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in RANK_TOOL_DEPS):
-        return out
-    cxx = os.environ.get("CXX", "c++")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-Wextra", *extra_flags, "-o", out + ".tmp", RANK_TOOL_SRC], check=True)
-    os.replace(out + ".tmp", out)
-    return out
+    return build_host_tool(RANK_TOOL_SRC, RANK_TOOL_DEPS, out, _cxx(), (*CXX_TOOL_FLAGS, *extra_flags), force)
 
 
 def build_train_batch_tool(out=TB_TOOL_OUT, force=False, extra_flags=()):
-    """tools/train_batch_host with the host compiler ($CXX, default c++); extra_flags e.g. ("-fsanitize=address,undefined", "-g")"""
-    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in TB_TOOL_DEPS):
-        return out
-    cxx = os.environ.get("CXX", "c++")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-Wextra", *extra_flags, "-o", out + ".tmp", TB_TOOL_SRC], check=True)
-    os.replace(out + ".tmp", out)
-    return out
+    """tools/train_batch_host, likewise"""
+    return build_host_tool(TB_TOOL_SRC, TB_TOOL_DEPS, out, _cxx(), (*CXX_TOOL_FLAGS, *extra_flags), force)
 
 
 def build_products_tool(out=PROD_TOOL_OUT, force=False):
     """tools/products_host with hipcc at -O1 (its kernels are never launched; it runs on a machine without a GPU)"""
-    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in PROD_TOOL_DEPS):
-        return out
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "-O1", "--offload-arch=gfx950", "-std=c++17", "-o", out + ".tmp", PROD_TOOL_SRC], check=True)
-    os.replace(out + ".tmp", out)
-    return out
+    return build_host_tool(PROD_TOOL_SRC, PROD_TOOL_DEPS, out, _hipcc(), CPU_HIP_TOOL_FLAGS, force)
 
 
 def build_step_slabs_tool(out=SLAB_TOOL_OUT, force=False):
     """tools/step_slabs_host with hipcc at -O1, as tools/products_host"""
-    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in SLAB_TOOL_DEPS):
-        return out
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, "-O1", "--offload-arch=gfx950", "-std=c++17", "-o", out + ".tmp", SLAB_TOOL_SRC], check=True)
-    os.replace(out + ".tmp", out)
-    return out
+    return build_host_tool(SLAB_TOOL_SRC, SLAB_TOOL_DEPS, out, _hipcc(), CPU_HIP_TOOL_FLAGS, force)
+
+
+def build_route_tool(out=ROUTE_TOOL_OUT, force=False, extra_flags=()):
+    """tools/route_host with hipcc at -O1, as tools/products_host; extra_flags e.g. ("-Xarch_host", "-fsanitize=address,undefined", "-g")"""
+    return build_host_tool(ROUTE_TOOL_SRC, ROUTE_TOOL_DEPS, out, _hipcc(), (*CPU_HIP_TOOL_FLAGS, *extra_flags), force)
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))
+    force = "--force" in sys.argv
+    print(build(force=force, verbose="--verbose" in sys.argv))
     if "--tool" in sys.argv:
-        print(build_tool(force="--force" in sys.argv))
-        print(build_rank_tool(force="--force" in sys.argv))
-        print(build_train_batch_tool(force="--force" in sys.argv))
-        print(build_products_tool(force="--force" in sys.argv))
-        print(build_step_slabs_tool(force="--force" in sys.argv))
+        for f in (build_tool, build_rank_tool, build_train_batch_tool, build_products_tool, build_step_slabs_tool, build_route_tool):
+            print(f(force=force))

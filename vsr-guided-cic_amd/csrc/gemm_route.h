@@ -11,8 +11,86 @@
 
 namespace vsr {
 
-struct Bf16Range { const float* lo; const float* hi; const uint16_t* b; };   // fp32 matrix [lo, hi) has a bf16 copy at b
-struct H2Range { const float* lo; const float* hi; const float* img; int slot; };   // ... an fp16-pair image (gemm_h2.h) at img, scale exponent in slot
+// An operand that exists as an image beside its fp32 buffer [lo, hi), or instead of it
+struct ImageRange {
+    enum Owner { WEIGHTS, TRAIN };       // the bound weights (set by the refreshes) | the transposed W operands of the current training workspace
+    const float* lo; const float* hi;
+    Owner owner;
+    const uint16_t* b16;                 // bf16 copy (gemm_bf16.h), or null
+    const float* h2;                     // fp16-pair image (gemm_h2.h), or null ...
+    int slot;                            // ... and the slot of its scale exponent (H2Slot)
+    bool holds(const float* p) const { return p >= lo && p < hi; }
+    const float* h2_at(const float* p) const { return h2 + (p - lo); }
+};
+
+// THE registry of operand images: GemmBuilder::finish(), the transposing kernels of the training pass and the optimizer find an operand's
+// image by the address of its fp32 buffer.  The entry points (vsrcap.hip, train.inc.h) change it through the named operations only.
+// A lookup prefers the weights' ranges: a training range may outlive the memory it was registered for.
+struct OperandImages {
+    std::vector<ImageRange> r;
+    bool train_h2_only = false;          // the running backward pass writes ONLY the fp16-pair images of the training ranges (train.inc.h: h2b)
+
+    // ---- the weights' images (vsr_bind_weights, vsr_refresh_*_weights, vsr_adam_step)
+    void clear_weights_bf16() { drop(ImageRange::WEIGHTS, true, false); }       // (the training ranges keep their twins: see clear_h2)
+    void add_weight_bf16(const float* p, size_t n, const uint16_t* b) { weight(p, n).b16 = b; }
+    void clear_weights_h2() { drop(ImageRange::WEIGHTS, false, true); }
+    void add_weight_h2(const float* p, size_t n, const float* img, int slot) { ImageRange& x = weight(p, n); x.h2 = img; x.slot = slot; }   // (the embedding table too: an A operand)
+    // Leaving the f16x2 flavour (bind, refresh(NULL)) also forgets the training ranges' fp16-pair images, leaving the bf16 mode keeps their
+    // twins.  Kept as it was: both transitions invalidate the training context, and the next forward or select registers anew, but
+    // stale_w (below) scans the twins for launches of the decoder too, so dropping them could in principle be observed
+    void clear_h2() { clear_weights_h2(); drop(ImageRange::TRAIN, false, true); }
+    // ---- the training workspace's.  register_train (train_begin, vsr_train_select: `ops` is the list carve_train built out of train_operands)
+    // replaces the registrations of the workspace before it; no entry point calls clear_train on its own (tools/route_host does)
+    void clear_train() { drop(ImageRange::TRAIN, true, true); train_h2_only = false; }
+    void register_train(const std::vector<ImageRange>& ops) { clear_train(); r.insert(r.end(), ops.begin(), ops.end()); }
+    void mark_train_image_only(bool on) { train_h2_only = on; }
+
+    // ---- lookups
+    const uint16_t* bf16_of(const float* p) const {
+        const ImageRange* x = find(p, true, [](const ImageRange& q) { return q.b16 != nullptr; });
+        return x ? x->b16 + (p - x->lo) : nullptr;
+    }
+    const ImageRange* h2_of(const float* p) const { return find(p, true, [](const ImageRange& q) { return q.h2 != nullptr; }); }
+    // A operands are looked up among the weights' ranges only (the embedding table): the training ranges describe W operands
+    const ImageRange* h2_of_weight(const float* p) const { return find(p, false, [](const ImageRange& q) { return q.h2 != nullptr; }); }
+    int h2_slot_of(const float* p) const { const ImageRange* x = h2_of(p); return x ? x->slot : 0; }
+    // p lies in a training range that exists ONLY as an image: its bf16 twin (bf16 mode) / its fp16-pair image (while a backward pass says so)
+    bool only_bf16(const float* p) const { return train(p, [](const ImageRange& q) { return q.b16 != nullptr; }); }
+    bool only_h2(const float* p) const { return train_h2_only && train(p, [](const ImageRange& q) { return q.h2 != nullptr; }); }
+    // the range registered for the weight tensor that begins at p (vsr_adam_step), or null
+    const ImageRange* weight_at(const float* p) const {
+        for (const ImageRange& x : r)
+            if (x.owner == ImageRange::WEIGHTS && x.lo == p) return &x;
+        return nullptr;
+    }
+
+private:
+    ImageRange& weight(const float* p, size_t n) {
+        for (ImageRange& x : r)
+            if (x.owner == ImageRange::WEIGHTS && x.lo == p && x.hi == p + n) return x;
+        r.push_back(ImageRange{p, p + n, ImageRange::WEIGHTS, nullptr, nullptr, 0});
+        return r.back();
+    }
+    void drop(ImageRange::Owner o, bool bf16, bool h2) {          // forgets the images of a kind; a range without any goes
+        for (ImageRange& x : r)
+            if (x.owner == o) { if (bf16) x.b16 = nullptr; if (h2) x.h2 = nullptr; }
+        r.erase(std::remove_if(r.begin(), r.end(), [](const ImageRange& x) { return !x.b16 && !x.h2; }), r.end());
+    }
+    template <class F> const ImageRange* find(const float* p, bool with_train, F&& has) const {
+        const ImageRange* hit = nullptr;
+        for (const ImageRange& x : r)
+            if (x.holds(p) && has(x)) {
+                if (x.owner == ImageRange::WEIGHTS) return &x;
+                if (with_train && !hit) hit = &x;
+            }
+        return hit;
+    }
+    template <class F> bool train(const float* p, F&& has) const {
+        for (const ImageRange& x : r)
+            if (x.owner == ImageRange::TRAIN && x.holds(p) && has(x)) return true;
+        return false;
+    }
+};
 
 // f16x2 flavour: slots of the scale-exponent table (device ints at the head of the image buffer; a twin table of float bounds next to it).
 // 0..13: the 14 weight matrices; then the bounds of the A operands a GEMM segment can name (GemmBuilder::seg's a_cls)
@@ -93,6 +171,9 @@ struct GemmKnobs {
     }
 };
 
+// The kernels a launch is offered first (GemmState::flavour(); the names of vsrcap/derived.py's table)
+enum class Flavour { F32, F32X3, F16X2, BF16 };
+
 // What routing reads of a handle (vsr_handle derives from it)
 struct GemmState {
     // bf16 throughput mode (gemm_bf16.h): off unless vsr_refresh_bf16_weights() has been given a buffer
@@ -102,41 +183,29 @@ struct GemmState {
     bool h2_on = false;
     bool x3_on = true;                // launches of >= gemm_x3_min_rows rows: fp32 products through three bf16 terms per operand (gemm_x3.h); fp32 operands, no copies.  vsr_set_gemm_mode(h, 0): exact fma chain everywhere
     GemmKnobs gk;
-    std::vector<H2Range> h2;
-    std::vector<H2Range> h2t;         // the training pass's transposed operands (vsr_train_forward registers the images of its workspace)
+    OperandImages img;
     int* h2_exps = nullptr;           // device: H2_NSLOT scale exponents ...
     unsigned* h2_bounds = nullptr;    // ... and the bounds they come from (bit patterns of non-negative floats)
-    const H2Range* map_h2(const float* p, bool with_train = true) const {
-        for (const H2Range& r : h2)
-            if (p >= r.lo && p < r.hi) return &r;
-        if (with_train)
-            for (const H2Range& r : h2t)
-                if (p >= r.lo && p < r.hi) return &r;
-        return nullptr;
-    }
-    // A operands are looked up among the images registered at refresh only (the embedding table): the training workspace's
-    // ranges (h2t) describe W operands and may outlive the memory they were registered for
-    const H2Range* map_h2_a(const float* p) const { return map_h2(p, false); }
-    bool h2t_only = false;            // the running backward pass writes ONLY the images of its transposed operands (train.inc.h: h2b)
-    bool is_h2_train_image(const float* p) const {      // p lies in a transposed operand of the training pass that exists ONLY as an fp16-pair image
-        if (!h2t_only) return false;
-        for (const H2Range& r : h2t)
-            if (p >= r.lo && p < r.hi) return true;
-        return false;
-    }
-    int h2_slot_of(const float* p) const { const H2Range* r = map_h2(p); return r ? r->slot : 0; }
-    std::vector<Bf16Range> b16;        // weights (refresh) + the training pass's transposed operands (carve_train)
-    size_t b16_weights = 0;            // entries of b16 that belong to the weights
-    const uint16_t* map16(const float* p) const {
-        for (const Bf16Range& r : b16)
-            if (p >= r.lo && p < r.hi) return r.b + (p - r.lo);
-        return nullptr;
-    }
-    bool is_train_twin(const float* p) const {       // p lies in a transposed operand of the training pass (bf16 image only)
-        for (size_t i = b16_weights; i < b16.size(); ++i)
-            if (p >= b16[i].lo && p < b16[i].hi) return true;
-        return false;
-    }
+
+    // THE flavour rule.  The three switches are what the C ABI sets, and it allows states Python never asks for: with both kinds of
+    // images on, bf16 is offered first and a launch it does not take falls to the f16x2 kernels; h2_on without x3_on is F32 with images nobody reads.
+    // Every reader of the flavour goes through flavour() or one of the predicates below; none spells a conjunction of the switches.
+    Flavour flavour() const { return bf16_on ? Flavour::BF16 : !x3_on ? Flavour::F32 : h2_on ? Flavour::F16X2 : Flavour::F32X3; }
+    bool bf16() const { return flavour() == Flavour::BF16; }
+    bool f16x2() const { return flavour() == Flavour::F16X2; }
+    // launches of this state route to the f16x2 kernels (when their operands qualify).  finish() and the backward pass's h2b must agree on it:
+    // the backward writes ONLY images for launches that finish() then has to route there.  (Under bf16_on too: see flavour())
+    bool routes_f16x2() const { return h2_on && x3_on && gk.gemm_tile == 0; }
+    // a training workspace carries fp16-pair images of its W operands (carve_train), which a backward pass may make the only copy (finish(): stale_h2).
+    // Without x3_on too: the workspace's size does not depend on vsr_set_gemm_mode
+    bool train_h2_images() const { return h2_on && !bf16_on; }
+    // the producers of the decoder's A operands write fp16-pair images beside the fp32 values (run_step, train_a_images).  Not tied to gemm_tile:
+    // with VSR_GEMM_TILE forced the images are written and no launch reads them - not needed, a diagnostic knob's cost
+    bool writes_h2_a_images() const { return f16x2() && gk.h2_aimg; }
+    // vsr_prepare*() measures the bounds of the region / detection operands.  h2_on alone: needed under bf16_on (launches fall through to
+    // the f16x2 kernels), not needed without x3_on, where the passes that carry the measurement are the same
+    bool measures_h2_bounds() const { return h2_on; }
+    bool has_weight_images() const { return h2_on || bf16_on; }      // something derived from the weights' values exists (vsr_adam_step)
 };
 
 // What vsr_profile_* measures.  GemmBuilder::launch times and counts a launch that is handed one (the decoder's); the ordering models hand none.
@@ -236,21 +305,22 @@ struct GemmBuilder {
         route = GemmRoute();
         int maxM = 0;
         for (int i = 0; i < a.nprob; ++i) maxM = std::max(maxM, a.p[i].M);
-        if (h->bf16_on && !(keep_fp32 && k.bf16_p_fp32)) {
+        const bool kept_fp32 = keep_fp32 && k.bf16_p_fp32;      // (a knob of the bf16 mode: only read together with bf16())
+        if (h->bf16() && !kept_fp32) {
             // bf16 mode: every W operand of the launch must have a bf16 copy (and 16-byte-aligned 8-element chunks);
             // a launch that does not qualify runs on the fp32 kernel
             const bool ok = all_segs(a, [&](const GemmSeg& S) {
-                const uint16_t* w16 = h->map16(S.W);
+                const uint16_t* w16 = h->img.bf16_of(S.W);
                 return w16 && (S.K % 8 == 0) && (S.ldw % 8 == 0) && (S.lda % 4 == 0) && aligned16(w16) && aligned16(S.A);
             });
             // the transposing kernels of the training pass write ONLY the bf16 image of such an operand: the fp32 kernel
             // would read a stale buffer.  (Does not happen for sizes the mode accepts: every K / leading dimension is a
             // multiple of 8.)
-            if (!ok) for_each_seg(a, [&](const GemmSeg& S) { stale_w = stale_w || h->is_train_twin(S.W); });
+            if (!ok) for_each_seg(a, [&](const GemmSeg& S) { stale_w = stale_w || h->img.only_bf16(S.W); });
             if (ok) {
                 route.a16 = true;
                 for_each_seg(a, [&](GemmSeg& S) {
-                    S.W = reinterpret_cast<const float*>(h->map16(S.W));
+                    S.W = reinterpret_cast<const float*>(h->img.bf16_of(S.W));
                     route.a16 = route.a16 && S.A16 && (S.lda % 8 == 0) && aligned16(S.A16);
                 });
                 route.kernel = (route.a16 && k.b16_dma) ? GemmKernel::B16A : GemmKernel::BF16W;   // both operands are images: the all-DMA kernel (gemm_b16a.h)
@@ -262,24 +332,24 @@ struct GemmBuilder {
                 return gemm_plan(a, k.gemm_slots_bf16, 4, 128, 64 * route.tn, B16_BK);
             }
         }
-        if (h->h2_on && h->x3_on && k.gemm_tile == 0) {
+        if (h->routes_f16x2()) {
             // f16x2 (gemm_h2.h): every W operand has an fp16-pair image (window starts and leading dimensions in whole 8-element
             // groups), every A operand a bound class
             const bool ok = all_segs(a, [&](const GemmSeg& S) {
-                const H2Range* r = h->map_h2(S.W);
+                const ImageRange* r = h->img.h2_of(S.W);
                 return r && S.exp_idx >= 0 && (S.K % 8 == 0) && (S.ldw % 8 == 0) && (S.lda % 4 == 0) && ((S.W - r->lo) % 8 == 0) && aligned16(S.A);
             });
             if (ok) {             // (every path below returns: the operands are rewritten in place)
                 for_each_seg(a, [&](GemmSeg& S) {
-                    const H2Range* r = h->map_h2(S.W);
+                    const ImageRange* r = h->img.h2_of(S.W);
                     S.exp_idx = (S.exp_idx << 16) | r->slot;
-                    S.W = r->img + (S.W - r->lo);
+                    S.W = r->h2_at(S.W);
                 });
                 a.exps = h->h2_exps;
                 // all-DMA kernel (gemm_h2a.h): every A operand has an fp16-pair image too - written by its producer (GemmSeg::A16 in this
                 // flavour) or a registered one (the embedding table)
                 const bool aimg = k.h2_aimg && all_segs(a, [&](const GemmSeg& S) {
-                    const H2Range* ra = S.A16 ? nullptr : h->map_h2_a(S.A);
+                    const ImageRange* ra = S.A16 ? nullptr : h->img.h2_of_weight(S.A);
                     return (S.lda % 8 == 0) && (S.A16 ? (reinterpret_cast<uintptr_t>(S.A16) & 31) == 0
                                                       : (ra && ra->slot == (S.exp_idx >> 16) && (S.A - ra->lo) % 8 == 0));
                 });
@@ -290,14 +360,14 @@ struct GemmBuilder {
                 if (aimg)
                     for_each_seg(a, [&](GemmSeg& S) {
                         if (S.A16) S.A = reinterpret_cast<const float*>(S.A16);
-                        else { const H2Range* ra = h->map_h2_a(S.A); S.A = ra->img + (S.A - ra->lo); }
+                        else S.A = h->img.h2_of_weight(S.A)->h2_at(S.A);
                     });
                 return plan_mfma128(a, route.tn, k, maxM, maxM <= 128, H2_BK, k.h2_aligned_min, k.h2_aligned_min_small, true, k.gemm_slots_bf16);
             }
         }
         // from here on the launch reads fp32 operands: the transposing kernels of an f16x2 backward pass wrote ONLY the images of theirs
-        if (h->h2_on && !h->bf16_on) for_each_seg(a, [&](const GemmSeg& S) { stale_h2 = stale_h2 || h->is_h2_train_image(S.W); });
-        if ((h->x3_on || (keep_fp32 && h->bf16_on && k.bf16_p_fp32)) && k.gemm_tile == 0) {
+        if (h->train_h2_images()) for_each_seg(a, [&](const GemmSeg& S) { stale_h2 = stale_h2 || h->img.only_h2(S.W); });
+        if ((h->x3_on || (h->bf16() && kept_fp32)) && k.gemm_tile == 0) {
             // f32x3 (gemm_x3.h): 128 x 256 tiles from 193 rows up; 128 x 128 tiles for launches whose rows fit ONE m-tile (greedy
             // decoding, sampling, the per-step GEMMs of the training pass at batch 100, a shard of a strong-scaled decode): the
             // number of tiles is then the number of n-tiles, which 256-wide tiles would have to cut into ~10 k pieces each.

@@ -95,7 +95,7 @@ inline int plan_products(const GemmState& st, const Prod* P, int n, size_t scrat
         if (P[i].keep && P[i].relu_y) return pl.refuse("a product has keep or relu_y, not both");
         in_place = in_place && P[i].in_place;
     }
-    g.a_image_only = a_img && !st.bf16_on;
+    g.a_image_only = a_img && !st.bf16();
     pl.ns = g.finish(&st);
     if (g.a_image_only && g.route.kernel != GemmKernel::H2A)
         return pl.refuse("an A operand exists only as an fp16-pair image but the launch did not take the all-DMA kernel");

@@ -25,7 +25,7 @@ enum { DW_dlogits = DYN_MAX_T * DYN_PER_STEP, DW_dP, DW_dpre1sum, DW_dpre2sum, D
 static_assert(DY_N <= DYN_PER_STEP && DW_N <= DW_step && DW_step + DYN_PER_STEP == H2_NDYN && DYN_MAX_T == 62,
               "the per-step blocks, then one block of whole-pass slots, then the block of the per-step maxima: k_h2_dyn_fold");
 
-struct TrainCtx {                      // (plain data + two vectors: copied into SavedForwards)
+struct TrainCtx {                      // (plain data + one vector, `images`: copied into SavedForwards)
     bool valid = false;
     const char* tws_lo = nullptr;      // the training workspace this forward was carved into
     size_t tws_bytes = 0;
@@ -61,14 +61,11 @@ struct TrainCtx {                      // (plain data + two vectors: copied into
     float* xproj_all;            // (T B, 6H): embedding rows through the x columns of the LSTM1 / gate input weights
     float* scratch;
     size_t scratch_floats = 0;
-    // bf16 mode: every transposed operand that a GEMM takes as W (transposed weights, transposed activations of the
-    // weight-gradient products) has a bf16 twin the transposing kernels write instead of the fp32 buffer
-    struct Twin { const float* f; size_t n; uint16_t* b; };
-    std::vector<Twin> twins;
-    // f16x2 flavour: the same operands have fp16-pair images (gemm_h2.h) in h2img, written by the transposing kernel INSTEAD of the
-    // fp32 buffer (transpose()); slot = exponent slot of the values (the weight's own, or the class of the activation)
-    struct Img { const float* f; size_t n; size_t off; int slot; };
-    std::vector<Img> imgs;
+    // Every transposed operand that a GEMM takes as W (transposed weights, transposed activations of the weight-gradient products), as
+    // the registry takes it (OperandImages::register_train; entry i = operand i of train_operands): its bf16 twin, which the transposing
+    // kernels write instead of the fp32 buffer in the bf16 mode, and in the f16x2 flavour its fp16-pair image (gemm_h2.h) in h2img,
+    // written likewise (transpose()); slot = exponent slot of the values (the weight's own, or the class of the activation)
+    std::vector<ImageRange> images;
     float* h2img = nullptr;
     // ... and the forward pass's A operands are written as fp16-pair images by their producers (kernels.h img_store; gemm_h2a.h takes them):
     // h1 / h2 of every step (T + 1 slots like the fp32 saves), s_t / g_t / the attended vector of the current step
@@ -100,8 +97,8 @@ static void train_operands(const vsr_handle* h, const TrainCtx& t, TOperand (&o)
     const int H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
     const int in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0), Bi = t.B / t.rpi;
     const size_t BH = (size_t)t.B * H;
-    // (N, K) weight -> (K, ld_out >= N); the transposed matrix has the bound of the matrix: its slot (0..13, field order of b16_weight_list)
-    auto W = [&](int i, float* TrainCtx::* buf, const float* src, int N, int K, long long ld_out) { o[i] = TOperand{buf, src, N, K, K, ld_out, h->h2_slot_of(src)}; };
+    // (N, K) weight -> (K, ld_out >= N); the transposed matrix has the bound of the matrix: its slot (0..13, the order of gemm_matrix_list)
+    auto W = [&](int i, float* TrainCtx::* buf, const float* src, int N, int K, long long ld_out) { o[i] = TOperand{buf, src, N, K, K, ld_out, h->img.h2_slot_of(src)}; };
     W(TW_ih1, &TrainCtx::wT_ih1, w.lstm1_weight_ih, 4 * H, in1, 4 * H); W(TW_is, &TrainCtx::wT_is, w.W1_is_weight, H, in1, H); W(TW_ig, &TrainCtx::wT_ig, w.W1_ig_weight, H, in1, H);
     W(TW_hh1, &TrainCtx::wT_hh1, w.lstm1_weight_hh, 4 * H, H, 4 * H); W(TW_hs, &TrainCtx::wT_hs, w.W1_hs_weight, H, H, H);
     W(TW_ih2, &TrainCtx::wT_ih2, w.lstm2_weight_ih, 4 * H, in2, 4 * H); W(TW_hh2, &TrainCtx::wT_hh2, w.lstm2_weight_hh, 4 * H, H, 4 * H);
@@ -164,20 +161,24 @@ static size_t carve_train(const vsr_handle* h, TrainCtx& t, char* base) {
     // the transposed operands (train_operands): the fp32 buffer of each, bf16 twin and fp16-pair image of a W operand, all sized and slotted by its entry
     TOperand ops[N_TOPS];
     train_operands(h, t, ops);
-    t.twins.clear();
+    t.images.clear();
     auto take = [&](int lo, int hi) { for (int i = lo; i < hi; ++i) t.*ops[i].buf = b.take<float>(ops[i].size()); };
-    auto twins = [&](int lo, int hi) { for (int i = lo; i < hi; ++i) t.twins.push_back(TrainCtx::Twin{t.*ops[i].buf, ops[i].size(), b.take<uint16_t>(ops[i].size())}); };
+    auto twins = [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i) t.images.push_back(ImageRange{t.*ops[i].buf, t.*ops[i].buf + ops[i].size(), ImageRange::TRAIN, b.take<uint16_t>(ops[i].size()), nullptr, ops[i].slot});
+    };
     take(0, N_TW);
     twins(0, N_TW);
     b.off = (b.off + 255) & ~size_t(255);
     take(N_TW, N_TOPS);               // (the gradients are A operands: no twins, no registered images)
     twins(N_TW, N_TWX);
-    t.imgs.clear(); t.h2img = nullptr;
-    if (h->h2_on && !h->bf16_on) {
+    t.h2img = nullptr;
+    if (h->train_h2_images()) {
         size_t off = 0;
-        for (int i = 0; i < N_TWX; ++i) { t.imgs.push_back(TrainCtx::Img{t.*ops[i].buf, ops[i].size(), off, ops[i].slot}); off += up4(ops[i].size()); }
+        for (int i = 0; i < N_TWX; ++i) off += up4(ops[i].size());
         b.off = (b.off + 255) & ~size_t(255);
         t.h2img = b.take<float>(off);
+        off = 0;
+        for (int i = 0; i < N_TWX; ++i) { t.images[i].h2 = t.h2img + off; off += up4(ops[i].size()); }
         b.off = (b.off + 255) & ~size_t(255);
         t.h1s16 = b.take<uint16_t>(2 * (T + 1) * B * H); t.h2s16 = b.take<uint16_t>(2 * (T + 1) * B * H);
         t.s_t16 = b.take<uint16_t>(2 * B * H); t.g_t16 = b.take<uint16_t>(2 * B * H); t.att16 = b.take<uint16_t>(2 * B * D);
@@ -273,9 +274,9 @@ struct TransBatch {
 // one of a W operand (h2img), else `out` itself when the caller names a slot (self_slot >= 0) and the buffer can hold an image in place
 struct TransDst { int kind; uint16_t* img; int slot; const int* exps; };
 static TransDst trans_dst(const vsr_handle* h, float* out, long long ld_out, bool h2img, int self_slot) {
-    if (uint16_t* tw = h->bf16_on ? const_cast<uint16_t*>(h->map16(out)) : nullptr) return TransDst{1, tw, 0, nullptr};
+    if (uint16_t* tw = h->bf16() ? const_cast<uint16_t*>(h->img.bf16_of(out)) : nullptr) return TransDst{1, tw, 0, nullptr};
     if (h2img) {
-        if (const H2Range* r2 = h->map_h2(out)) return TransDst{2, reinterpret_cast<uint16_t*>(const_cast<float*>(r2->img + (out - r2->lo))), r2->slot, h->h2_exps};
+        if (const ImageRange* r2 = h->img.h2_of(out)) return TransDst{2, reinterpret_cast<uint16_t*>(const_cast<float*>(r2->h2_at(out))), r2->slot, h->h2_exps};
         if (self_slot >= 0 && ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 31) == 0) return TransDst{2, reinterpret_cast<uint16_t*>(out), self_slot, h->h2_exps};
     }
     return TransDst{0, nullptr, 0, nullptr};
@@ -317,13 +318,7 @@ static void drop_saved_forwards_in(SavedForwards* s, const void* lo, size_t byte
             s->v.erase(s->v.begin() + i);
 }
 // the images of a training workspace's transposed operands: the GEMM builder finds them by address
-static void register_train_images(vsr_handle* h, const TrainCtx& t) {
-    h->b16.resize(h->b16_weights);
-    for (const TrainCtx::Twin& tw : t.twins) h->b16.push_back(Bf16Range{tw.f, tw.f + tw.n, tw.b});
-    h->h2t.clear();
-    h->h2t_only = false;
-    for (const TrainCtx::Img& im : t.imgs) h->h2t.push_back(H2Range{im.f, im.f + im.n, t.h2img + im.off, im.slot});
-}
+static void register_train_images(vsr_handle* h, const TrainCtx& t) { h->img.register_train(t.images); }
 // rows of the f16x2 exponent / bound tables that vsr_prepare*() fills per batch (H2A_REGION, H2A_DET, H2A_ATT): dir 0 = table -> stash
 __global__ void k_h2_stash(int* __restrict__ exps, unsigned* __restrict__ bounds, int* __restrict__ stash, int dir) {
     const int i = threadIdx.x;
@@ -345,7 +340,7 @@ extern "C" int vsr_train_select(vsr_handle* h, int64_t generation, void* stream)
             h->ws_lo = sf.ws_lo; h->ws_bytes = sf.ws_bytes;
             h->prepared = true;
             register_train_images(h, *h->tc);
-            if (h->h2_on && h->tc->h2_stash) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, (hipStream_t)stream, h->h2_exps, h->h2_bounds, h->tc->h2_stash, 1);
+            if (h->measures_h2_bounds() && h->tc->h2_stash) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, (hipStream_t)stream, h->h2_exps, h->h2_bounds, h->tc->h2_stash, 1);
             LAUNCHCHK();
             return 0;
         }
@@ -364,7 +359,7 @@ extern "C" size_t vsr_train_workspace_bytes(const vsr_handle* h, int32_t B, int3
 // ---------------------------------------------------------------------------------------------- forward with saves
 // f16x2 flavour: fp16-pair images of the A operands (all-DMA kernel); BH elements of 4 bytes per state slot
 static bool train_a_images(const vsr_handle* h, const TrainCtx& t) {
-    return h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg && t.h1s16 && (t.B * h->d.rnn_size) % 8 == 0;
+    return h->writes_h2_a_images() && t.h1s16 && (t.B * h->d.rnn_size) % 8 == 0;
 }
 // Begins a saved forward of K rows per image and T steps in the caller's buffer: carves it, drops the forwards filed in it, registers the
 // images of its transposed operands and zeroes the states of step 0.  `who`: the public function, for the messages
@@ -385,7 +380,7 @@ static int train_begin(vsr_handle* h, TrainCtx& t, int K, int T, void* train_ws,
 }
 // the per-batch rows of the f16x2 exponent table as they are now -> the forward's stash (vsr_train_select restores from there)
 static void train_stash(vsr_handle* h, TrainCtx& t, hipStream_t s) {
-    if (h->h2_on) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
+    if (h->measures_h2_bounds()) hipLaunchKernelGGL(k_h2_stash, dim3(1), dim3(64), 0, s, h->h2_exps, h->h2_bounds, t.h2_stash, 0);
 }
 // Files the forward under a new generation: from here on vsr_train_select can make it the handle's current one again
 static int train_file(vsr_handle* h, TrainCtx& t, hipStream_t s) {
@@ -1032,10 +1027,11 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     // f16x2 flavour: the W operands of the backward GEMMs - transposed weights here, transposed activations in phase B - are written as
     // fp16-pair images by the transposing kernel itself; the A operands are gradients: their producers fold max |x| into the dynamic slots
     // of the exponent table (DY_* / DW_*)
-    // (the same conditions GemmBuilder::finish(), gemm_route.h, routes a launch to the f16x2 kernels by: a backward pass that wrote only images for
-    // launches that then fall through to the fp32-operand kernels would read unwritten buffers - finish() refuses such a launch too)
-    const bool h2b = h->h2_on && h->x3_on && h->gk.gemm_tile == 0 && !h->bf16_on && t.h2img && T <= DYN_MAX_T;
-    h->h2t_only = h2b;
+    // (routes_f16x2(): THE condition GemmBuilder::finish(), gemm_route.h, routes a launch to the f16x2 kernels by: a backward pass that wrote only images
+    // for launches that then fall through to the fp32-operand kernels would read unwritten buffers - finish() refuses such a launch too.  Not under
+    // bf16(): there the transposes write the twins)
+    const bool h2b = h->routes_f16x2() && !h->bf16() && t.h2img && T <= DYN_MAX_T;
+    h->img.mark_train_image_only(h2b);
     BwdPass p;
     p.dlg = grad_logp_gates;
     p.dyn = h2b ? h->h2_exps + H2_DYN0 : nullptr;
@@ -1062,8 +1058,8 @@ static int train_backward_impl(vsr_handle* h, bool sel, const float* grad_logp_w
     const int Vp = (int)up4(V);        // K of the dh2_vocab GEMM must be a multiple of 8: zero-padded columns
     if (Vp != V) {
         HIPCHK(hipMemsetAsync(t.wT_out, 0, (size_t)H * Vp * sizeof(float), s));
-        if (uint16_t* tw = h->bf16_on ? const_cast<uint16_t*>(h->map16(t.wT_out)) : nullptr) HIPCHK(hipMemsetAsync(tw, 0, (size_t)H * Vp * sizeof(uint16_t), s));
-        if (const H2Range* r2 = h2b ? h->map_h2(t.wT_out) : nullptr) HIPCHK(hipMemsetAsync(const_cast<float*>(r2->img), 0, (size_t)H * Vp * sizeof(float), s));
+        if (uint16_t* tw = h->bf16() ? const_cast<uint16_t*>(h->img.bf16_of(t.wT_out)) : nullptr) HIPCHK(hipMemsetAsync(tw, 0, (size_t)H * Vp * sizeof(uint16_t), s));
+        if (const ImageRange* r2 = h2b ? h->img.h2_of(t.wT_out) : nullptr) HIPCHK(hipMemsetAsync(const_cast<float*>(r2->h2), 0, (size_t)H * Vp * sizeof(float), s));
     }
     transpose_ops(0, N_TW);
     {   // dP, the carries of the last step: one launch

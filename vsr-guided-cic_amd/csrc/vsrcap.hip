@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -363,12 +364,11 @@ extern "C" int vsr_bind_weights(vsr_handle* h, const vsr_weights* w) {
     void_derived(h, VOID_FLAVOUR);    // cache, statics and saved forwards were taken with the old tensors
     if (h->bf16_on) {                 // ... and so were the bf16 copies: back to fp32 until vsr_refresh_bf16_weights is called again
         h->bf16_on = false;
-        h->b16.erase(h->b16.begin(), h->b16.begin() + h->b16_weights);
-        h->b16_weights = 0;
+        h->img.clear_weights_bf16();
     }
     if (h->h2_on) {                   // ... and the fp16-pair images (vsr_refresh_h2_weights)
         h->h2_on = false;
-        h->h2.clear(); h->h2t.clear();
+        h->img.clear_h2();
     }
     return 0;
 }
@@ -399,25 +399,38 @@ extern "C" int vsr_build_decode_cache(vsr_handle* h, float* buf, size_t n_floats
     return 0;
 }
 
-// ---- bf16 throughput mode: bf16 copies of the 14 weight matrices the GEMMs multiply by (fp32 stays the master copy)
-static const int B16_NW = 14;
-static void b16_weight_list(const vsr_dims& d, const vsr_weights& w, const float* (&ptr)[B16_NW], size_t (&n)[B16_NW]) {
+static void weight_sizes(const vsr_dims& d, size_t (&n)[ADAM_NT]) {          // elements of the 28 tensors, in the order of vsr_weights
     const size_t H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
     const size_t in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0);
-    const float* p[B16_NW] = {w.W1_is_weight, w.W1_hs_weight, w.att_va_weight, w.att_ha_weight, w.att_sa_weight, w.lstm1_weight_ih,
-                              w.lstm1_weight_hh, w.lstm2_weight_ih, w.lstm2_weight_hh, w.out_fc_weight, w.s_fc_weight, w.W1_ig_weight,
-                              w.W1_hg_weight, w.att_ga_weight};
-    const size_t c[B16_NW] = {H * in1, H * H, A * D, A * H, A * H, 4 * H * in1, 4 * H * H, 4 * H * in2, 4 * H * H, V * H, D * H, H * in1, H * H, A * H};
-    for (int i = 0; i < B16_NW; ++i) { ptr[i] = p[i]; n[i] = c[i]; }
+    const size_t c[ADAM_NT] = {V * E, H * in1, H, H * H, H, A * D, A * H, A, A * H, A, 4 * H * in1, 4 * H * H, 4 * H, 4 * H,
+                               4 * H * in2, 4 * H * H, 4 * H, 4 * H, V * H, V, D * H, D, H * in1, H, H * H, H, A * H, A};
+    for (int i = 0; i < ADAM_NT; ++i) n[i] = c[i];
 }
+static_assert(sizeof(vsr_weights) == ADAM_NT * sizeof(float*), "one table entry per tensor of vsr_weights");
+// The 14 matrices the GEMMs multiply by, as tensors of vsr_weights: what the bf16 mode copies, the f16x2 flavour makes images of (exponent
+// slot = position in this list) and the optimizer rewrites both for.  Sizes: weight_sizes
+#define VSR_W(f) (int)(offsetof(vsr_weights, f) / sizeof(float*))
+static const int GEMM_NW = 14;
+static const int GEMM_MATRIX[GEMM_NW] = {VSR_W(W1_is_weight), VSR_W(W1_hs_weight), VSR_W(att_va_weight), VSR_W(att_ha_weight), VSR_W(att_sa_weight),
+                                         VSR_W(lstm1_weight_ih), VSR_W(lstm1_weight_hh), VSR_W(lstm2_weight_ih), VSR_W(lstm2_weight_hh), VSR_W(out_fc_weight),
+                                         VSR_W(s_fc_weight), VSR_W(W1_ig_weight), VSR_W(W1_hg_weight), VSR_W(att_ga_weight)};
+#undef VSR_W
+static void gemm_matrix_list(const vsr_dims& d, const vsr_weights& w, const float* (&ptr)[GEMM_NW], size_t (&n)[GEMM_NW]) {
+    size_t all[ADAM_NT];
+    weight_sizes(d, all);
+    const float* const* W = reinterpret_cast<const float* const*>(&w);
+    for (int i = 0; i < GEMM_NW; ++i) { ptr[i] = W[GEMM_MATRIX[i]]; n[i] = all[GEMM_MATRIX[i]]; }
+}
+
+// ---- bf16 throughput mode: bf16 copies of those matrices (fp32 stays the master copy)
 extern "C" size_t vsr_bf16_weight_bytes(const vsr_handle* h) {
     if (!h) return 0;
-    const float* p[B16_NW]; size_t n[B16_NW];
+    const float* p[GEMM_NW]; size_t n[GEMM_NW];
     vsr_weights none;                          // only the sizes are needed (the weights may be unbound)
     memset(&none, 0, sizeof(none));
-    b16_weight_list(h->d, none, p, n);
+    gemm_matrix_list(h->d, none, p, n);
     size_t tot = 0;
-    for (int i = 0; i < B16_NW; ++i) tot += ((n[i] + 7) & ~size_t(7)) * sizeof(uint16_t);
+    for (int i = 0; i < GEMM_NW; ++i) tot += ((n[i] + 7) & ~size_t(7)) * sizeof(uint16_t);
     return tot + 256;
 }
 extern "C" int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t bytes, void* stream) {
@@ -425,8 +438,7 @@ extern "C" int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t byte
     if (!buffer) {                                          // back to the fp32 parity mode
         if (h->bf16_on) void_derived(h, VOID_FLAVOUR);
         h->bf16_on = false;
-        h->b16.erase(h->b16.begin(), h->b16.begin() + h->b16_weights);     // the weight copies only: the training workspace's twins stay registered
-        h->b16_weights = 0;
+        h->img.clear_weights_bf16();                       // the weight copies only: the training workspace's twins stay registered
         return 0;
     }
     if (!h->bound) return fail("vsr_refresh_bf16_weights: weights not bound");
@@ -437,18 +449,15 @@ extern "C" int vsr_refresh_bf16_weights(vsr_handle* h, void* buffer, size_t byte
     if (bytes < vsr_bf16_weight_bytes(h)) return fail("vsr_refresh_bf16_weights: buffer too small");
     if (reinterpret_cast<uintptr_t>(buffer) & 15) return fail("vsr_refresh_bf16_weights: buffer must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const float* p[B16_NW]; size_t n[B16_NW];
-    b16_weight_list(h->d, h->w, p, n);
-    std::vector<Bf16Range> keep(h->b16.begin() + h->b16_weights, h->b16.end());   // training operands registered by carve_train
-    h->b16.resize(0);
+    const float* p[GEMM_NW]; size_t n[GEMM_NW];
+    gemm_matrix_list(h->d, h->w, p, n);
+    h->img.clear_weights_bf16();
     uint16_t* out = reinterpret_cast<uint16_t*>(buffer);
-    for (int i = 0; i < B16_NW; ++i) {
+    for (int i = 0; i < GEMM_NW; ++i) {
         hipLaunchKernelGGL(k_f32_to_bf16, dim3(cdiv((long long)n[i], 8 * 256)), dim3(256), 0, s, p[i], out, (long long)n[i]);
-        h->b16.push_back(Bf16Range{p[i], p[i] + n[i], out});
+        h->img.add_weight_bf16(p[i], n[i], out);
         out += (n[i] + 7) & ~size_t(7);
     }
-    h->b16_weights = h->b16.size();
-    h->b16.insert(h->b16.end(), keep.begin(), keep.end());
     LAUNCHCHK();
     void_derived(h, h->bf16_on ? VOID_REFRESH : VOID_FLAVOUR);
     h->bf16_on = true;
@@ -462,12 +471,12 @@ constexpr int H2_NDYN = 512;             // 64 blocks of 8: one block per timest
 static_assert(H2_DYN0 * 4 + H2_NDYN * 4 <= 4096, "dynamic slots inside the head");
 extern "C" size_t vsr_h2_weight_bytes(const vsr_handle* h) {
     if (!h) return 0;
-    const float* p[B16_NW]; size_t n[B16_NW];
+    const float* p[GEMM_NW]; size_t n[GEMM_NW];
     vsr_weights none;
     memset(&none, 0, sizeof(none));
-    b16_weight_list(h->d, none, p, n);
+    gemm_matrix_list(h->d, none, p, n);
     size_t tot = H2_HEAD;
-    for (int i = 0; i < B16_NW; ++i) tot += ((n[i] + 7) & ~size_t(7)) * sizeof(float);
+    for (int i = 0; i < GEMM_NW; ++i) tot += ((n[i] + 7) & ~size_t(7)) * sizeof(float);
     tot += (((size_t)h->d.vocab_size * h->d.input_encoding_size + 7) & ~size_t(7)) * sizeof(float);      // the embedding table (an A operand: gemm_h2a.h)
     return tot + 256;
 }
@@ -501,54 +510,54 @@ __global__ __launch_bounds__(1024) void k_h2_prepare_exps(const float* __restric
 struct AdamLaunch { AdamMulti t; AdamHyper hy; };
 static int h2_refresh_launches(vsr_handle* h, char* base, hipStream_t s, const AdamLaunch* adam) {
     const vsr_dims& d = h->d;
-    const float* p[B16_NW]; size_t n[B16_NW];
-    b16_weight_list(h->d, h->w, p, n);
+    const float* p[GEMM_NW]; size_t n[GEMM_NW];
+    gemm_matrix_list(h->d, h->w, p, n);
     int* exps = reinterpret_cast<int*>(base);
     unsigned* bounds = reinterpret_cast<unsigned*>(base + 128);
     int* idx = reinterpret_cast<int*>(base + 256);          // 3 x H2_NSLOT ints of index lists for k_h2_exps
     hipLaunchKernelGGL(k_h2_head_init, dim3(1), dim3(64), 0, s, exps, bounds, idx);
     // bounds of the 14 matrices and of the embedding rows in one launch, the images in another (a training step refreshes them)
-    static_assert(B16_NW + 1 <= H2_MT, "multi-tensor table");
+    static_assert(GEMM_NW + 1 <= H2_MT, "multi-tensor table");
     H2Multi mt;
     memset(&mt, 0, sizeof(mt));
     const long long ne = (long long)d.vocab_size * d.input_encoding_size;
     int blocks = 0;
-    for (int i = 0; i <= B16_NW; ++i) {
-        mt.src[i] = i < B16_NW ? p[i] : h->w.embed_weight;
-        mt.n[i] = i < B16_NW ? (long long)n[i] : ne;
-        mt.slot[i] = i < B16_NW ? i : (int)H2A_EMBED;
+    for (int i = 0; i <= GEMM_NW; ++i) {
+        mt.src[i] = i < GEMM_NW ? p[i] : h->w.embed_weight;
+        mt.n[i] = i < GEMM_NW ? (long long)n[i] : ne;
+        mt.slot[i] = i < GEMM_NW ? i : (int)H2A_EMBED;
         mt.blk[i] = blocks;
         blocks += (int)std::max<long long>(1, std::min<long long>(256, cdiv(mt.n[i], 8192)));
     }
-    mt.blk[B16_NW + 1] = blocks;
-    mt.nt = B16_NW + 1;
+    mt.blk[GEMM_NW + 1] = blocks;
+    mt.nt = GEMM_NW + 1;
     if (adam) hipLaunchKernelGGL(k_adam_multi, dim3(adam->t.blk[ADAM_NT]), dim3(256), 0, s, adam->t, adam->hy, bounds);
     else hipLaunchKernelGGL(k_absmax_multi, dim3(blocks), dim3(256), 0, s, mt, bounds);
     // |sentinel| = |s_fc s_t + b| <= max_d (sum_j |W_dj| + |b_d|) since |s_t| < 1                                   (step :155)
     hipLaunchKernelGGL(k_row_l1_max, dim3(cdiv(d.det_feat_size, L1MAX_ROWS)), dim3(256), 0, s, h->w.s_fc_weight, h->w.s_fc_bias, d.det_feat_size, d.rnn_size, bounds + H2B_SENT);
     hipLaunchKernelGGL(k_h2_exps, dim3(1), dim3(64), 0, s, bounds, idx, idx + H2_NSLOT, idx + 2 * H2_NSLOT, (int)H2A_REGION, exps);   // slots 0 .. 15
-    h->h2.clear();
+    h->img.clear_weights_h2();
     float* out = reinterpret_cast<float*>(base + H2_HEAD);
     H2Multi mc;
     memset(&mc, 0, sizeof(mc));
     long long off = 0;
     blocks = 0;
-    for (int i = 0; i < B16_NW; ++i) {
+    for (int i = 0; i < GEMM_NW; ++i) {
         const size_t n8 = (n[i] + 7) & ~size_t(7);
         mc.src[i] = p[i]; mc.n[i] = (long long)n8; mc.dst_off[i] = off; mc.slot[i] = i; mc.blk[i] = blocks;
         blocks += cdiv((long long)n8, 8 * 256);
-        h->h2.push_back(H2Range{p[i], p[i] + n[i], out + off, i});
+        h->img.add_weight_h2(p[i], n[i], out + off, i);
         off += (long long)n8;
     }
     {   // the embedding table: an A operand (gathered rows) of the all-DMA kernel, scaled by its own bound class
         const size_t n8 = ((size_t)ne + 7) & ~size_t(7);
-        mc.src[B16_NW] = h->w.embed_weight; mc.n[B16_NW] = (long long)n8; mc.dst_off[B16_NW] = off; mc.slot[B16_NW] = H2A_EMBED; mc.blk[B16_NW] = blocks;
+        mc.src[GEMM_NW] = h->w.embed_weight; mc.n[GEMM_NW] = (long long)n8; mc.dst_off[GEMM_NW] = off; mc.slot[GEMM_NW] = H2A_EMBED; mc.blk[GEMM_NW] = blocks;
         blocks += cdiv((long long)n8, 8 * 256);
-        h->h2.push_back(H2Range{h->w.embed_weight, h->w.embed_weight + ne, out + off, H2A_EMBED});
+        h->img.add_weight_h2(h->w.embed_weight, (size_t)ne, out + off, H2A_EMBED);
         off += (long long)n8;
     }
-    mc.blk[B16_NW + 1] = blocks;
-    mc.nt = B16_NW + 1;
+    mc.blk[GEMM_NW + 1] = blocks;
+    mc.nt = GEMM_NW + 1;
     hipLaunchKernelGGL(k_f32_to_h2_multi, dim3(blocks), dim3(256), 0, s, mc, reinterpret_cast<uint32_t*>(out), exps);
     LAUNCHCHK();
     h->h2_exps = exps; h->h2_bounds = bounds;
@@ -559,7 +568,7 @@ extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes,
     if (!buffer) {                                          // back to f32x3 for every launch
         if (h->h2_on) void_derived(h, VOID_FLAVOUR);
         h->h2_on = false;
-        h->h2.clear(); h->h2t.clear();
+        h->img.clear_h2();
         return 0;
     }
     if (!h->bound) return fail("vsr_refresh_h2_weights: weights not bound");
@@ -576,14 +585,6 @@ extern "C" int vsr_refresh_h2_weights(vsr_handle* h, void* buffer, size_t bytes,
 }
 
 // ---- the optimizer step (optim_kernels.h): Adam on the 28 bound tensors and, in the same pass, what the flavour derives from them
-static void weight_sizes(const vsr_dims& d, size_t (&n)[ADAM_NT]) {          // elements of the 28 tensors, in the order of vsr_weights
-    const size_t H = d.rnn_size, A = d.att_size, D = d.det_feat_size, E = d.input_encoding_size, V = d.vocab_size;
-    const size_t in1 = (d.h2_first_lstm ? H : 0) + D + E, in2 = H + D + (d.img_second_lstm ? D : 0);
-    const size_t c[ADAM_NT] = {V * E, H * in1, H, H * H, H, A * D, A * H, A, A * H, A, 4 * H * in1, 4 * H * H, 4 * H, 4 * H,
-                               4 * H * in2, 4 * H * H, 4 * H, 4 * H, V * H, V, D * H, D, H * in1, H, H * H, H, A * H, A};
-    for (int i = 0; i < ADAM_NT; ++i) n[i] = c[i];
-}
-static_assert(sizeof(vsr_weights) == ADAM_NT * sizeof(float*), "one table entry per tensor of vsr_weights");
 extern "C" int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr_weights* grads, const vsr_weights* exp_avg,
                              const vsr_weights* exp_avg_sq, const vsr_adam_args* a, void* stream) {
     if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !a) return fail("vsr_adam_step: null argument");
@@ -599,8 +600,8 @@ extern "C" int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr
     float* const* V = reinterpret_cast<float* const*>(exp_avg_sq);
     size_t n[ADAM_NT];
     weight_sizes(h->d, n);
-    const float* wp[B16_NW]; size_t wn[B16_NW];
-    b16_weight_list(h->d, h->w, wp, wn);
+    bool matrix[ADAM_NT] = {};           // one of the 14 matrices the GEMMs multiply by
+    for (int j = 0; j < GEMM_NW; ++j) matrix[GEMM_MATRIX[j]] = true;
     if (!h->adam_blocks) {               // one resident round of workgroups: a second, partial round would be the tail of the launch
         int per_cu = 0, dev = 0, cus = 0;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_adam_multi, 256, 0));
@@ -617,12 +618,12 @@ extern "C" int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr
         if (!M[i] || !V[i]) return fail("vsr_adam_step: moment pointer %d is null", i);
         L.t.p[i] = P[i]; L.t.g[i] = G[i]; L.t.m[i] = M[i]; L.t.v[i] = V[i]; L.t.n[i] = (long long)n[i];
         L.t.slot[i] = -1;
-        int mat = -1;                                  // index among the 14 matrices the GEMMs multiply by
-        for (int j = 0; j < B16_NW; ++j) if (wp[j] == P[i]) mat = j;
-        if (h->h2_on) L.t.slot[i] = mat >= 0 ? mat : (P[i] == h->w.embed_weight ? (int)H2A_EMBED : -1);
-        if (h->bf16_on && mat >= 0) {
-            if ((size_t)mat >= h->b16_weights || h->b16[mat].lo != wp[mat]) return fail("vsr_adam_step: internal: bf16 copy %d is not registered", mat);
-            L.t.b16[i] = const_cast<uint16_t*>(h->b16[mat].b);
+        // what the flavour derives from tensor i: the refreshes registered it (params are the bound tensors; a bind would have switched the flavour off)
+        const ImageRange* im = h->img.weight_at(P[i]);
+        if (h->h2_on && im && im->h2) L.t.slot[i] = im->slot;       // (a matrix's position in gemm_matrix_list, or H2A_EMBED)
+        if (h->bf16_on && matrix[i]) {
+            if (!im || !im->b16) return fail("vsr_adam_step: internal: the bf16 copy of tensor %d of vsr_weights (a GEMM matrix) is not registered", i);
+            L.t.b16[i] = const_cast<uint16_t*>(im->b16);
         }
         // blocks by the tensor's share of the elements, at least one, no more than it has 16-byte groups for; grid-stride covers the rest
         L.t.blk[i] = blocks;
@@ -644,7 +645,7 @@ extern "C" int vsr_adam_step(vsr_handle* h, const vsr_weights* params, const vsr
     }
     // what a refresh voids (vsr_bind_weights has the rules); with no flavour product the fp32 kernels read the weights live: only the
     // decode cache is of the old weights
-    if (h->h2_on || h->bf16_on) void_derived(h, VOID_REFRESH);
+    if (h->has_weight_images()) void_derived(h, VOID_REFRESH);
     else set_xproj(h, nullptr);
     return 0;
 }
@@ -730,7 +731,7 @@ static int prepare_impl(vsr_handle* h, const float* det, int B, int R0, const fl
     const long long prows = indexed ? (long long)n_img * Rb : rows;      // rows att_va runs over
     // f16x2 flavour: the bounds of the region / detection operands are measured in the passes that read them anyway (per-block maxima
     // into the idle GEMM scratch, folded by one block); exponents of the region rows, the pooled descriptor and the attended vector
-    const bool h2b = h->h2_on;
+    const bool h2b = h->measures_h2_bounds();         // (h2_on alone, unlike the routing: needed under bf16_on too - GemmState says why)
     float* bm_regions = h2b ? c.scratch : nullptr;
     float* bm_det = h2b ? c.scratch + cdiv(prows, 4) : nullptr;
     if (h2b && (size_t)(cdiv(prows, 4) + cdiv((long long)(indexed ? n_img : B) * R0, 4)) > c.scratch_floats) return fail("%s: scratch too small for the operand bounds", who);
@@ -934,8 +935,8 @@ static int run_step(vsr_handle* h, const StepIO& io, hipStream_t s) {
     float *h1n = sn[0], *c1n = sn[1], *h2n = sn[2], *c2n = sn[3];
     // bf16 images of the A operands (bf16 mode): the producers below write them, the GEMM segments name them
     // ... or fp16-pair images (f16x2 flavour, gemm_h2a.h): isc = the scale of the unit-bounded ones (2^15), the attended vector's from the table
-    const bool sh2 = h->h2_on && !h->bf16_on && h->x3_on && h->gk.h2_aimg;
-    const bool sh = (h->bf16_on && h->bf16_a16) || sh2;
+    const bool sh2 = h->writes_h2_a_images();         // (also with VSR_GEMM_TILE forced, when no launch reads them: not needed, kept)
+    const bool sh = (h->bf16() && h->bf16_a16) || sh2;
     const float isc = sh2 ? 32768.f : 0.f;
     const int* att_exp = sh2 ? h->h2_exps + H2A_ATT : nullptr;
     const bool sh_old = sh && c.st16_ok[io.cur];
@@ -1253,7 +1254,8 @@ extern "C" int vsr_step(vsr_handle* h, int32_t t, int32_t rows_per_image, const 
     float* out[4] = {h1_out, c1_out, h2_out, c2_out};
     for (int j = 0; j < 4; ++j) HIPCHK(hipMemcpyAsync(c.st[0][j], in[j], n, hipMemcpyDeviceToDevice, s));
     c.st16_ok[0] = false;                     // the caller's state has no bf16 image
-    if (h->h2_on && !h->bf16_on && h->x3_on) {           // f16x2: the hidden states are unit-class GEMM operands (include/vsrcap.h, limits of the flavour)
+    // (not tied to gemm_tile: with VSR_GEMM_TILE forced the count is still taken though no launch scales the states by the unit bound - not needed, kept)
+    if (h->f16x2()) {                         // f16x2: the hidden states are unit-class GEMM operands (include/vsrcap.h, limits of the flavour)
         const long long ne = (long long)M * H;
         hipLaunchKernelGGL(k_count_outside_unit, dim3(cdiv(ne, 256)), dim3(256), 0, s, h1, ne, c.nvalid_dev + 2);
         hipLaunchKernelGGL(k_count_outside_unit, dim3(cdiv(ne, 256)), dim3(256), 0, s, h2, ne, c.nvalid_dev + 2);
